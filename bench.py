@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- RAS iterations/sec of the MI355X hot path on the 3-D Poisson problem.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (value, ms_per_step, config).
+Everything else it can measure -- the roofline legs, the plain-CSR SpMV on other shapes, the HBM
+ceilings, the strong-scaling leg, the plain-CSR loop, time-to-residual, the CPU baseline and the C++
+mirror's own line -- runs only with --full.  --dump-outputs DIR writes what the last timed step left
+(see dump_outputs) as DIR/<name>.npy, so that two builds can be compared output for output.
 
 N = 1 runs in this process.  N > 1 without a launcher around it (no WORLD_SIZE in the
 environment) starts N rank processes itself -- before anything touches the GPU -- and relays
@@ -85,6 +91,11 @@ def parse(argv=None):
     ap.add_argument("--strong-grid", default="512,512,512",
                     help="grid of the strong-scaling leg every N runs after its weak-scaling leg ('' = skip)")
     ap.add_argument("--strong-steps", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (roofline, HBM ceilings, other shapes, strong scaling, "
+                         "plain-CSR loop, time-to-residual, CPU baseline, C++ mirror); off: the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the solution and residual history of the last timed step as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -329,6 +340,33 @@ def timed_steps(solver, comm, torch, warmup, steps):
     return time.perf_counter() - t0
 
 
+DUMP_SAMPLE_ROWS = 1 << 21  # past this many rows the solution is dumped at a fixed sample of rows (16 MiB)
+DUMP_SEED = 12345
+
+
+def dump_outputs(path, solver, comm):
+    """--dump-outputs DIR, called right after the last timed step (every rank; rank 0 writes):
+      solution.npy          the iterate x a caller of the loop receives (interiors in global row order), float64;
+                            at most DUMP_SAMPLE_ROWS values: a larger grid is sampled at fixed rows,
+      solution_rows.npy     those rows (sorted, drawn with DUMP_SEED; float64), only when sampled,
+      residual_history.npy  the global residual norm of every subdomain at every warm-up and timed step
+                            (subdomains x steps, float64; empty in the one-sided modes)."""
+    import numpy as np
+    stream = solver.backend.stream()
+    x = comm.gather_vectors({me: sd.get_interior(stream) for me, sd in solver.subdomains.items()})
+    if comm.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    if x.size > DUMP_SAMPLE_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, DUMP_SAMPLE_ROWS, replace=False))
+        np.save(os.path.join(path, "solution_rows.npy"), rows.astype(np.float64))
+        x = x[rows]
+    np.save(os.path.join(path, "solution.npy"), x)
+    hist = solver.metadata.post_process_data["global_residual_vector_out"]
+    np.save(os.path.join(path, "residual_history.npy"), np.asarray(hist, dtype=np.float64))
+
+
 def time_to_residual(schwz, torch, comm, shape, variant, budget_s):
     """time-to-residual(1e-6) at the authors' inexact setting (local_tol 0.1, <= 70 inner
     iterations; run_script:35-38), capped at 3000 outer iterations and `budget_s` seconds."""
@@ -357,6 +395,17 @@ def time_to_residual(schwz, torch, comm, shape, variant, budget_s):
     return res
 
 
+def emit_line(line, rank, json_fd, comm):
+    """Rank 0 writes the JSON line to the real stdout; the process group (N > 1) is taken down."""
+    sys.stdout.flush()
+    if rank == 0:
+        os.write(json_fd, (json.dumps(line) + "\n").encode())
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        comm.barrier()
+        dist.destroy_process_group()
+
+
 # ----------------------------------------------------------------------------- main
 
 def main():
@@ -372,7 +421,7 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
     mirror = None
-    if a.gpus == 1 and not a.no_mirror and os.environ.get("WORLD_SIZE", "1") == "1":
+    if a.full and a.gpus == 1 and not a.no_mirror and os.environ.get("WORLD_SIZE", "1") == "1":
         # a child process, finished before this process touches the GPU
         mirror = mirror_bench_ras(a.size, a.inner, a.mirror_iters)
     import torch
@@ -441,36 +490,85 @@ def main():
     early_exchange = (not a.overlapped) and solver._early_exchange_ok()
     # timed region: W warmup steps, then exactly K steps, no instrumentation
     elapsed = timed_steps(solver, comm, torch, a.warmup, a.steps)
-    # roofline leg: the same K steps again with a HIP-event pair around every launch of the
-    # dominant kernel on its launch stream.  Kept out of the timed region above because each
-    # event record costs ~5 us of GPU idle (measured with rocprofv3 --kernel-trace), which
-    # would tax the headline value; the kernel durations themselves are unaffected.
-    check(lib.schwz_profile_begin(2 * a.steps * a.inner + 8))
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        solver.step()
-    torch.cuda.synchronize()
-    comm.barrier()
-    elapsed_instrumented = time.perf_counter() - t1
-    tot_ms, launches = ctypes.c_double(0.0), ctypes.c_int64(0)
-    check(lib.schwz_profile_end(ctypes.byref(tot_ms), ctypes.byref(launches)))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, solver, comm)
+    if a.full:
+        # roofline leg: the same K steps again with a HIP-event pair around every launch of the
+        # dominant kernel on its launch stream.  Kept out of the timed region above because each
+        # event record costs ~5 us of GPU idle (measured with rocprofv3 --kernel-trace), which
+        # would tax the headline value; the kernel durations themselves are unaffected.
+        check(lib.schwz_profile_begin(2 * a.steps * a.inner + 8))
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            solver.step()
+        torch.cuda.synchronize()
+        comm.barrier()
+        elapsed_instrumented = time.perf_counter() - t1
+        tot_ms, launches = ctypes.c_double(0.0), ctypes.c_int64(0)
+        check(lib.schwz_profile_end(ctypes.byref(tot_ms), ctypes.byref(launches)))
     if N > 1:
         elapsed = max(comm.allgather_scalars({rank: elapsed}))
-        elapsed_instrumented = max(comm.allgather_scalars({rank: elapsed_instrumented}))
-    upd_ms, upd_launches = ctypes.c_double(0.0), ctypes.c_int64(0)
-    check(lib.schwz_profile_kind(1, ctypes.byref(upd_ms), ctypes.byref(upd_launches)))
+        if a.full:
+            elapsed_instrumented = max(comm.allgather_scalars({rank: elapsed_instrumented}))
     iters_per_s = a.steps / elapsed
-    n_rows = sd.local_size_x
-    csr_spmv_bytes = sd.algorithmic_bytes(0)  # SURVEY 8(d): 12 nnz + 4 (n + 1) + 16 n, uncoded CSR
     hist = m.post_process_data["global_residual_vector_out"]
     csr_h = sd_csr(sd, schwz)
     fmt = int(lib.schwz_csr_format(csr_h)) if a.spmv_variant == 0 else 0
-    mat_bytes = int(lib.schwz_csr_matrix_bytes(csr_h, a.spmv_variant))  # matrix bytes of the launched format
     coded = fmt != 0
+    fmt_name = {3: "row-pair coded", 2: "row-pattern coded", 1: "dictionary coded", 0: "plain CSR"}[fmt]
+    line = {
+        # BASELINE.json's metric string; `value` is its first half (outer RAS iterations per second,
+        # counted per subdomain and summed over the GPUs), the time-to-residual half is reported in
+        # the time_to_residual_* fields of the --full line
+        "metric": BASELINE_METRIC,
+        "metric_note": "value = RAS outer iterations/s x subdomains (whole-job aggregate); "
+                       "time-to-residual(1e-6) in time_to_residual_1e-6_s (--full)",
+        # weak scaling: subdomain-iterations/s of the whole job; strong scaling (fixed grid): the job's
+        # outer iterations/s
+        "value": iters_per_s if a.strong else N * iters_per_s,
+        "unit": "outer-iter/s" if a.strong else "subdomain-iter/s",
+        "n_gpus": N,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * elapsed / a.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if a.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (7-point Dirichlet Laplacian generated in place, rhs = 1, x0 = 0)",
+        "config": {"workload": workload, "inner_cg_iters": a.inner, "precond": "jacobi",
+                   "local_tol": 0.0, "overlap": 2, "partition": "regular",
+                   "rows_per_gpu": sd.local_size_x, "nnz_per_gpu": sd.nnz_local,
+                   "spmv_variant": a.spmv_variant, "matrix_format": fmt_name,
+                   "cg_launches_per_iteration": (2 if int(lib.schwz_ras_cg_flavour(sd.h)) & 3 == 2 else 3),
+                   "cg_flavour": int(lib.schwz_ras_cg_flavour(sd.h)),
+                   "exchange": ("one-sided overlapped, decentralised stop" if a.overlapped
+                                else "two-sided, all-gathered residual norms") +
+                               (", fp32 halos" if a.mixed_halo else "") +
+                               (", posted on a side stream beside the tail of the local solve" if early_exchange else ""),
+                   "exchange_backend": (None if backend is None else
+                                        ("nccl (RCCL, one GPU per rank)" if backend == "nccl" else
+                                         backend + " (ranks share %d GPU(s), halos staged through host: "
+                                                   "rehearsal, not a scaling measurement)" %
+                                         torch.cuda.device_count()))},
+        "ras_iters_per_s": iters_per_s,
+        "setup_s": setup_s,
+        "setup_note": "problem generation, index sets, matrix codings, upload, solver objects and one untimed step "
+                      "(first-use allocations); the process's GPU context (%.2f s) is created before" % gpu_context_s,
+        "residual_reduction_in_timed_steps": (sum(h[-1] for h in hist) / sum(h[0] for h in hist))
+        if hist and hist[0] else None,
+    }
+    if not a.full:
+        emit_line(line, rank, json_fd, comm)
+        return
+    upd_ms, upd_launches = ctypes.c_double(0.0), ctypes.c_int64(0)
+    check(lib.schwz_profile_kind(1, ctypes.byref(upd_ms), ctypes.byref(upd_launches)))
+    n_rows = sd.local_size_x
+    csr_spmv_bytes = sd.algorithmic_bytes(0)  # SURVEY 8(d): 12 nnz + 4 (n + 1) + 16 n, uncoded CSR
+    mat_bytes = int(lib.schwz_csr_matrix_bytes(csr_h, a.spmv_variant))  # matrix bytes of the launched format
     qfree = upd_launches.value > 0
     csr_spmv_equiv = csr_spmv_bytes
     spmv_avg_ms = tot_ms.value / max(launches.value, 1)
-    fmt_name = {3: "row-pair coded", 2: "row-pattern coded", 1: "dictionary coded", 0: "plain CSR"}[fmt]
     spmv_name = {3: "spmv_pair_kernel<kSpmvDot> (q = A p, fused p.q; row-pair pattern coded CSR)",
                  2: "spmv_pattern_kernel<kSpmvDot> (q = A p, fused p.q; row-pattern coded CSR tiles)",
                  1: "spmv_dict_kernel<kSpmvDot> (q = A p, fused p.q; dictionary-coded CSR tiles)",
@@ -546,52 +644,10 @@ def main():
                 "csr_equivalent_x": (csr_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if ms else None,
                 "launches": n_launch, "avg_launch_ms": ms}
 
-    line = {
-        # BASELINE.json's metric string; `value` is its first half (outer RAS iterations per second,
-        # counted per subdomain and summed over the GPUs), the time-to-residual half is reported in
-        # the time_to_residual_* fields of the same line
-        "metric": BASELINE_METRIC,
-        "metric_note": "value = RAS outer iterations/s x subdomains (whole-job aggregate); "
-                       "time-to-residual(1e-6) in time_to_residual_1e-6_s",
-        # weak scaling: subdomain-iterations/s of the whole job; strong scaling (fixed grid): the job's
-        # outer iterations/s
-        "value": iters_per_s if a.strong else N * iters_per_s,
-        "unit": "outer-iter/s" if a.strong else "subdomain-iter/s",
-        "n_gpus": N,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": 1e3 * elapsed / a.steps,
-        "higher_is_better": True,
-        "scaling": "strong" if a.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (7-point Dirichlet Laplacian generated in place, rhs = 1, x0 = 0)",
-        "config": {"workload": workload, "inner_cg_iters": a.inner, "precond": "jacobi",
-                   "local_tol": 0.0, "overlap": 2, "partition": "regular",
-                   "rows_per_gpu": sd.local_size_x, "nnz_per_gpu": sd.nnz_local,
-                   "spmv_variant": a.spmv_variant, "matrix_format": fmt_name,
-                   "cg_launches_per_iteration": (2 if int(lib.schwz_ras_cg_flavour(sd.h)) & 3 == 2 else 3),
-                   "cg_flavour": int(lib.schwz_ras_cg_flavour(sd.h)),
-                   "exchange": ("one-sided overlapped, decentralised stop" if a.overlapped
-                                else "two-sided, all-gathered residual norms") +
-                               (", fp32 halos" if a.mixed_halo else "") +
-                               (", posted on a side stream beside the tail of the local solve" if early_exchange else ""),
-                   "exchange_backend": (None if backend is None else
-                                        ("nccl (RCCL, one GPU per rank)" if backend == "nccl" else
-                                         backend + " (ranks share %d GPU(s), halos staged through host: "
-                                                   "rehearsal, not a scaling measurement)" %
-                                         torch.cuda.device_count()))},
-        "ras_iters_per_s": iters_per_s,
-        "setup_s": setup_s,
-        "setup_note": "problem generation, index sets, matrix codings, upload, solver objects and one untimed step "
-                      "(first-use allocations); the process's GPU context (%.2f s) is created before" % gpu_context_s,
-        "residual_reduction_in_timed_steps": (sum(h[-1] for h in hist) / sum(h[0] for h in hist))
-        if hist and hist[0] else None,
-        "roofline": dict(roof(kernel_name, dom_fmt_bytes, dom_csr_bytes, achieved, avg_ms, dom_launches, dom_tag),
-                         ms_per_step_instrumented=1e3 * elapsed_instrumented / a.steps),
-        "roofline_spmv": roof(spmv_name, spmv_fmt_bytes, csr_spmv_equiv, spmv_achieved, spmv_avg_ms,
-                              launches.value, spmv_tag),
-    }
+    line["roofline"] = dict(roof(kernel_name, dom_fmt_bytes, dom_csr_bytes, achieved, avg_ms, dom_launches, dom_tag),
+                            ms_per_step_instrumented=1e3 * elapsed_instrumented / a.steps)
+    line["roofline_spmv"] = roof(spmv_name, spmv_fmt_bytes, csr_spmv_equiv, spmv_achieved, spmv_avg_ms,
+                                 launches.value, spmv_tag)
     stream = torch.cuda.current_stream().cuda_stream
     # the plain-CSR kernel (variant 6), timed on its own: the figure the north_star's ">= 60 % of the HBM
     # roofline on the local CSR SpMV" refers to -- on this run's matrix and (N = 1) on the slabs a GPU holds
@@ -746,13 +802,7 @@ def main():
             mirror["vs_python_host"] = mirror["value"] / line["value"]
             mirror["same_cg_flavour_as_python_host"] = mirror["cg_flavour"] == line["config"]["cg_flavour"]
         line["mirror_bench_ras"] = mirror
-    sys.stdout.flush()
-    if rank == 0:
-        os.write(json_fd, (json.dumps(line) + "\n").encode())
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        comm.barrier()
-        dist.destroy_process_group()
+    emit_line(line, rank, json_fd, comm)
 
 
 if __name__ == "__main__":

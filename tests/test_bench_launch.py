@@ -53,12 +53,13 @@ def test_self_launch_ends_the_other_ranks_when_one_dies_at_start_up():
 
 @pytest.mark.gpu
 def test_bench_gpus_2_starts_itself_and_prints_one_line():
-    """`python bench.py --gpus 2` exactly as the driver calls it.  On a box with fewer GPUs than
+    """`python bench.py --gpus 2 --full` as the driver calls it.  On a box with fewer GPUs than
     ranks the two ranks share the GPU and stage halos through host over gloo (the line says so);
     with two GPUs the same command runs on RCCL.  Small slabs: this checks the launch path, the
     distributed branch and the shape of the line, not performance."""
     p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--slab", "48,40,16",
-                        "--no-cpu-baseline", "--ttr-budget-s", "20", "--strong-grid", "48,40,32", "--strong-steps", "3"],
+                        "--full", "--no-cpu-baseline", "--ttr-budget-s", "20", "--strong-grid", "48,40,32",
+                        "--strong-steps", "3"],
                        capture_output=True, text=True, timeout=900, env=_clean_env())
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -75,3 +76,45 @@ def test_bench_gpus_2_starts_itself_and_prints_one_line():
     assert got["strong"]["grid"] == "48x40x32" and got["strong"]["subdomains"] == 2 and got["strong"]["outer_iter_per_s"] > 0
     assert "mirror_bench_ras" not in got   # the C++ mirror's line belongs to the N = 1 run
     assert got["time_to_residual_converged"] and got["true_relative_residual"] < 1e-4
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(oracle, tmp_path):
+    """A plain run (no --full) prints the headline line only, over exactly --steps timed steps, and
+    --dump-outputs writes what the last timed step left: the iterate of the whole grid (the oracle's
+    after the same 1 + warmup + steps outer iterations) and the residual history of the warm-up and timed
+    steps, the same from run to run."""
+    import numpy as np
+    n, warmup, steps = 40, 2, 4
+    got = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--size", str(n), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, env=_clean_env())
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["n_gpus"] == 1
+        assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "subdomain-iter/s"
+        assert line["dtype"] == "f64" and line["higher_is_better"] is True
+        for leg in ("roofline", "roofline_csr_plain", "hbm_measured", "strong", "csr_plain_loop",
+                    "time_to_residual_1e-6_s", "cpu_baseline", "mirror_bench_ras"):
+            assert leg not in line, leg
+        assert sorted(os.listdir(d)) == ["residual_history.npy", "solution.npy"]
+        x, h = np.load(d / "solution.npy"), np.load(d / "residual_history.npy")
+        assert x.dtype == np.float64 and x.shape == (n ** 3,)
+        # the timed run restarts the history after the untimed set-up step; the iterate carries on from it
+        assert h.dtype == np.float64 and h.shape == (1, warmup + steps)
+        got.append((x, h))
+    np.testing.assert_allclose(got[1][0], got[0][0], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(got[1][1], got[0][1], rtol=1e-12, atol=0)
+    rp, col, val = oracle.laplacian3d(n, n, n)
+    N = len(rp) - 1
+    r = oracle.ras_run(rp, col, val, np.ones(N), 1, oracle.first_rows_regular(N, 1),
+                       oracle.make_settings(max_iters=1 + warmup + steps, tol=1e-30, precond=oracle.PRECOND_JACOBI,
+                                            local_tol=0.0, local_max_iters=10))
+    assert r["iter_count"] == 1 + warmup + steps
+    x = got[0][0]
+    assert np.abs(x - r["solution"]).max() <= 1e-8 * np.abs(r["solution"]).max()

@@ -11,7 +11,7 @@ run() {
     local envs=()
     while [ "$1" != "--" ]; do envs+=("$1"); shift; done
     shift
-    line=$(env "${envs[@]}" python3 $ROOT/bench.py --steps 30 --warmup 3 --no-ttr --no-cpu-baseline --no-mirror --no-shapes --strong-grid "" "$@" 2>/dev/null)
+    line=$(env "${envs[@]}" python3 $ROOT/bench.py --full --steps 30 --warmup 3 --no-ttr --no-cpu-baseline --no-mirror --no-shapes --strong-grid "" "$@" 2>/dev/null)
     echo "$label $(echo "$line" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("value %.1f ms/step %.4f  update %.4f  dirdot %.4f  plain_loop %s reduction %.17g" % (d["value"], d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline_spmv"]["avg_launch_ms"], d.get("csr_plain_loop",{}).get("value"), d["residual_reduction_in_timed_steps"]))')" | tee -a $OUT
 }
 for rep in 1 2; do

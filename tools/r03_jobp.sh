@@ -10,7 +10,7 @@ run() {
     local envs=()
     while [ "$1" != "--" ]; do envs+=("$1"); shift; done
     shift
-    line=$(env "${envs[@]}" python3 $ROOT/bench.py --steps 20 --warmup 3 --no-ttr --no-cpu-baseline --no-plain-loop --no-mirror --no-shapes --strong-grid= "$@" 2>/dev/null)
+    line=$(env "${envs[@]}" python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-ttr --no-cpu-baseline --no-plain-loop --no-mirror --no-shapes --strong-grid= "$@" 2>/dev/null)
     echo "$label $(echo "$line" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("value %.1f ms/step %.4f  update %.4f (%.3f)  dirdot %.4f (%.3f) flav %d reduction %.17g" % (d["value"], d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline"]["frac"], d["roofline_spmv"]["avg_launch_ms"], d["roofline_spmv"]["frac"], d["config"]["cg_flavour"], d["residual_reduction_in_timed_steps"]))')" | tee -a $OUT
 }
 run "200 gen off " SCHWZ_SWEEP_GEN=0 -- --size 200

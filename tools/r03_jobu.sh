@@ -11,7 +11,7 @@ for setting in "$@"; do
   OUT=$ROOT/gpurun_out/prof_r03_plainloop_$n
   rm -rf $OUT && mkdir -p $OUT
   [ "$setting" != "-" ] && export $setting
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-ttr --no-plain-loop --no-mirror --no-shapes --strong-grid= --spmv-variant 6 > $OUT/stats.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-ttr --no-plain-loop --no-mirror --no-shapes --strong-grid= --spmv-variant 6 > $OUT/stats.log 2>&1 || exit 1
   [ "$setting" != "-" ] && unset ${setting%%=*}
   f=$(find $OUT/stats -name "*_kernel_stats.csv" | head -1)
   echo "== $setting" >> $ROOT/gpurun_out/r03_plainloop_kernels.txt

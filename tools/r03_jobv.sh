@@ -9,7 +9,7 @@ REPS=${REPS:-4}
 for rep in $(seq $REPS); do
   for setting in "$@"; do
     [ "$setting" != "-" ] && export $setting
-    line=$(python3 $ROOT/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-ttr --no-plain-loop --no-mirror --no-shapes --strong-grid= --spmv-variant 6 2>/dev/null | tail -1) || exit 1
+    line=$(python3 $ROOT/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-ttr --no-plain-loop --no-mirror --no-shapes --strong-grid= --spmv-variant 6 2>/dev/null | tail -1) || exit 1
     [ "$setting" != "-" ] && unset ${setting%%=*}
     python3 - "$setting" "$line" >> $OUT <<'PY'
 import json, sys

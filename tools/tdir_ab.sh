@@ -3,7 +3,7 @@
 # slab and (optionally) the 1024 x 1024 x 128 slab of configs[4]
 set -o pipefail
 run() {  # label, env, bench args
-  echo "$1: $(env $2 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-ttr --no-plain-loop $3 2>/dev/null | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("%.4f ms/step  upd %.4f ms  dirdot %.4f ms (%.3f)" % (d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline_spmv"]["avg_launch_ms"], d["roofline_spmv"]["frac"]))')"
+  echo "$1: $(env $2 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-ttr --no-plain-loop $3 2>/dev/null | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("%.4f ms/step  upd %.4f ms  dirdot %.4f ms (%.3f)" % (d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline_spmv"]["avg_launch_ms"], d["roofline_spmv"]["frac"]))')"
 }
 for rep in 1 2; do
   run "cube  T_dir=512 (= update launch)" "SCHWZ_SWEEP_TDIR=512" ""

@@ -10,7 +10,7 @@ for shape in ${SHAPES:-cube slab}; do
     for LE in $LIBS; do
         L=${LE%%:*}                      # an entry may carry one environment setting: libschwz_hip.so:SCHWZ_WALK_CACHED=0
         [ "$LE" != "$L" ] && export ${LE#*:}
-        line=$(SCHWZ_HIP_LIB=$ROOT/schwarz-lib_amd/lib/$L python3 $ROOT/bench.py --steps 20 --warmup 3 --no-ttr --no-cpu-baseline --no-plain-loop --no-mirror --no-shapes --strong-grid "" $ARGS 2>/dev/null) || exit 1
+        line=$(SCHWZ_HIP_LIB=$ROOT/schwarz-lib_amd/lib/$L python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-ttr --no-cpu-baseline --no-plain-loop --no-mirror --no-shapes --strong-grid "" $ARGS 2>/dev/null) || exit 1
         [ "$LE" != "$L" ] && { v=${LE#*:}; unset ${v%%=*}; }
         echo "$shape $LE $(echo "$line" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print("ms/step %.4f  update %.4f ms frac %.3f  dirdot %.4f ms frac %.3f  reduction %.17g" % (d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline"]["frac"], d["roofline_spmv"]["avg_launch_ms"], d["roofline_spmv"]["frac"], d["residual_reduction_in_timed_steps"]))')" | tee -a $OUT
     done
