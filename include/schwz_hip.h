@@ -50,7 +50,10 @@ enum schwz_op { SCHWZ_OP_ADD = 0, SCHWZ_OP_COPY = 1, SCHWZ_OP_DIFF = 2, SCHWZ_OP
 
 /* Settings::local_solver_settings (include/settings.hpp) as used by
  * Solve::local_solve (source/solve.cpp:667-792) */
-enum schwz_local_solver { SCHWZ_SOLVER_ITERATIVE = 0, SCHWZ_SOLVER_DIRECT = 1 };
+/* SCHWZ_SOLVER_DIRECT: LL^T (schwz_cholesky, "cholmod"); SCHWZ_SOLVER_DIRECT_LU: pivoted LU
+ * (schwz_lu, settings.factorization == "umfpack"), also for non-symmetric matrices.  Both run
+ * the triangular solves on the GPU (schwz_trs). */
+enum schwz_local_solver { SCHWZ_SOLVER_ITERATIVE = 0, SCHWZ_SOLVER_DIRECT = 1, SCHWZ_SOLVER_DIRECT_LU = 2 };
 /* metadata.local_precond (source/solve.cpp:486-652): "null", "block-jacobi"
  * (gko::preconditioner::Jacobi, :490-505,575-589) and "ilu" (ParIlu + LowerTrs/UpperTrs,
  * :506-532,590-615) and "isai" (Ilu<LowerIsai, UpperIsai>, :616-638) */
@@ -214,6 +217,15 @@ int schwz_trs_create(int64_t n, const schwz_idx *h_l_rp, const schwz_idx *h_l_co
                      const double *h_l_val, const schwz_idx *h_u_rp,
                      const schwz_idx *h_u_col, const double *h_u_val,
                      const schwz_idx *h_perm, schwz_trs **out);
+/* The LU variant: y[h_col_perm[i]] = (U^-1 L^-1 w)[i] with w[i] = b[h_row_perm[i]], i.e.
+ * y = Q U^-1 L^-1 P b for A(row_perm, col_perm) = L U (schwz_lu).  Same factor layout as above;
+ * both permutations are required.  Factors beyond the one-workgroup kernel whose rows exceed 64
+ * entries (LU fill of a banded subdomain) are swept by a flag-driven kernel with one wave per row. */
+int schwz_trs_create_lu(int64_t n, const schwz_idx *h_l_rp, const schwz_idx *h_l_col,
+                        const double *h_l_val, const schwz_idx *h_u_rp,
+                        const schwz_idx *h_u_col, const double *h_u_val,
+                        const schwz_idx *h_row_perm, const schwz_idx *h_col_perm,
+                        schwz_trs **out);
 void schwz_trs_destroy(schwz_trs *t);
 int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream stream);
 
@@ -323,6 +335,20 @@ int schwz_cholesky(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col,
                    const double *h_val, int natural_ordering, schwz_idx **l_rp,
                    schwz_idx **l_col, double **l_val, schwz_idx **u_rp,
                    schwz_idx **u_col, double **u_val, schwz_idx **perm);
+/* Host sparse LU with threshold partial pivoting, standing in for UMFPACK (Solve::compute_local_factors
+ * with factorization == "umfpack", source/solve.cpp:144-173,321-390): A(row_perm, col_perm) = L U,
+ * L unit lower with the 1 stored LAST in each row, U upper with its diagonal FIRST, columns sorted
+ * -- the layout schwz_trs_create_lu expects.  Columns are pre-ordered by reverse Cuthill-McKee on
+ * the pattern of A + A^T (identity when natural_ordering is set); left-looking Gilbert-Peierls;
+ * the pivot of a column is the pre-order's diagonal entry when |a| >= 0.1 * max|column|
+ * (UMFPACK's default tolerance), else the largest entry.  NO row scaling: the reference hands
+ * UMFPACK's L and U to the triangular solves without the row-scale vector, which is exact only
+ * when scaling is off; here the factors are those of A itself.  A column without a nonzero pivot
+ * candidate returns SCHWZ_ERR_NOT_SPD.  Outputs are malloc'd; free with schwz_free. */
+int schwz_lu(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, const double *h_val,
+             int natural_ordering, schwz_idx **l_rp, schwz_idx **l_col, double **l_val,
+             schwz_idx **u_rp, schwz_idx **u_col, double **u_val, schwz_idx **row_perm,
+             schwz_idx **col_perm);
 /* Host ILU(0) on the pattern of A (columns sorted): L unit lower with the 1 stored LAST in each
  * row, U upper with its diagonal FIRST -- the layout schwz_trs_create expects.  Stands in for
  * gko::factorization::ParIlu (source/solve.cpp:506-532), whose sweeps converge to these

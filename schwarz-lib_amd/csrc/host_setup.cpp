@@ -1458,6 +1458,195 @@ int schwz_cholesky(int64_t n, const schwz_idx *rp, const schwz_idx *col, const d
     return SCHWZ_OK;
 }
 
+// ---------------------------------------------------------------------------
+// sparse LU with threshold partial pivoting (left-looking, Gilbert-Peierls)
+// ---------------------------------------------------------------------------
+
+// Stands in for UMFPACK (solve.cpp:144-173,321-390).  Column k of the factors is the sparse
+// triangular solve L(:,0:k) x = A(:, q[k]) over the rows reachable from A(:, q[k])'s pattern in
+// the graph of the finished L columns (an iterative DFS gives them in topological order), then the
+// pivot is chosen among the rows not yet pivoted.  No row scaling: y = Q U^-1 L^-1 P b is exact.
+int schwz_lu(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double *val, int natural,
+             schwz_idx **l_rp_o, schwz_idx **l_col_o, double **l_val_o, schwz_idx **u_rp_o, schwz_idx **u_col_o,
+             double **u_val_o, schwz_idx **row_perm_o, schwz_idx **col_perm_o)
+{
+    SCHWZ_REQUIRE(rp && l_rp_o && l_col_o && l_val_o && u_rp_o && u_col_o && u_val_o && row_perm_o && col_perm_o &&
+                      n >= 0 && n < INT_MAX,
+                  "schwz_lu: bad arguments");
+    const size_t N = (size_t)n;
+    for (int64_t i = 0; i < n; ++i)
+        for (schwz_idx t = rp[i]; t < rp[i + 1]; ++t)
+            SCHWZ_REQUIRE(col[t] >= 0 && col[t] < n, "schwz_lu: column index out of range");
+    // A in CSC: column c's rows and values
+    std::vector<schwz_idx> cp(N + 1, 0), ci((size_t)rp[n]);
+    std::vector<double> cx((size_t)rp[n]);
+    for (int64_t i = 0; i < n; ++i)
+        for (schwz_idx t = rp[i]; t < rp[i + 1]; ++t) cp[(size_t)col[t] + 1]++;
+    for (size_t c = 0; c < N; ++c) cp[c + 1] += cp[c];
+    {
+        std::vector<schwz_idx> fill(cp.begin(), cp.end() - 1);
+        for (int64_t i = 0; i < n; ++i)
+            for (schwz_idx t = rp[i]; t < rp[i + 1]; ++t) {
+                const schwz_idx o = fill[(size_t)col[t]]++;
+                ci[(size_t)o] = (schwz_idx)i;
+                cx[(size_t)o] = val[t];
+            }
+    }
+    // column pre-order: RCM on the pattern of A + A^T (the LL^T ordering for a symmetric pattern)
+    std::vector<schwz_idx> q;
+    if (natural) {
+        q.resize(N);
+        std::iota(q.begin(), q.end(), 0);
+    } else {
+        std::vector<schwz_idx> srp(N + 1, 0), scol;
+        scol.reserve((size_t)rp[n] * 2);
+        std::vector<schwz_idx> row;
+        for (int64_t i = 0; i < n; ++i) {
+            row.assign(col + rp[i], col + rp[i + 1]);
+            row.insert(row.end(), ci.begin() + cp[(size_t)i], ci.begin() + cp[(size_t)i + 1]);
+            std::sort(row.begin(), row.end());
+            row.erase(std::unique(row.begin(), row.end()), row.end());
+            scol.insert(scol.end(), row.begin(), row.end());
+            srp[(size_t)i + 1] = (schwz_idx)scol.size();
+        }
+        rcm(n, srp.data(), scol.data(), q);
+    }
+    // L by columns (original row ids, the pivot row first with its 1), U by columns (pivot steps)
+    std::vector<int64_t> lp(1, 0), up(1, 0);
+    std::vector<schwz_idx> li, ui;
+    std::vector<double> lx, ux;
+    std::vector<schwz_idx> pinv(N, -1), mark(N, -1), xi(N), stack(N);
+    std::vector<int64_t> pstack(N);
+    std::vector<double> x(N, 0.0);
+    constexpr double kPivotTol = 0.1;  // UMFPACK's default (UMFPACK_SYM_PIVOT_TOLERANCE)
+    for (int64_t k = 0; k < n; ++k) {
+        const schwz_idx c = q[(size_t)k];
+        // reach of A(:, c) in the graph of L: xi[top:n) in topological order
+        int64_t top = n;
+        for (schwz_idx t = cp[(size_t)c]; t < cp[(size_t)c + 1]; ++t) {
+            if (mark[(size_t)ci[(size_t)t]] == k) continue;
+            int64_t head = 0;
+            stack[0] = ci[(size_t)t];
+            while (head >= 0) {
+                const schwz_idx j = stack[(size_t)head];
+                const schwz_idx jj = pinv[(size_t)j];
+                if (mark[(size_t)j] != k) {
+                    mark[(size_t)j] = (schwz_idx)k;
+                    pstack[(size_t)head] = jj < 0 ? 0 : lp[(size_t)jj] + 1;
+                }
+                bool done = true;
+                if (jj >= 0) {
+                    const int64_t p2 = lp[(size_t)jj + 1];
+                    for (int64_t p = pstack[(size_t)head]; p < p2; ++p) {
+                        const schwz_idx i = li[(size_t)p];
+                        if (mark[(size_t)i] == k) continue;
+                        pstack[(size_t)head] = p + 1;
+                        stack[(size_t)++head] = i;
+                        done = false;
+                        break;
+                    }
+                }
+                if (done) {
+                    --head;
+                    xi[(size_t)--top] = j;
+                }
+            }
+        }
+        // x = L \ A(:, c) on the reach
+        for (schwz_idx t = cp[(size_t)c]; t < cp[(size_t)c + 1]; ++t) x[(size_t)ci[(size_t)t]] += cx[(size_t)t];
+        for (int64_t p = top; p < n; ++p) {
+            const schwz_idx j = xi[(size_t)p];
+            const schwz_idx jj = pinv[(size_t)j];
+            if (jj < 0) continue;
+            const double xj = x[(size_t)j];
+            for (int64_t t = lp[(size_t)jj] + 1; t < lp[(size_t)jj + 1]; ++t) x[(size_t)li[(size_t)t]] -= lx[(size_t)t] * xj;
+        }
+        // threshold partial pivoting among the rows not yet pivoted
+        schwz_idx piv = -1;
+        double amax = 0.0;
+        for (int64_t p = top; p < n; ++p) {
+            const schwz_idx i = xi[(size_t)p];
+            if (pinv[(size_t)i] < 0 && std::fabs(x[(size_t)i]) > amax) {
+                amax = std::fabs(x[(size_t)i]);
+                piv = i;
+            }
+        }
+        if (!(amax > 0.0) || !std::isfinite(amax)) {
+            set_error("schwz_lu: factorization failed: matrix is singular (no usable pivot in column " +
+                      std::to_string(c) + ")");
+            return SCHWZ_ERR_NOT_SPD;
+        }
+        if (pinv[(size_t)c] < 0 && mark[(size_t)c] == k && std::fabs(x[(size_t)c]) >= kPivotTol * amax) piv = c;
+        const double pv = x[(size_t)piv];
+        pinv[(size_t)piv] = (schwz_idx)k;
+        // U(:, k): the pivoted rows of the reach, pivot last; L(:, k): the pivot, then the others / pv
+        for (int64_t p = top; p < n; ++p) {
+            const schwz_idx i = xi[(size_t)p];
+            if (pinv[(size_t)i] >= 0 && i != piv) {
+                ui.push_back(pinv[(size_t)i]);
+                ux.push_back(x[(size_t)i]);
+            }
+        }
+        ui.push_back((schwz_idx)k);
+        ux.push_back(pv);
+        up.push_back((int64_t)ui.size());
+        li.push_back(piv);
+        lx.push_back(1.0);
+        for (int64_t p = top; p < n; ++p) {
+            const schwz_idx i = xi[(size_t)p];
+            if (pinv[(size_t)i] < 0) {
+                li.push_back(i);
+                lx.push_back(x[(size_t)i] / pv);
+            }
+            x[(size_t)i] = 0.0;
+        }
+        lp.push_back((int64_t)li.size());
+        if (li.size() >= (size_t)INT_MAX || ui.size() >= (size_t)INT_MAX) {
+            set_error("schwz_lu: factors exceed 2^31-1 nonzeros");
+            return SCHWZ_ERR_INVALID;
+        }
+    }
+    // CSR of L (rows = steps, unit diagonal LAST) and U (diagonal FIRST), columns ascending:
+    // walking the columns in order appends to every row in column order
+    std::vector<schwz_idx> l_rp(N + 1, 0), u_rp(N + 1, 0);
+    for (size_t t = 0; t < li.size(); ++t) l_rp[(size_t)pinv[(size_t)li[t]] + 1]++;
+    for (size_t t = 0; t < ui.size(); ++t) u_rp[(size_t)ui[t] + 1]++;
+    for (size_t i = 0; i < N; ++i) {
+        l_rp[i + 1] += l_rp[i];
+        u_rp[i + 1] += u_rp[i];
+    }
+    std::vector<schwz_idx> l_col(li.size()), u_col(ui.size());
+    std::vector<double> l_val(li.size()), u_val(ui.size());
+    std::vector<schwz_idx> lf(l_rp.begin(), l_rp.end() - 1), uf(u_rp.begin(), u_rp.end() - 1);
+    for (size_t j = 0; j < N; ++j) {
+        // L column j: strictly-lower entries first so that the row's 1 (column j of row j) lands last
+        for (int64_t t = lp[j] + 1; t < lp[j + 1]; ++t) {
+            const schwz_idx r = pinv[(size_t)li[(size_t)t]];
+            l_col[(size_t)lf[(size_t)r]] = (schwz_idx)j;
+            l_val[(size_t)lf[(size_t)r]++] = lx[(size_t)t];
+        }
+        const schwz_idx r = pinv[(size_t)li[(size_t)lp[j]]];
+        l_col[(size_t)lf[(size_t)r]] = (schwz_idx)j;
+        l_val[(size_t)lf[(size_t)r]++] = 1.0;
+        for (int64_t t = up[j]; t < up[j + 1]; ++t) {
+            const schwz_idx rr = ui[(size_t)t];
+            u_col[(size_t)uf[(size_t)rr]] = (schwz_idx)j;
+            u_val[(size_t)uf[(size_t)rr]++] = ux[(size_t)t];
+        }
+    }
+    std::vector<schwz_idx> row_perm(N);
+    for (size_t i = 0; i < N; ++i) row_perm[(size_t)pinv[i]] = (schwz_idx)i;
+    *l_rp_o = to_malloc(l_rp);
+    *l_col_o = to_malloc(l_col);
+    *l_val_o = to_malloc(l_val);
+    *u_rp_o = to_malloc(u_rp);
+    *u_col_o = to_malloc(u_col);
+    *u_val_o = to_malloc(u_val);
+    *row_perm_o = to_malloc(row_perm);
+    *col_perm_o = to_malloc(q);
+    return SCHWZ_OK;
+}
+
 // ISAI of a triangular factor on its own pattern (Anzt, Huckle, Braeckle, Dongarra 2018): per row
 // one small triangular substitution with T(S,S), S the row's pattern; rows are independent.
 int schwz_isai(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double *val, int lower, double **w_val)

@@ -565,7 +565,9 @@ struct schwz_trs {
     int64_t n = 0;
     schwz_idx *l_rp = nullptr, *l_col = nullptr, *u_rp = nullptr, *u_col = nullptr;
     double *l_val = nullptr, *u_val = nullptr;
-    schwz_idx *perm = nullptr;
+    // w[i] = b[perm[i]] before the sweeps, y[perm_out[i]] = w[i] after them: the same array for LL^T and
+    // ILU (perm_out == perm), the row and the column permutation of an LU (schwz_trs_create_lu)
+    schwz_idx *perm = nullptr, *perm_out = nullptr;
     // level schedules: rows sorted by level, level pointers
     schwz_idx *l_order = nullptr, *l_lvl = nullptr, *u_order = nullptr, *u_lvl = nullptr;
     int l_nlvl = 0, u_nlvl = 0;
@@ -598,6 +600,8 @@ struct schwz_trs {
     double *fl_val = nullptr, *fu_val = nullptr;
     schwz_idx *fl_src = nullptr, *fu_src = nullptr, *fu_dst = nullptr;  // rhs gather / y scatter per position
     int flag_grid = 0;
+    // LU factors (schwz_trs_create_lu) with rows beyond one lane each: trs_flag_wave_kernel, one wave per row
+    bool wave = false;
 };
 
 // host-side global problem (explicit CSR or analytic stencil)

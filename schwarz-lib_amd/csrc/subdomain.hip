@@ -59,7 +59,8 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
     StageTimer timer_all("subdomain_to_device total");
     SCHWZ_REQUIRE(sd && h_local_rhs && opt, "schwz_subdomain_to_device: null argument");
     SCHWZ_REQUIRE(!sd->on_device, "schwz_subdomain_to_device: already on the device");
-    SCHWZ_REQUIRE(opt->local_solver == SCHWZ_SOLVER_ITERATIVE || opt->local_solver == SCHWZ_SOLVER_DIRECT,
+    SCHWZ_REQUIRE(opt->local_solver == SCHWZ_SOLVER_ITERATIVE || opt->local_solver == SCHWZ_SOLVER_DIRECT ||
+                      opt->local_solver == SCHWZ_SOLVER_DIRECT_LU,
                   "schwz_subdomain_to_device: unknown local solver");
     if (schwz_device_count() < 1) {
         set_error("schwz_subdomain_to_device: no HIP device visible (there is no CPU fallback)");
@@ -149,6 +150,19 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
                 }
             }
         }
+    } else if (opt->local_solver == SCHWZ_SOLVER_DIRECT_LU) {
+        // factorization == "umfpack": P A Q = L U on the host, the triangular solves with both
+        // permutations on the GPU (solve.cpp:144-173,253-267,321-390)
+        schwz_idx *l_rp, *l_col, *u_rp, *u_col, *row_perm, *col_perm;
+        double *l_val, *u_val;
+        if ((rc = schwz_lu(n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), opt->natural_factor_ordering,
+                           &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val, &row_perm, &col_perm)))
+            return rc;
+        rc = schwz_trs_create_lu(n, l_rp, l_col, l_val, u_rp, u_col, u_val, row_perm, col_perm, &sd->trs);
+        for (void *p : {(void *)l_rp, (void *)l_col, (void *)l_val, (void *)u_rp, (void *)u_col, (void *)u_val,
+                        (void *)row_perm, (void *)col_perm})
+            schwz_free(p);
+        if (rc) return rc;
     } else {
         // Solve::compute_local_factors + the Ginkgo TRS setup (solve.cpp:75-143,281-399)
         schwz_idx *l_rp, *l_col, *u_rp, *u_col, *perm;
@@ -449,7 +463,7 @@ static void restrict_by_solver(schwz_subdomain *sd)
 int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_local_solve");
-    if (sd->opt.local_solver == SCHWZ_SOLVER_DIRECT) {
+    if (sd->opt.local_solver == SCHWZ_SOLVER_DIRECT || sd->opt.local_solver == SCHWZ_SOLVER_DIRECT_LU) {
         if (h_inner_iters) *h_inner_iters = 0;
         return schwz_trs_solve(sd->trs, sd->d_btilde, sd->d_y, stream);
     }

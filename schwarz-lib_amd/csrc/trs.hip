@@ -23,9 +23,10 @@ namespace schwz {
 constexpr int kTrsBlock = 1024;
 
 // out[i] = in[perm[i]]   (gko Permutation row_permute)
-// L t = out ; U out = t ; y[perm[i]] = out[i]
+// L t = out ; U out = t ; y[perm_out[i]] = out[i]   (perm_out == perm but for an LU's column permutation)
 __global__ __launch_bounds__(kTrsBlock) void trs_solve_kernel(
-    int64_t n, const schwz_idx *__restrict__ perm, const schwz_idx *__restrict__ l_rp,
+    int64_t n, const schwz_idx *__restrict__ perm, const schwz_idx *__restrict__ perm_out,
+    const schwz_idx *__restrict__ l_rp,
     const schwz_idx *__restrict__ l_col, const double *__restrict__ l_val,
     const schwz_idx *__restrict__ l_order, const schwz_idx *__restrict__ l_lvl, int l_nlvl,
     const schwz_idx *__restrict__ u_rp, const schwz_idx *__restrict__ u_col,
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(kTrsBlock) void trs_solve_kernel(
         __threadfence_block();
         __syncthreads();
     }
-    for (int64_t i = tid; i < n; i += kTrsBlock) y[perm[i]] = w0[i];
+    for (int64_t i = tid; i < n; i += kTrsBlock) y[perm_out[i]] = w0[i];
 }
 
 // ---- the same solves level by level, for factors that do not fit one workgroup ----------------
@@ -256,6 +257,93 @@ __global__ __launch_bounds__(kBlock) void trs_flag_kernel(int64_t n, const schwz
     }
 }
 
+// ---- the flag-driven sweep with ONE WAVE per row, for LU factors -----------------------------------------
+// The LU factors of an RCM-ordered 2-D subdomain have rows about as long as the bandwidth (often more than the
+// 64 a lane of trs_flag_kernel takes) and about one row per level: the level plan runs them as one
+// trs_narrow_kernel launch, i.e. every factor byte through one CU with a barrier per row.  Here the positions of
+// the level-sorted order are dealt to the resident waves in ascending order (position k to wave k mod nwaves),
+// a wave works on one row at a time and its 64 lanes split the row's entries (lane l: entries l, l + 64, ...).
+// Each lane consumes its own entries in that fixed order as their dependencies arrive, so by the time the last
+// dependency is published only a few FMAs, the wave's butterfly reduction (a fixed order: the same bits on
+// every run) and one store remain.  The protocol is trs_flag_kernel's: the solution vector is the flag
+// (kTrsUnset), a row is published with ONE 8-byte agent-scope store, polls are relaxed agent-scope loads, the
+// other sweep's vector is reset on the way, and every wait is bounded by kTrsTimeoutTicks (NaN + *err).
+// Progress: the wave holding the smallest unfinished position has finished its earlier (smaller) positions, so
+// it is working on that one, whose dependencies are all finished; the whole grid is resident.
+template <bool LOWER>
+__global__ __launch_bounds__(kBlock) void trs_flag_wave_kernel(int64_t n, const schwz_idx *__restrict__ rp,
+                                                               const schwz_idx *__restrict__ col,
+                                                               const double *__restrict__ val, const double *rhs,
+                                                               const schwz_idx *__restrict__ src, u64 *out,
+                                                               u64 *reset, double *y_out,
+                                                               const schwz_idx *__restrict__ dst, int *err)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const u64 t_start = __builtin_amdgcn_s_memrealtime();
+    bool timed_out = false;  // wave-uniform
+    unsigned spins = 0;
+    for (int64_t k = wave; k < n; k += nwaves) {
+        const int s0 = rp[k], e = rp[k + 1];
+        const int jend = LOWER ? e - 1 : e;
+        const double diag = LOWER ? val[e - 1] : val[s0];
+        const double b = rhs[src[k]];
+        int j = (LOWER ? s0 : s0 + 1) + lane;
+        double part = 0.0;
+        int cc[4] = {0, 0, 0, 0};
+        double vv[4] = {0.0, 0.0, 0.0, 0.0};
+        int loaded_at = -1;
+        while (!timed_out) {
+            if (j < jend) {
+                if (loaded_at != j) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const bool in = j + 64 * q < jend;
+                        cc[q] = in ? col[j + 64 * q] : 0;
+                        vv[q] = in ? val[j + 64 * q] : 0.0;
+                    }
+                    loaded_at = j;
+                }
+                u64 got[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    got[q] = j + 64 * q < jend ? __hip_atomic_load(out + cc[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                               : 0ull;
+                bool ok = true;
+                int used = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (j + 64 * q < jend && ok) {
+                        if (got[q] != kTrsUnset) {
+                            part += vv[q] * __longlong_as_double((long long)got[q]);
+                            ++used;
+                        } else {
+                            ok = false;
+                        }
+                    }
+                }
+                j += 64 * used;  // a group that moved on is fetched anew (loaded_at != j)
+            }
+            if (__builtin_amdgcn_ballot_w64(j < jend) == 0) break;
+            if ((++spins & 255u) == 0 && __builtin_amdgcn_s_memrealtime() - t_start > kTrsTimeoutTicks)
+                timed_out = true;
+            else if (SCHWZ_TRS_SLEEP_EVERY && (spins & (SCHWZ_TRS_SLEEP_EVERY - 1)) == 0)
+                __builtin_amdgcn_s_sleep(1);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+        if (lane == 0) {
+            const double res = timed_out ? __longlong_as_double(0x7ff8000000000000ll) : (b - part) / diag;
+            __hip_atomic_store(out + k, (u64)__double_as_longlong(res), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            reset[LOWER ? k : (int64_t)src[k]] = kTrsUnset;
+            if (!LOWER) y_out[dst[k]] = res;
+            if (timed_out) *err = 1;
+        }
+    }
+}
+
 // A flag-driven sweep that waited longer than kTrsTimeoutTicks gave up with NaNs and set the error word: read
 // and clear it (callers stand at a point where the stream is idle: the NaN has already reached the host).
 int trs_take_error(schwz_trs *t)
@@ -310,18 +398,26 @@ static void level_schedule(int64_t n, const schwz_idx *rp, const schwz_idx *col,
     for (int64_t i = 0; i < n; ++i) order[fill[level[i]]++] = (schwz_idx)i;
 }
 
-int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, const double *l_val,
-                     const schwz_idx *u_rp, const schwz_idx *u_col, const double *u_val,
-                     const schwz_idx *perm, schwz_trs **out)
+// perm: the input permutation, perm_out: the output one (the same pointer but for an LU); lu: factors of
+// schwz_lu, which may take the one-wave-per-row flag sweep
+static int trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, const double *l_val,
+                      const schwz_idx *u_rp, const schwz_idx *u_col, const double *u_val, const schwz_idx *perm,
+                      const schwz_idx *perm_out, bool lu, schwz_trs **out)
 {
     SCHWZ_REQUIRE(out && n >= 0 && l_rp && u_rp, "schwz_trs_create: bad arguments");
+    SCHWZ_REQUIRE(!perm == !perm_out, "schwz_trs_create: both permutations or none");
     for (int64_t i = 0; i < n; ++i) {
         SCHWZ_REQUIRE(l_rp[i + 1] > l_rp[i] && l_col[l_rp[i + 1] - 1] == i,
                       "schwz_trs_create: L must hold its diagonal last in each row");
         SCHWZ_REQUIRE(u_rp[i + 1] > u_rp[i] && u_col[u_rp[i]] == i,
                       "schwz_trs_create: U must hold its diagonal first in each row");
         SCHWZ_REQUIRE(!perm || (perm[i] >= 0 && perm[i] < n), "schwz_trs_create: permutation out of range");
+        SCHWZ_REQUIRE(!perm_out || (perm_out[i] >= 0 && perm_out[i] < n), "schwz_trs_create: permutation out of range");
     }
+    for (int64_t j = 0; j < l_rp[n]; ++j)
+        SCHWZ_REQUIRE(l_col[j] >= 0 && l_col[j] < n, "schwz_trs_create: column index out of range");
+    for (int64_t j = 0; j < u_rp[n]; ++j)
+        SCHWZ_REQUIRE(u_col[j] >= 0 && u_col[j] < n, "schwz_trs_create: column index out of range");
     schwz_trs *t = new schwz_trs();
     t->n = n;
     std::vector<schwz_idx> lo, ll, uo, ul;
@@ -370,6 +466,11 @@ int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, c
     if (perm) {
         UP(t->perm, perm, n, schwz_idx)
     }
+    if (perm_out == perm) {
+        t->perm_out = t->perm;
+    } else {
+        UP(t->perm_out, perm_out, n, schwz_idx)
+    }
     UP(t->l_order, lo.data(), lo.size(), schwz_idx)
     UP(t->l_lvl, ll.data(), ll.size(), schwz_idx)
     UP(t->u_order, uo.data(), uo.size(), schwz_idx)
@@ -382,13 +483,15 @@ int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, c
     SCHWZ_HIP_TRY(hipMalloc((void **)&t->w0, sizeof(double) * (size_t)(n ? n : 1)));
     SCHWZ_HIP_TRY(hipMalloc((void **)&t->w1, sizeof(double) * (size_t)(n ? n : 1)));
     // flag-driven sweeps (one persistent launch per factor) for factors beyond the one-workgroup kernel
-    // whose rows are short enough for one lane each; SCHWZ_TRS_FLAGS=0: the level-by-level plan
+    // whose rows are short enough for one lane each, and for LU factors with longer rows one wave per
+    // row (trs_flag_wave_kernel); SCHWZ_TRS_FLAGS=0: the level-by-level plan
     {
         const char *fenv = std::getenv("SCHWZ_TRS_FLAGS");
         int64_t longest = 0;
         for (int64_t i = 0; i < n; ++i)
             longest = std::max<int64_t>(longest, std::max<int64_t>(l_rp[i + 1] - l_rp[i], u_rp[i + 1] - u_rp[i]));
-        if (!t->fused && !(fenv && fenv[0] == '0') && longest <= 64) {
+        if (!t->fused && !(fenv && fenv[0] == '0') && (longest <= 64 || lu)) {
+            t->wave = longest > 64;
             // the factors in level order (see trs_flag_kernel)
             std::vector<schwz_idx> lpos((size_t)n), upos((size_t)n);
             for (int64_t k = 0; k < n; ++k) {
@@ -425,7 +528,7 @@ int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, c
             for (int64_t k = 0; k < n; ++k) {
                 lsrc[(size_t)k] = perm ? perm[lo[(size_t)k]] : lo[(size_t)k];
                 usrc[(size_t)k] = lpos[(size_t)uo[(size_t)k]];
-                udst[(size_t)k] = perm ? perm[uo[(size_t)k]] : uo[(size_t)k];
+                udst[(size_t)k] = perm_out ? perm_out[uo[(size_t)k]] : uo[(size_t)k];
             }
             if (!rc2) rc2 = upload(lsrc.data(), lsrc.size(), &d), t->fl_src = (schwz_idx *)d;
             if (!rc2) rc2 = upload(usrc.data(), usrc.size(), &d), t->fu_src = (schwz_idx *)d;
@@ -457,8 +560,10 @@ int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, c
             // the query may answer one workgroup per CU too many at some SGPR counts (MI355X_MICROARCH.md,
             // "Correctness boundaries").  No residency at all: the level-by-level launch plan.
             int occ_l = 0, occ_u = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_l, trs_flag_kernel<true>, kBlock, 0) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_u, trs_flag_kernel<false>, kBlock, 0) != hipSuccess) {
+            const void *kl = t->wave ? (const void *)trs_flag_wave_kernel<true> : (const void *)trs_flag_kernel<true>;
+            const void *ku = t->wave ? (const void *)trs_flag_wave_kernel<false> : (const void *)trs_flag_kernel<false>;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_l, kl, kBlock, 0) != hipSuccess ||
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_u, ku, kBlock, 0) != hipSuccess) {
                 (void)hipGetLastError();
                 occ_l = occ_u = 0;
             }
@@ -467,7 +572,8 @@ int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, c
             const char *genv = std::getenv("SCHWZ_TRS_FLAG_GRID");
             int g = genv ? std::atoi(genv) : cus;
             g = std::max(1, std::min(g, std::min(4, per_cu) * cus));
-            t->flag_grid = (int)std::min<int64_t>(g, (n + kBlock - 1) / kBlock);
+            const int64_t rows_per_wg = t->wave ? kBlock / 64 : kBlock;  // a wave per row, or a lane per row
+            t->flag_grid = (int)std::min<int64_t>(g, (n + rows_per_wg - 1) / rows_per_wg);
             if (per_cu < 1) t->flags = false;
         }
     }
@@ -475,9 +581,25 @@ int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, c
     return SCHWZ_OK;
 }
 
+int schwz_trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, const double *l_val,
+                     const schwz_idx *u_rp, const schwz_idx *u_col, const double *u_val,
+                     const schwz_idx *perm, schwz_trs **out)
+{
+    return trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, perm, false, out);
+}
+
+int schwz_trs_create_lu(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, const double *l_val,
+                        const schwz_idx *u_rp, const schwz_idx *u_col, const double *u_val,
+                        const schwz_idx *row_perm, const schwz_idx *col_perm, schwz_trs **out)
+{
+    SCHWZ_REQUIRE(row_perm && col_perm, "schwz_trs_create_lu: both permutations are required");
+    return trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, row_perm, col_perm, true, out);
+}
+
 void schwz_trs_destroy(schwz_trs *t)
 {
     if (!t) return;
+    if (t->perm_out != t->perm) (void)hipFree(t->perm_out);
     void *ptrs[] = {t->l_rp, t->l_col, t->l_val, t->u_rp, t->u_col, t->u_val, t->perm,
                     t->l_order, t->l_lvl, t->u_order, t->u_lvl, t->w0, t->w1, t->f0, t->f1, t->d_err,
                     t->fl_rp, t->fl_col, t->fl_val, t->fu_rp, t->fu_col, t->fu_val, t->fl_src, t->fu_src, t->fu_dst};
@@ -493,9 +615,20 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
     if (t->n == 0) return SCHWZ_OK;
     hipStream_t st = (hipStream_t)stream;
     if (t->fused && t->perm) {
-        hipLaunchKernelGGL(trs_solve_kernel, dim3(1), dim3(kTrsBlock), 0, st, t->n, t->perm, t->l_rp, t->l_col,
+        hipLaunchKernelGGL(trs_solve_kernel, dim3(1), dim3(kTrsBlock), 0, st, t->n, t->perm, t->perm_out, t->l_rp, t->l_col,
                            t->l_val, t->l_order, t->l_lvl, t->l_nlvl, t->u_rp, t->u_col, t->u_val, t->u_order,
                            t->u_lvl, t->u_nlvl, d_b, d_y, t->w0, t->w1);
+        SCHWZ_HIP_TRY(hipGetLastError());
+        return SCHWZ_OK;
+    }
+    if (t->flags && t->wave) {
+        // the same two sweeps, one wave per row (LU factors with long rows)
+        hipLaunchKernelGGL((trs_flag_wave_kernel<true>), dim3(t->flag_grid), dim3(kBlock), 0, st, t->n, t->fl_rp,
+                           t->fl_col, t->fl_val, d_b, t->fl_src, t->f1, t->f0, (double *)nullptr,
+                           (const schwz_idx *)nullptr, t->d_err);
+        hipLaunchKernelGGL((trs_flag_wave_kernel<false>), dim3(t->flag_grid), dim3(kBlock), 0, st, t->n, t->fu_rp,
+                           t->fu_col, t->fu_val, reinterpret_cast<const double *>(t->f1), t->fu_src, t->f0, t->f1, d_y,
+                           t->fu_dst, t->d_err);
         SCHWZ_HIP_TRY(hipGetLastError());
         return SCHWZ_OK;
     }
@@ -556,7 +689,7 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
                                t->u_order, t->u_rp, t->u_col, t->u_val, t->w1, t->w0);
         }
     }
-    hipLaunchKernelGGL(trs_permute_out_kernel, dim3(grid_for(t->n)), dim3(kBlock), 0, st, t->n, t->perm, t->w0, d_y);
+    hipLaunchKernelGGL(trs_permute_out_kernel, dim3(grid_for(t->n)), dim3(kBlock), 0, st, t->n, t->perm_out, t->w0, d_y);
     if (capturing) {
         hipGraph_t graph = nullptr;
         if (hipStreamEndCapture(t->capture_stream, &graph) != hipSuccess || !graph) {

@@ -215,7 +215,8 @@ void SchwarzBase<V, I, M>::initialize()
         break;
     case Settings::local_solver_settings::direct_solver_ginkgo:
     case Settings::local_solver_settings::direct_solver_cholmod:
-        opt.local_solver = SCHWZ_SOLVER_DIRECT;
+        // factorization == "umfpack": pivoted LU (solve.cpp:144-173), else LL^T
+        opt.local_solver = s.factorization == "umfpack" ? SCHWZ_SOLVER_DIRECT_LU : SCHWZ_SOLVER_DIRECT;
         break;
     default:
         SCHWARZ_NOT_IMPLEMENTED;
@@ -237,8 +238,9 @@ void SchwarzBase<V, I, M>::initialize()
     opt.local_max_iters = (int)m.local_max_iters;
     opt.non_symmetric = s.non_symmetric_matrix ? 1 : 0;  // GMRES(restart_iter), solve.cpp:486-520
     opt.restart_iter = (int)s.restart_iter;
-    if (s.non_symmetric_matrix && opt.local_solver != SCHWZ_SOLVER_ITERATIVE)
-        throw ::NotImplemented(__FILE__, __LINE__, "non_symmetric_matrix with a direct local solver (LL^T only)");
+    if (s.non_symmetric_matrix && opt.local_solver == SCHWZ_SOLVER_DIRECT)
+        throw ::NotImplemented(__FILE__, __LINE__,
+                               "non_symmetric_matrix with the LL^T direct local solver (use --local_factorization=umfpack)");
     opt.natural_factor_ordering = s.naturally_ordered_factor;
 
     // ---- Initialize::setup_global_matrix (initialization.cpp:197-272) ----------------------
@@ -610,9 +612,17 @@ void SchwarzBase<V, I, M>::materialize_public_members()
     if (s.local_solver == Settings::local_solver_settings::direct_solver_ginkgo ||
         s.local_solver == Settings::local_solver_settings::direct_solver_cholmod) {
         schwz_idx *l_rp = nullptr, *l_col = nullptr, *u_rp = nullptr, *u_col = nullptr, *perm = nullptr;
+        schwz_idx *col_perm = nullptr;
         double *l_val = nullptr, *u_val = nullptr;
-        SCHWZ_CALL(schwz_cholesky(n, rp.data(), col.data(), val.data(), s.naturally_ordered_factor ? 1 : 0, &l_rp, &l_col,
-                                  &l_val, &u_rp, &u_col, &u_val, &perm));
+        // LU (factorization == "umfpack"): A(perm, col_perm) = L U; local_inv_perm is the inverse of the column
+        // permutation (solve.cpp:321-390: inverse_permute of umf_col_perm)
+        if (s.factorization == "umfpack")
+            SCHWZ_CALL(schwz_lu(n, rp.data(), col.data(), val.data(), s.naturally_ordered_factor ? 1 : 0, &l_rp, &l_col,
+                                &l_val, &u_rp, &u_col, &u_val, &perm, &col_perm));
+        else
+            SCHWZ_CALL(schwz_cholesky(n, rp.data(), col.data(), val.data(), s.naturally_ordered_factor ? 1 : 0, &l_rp,
+                                      &l_col, &l_val, &u_rp, &u_col, &u_val, &perm));
+        const schwz_idx *q = col_perm ? col_perm : perm;
         auto fill = [&](std::shared_ptr<gko::matrix::Csr<V, I>> &dst, const schwz_idx *frp, const schwz_idx *fcol,
                         const double *fval) {
             dst = gko::share(gko::matrix::Csr<V, I>::create(host, gko::dim<2>((gko::size_type)n, (gko::size_type)n),
@@ -629,7 +639,7 @@ void SchwarzBase<V, I, M>::materialize_public_members()
         local_inv_perm = gko::share(gko::matrix::Permutation<I>::create(host, (gko::size_type)n));
         for (int64_t i = 0; i < n; ++i) {
             local_perm->get_permutation()[i] = (I)perm[i];
-            local_inv_perm->get_permutation()[perm[i]] = (I)i;
+            local_inv_perm->get_permutation()[q[i]] = (I)i;
         }
         schwz_free(l_rp);
         schwz_free(l_col);
@@ -638,6 +648,7 @@ void SchwarzBase<V, I, M>::materialize_public_members()
         schwz_free(u_col);
         schwz_free(u_val);
         schwz_free(perm);
+        schwz_free(col_perm);
     }
 }
 

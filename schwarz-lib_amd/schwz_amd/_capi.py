@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("SCHWZ_HIP_LIB") or os.path.join(os.path.dirname(_PKG)
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOT_IMPLEMENTED, ERR_NOT_SPD, ERR_IO, ERR_DIVERGED = 1, 2, 3, 4, 5, 6
 OP_ADD, OP_COPY, OP_DIFF, OP_AVG = 0, 1, 2, 3
-SOLVER_ITERATIVE, SOLVER_DIRECT = 0, 1
+SOLVER_ITERATIVE, SOLVER_DIRECT, SOLVER_DIRECT_LU = 0, 1, 2
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_ILU, PRECOND_ISAI = 0, 1, 2, 3, 4
 
 # every symbol include/schwz_hip.h declares (checked by tests/test_abi.py)
@@ -32,7 +32,7 @@ SYMBOLS = [
     "schwz_pcg_create", "schwz_pcg_create_ex", "schwz_pcg_destroy", "schwz_pcg_flavour", "schwz_pcg_solve",
     "schwz_gmres_create", "schwz_gmres_destroy", "schwz_gmres_solve", "schwz_gmres_last_stats",
     "schwz_profile_begin", "schwz_profile_end", "schwz_profile_kind", "schwz_stream_probe",
-    "schwz_trs_create", "schwz_trs_destroy", "schwz_trs_solve",
+    "schwz_trs_create", "schwz_trs_create_lu", "schwz_trs_destroy", "schwz_trs_solve",
     "schwz_problem_laplacian", "schwz_problem_from_csr", "schwz_problem_from_matrix_market",
     "schwz_problem_destroy", "schwz_problem_size", "schwz_problem_nnz", "schwz_problem_row",
     "schwz_problem_permute",
@@ -43,7 +43,7 @@ SYMBOLS = [
     "schwz_subdomain_add_put_list", "schwz_subdomain_put_list",
     "schwz_subdomain_send_offset", "schwz_subdomain_recv_offset",
     "schwz_problem_from_rows", "schwz_problem_extract_rows",
-    "schwz_cholesky", "schwz_ilu0", "schwz_isai", "schwz_free",
+    "schwz_cholesky", "schwz_lu", "schwz_ilu0", "schwz_isai", "schwz_free",
     "schwz_subdomain_to_device", "schwz_ras_pack", "schwz_ras_unpack", "schwz_ras_pack_f32",
     "schwz_ras_unpack_f32", "schwz_ras_pack_neighbor", "schwz_ras_unpack_neighbor",
     "schwz_ras_early_pack_ok", "schwz_ras_pack_early",
@@ -135,6 +135,7 @@ _sig("schwz_profile_end", i32, [C.POINTER(dbl), C.POINTER(i64)])
 _sig("schwz_profile_kind", i32, [i32, C.POINTER(dbl), C.POINTER(i64)])
 _sig("schwz_stream_probe", i32, [i64, i32, vp, vp, vp])
 _sig("schwz_trs_create", i32, [i64] + [vp] * 7 + [pvp])
+_sig("schwz_trs_create_lu", i32, [i64] + [vp] * 8 + [pvp])
 _sig("schwz_trs_destroy", None, [vp])
 _sig("schwz_trs_solve", i32, [vp, vp, vp, vp])
 _sig("schwz_problem_laplacian", i32, [i32, i64, i64, i64, pvp])
@@ -163,6 +164,7 @@ _sig("schwz_subdomain_add_put_list", i32, [vp, i32, i64, vp])
 _sig("schwz_subdomain_send_offset", i32, [vp, i32, C.POINTER(i64)])
 _sig("schwz_subdomain_recv_offset", i32, [vp, i32, C.POINTER(i64)])
 _sig("schwz_cholesky", i32, [i64, vp, vp, vp, i32] + [pvp] * 7)
+_sig("schwz_lu", i32, [i64, vp, vp, vp, i32] + [pvp] * 8)
 _sig("schwz_ilu0", i32, [i64, vp, vp, vp] + [pvp] * 6)
 _sig("schwz_isai", i32, [i64, vp, vp, vp, i32, pvp])
 _sig("schwz_free", None, [vp])

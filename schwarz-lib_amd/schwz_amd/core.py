@@ -160,6 +160,19 @@ class Trs:
         self.close()
 
 
+class TrsLU(Trs):
+    """y = Q U^-1 L^-1 P b for A(row_perm, col_perm) = L U (schwz_lu factors)."""
+
+    def __init__(self, l_rp, l_col, l_val, u_rp, u_col, u_val, row_perm, col_perm):
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in
+                ((l_rp, IDX), (l_col, IDX), (l_val, np.float64), (u_rp, IDX), (u_col, IDX),
+                 (u_val, np.float64), (row_perm, IDX), (col_perm, IDX))]
+        self.n = len(l_rp) - 1
+        h = C.c_void_p()
+        check(lib.schwz_trs_create_lu(self.n, *[ptr(a) for a in arrs], C.byref(h)))
+        self.h = h
+
+
 def ilu0(rp, col, val):
     """Host ILU(0) standing in for gko::factorization::ParIlu (solve.cpp:506-532)."""
     rp = np.ascontiguousarray(rp, dtype=IDX)
@@ -612,3 +625,31 @@ class Subdomain:
 
     def __del__(self):
         self.close()
+
+
+def lu(rp, col, val, natural=False):
+    """Host sparse LU with threshold partial pivoting standing in for UMFPACK (solve.cpp:144-173):
+    A(row_perm, col_perm) = L U, no row scaling."""
+    rp = np.ascontiguousarray(rp, dtype=IDX)
+    col = np.ascontiguousarray(col, dtype=IDX)
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    n = len(rp) - 1
+    out = [C.c_void_p() for _ in range(8)]
+    check(lib.schwz_lu(n, ptr(rp), ptr(col), ptr(val), int(natural), *[C.byref(o) for o in out]))
+
+    def take(p, cnt, ctype, dtype):
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(max(cnt, 1),))[:cnt].copy()
+        return a.astype(dtype, copy=False)
+
+    l_rp = take(out[0], n + 1, C.c_int32, IDX)
+    u_rp = take(out[3], n + 1, C.c_int32, IDX)
+    lnz, unz = (int(l_rp[-1]), int(u_rp[-1])) if n else (0, 0)
+    res = dict(l_rp=l_rp, l_col=take(out[1], lnz, C.c_int32, IDX),
+               l_val=take(out[2], lnz, C.c_double, np.float64), u_rp=u_rp,
+               u_col=take(out[4], unz, C.c_int32, IDX),
+               u_val=take(out[5], unz, C.c_double, np.float64),
+               row_perm=take(out[6], n, C.c_int32, IDX),
+               col_perm=take(out[7], n, C.c_int32, IDX))
+    for o in out:
+        lib.schwz_free(o)
+    return res

@@ -193,6 +193,20 @@ def _local_solver_code(settings):
                                    "local solver '%s' is not implemented" % ls)
 
 
+def _factor_solver_code(settings):
+    """The local solver code initialize() hands the library: the direct path factors with LL^T, or with
+    the pivoted LU when settings.factorization == "umfpack" (the reference's direct-ginkgo + UMFPACK
+    factors, solve.cpp:144-173).  non_symmetric_matrix needs GMRES or the LU."""
+    code = _local_solver_code(settings)
+    if code == capi.SOLVER_DIRECT and settings.factorization == "umfpack":
+        code = capi.SOLVER_DIRECT_LU
+    if settings.non_symmetric_matrix and code == capi.SOLVER_DIRECT:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "non_symmetric_matrix needs the iterative local solver (GMRES) or "
+                                       "factorization='umfpack'; the direct path is an LL^T factorization")
+    return code
+
+
 def _precond_code(metadata):
     lp = metadata.local_precond
     if lp in ("null", "", None):
@@ -385,12 +399,8 @@ class SolverRAS:
         s, m, be, comm = self.settings, self.metadata, self.backend, self.comm
         self._user_matrix = matrix
         self._user_rhs = None if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
-        solver_code = _local_solver_code(s)
+        solver_code = _factor_solver_code(s)
         precond_code = _precond_code(m)
-        if s.non_symmetric_matrix and solver_code != capi.SOLVER_ITERATIVE:
-            raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
-                                           "non_symmetric_matrix needs the iterative local solver (GMRES); "
-                                           "the direct path is an LL^T factorization")
         if self._distributed_ingest():
             prob = self._ingest_distributed()
         else:
@@ -453,7 +463,8 @@ class SolverRAS:
         """The reference's debug output for executors other than "cuda" (schwarz_base.cpp:252-257, solve.cpp:401-450,
         utils.cpp:94-108): print_matrices -> local_mat_<rank>.csv / int_mat_<rank>.csv (and L_mat / U_mat of the
         direct local solver) as 1-based "row,col,value" lines; write_perm_data -> perm_<rank>.csv / inv_perm_<rank>.csv
-        of the factor ordering; debug_print -> the permutation check."""
+        of the factor ordering (LU: the row permutation and the inverse of the column permutation, the reference's
+        local_perm and local_inv_perm); debug_print -> the permutation check."""
         s = self.settings
 
         def dump(name, me, rp, col, val):
@@ -466,17 +477,22 @@ class SolverRAS:
             if s.print_matrices:
                 dump("local_mat", me, rp, col, val)
                 dump("int_mat", me, *sd.interface_matrix())
-            if solver_code != capi.SOLVER_DIRECT:
+            if solver_code not in (capi.SOLVER_DIRECT, capi.SOLVER_DIRECT_LU):
                 continue
-            f = core.cholesky(rp, col, val, s.naturally_ordered_factor)
+            if solver_code == capi.SOLVER_DIRECT_LU:
+                f = core.lu(rp, col, val, s.naturally_ordered_factor)
+                perm, q = np.asarray(f["row_perm"]), np.asarray(f["col_perm"])
+            else:
+                f = core.cholesky(rp, col, val, s.naturally_ordered_factor)
+                perm = q = np.asarray(f["perm"])
             if s.print_matrices:
                 dump("U_mat", me, f["u_rp"], f["u_col"], f["u_val"])
                 dump("L_mat", me, f["l_rp"], f["l_col"], f["l_val"])
-            perm = np.asarray(f["perm"])
-            inv = np.empty_like(perm)
-            inv[perm] = np.arange(len(perm), dtype=perm.dtype)
+            inv = np.empty_like(q)
+            inv[q] = np.arange(len(q), dtype=q.dtype)
             if s.debug_print:
-                ok = np.array_equal(np.sort(perm), np.arange(len(perm)))
+                ok = np.array_equal(np.sort(perm), np.arange(len(perm))) and \
+                    np.array_equal(np.sort(inv), np.arange(len(inv)))
                 self._print(" Rank %d Permutation is %s\n Rank %d Inverse Permutation is %s" %
                             (me, "correct" if ok else "incorrect", me, "correct" if ok else "incorrect"))
             if s.write_perm_data:
