@@ -157,6 +157,14 @@ int schwz_pcg_create(const schwz_csr *A, int precond, schwz_pcg **out);
 /* the same with the block size of SCHWZ_PRECOND_BLOCK_JACOBI (metadata.precond_max_block_size,
  * 1..32) */
 int schwz_pcg_create_ex(const schwz_csr *A, int precond, int block_size, schwz_pcg **out);
+/* ILU / ISAI with the ParILU options of the reference's ParIlu (source/solve.cpp:506-532, :616-638):
+ * par_ilu_sweeps > 0 computes the factors by that many ParILU sweeps on the GPU (schwz_parilu) instead of
+ * the exact host ILU(0) (ilu and isai); trisolve_sweeps > 0 applies each factor by that many Jacobi passes
+ * (schwz_trs_create_sweeps) instead of exact triangular solves (ilu only).  Both 0: schwz_pcg_create_ex.
+ * Negative counts: SCHWZ_ERR_INVALID; a nonzero count with another preconditioner, or trisolve_sweeps
+ * with isai: SCHWZ_ERR_NOT_IMPLEMENTED. */
+int schwz_pcg_create_ilu(const schwz_csr *A, int precond, int par_ilu_sweeps, int trisolve_sweeps,
+                         schwz_pcg **out);
 void schwz_pcg_destroy(schwz_pcg *s);
 /* how the last solve iterated (bench.py needs it to name and price its launches): bits 0-1: 0 = q = A p
  * stored, 1 = q-free, three launches per iteration, 2 = q-free with the direction update fused into the
@@ -176,6 +184,9 @@ int schwz_pcg_solve(schwz_pcg *s, const double *d_b, double *d_x, double rtol,
  * stop test saw (the rotated right-hand side inside a cycle). */
 typedef struct schwz_gmres schwz_gmres;
 int schwz_gmres_create(const schwz_csr *A, int precond, int block_size, int restart, schwz_gmres **out);
+/* the same with the ParILU options of schwz_pcg_create_ilu (both 0: schwz_gmres_create) */
+int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int restart, int par_ilu_sweeps,
+                          int trisolve_sweeps, schwz_gmres **out);
 void schwz_gmres_destroy(schwz_gmres *s);
 int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rtol, int max_iters,
                       int *h_iters, double *h_resnorm, schwz_stream stream);
@@ -226,8 +237,38 @@ int schwz_trs_create_lu(int64_t n, const schwz_idx *h_l_rp, const schwz_idx *h_l
                         const schwz_idx *h_u_col, const double *h_u_val,
                         const schwz_idx *h_row_perm, const schwz_idx *h_col_perm,
                         schwz_trs **out);
+/* The Jacobi-sweep mode (the triangular solves Ginkgo's ParIlu preconditioner can run instead of exact sweeps,
+ * source/solve.cpp:506-532): each factor T = D + T_s is applied by `sweeps` (>= 1) Jacobi passes,
+ * x_0 = D^-1 b, x_{m+1} = D^-1 (b - T_s x_m), i.e. y = sum_{m=0..k} (-D^-1 T_s)^m D^-1 b -- exact once
+ * sweeps >= levels - 1 of the factor.  No permutation; same factor layout as schwz_trs_create (any nonzero
+ * diagonals).  One launch per pass, no level plan, no waits between workgroups (csrc/parilu.hip). */
+int schwz_trs_create_sweeps(int64_t n, const schwz_idx *h_l_rp, const schwz_idx *h_l_col,
+                            const double *h_l_val, const schwz_idx *h_u_rp,
+                            const schwz_idx *h_u_col, const double *h_u_val, int sweeps,
+                            schwz_trs **out);
+/* passes per factor of a triangular-solve object in the sweep mode; 0: exact solves */
+int schwz_trs_sweeps(const schwz_trs *t);
 void schwz_trs_destroy(schwz_trs *t);
 int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream stream);
+
+/* ParILU on the GPU: gko::factorization::ParIlu (source/solve.cpp:506-532, and the factors of
+ * Ilu<LowerIsai, UpperIsai>, :616-638) as `sweeps` (>= 1) SYNCHRONOUS fixed-point sweeps on the ILU(0)
+ * pattern of A (Ginkgo sweeps asynchronously in place; the synchronous form is reproducible).  Start:
+ * L0 = strict lower part of A with a unit diagonal, U0 = upper part of A; one sweep sets
+ *   l_ij = (a_ij - sum_{k<j} l_ik u_kj) / u_jj  (i > j),   u_ij = a_ij - sum_{k<i} l_ik u_kj  (i <= j)
+ * from the previous iterate.  Once sweeps reaches the longest dependency chain among the entries the
+ * factors are those of schwz_ilu0 (up to rounding).  Same layout as schwz_ilu0: L unit lower with the 1
+ * LAST in each row, U upper with its diagonal FIRST.  A's columns must be sorted with the diagonal
+ * present.  A zero or non-finite u_ii after the last sweep returns SCHWZ_ERR_NOT_SPD.
+ * schwz_parilu reads A in HBM (only its pattern comes back, for the symbolic pass); the patterns are
+ * malloc'd host arrays (schwz_free), the values device arrays (schwz_device_free).  Synchronous.
+ * schwz_parilu_host: schwz_ilu0's signature plus `sweeps`, runs on the GPU, all outputs malloc'd. */
+int schwz_parilu(const schwz_csr *A, int sweeps, schwz_idx **l_rp, schwz_idx **l_col, double **d_l_val,
+                 schwz_idx **u_rp, schwz_idx **u_col, double **d_u_val);
+int schwz_parilu_host(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, const double *h_val,
+                      int sweeps, schwz_idx **l_rp, schwz_idx **l_col, double **l_val, schwz_idx **u_rp,
+                      schwz_idx **u_col, double **u_val);
+void schwz_device_free(void *d_ptr);
 
 /* ------------------------------------------------------------------------ */
 /* 2. Host-side setup (no GPU needed)                                        */
@@ -378,6 +419,11 @@ typedef struct {
     int32_t precond_block_size; /* metadata.precond_max_block_size (block-jacobi) */
     int32_t non_symmetric;   /* settings.non_symmetric_matrix: GMRES instead of CG */
     int32_t restart_iter;    /* settings.restart_iter (GMRES krylov_dim), >= 1 */
+    /* ParILU options of the iterative local solver (schwz_pcg_create_ilu); 0 = exact ILU(0) / exact
+     * triangular solves.  Nonzero only with SCHWZ_SOLVER_ITERATIVE and precond ilu (both) or isai
+     * (par_ilu_sweeps), else SCHWZ_ERR_NOT_IMPLEMENTED; negative: SCHWZ_ERR_INVALID. */
+    int32_t par_ilu_sweeps;
+    int32_t trisolve_sweeps;
 } schwz_solver_options;
 
 /* Upload matrices / index lists, allocate x~=[interior|overlap|halo] (zero,

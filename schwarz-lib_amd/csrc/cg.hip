@@ -568,17 +568,28 @@ static int pcg_setup_general(schwz_pcg *s)
     const CsrView &A = s->A->v;
     const int64_t n = s->n;
     std::vector<schwz_idx> rp((size_t)n + 1), col((size_t)A.nnz);
-    std::vector<double> val((size_t)A.nnz);
+    // (ParILU reads the values in HBM: only the pattern comes back)
+    std::vector<double> val(s->par_ilu_sweeps > 0 ? 0 : (size_t)A.nnz);
     SCHWZ_HIP_TRY(hipMemcpy(rp.data(), A.rp, rp.size() * sizeof(schwz_idx), hipMemcpyDeviceToHost));
     if (A.nnz) {
         SCHWZ_HIP_TRY(hipMemcpy(col.data(), A.col, col.size() * sizeof(schwz_idx), hipMemcpyDeviceToHost));
-        SCHWZ_HIP_TRY(hipMemcpy(val.data(), A.val, val.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (!val.empty())
+            SCHWZ_HIP_TRY(hipMemcpy(val.data(), A.val, val.size() * sizeof(double), hipMemcpyDeviceToHost));
     }
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->z, (size_t)(n ? n : 1) * sizeof(double)));
     if (s->precond == SCHWZ_PRECOND_ILU || s->precond == SCHWZ_PRECOND_ISAI) {
         schwz_idx *l_rp, *l_col, *u_rp, *u_col;
         double *l_val, *u_val;
-        int rc = schwz_ilu0(n, rp.data(), col.data(), val.data(), &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val);
+        int rc;
+        if (s->par_ilu_sweeps > 0) {
+            // ParILU sweeps on the GPU over the matrix in HBM (csrc/parilu.hip); the factors come back once
+            StageTimer timer_pi("pcg_create: ParILU factors");
+            rc = parilu_host_factors(n, rp.data(), col.data(), A.val, s->par_ilu_sweeps, &l_rp, &l_col, &l_val, &u_rp,
+                                     &u_col, &u_val);
+        } else {
+            StageTimer timer_ilu("pcg_create: host ILU(0)");
+            rc = schwz_ilu0(n, rp.data(), col.data(), val.data(), &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val);
+        }
         if (rc) return rc;
         if (s->precond == SCHWZ_PRECOND_ISAI) {
             // Ilu<LowerIsai, UpperIsai> (solve.cpp:616-638): z = W_U (W_L r), two CSR products on
@@ -594,7 +605,11 @@ static int pcg_setup_general(schwz_pcg *s)
             }
             schwz_free(wl);
             schwz_free(wu);
+        } else if (s->trisolve_sweeps > 0) {
+            StageTimer timer_trs("pcg_create: Jacobi-sweep triangular solves");
+            rc = schwz_trs_create_sweeps(n, l_rp, l_col, l_val, u_rp, u_col, u_val, s->trisolve_sweeps, &s->ilu);
         } else {
+            StageTimer timer_trs("pcg_create: triangular-solve analysis");
             rc = schwz_trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, nullptr, &s->ilu);
         }
         schwz_free(l_rp);
@@ -803,6 +818,35 @@ static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
 
 int schwz_pcg_create_ex(const schwz_csr *A, int precond, int block_size, schwz_pcg **out)
 {
+    return pcg_create_impl(A, precond, block_size, 0, 0, out);
+}
+
+int schwz_pcg_create_ilu(const schwz_csr *A, int precond, int par_ilu_sweeps, int trisolve_sweeps, schwz_pcg **out)
+{
+    const int rc = pcg_check_ilu_sweeps(precond, par_ilu_sweeps, trisolve_sweeps);
+    if (rc) return rc;
+    return pcg_create_impl(A, precond, 1, par_ilu_sweeps, trisolve_sweeps, out);
+}
+
+}  // extern "C"
+
+int schwz::pcg_check_ilu_sweeps(int precond, int par_ilu_sweeps, int trisolve_sweeps)
+{
+    SCHWZ_REQUIRE(par_ilu_sweeps >= 0 && trisolve_sweeps >= 0, "par_ilu_sweeps / trisolve_sweeps must be >= 0");
+    if (par_ilu_sweeps > 0 && precond != SCHWZ_PRECOND_ILU && precond != SCHWZ_PRECOND_ISAI) {
+        set_error("par_ilu_sweeps applies to the ilu and isai preconditioners only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (trisolve_sweeps > 0 && precond != SCHWZ_PRECOND_ILU) {
+        set_error("trisolve_sweeps applies to the ilu preconditioner only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    return SCHWZ_OK;
+}
+
+int schwz::pcg_create_impl(const schwz_csr *A, int precond, int block_size, int par_ilu_sweeps, int trisolve_sweeps,
+                           schwz_pcg **out)
+{
     StageTimer timer_all("pcg_create (diagonal, preconditioner data, vectors)");
     SCHWZ_REQUIRE(A && out, "schwz_pcg_create: null argument");
     SCHWZ_REQUIRE(A->v.nrows == A->v.ncols, "schwz_pcg_create: matrix not square");
@@ -814,6 +858,8 @@ int schwz_pcg_create_ex(const schwz_csr *A, int precond, int block_size, schwz_p
     s->A = A;
     s->precond = precond;
     s->block_size = block_size;
+    s->par_ilu_sweeps = par_ilu_sweeps;
+    s->trisolve_sweeps = trisolve_sweeps;
     s->n = A->v.nrows;
     const int rc = pcg_build(s, A, precond);
     if (rc) {
@@ -823,6 +869,8 @@ int schwz_pcg_create_ex(const schwz_csr *A, int precond, int block_size, schwz_p
     *out = s;
     return SCHWZ_OK;
 }
+
+extern "C" {
 
 void schwz_pcg_destroy(schwz_pcg *s)
 {

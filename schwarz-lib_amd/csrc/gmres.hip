@@ -203,6 +203,14 @@ extern "C" {
 
 int schwz_gmres_create(const schwz_csr *A, int precond, int block_size, int restart, schwz_gmres **out)
 {
+    return schwz_gmres_create_ex(A, precond, block_size, restart, 0, 0, out);
+}
+
+int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int restart, int par_ilu_sweeps,
+                          int trisolve_sweeps, schwz_gmres **out)
+{
+    int rc = pcg_check_ilu_sweeps(precond, par_ilu_sweeps, trisolve_sweeps);
+    if (rc) return rc;
     SCHWZ_REQUIRE(A && out, "schwz_gmres_create: null argument");
     SCHWZ_REQUIRE(A->v.nrows == A->v.ncols, "schwz_gmres_create: matrix must be square");
     SCHWZ_REQUIRE(restart >= 1, "schwz_gmres_create: restart (krylov_dim) must be >= 1");
@@ -212,7 +220,9 @@ int schwz_gmres_create(const schwz_csr *A, int precond, int block_size, int rest
     s->n = A->v.nrows;
     s->m = restart;
     s->ldv = (s->n + 1) & ~int64_t(1);  // 16-byte aligned columns
-    int rc = schwz_pcg_create_ex(A, precond, block_size, &s->pre);
+    rc = par_ilu_sweeps || trisolve_sweeps
+             ? pcg_create_impl(A, precond, block_size, par_ilu_sweeps, trisolve_sweeps, &s->pre)
+             : schwz_pcg_create_ex(A, precond, block_size, &s->pre);
     if (rc) {
         delete s;
         return rc;

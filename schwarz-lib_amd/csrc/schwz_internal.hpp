@@ -456,6 +456,11 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
 int precond_apply(schwz_pcg *s, const double *in, double *out, hipStream_t st);
 int pcg_last_stats(schwz_pcg *s, int *h_iters, double *h_resnorm);  // device sync + state copy
 int pcg_take_trs_error(schwz_pcg *s);
+// the checks of schwz_pcg_create_ilu on the ParILU options (SCHWZ_OK, SCHWZ_ERR_INVALID or
+// SCHWZ_ERR_NOT_IMPLEMENTED, message set)
+int pcg_check_ilu_sweeps(int precond, int par_ilu_sweeps, int trisolve_sweeps);
+int pcg_create_impl(const schwz_csr *A, int precond, int block_size, int par_ilu_sweeps, int trisolve_sweeps,
+                    schwz_pcg **out);
 int pcg_finish_lazy(schwz_pcg *s);  // the postponed residual update / state advance of the last solve, if any  // ILU(0) sweeps: trs_take_error of the factor solves
 }  // namespace schwz
 
@@ -501,6 +506,8 @@ struct schwz_pcg {
     double *d_blk_inv = nullptr;    // unique inverse blocks, [nunique][bs][bs] (a k x k inverse in the top left corner)
     schwz_idx *d_row_blk = nullptr, *d_blk_ptr = nullptr;  // detected blocks of different sizes: block of a row, boundaries
     schwz_trs *ilu = nullptr;       // ILU(0): level-scheduled L and U sweeps
+    int par_ilu_sweeps = 0;         // ILU / ISAI factors from this many ParILU sweeps (0: exact host ILU(0))
+    int trisolve_sweeps = 0;        // ILU applied by this many Jacobi passes per factor (0: exact solves)
     schwz_csr *isai_l = nullptr, *isai_u = nullptr;  // ISAI: approximate inverses of L and U
     double *isai_tmp = nullptr;
     schwz::DiagView diag;
@@ -602,7 +609,23 @@ struct schwz_trs {
     int flag_grid = 0;
     // LU factors (schwz_trs_create_lu) with rows beyond one lane each: trs_flag_wave_kernel, one wave per row
     bool wave = false;
+    // Jacobi-sweep mode (schwz_trs_create_sweeps, csrc/parilu.hip): `sweeps` passes per factor over the strict
+    // parts (CSR) with the reciprocal diagonals; w0, w1, w2 double-buffer the passes.  0: exact solves.
+    int sweeps = 0;
+    schwz_idx *js_l_rp = nullptr, *js_l_col = nullptr, *js_u_rp = nullptr, *js_u_col = nullptr;
+    double *js_l_val = nullptr, *js_u_val = nullptr, *js_l_dinv = nullptr, *js_u_dinv = nullptr;
+    double *w2 = nullptr;
 };
+
+namespace schwz {
+// y = U^-1 L^-1 b in the Jacobi-sweep mode of schwz_trs (csrc/parilu.hip)
+int trs_sweeps_solve(schwz_trs *t, const double *b, double *y, hipStream_t st);
+// ParILU factors of the matrix whose pattern h_rp / h_col is and whose values d_val hold (HBM), with the values
+// copied back to malloc'd host arrays (csrc/parilu.hip)
+int parilu_host_factors(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, const double *d_val, int sweeps,
+                        schwz_idx **l_rp, schwz_idx **l_col, double **l_val, schwz_idx **u_rp, schwz_idx **u_col,
+                        double **u_val);
+}  // namespace schwz
 
 // host-side global problem (explicit CSR or analytic stencil)
 struct schwz_problem {

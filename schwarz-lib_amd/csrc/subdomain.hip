@@ -62,6 +62,16 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
     SCHWZ_REQUIRE(opt->local_solver == SCHWZ_SOLVER_ITERATIVE || opt->local_solver == SCHWZ_SOLVER_DIRECT ||
                       opt->local_solver == SCHWZ_SOLVER_DIRECT_LU,
                   "schwz_subdomain_to_device: unknown local solver");
+    SCHWZ_REQUIRE(opt->par_ilu_sweeps >= 0 && opt->trisolve_sweeps >= 0,
+                  "schwz_subdomain_to_device: par_ilu_sweeps / trisolve_sweeps must be >= 0");
+    if ((opt->par_ilu_sweeps || opt->trisolve_sweeps) && opt->local_solver != SCHWZ_SOLVER_ITERATIVE) {
+        set_error("schwz_subdomain_to_device: par_ilu_sweeps / trisolve_sweeps apply to the iterative local solver only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (opt->local_solver == SCHWZ_SOLVER_ITERATIVE) {
+        const int rc_sw = pcg_check_ilu_sweeps(opt->precond, opt->par_ilu_sweeps, opt->trisolve_sweeps);
+        if (rc_sw) return rc_sw;
+    }
     if (schwz_device_count() < 1) {
         set_error("schwz_subdomain_to_device: no HIP device visible (there is no CPU fallback)");
         return SCHWZ_ERR_HIP;
@@ -110,13 +120,16 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
     SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->ev_scalar, hipEventDisableTiming));
     if (opt->local_solver == SCHWZ_SOLVER_ITERATIVE) {
         const int bsz = opt->precond_block_size < 1 ? 1 : opt->precond_block_size;
+        const bool sweeps = opt->par_ilu_sweeps || opt->trisolve_sweeps;
         if (opt->non_symmetric) {
             // solve.cpp:486-520: GMRES(restart_iter); the preconditioner objects are the CG's
-            if ((rc = schwz_gmres_create(sd->A, opt->precond, bsz, opt->restart_iter < 1 ? 1 : opt->restart_iter,
-                                         &sd->gmres)))
+            if ((rc = schwz_gmres_create_ex(sd->A, opt->precond, bsz, opt->restart_iter < 1 ? 1 : opt->restart_iter,
+                                            opt->par_ilu_sweeps, opt->trisolve_sweeps, &sd->gmres)))
                 return rc;
         } else {
-            if ((rc = schwz_pcg_create_ex(sd->A, opt->precond, bsz, &sd->cg))) return rc;
+            if ((rc = sweeps ? schwz_pcg_create_ilu(sd->A, opt->precond, opt->par_ilu_sweeps, opt->trisolve_sweeps, &sd->cg)
+                             : schwz_pcg_create_ex(sd->A, opt->precond, bsz, &sd->cg)))
+                return rc;
             sd->cg->variant = opt->spmv_variant;
             // Rows the neighbours wait for (the put lists: interior rows next to the subdomain boundary) become
             // final ahead of the rest of the solution, so that the next halo exchange can start beside the tail

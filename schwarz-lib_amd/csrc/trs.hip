@@ -602,7 +602,9 @@ void schwz_trs_destroy(schwz_trs *t)
     if (t->perm_out != t->perm) (void)hipFree(t->perm_out);
     void *ptrs[] = {t->l_rp, t->l_col, t->l_val, t->u_rp, t->u_col, t->u_val, t->perm,
                     t->l_order, t->l_lvl, t->u_order, t->u_lvl, t->w0, t->w1, t->f0, t->f1, t->d_err,
-                    t->fl_rp, t->fl_col, t->fl_val, t->fu_rp, t->fu_col, t->fu_val, t->fl_src, t->fu_src, t->fu_dst};
+                    t->fl_rp, t->fl_col, t->fl_val, t->fu_rp, t->fu_col, t->fu_val, t->fl_src, t->fu_src, t->fu_dst,
+                    t->w2, t->js_l_rp, t->js_l_col, t->js_l_val, t->js_l_dinv, t->js_u_rp, t->js_u_col, t->js_u_val,
+                    t->js_u_dinv};
     for (void *p : ptrs) (void)hipFree(p);
     for (auto &g : t->graphs) (void)hipGraphExecDestroy(g.exec);
     if (t->capture_stream) (void)hipStreamDestroy(t->capture_stream);
@@ -614,6 +616,7 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
     SCHWZ_REQUIRE(t && d_b && d_y, "schwz_trs_solve: null argument");
     if (t->n == 0) return SCHWZ_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (t->sweeps > 0) return trs_sweeps_solve(t, d_b, d_y, st);
     if (t->fused && t->perm) {
         hipLaunchKernelGGL(trs_solve_kernel, dim3(1), dim3(kTrsBlock), 0, st, t->n, t->perm, t->perm_out, t->l_rp, t->l_col,
                            t->l_val, t->l_order, t->l_lvl, t->l_nlvl, t->u_rp, t->u_col, t->u_val, t->u_order,

@@ -116,6 +116,11 @@ struct Metadata {
     IndexType updated_max_iters = -1;
     std::string local_precond = "null";
     unsigned int precond_max_block_size = 16;
+    // extensions: ParILU options of the ilu / isai local preconditioner (schwz_solver_options): factors from
+    // par_ilu_sweeps ParILU sweeps on the GPU (ilu, isai), factors applied by trisolve_sweeps Jacobi sweeps
+    // (ilu); 0 = the exact ILU(0) and exact triangular solves
+    int par_ilu_sweeps = 0;
+    int trisolve_sweeps = 0;
     ValueType current_residual_norm = -1.0;
     ValueType min_residual_norm = -1.0;
 

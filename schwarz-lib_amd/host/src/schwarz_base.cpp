@@ -242,6 +242,16 @@ void SchwarzBase<V, I, M>::initialize()
         throw ::NotImplemented(__FILE__, __LINE__,
                                "non_symmetric_matrix with the LL^T direct local solver (use --local_factorization=umfpack)");
     opt.natural_factor_ordering = s.naturally_ordered_factor;
+    if (m.par_ilu_sweeps < 0 || m.trisolve_sweeps < 0)
+        throw ::BadDimension(__FILE__, __LINE__, "initialize", "par_ilu_sweeps / trisolve_sweeps must be >= 0");
+    if ((m.par_ilu_sweeps || m.trisolve_sweeps) && opt.local_solver != SCHWZ_SOLVER_ITERATIVE)
+        throw ::NotImplemented(__FILE__, __LINE__, "par_ilu_sweeps / trisolve_sweeps with a direct local solver");
+    if (m.par_ilu_sweeps && opt.precond != SCHWZ_PRECOND_ILU && opt.precond != SCHWZ_PRECOND_ISAI)
+        throw ::NotImplemented(__FILE__, __LINE__, "par_ilu_sweeps with local_precond '" + m.local_precond + "'");
+    if (m.trisolve_sweeps && opt.precond != SCHWZ_PRECOND_ILU)
+        throw ::NotImplemented(__FILE__, __LINE__, "trisolve_sweeps with local_precond '" + m.local_precond + "'");
+    opt.par_ilu_sweeps = m.par_ilu_sweeps;
+    opt.trisolve_sweeps = m.trisolve_sweeps;
 
     // ---- Initialize::setup_global_matrix (initialization.cpp:197-272) ----------------------
     // extension: "--matrix_filename=poisson3d:NX[xNYxNZ]" or SCHWZ_LAPLACIAN_DIM=3 select the 3-D

@@ -33,6 +33,8 @@ SYMBOLS = [
     "schwz_gmres_create", "schwz_gmres_destroy", "schwz_gmres_solve", "schwz_gmres_last_stats",
     "schwz_profile_begin", "schwz_profile_end", "schwz_profile_kind", "schwz_stream_probe",
     "schwz_trs_create", "schwz_trs_create_lu", "schwz_trs_destroy", "schwz_trs_solve",
+    "schwz_trs_create_sweeps", "schwz_trs_sweeps", "schwz_parilu", "schwz_parilu_host", "schwz_device_free",
+    "schwz_pcg_create_ilu", "schwz_gmres_create_ex",
     "schwz_problem_laplacian", "schwz_problem_from_csr", "schwz_problem_from_matrix_market",
     "schwz_problem_destroy", "schwz_problem_size", "schwz_problem_nnz", "schwz_problem_row",
     "schwz_problem_permute",
@@ -83,6 +85,8 @@ class SolverOptions(C.Structure):
         ("precond_block_size", C.c_int32),
         ("non_symmetric", C.c_int32),
         ("restart_iter", C.c_int32),
+        ("par_ilu_sweeps", C.c_int32),
+        ("trisolve_sweeps", C.c_int32),
     ]
 
 
@@ -138,6 +142,13 @@ _sig("schwz_trs_create", i32, [i64] + [vp] * 7 + [pvp])
 _sig("schwz_trs_create_lu", i32, [i64] + [vp] * 8 + [pvp])
 _sig("schwz_trs_destroy", None, [vp])
 _sig("schwz_trs_solve", i32, [vp, vp, vp, vp])
+_sig("schwz_trs_create_sweeps", i32, [i64] + [vp] * 6 + [i32, pvp])
+_sig("schwz_trs_sweeps", i32, [vp])
+_sig("schwz_parilu", i32, [vp, i32] + [pvp] * 6)
+_sig("schwz_parilu_host", i32, [i64, vp, vp, vp, i32] + [pvp] * 6)
+_sig("schwz_device_free", None, [vp])
+_sig("schwz_pcg_create_ilu", i32, [vp, i32, i32, i32, pvp])
+_sig("schwz_gmres_create_ex", i32, [vp, i32, i32, i32, i32, i32, pvp])
 _sig("schwz_problem_laplacian", i32, [i32, i64, i64, i64, pvp])
 _sig("schwz_problem_from_csr", i32, [i64, vp, vp, vp, pvp])
 _sig("schwz_problem_from_rows", i32, [i64, i64, vp, vp, vp, vp, pvp])

@@ -81,10 +81,14 @@ class Csr:
 class Pcg:
     """Device-resident preconditioned CG (gko::solver::Cg + stop::Combined)."""
 
-    def __init__(self, csr, precond=capi.PRECOND_NONE, block_size=1):
+    def __init__(self, csr, precond=capi.PRECOND_NONE, block_size=1, par_ilu_sweeps=0, trisolve_sweeps=0):
         self.csr = csr
         h = C.c_void_p()
-        check(lib.schwz_pcg_create_ex(csr.h, precond, block_size, C.byref(h)))
+        if par_ilu_sweeps or trisolve_sweeps:
+            # ilu / isai with ParILU factors and / or Jacobi-sweep solves (schwz_pcg_create_ilu)
+            check(lib.schwz_pcg_create_ilu(csr.h, precond, int(par_ilu_sweeps), int(trisolve_sweeps), C.byref(h)))
+        else:
+            check(lib.schwz_pcg_create_ex(csr.h, precond, block_size, C.byref(h)))
         self.h = h
 
     def solve(self, d_b, d_x, rtol, max_iters, stream=0, want_stats=True):
@@ -112,10 +116,15 @@ class Gmres:
     """Device-resident restarted GMRES, right preconditioned (gko::solver::Gmres with
     krylov_dim = restart; solve.cpp:486-520)."""
 
-    def __init__(self, csr, precond=capi.PRECOND_NONE, block_size=1, restart=1):
+    def __init__(self, csr, precond=capi.PRECOND_NONE, block_size=1, restart=1, par_ilu_sweeps=0,
+                 trisolve_sweeps=0):
         self.csr = csr
         h = C.c_void_p()
-        check(lib.schwz_gmres_create(csr.h, precond, block_size, restart, C.byref(h)))
+        if par_ilu_sweeps or trisolve_sweeps:
+            check(lib.schwz_gmres_create_ex(csr.h, precond, block_size, restart, int(par_ilu_sweeps),
+                                            int(trisolve_sweeps), C.byref(h)))
+        else:
+            check(lib.schwz_gmres_create(csr.h, precond, block_size, restart, C.byref(h)))
         self.h = h
 
     def solve(self, d_b, d_x, rtol, max_iters, stream=0, want_stats=True):
@@ -173,14 +182,42 @@ class TrsLU(Trs):
         self.h = h
 
 
+class TrsSweeps(Trs):
+    """y = U^-1 L^-1 b with each factor applied by `sweeps` Jacobi passes: x_0 = D^-1 b,
+    x_{m+1} = D^-1 (b - T_s x_m) (schwz_trs_create_sweeps)."""
+
+    def __init__(self, l_rp, l_col, l_val, u_rp, u_col, u_val, sweeps):
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in
+                ((l_rp, IDX), (l_col, IDX), (l_val, np.float64), (u_rp, IDX), (u_col, IDX),
+                 (u_val, np.float64))]
+        self.n = len(l_rp) - 1
+        h = C.c_void_p()
+        check(lib.schwz_trs_create_sweeps(self.n, *[ptr(a) for a in arrs], int(sweeps), C.byref(h)))
+        self.h = h
+
+    @property
+    def sweeps(self):
+        return int(lib.schwz_trs_sweeps(self.h))
+
+
 def ilu0(rp, col, val):
     """Host ILU(0) standing in for gko::factorization::ParIlu (solve.cpp:506-532)."""
+    return _ilu_factors(lib.schwz_ilu0, rp, col, val)
+
+
+def parilu(rp, col, val, sweeps):
+    """ILU(0)-pattern factors from `sweeps` synchronous ParILU sweeps on the GPU
+    (gko::factorization::ParIlu, solve.cpp:506-532); same layout as ilu0."""
+    return _ilu_factors(lambda n, *a: lib.schwz_parilu_host(n, *a[:3], int(sweeps), *a[3:]), rp, col, val)
+
+
+def _ilu_factors(fn, rp, col, val):
     rp = np.ascontiguousarray(rp, dtype=IDX)
     col = np.ascontiguousarray(col, dtype=IDX)
     val = np.ascontiguousarray(val, dtype=np.float64)
     n = len(rp) - 1
     out = [C.c_void_p() for _ in range(6)]
-    check(lib.schwz_ilu0(n, ptr(rp), ptr(col), ptr(val), *[C.byref(o) for o in out]))
+    check(fn(n, ptr(rp), ptr(col), ptr(val), *[C.byref(o) for o in out]))
 
     def take(p, cnt, ctype, dtype):
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(max(cnt, 1),))[:cnt].copy().astype(dtype)
@@ -512,12 +549,13 @@ class Subdomain:
     def to_device(self, local_rhs, local_solver=capi.SOLVER_ITERATIVE,
                   precond=capi.PRECOND_NONE, local_tol=1e-12, local_max_iters=-1,
                   natural_factor_ordering=False, spmv_variant=0, precond_block_size=1,
-                  non_symmetric=False, restart_iter=1):
+                  non_symmetric=False, restart_iter=1, par_ilu_sweeps=0, trisolve_sweeps=0):
         local_rhs = np.ascontiguousarray(local_rhs, dtype=np.float64)
         assert len(local_rhs) == self.local_size_x
         opt = capi.SolverOptions(local_solver, precond, local_tol, local_max_iters,
                                  int(natural_factor_ordering), spmv_variant, int(precond_block_size),
-                                 int(bool(non_symmetric)), int(restart_iter))
+                                 int(bool(non_symmetric)), int(restart_iter), int(par_ilu_sweeps),
+                                 int(trisolve_sweeps))
         check(lib.schwz_subdomain_to_device(self.h, ptr(local_rhs), C.byref(opt)))
         self.on_device = True
 

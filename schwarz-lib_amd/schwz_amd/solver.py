@@ -117,6 +117,12 @@ class Metadata:
     updated_max_iters: int = -1
     local_precond: str = "null"
     precond_max_block_size: int = 16
+    # extensions (no field of the reference's Metadata): the ParILU options of the ilu / isai local
+    # preconditioner.  par_ilu_sweeps > 0: factors from that many ParILU sweeps on the GPU instead of the exact
+    # ILU(0) (ilu, isai); trisolve_sweeps > 0: each factor applied by that many Jacobi sweeps instead of exact
+    # triangular solves (ilu).  0 = today's exact paths.
+    par_ilu_sweeps: int = 0
+    trisolve_sweeps: int = 0
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
@@ -193,11 +199,23 @@ def _local_solver_code(settings):
                                    "local solver '%s' is not implemented" % ls)
 
 
-def _factor_solver_code(settings):
+def _sweep_counts(metadata):
+    """(par_ilu_sweeps, trisolve_sweeps) of the metadata; negative counts are refused."""
+    par, tri = int(getattr(metadata, "par_ilu_sweeps", 0)), int(getattr(metadata, "trisolve_sweeps", 0))
+    if par < 0 or tri < 0:
+        raise capi.SchwzError(capi.ERR_INVALID, "par_ilu_sweeps / trisolve_sweeps must be >= 0")
+    return par, tri
+
+
+def _factor_solver_code(settings, metadata=None):
     """The local solver code initialize() hands the library: the direct path factors with LL^T, or with
     the pivoted LU when settings.factorization == "umfpack" (the reference's direct-ginkgo + UMFPACK
-    factors, solve.cpp:144-173).  non_symmetric_matrix needs GMRES or the LU."""
+    factors, solve.cpp:144-173).  non_symmetric_matrix needs GMRES or the LU.  The ParILU options of
+    `metadata` apply to the iterative local solver only."""
     code = _local_solver_code(settings)
+    if metadata is not None and any(_sweep_counts(metadata)) and code != capi.SOLVER_ITERATIVE:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "par_ilu_sweeps / trisolve_sweeps apply to the iterative local solver only")
     if code == capi.SOLVER_DIRECT and settings.factorization == "umfpack":
         code = capi.SOLVER_DIRECT_LU
     if settings.non_symmetric_matrix and code == capi.SOLVER_DIRECT:
@@ -208,6 +226,18 @@ def _factor_solver_code(settings):
 
 
 def _precond_code(metadata):
+    code = _precond_name_code(metadata)
+    par, tri = _sweep_counts(metadata)
+    if par > 0 and code not in (capi.PRECOND_ILU, capi.PRECOND_ISAI):
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "par_ilu_sweeps applies to local_precond 'ilu' and 'isai' only")
+    if tri > 0 and code != capi.PRECOND_ILU:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "trisolve_sweeps applies to local_precond 'ilu' only")
+    return code
+
+
+def _precond_name_code(metadata):
     lp = metadata.local_precond
     if lp in ("null", "", None):
         return capi.PRECOND_NONE
@@ -399,7 +429,7 @@ class SolverRAS:
         s, m, be, comm = self.settings, self.metadata, self.backend, self.comm
         self._user_matrix = matrix
         self._user_rhs = None if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
-        solver_code = _factor_solver_code(s)
+        solver_code = _factor_solver_code(s, m)
         precond_code = _precond_code(m)
         if self._distributed_ingest():
             prob = self._ingest_distributed()
@@ -415,12 +445,15 @@ class SolverRAS:
             for q, ids in puts[me]:
                 sd.add_put_list(q, ids)
         self.send_buf, self.recv_buf = {}, {}
+        # the ParILU options travel only when set (a backend without them keeps working with the defaults)
+        par, tri = _sweep_counts(m)
+        sweeps = dict(par_ilu_sweeps=par, trisolve_sweeps=tri) if par or tri else {}
         for me, sd in self.subdomains.items():
             sd.to_device(self._rhs_first_rows(sd, sd.local_size_x), local_solver=solver_code, precond=precond_code,
                          local_tol=m.local_solver_tolerance, local_max_iters=m.local_max_iters,
                          natural_factor_ordering=s.naturally_ordered_factor,
                          spmv_variant=s.spmv_variant, precond_block_size=m.precond_max_block_size,
-                         non_symmetric=s.non_symmetric_matrix, restart_iter=s.restart_iter)
+                         non_symmetric=s.non_symmetric_matrix, restart_iter=s.restart_iter, **sweeps)
             # use_mixed_precision (MixedValueType = float): halos travel as fp32
             self.send_buf[me] = be.empty(sd.num_send, s.use_mixed_precision)
             self.recv_buf[me] = be.empty(sd.num_recv, s.use_mixed_precision)
