@@ -1,0 +1,595 @@
+"""Extended-precision references for the GPU tests, in plain numpy.
+
+Everything here is written from the textbook statement of the operation (CSR row sums, forward / backward
+substitution, right-preconditioned MGS-GMRES with Givens rotations, truncated Neumann series, synchronous
+ParILU sweeps) and runs in `np.longdouble`, which has a 64-bit mantissa on x86 (eps = 1.08e-19): 11 bits
+more than the float64 the kernels compute in, so a kernel's summation-order error of a few hundred ulp is
+visible against it.  Where `np.longdouble` is no wider than float64 the functions call `pytest.skip`
+instead of quietly comparing float64 with float64.
+
+Most routines take a `dtype` argument so that the same text also runs in float64: the distance between the
+two runs is what float64 rounding alone does to the result, and the GMRES tests size their tolerance from it.
+
+Layout of triangular factors (the library's, `schwz.ilu0` / `schwz.Trs`): CSR, L holds its diagonal LAST in
+each row, U holds it FIRST.
+"""
+import numpy as np
+
+LD = np.longdouble
+U64 = 2.0 ** -53   # unit roundoff of float64
+
+
+def require_extended_precision():
+    """The one skip of the modules that import this file: no extended precision on this platform."""
+    if np.finfo(LD).eps >= 2.0 ** -53:
+        import pytest
+        pytest.skip("np.longdouble is no wider than float64 on this platform")
+
+
+def _guard(dtype):
+    if np.dtype(dtype) == np.dtype(LD):
+        require_extended_precision()
+
+
+# ---- CSR row sums -------------------------------------------------------------------------------------
+
+def _row_passes(rp):
+    """For k = 0, 1, ...: the rows that own a k-th entry (row lengths sorted once)."""
+    rp = np.asarray(rp, dtype=np.int64)
+    ln = np.diff(rp)
+    order = np.argsort(-ln, kind="stable")
+    sorted_len = ln[order]
+    k = 0
+    while True:
+        cnt = int(np.searchsorted(-sorted_len, -k, side="left"))   # rows with length > k
+        if cnt == 0:
+            return
+        rows = order[:cnt]
+        yield rows, rp[rows] + k
+        k += 1
+
+
+def spmv(rp, col, val, x, dtype=LD):
+    """y = A x, every row summed entry by entry in CSR order, in `dtype`."""
+    _guard(dtype)
+    col = np.asarray(col, dtype=np.int64)
+    val = np.asarray(val, dtype=dtype)
+    x = np.asarray(x, dtype=dtype)
+    y = np.zeros(len(rp) - 1, dtype=dtype)
+    for rows, at in _row_passes(rp):
+        y[rows] += val[at] * x[col[at]]
+    return y
+
+
+# ---- triangular factors -------------------------------------------------------------------------------
+
+class Tri:
+    """One triangular factor prepared for substitution: rows grouped into dependency levels, so that a solve
+    is one vectorised pass per level (rows of a level are independent) with every row summed in CSR order
+    (a level of one row: numpy's dot over the row)."""
+
+    def __init__(self, rp, col, val, lower):
+        self.rp = np.asarray(rp, dtype=np.int64)
+        self.col = np.asarray(col, dtype=np.int64)
+        self.val64 = np.asarray(val, dtype=np.float64)
+        self.lower = bool(lower)
+        self.n = n = len(self.rp) - 1
+        rp_, col_ = self.rp, self.col
+        dpos = rp_[1:] - 1 if lower else rp_[:-1].copy()
+        assert n == 0 or np.array_equal(col_[dpos], np.arange(n)), "diagonal must be last in L, first in U"
+        self.dpos = dpos
+        self.s0 = rp_[:-1] if lower else rp_[:-1] + 1     # strict part of each row
+        self.s1 = rp_[1:] - 1 if lower else rp_[1:]
+        self.longest = int(np.diff(rp_).max()) if n else 0
+        # levels: a python loop, once per factor
+        level = [0] * n
+        cl, s0l, s1l = col_.tolist(), self.s0.tolist(), self.s1.tolist()
+        for i in (range(n) if lower else range(n - 1, -1, -1)):
+            m = -1
+            for j in range(s0l[i], s1l[i]):
+                lv = level[cl[j]]
+                if lv > m:
+                    m = lv
+            level[i] = m + 1
+        level = np.asarray(level, dtype=np.int64)
+        self.nlevels = int(level.max()) + 1 if n else 0
+        order = np.argsort(level, kind="stable")
+        bounds = np.searchsorted(level[order], np.arange(self.nlevels + 1))
+        self.plan = []
+        for lv in range(self.nlevels):
+            rows = order[bounds[lv]:bounds[lv + 1]]
+            if len(rows) == 1:   # a chain link or a long banded row: one dot product over the row's slice
+                r = int(rows[0])
+                self.plan.append((r, slice(int(self.s0[r]), int(self.s1[r]))))
+                continue
+            ln = self.s1[rows] - self.s0[rows]
+            byl = np.argsort(-ln, kind="stable")
+            rows, ln = rows[byl], ln[byl]
+            passes = []
+            for k in range(int(ln[0]) if len(ln) else 0):
+                cnt = int(np.searchsorted(-ln, -k, side="left"))
+                passes.append((cnt, self.s0[rows[:cnt]] + k))
+            self.plan.append((rows, passes))
+
+    def solve(self, b, dtype=LD, comparison=False):
+        """T x = b by substitution in `dtype`.  comparison: with M(T) (|t_ii| on the diagonal, -|t_ij| off it)
+        in place of T."""
+        _guard(dtype)
+        val = np.asarray(self.val64, dtype=dtype)
+        if comparison:
+            val = -np.abs(val)
+            val[self.dpos] = -val[self.dpos]
+        x = np.zeros(self.n, dtype=dtype)
+        b = np.asarray(b, dtype=dtype)
+        diag = val[self.dpos]
+        xcol = self.col
+        for rows, passes in self.plan:
+            if isinstance(passes, slice):
+                x[rows] = (b[rows] - np.dot(val[passes], x[xcol[passes]])) / diag[rows]
+                continue
+            s = b[rows].copy()
+            for cnt, at in passes:
+                s[:cnt] -= val[at] * x[self.col[at]]
+            x[rows] = s / diag[rows]
+        return x
+
+    def abs_times(self, x, dtype=LD):
+        """|T| |x| in `dtype`."""
+        return spmv(self.rp, self.col, np.abs(np.asarray(self.val64, dtype=dtype)), np.abs(np.asarray(x, dtype=dtype)),
+                    dtype)
+
+
+def lower_solve(rp, col, val, b, dtype=LD):
+    return Tri(rp, col, val, True).solve(b, dtype)
+
+
+def upper_solve(rp, col, val, b, dtype=LD):
+    return Tri(rp, col, val, False).solve(b, dtype)
+
+
+def factors(f):
+    """(Tri L, Tri U) from a dict with l_rp, l_col, l_val, u_rp, u_col, u_val (what schwz.ilu0 returns)."""
+    return Tri(f["l_rp"], f["l_col"], f["l_val"], True), Tri(f["u_rp"], f["u_col"], f["u_val"], False)
+
+
+def trs_apply(L, U, perm_in, perm_out, b, dtype=LD, parts=False):
+    """w = b[perm_in]; L w1 = w; U w0 = w1; y[perm_out] = w0 (None: identity), what trs_create documents."""
+    b = np.asarray(b, dtype=dtype)
+    w = b if perm_in is None else b[np.asarray(perm_in, dtype=np.int64)]
+    w1 = L.solve(w, dtype)
+    w0 = U.solve(w1, dtype)
+    if perm_out is None:
+        y = w0
+    else:
+        y = np.zeros_like(w0)
+        y[np.asarray(perm_out, dtype=np.int64)] = w0
+    return (y, w1, w0) if parts else y
+
+
+def trs_error_bound(L, U, x_L, x_U):
+    """Componentwise forward-error bound of the two substitutions carried out in float64, rows summed in ANY
+    order (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., Thm 8.5: the computed solution
+    solves (T + dT) x = b with |dT| <= gamma_k |T|; with |T^-1| <= M(T)^-1 for the comparison matrix M(T)):
+
+        e_L = k u M(L)^-1 |L| |x_L|,      e_U = M(U)^-1 (k u |U| |x_U| + e_L),
+
+    k = longest row + 1, u = 2^-53.  Returned in the order of x_U (before the output permutation)."""
+    k = max(L.longest, U.longest) + 1
+    ku = LD(k) * LD(U64)
+    e_L = L.solve(ku * L.abs_times(x_L), LD, comparison=True)
+    return U.solve(ku * U.abs_times(x_U) + e_L, LD, comparison=True)
+
+
+# ---- Jacobi-sweep triangular solves (trs_jacobi_kernel) ---------------------------------------------------
+
+def _jacobi_factor(T, b, sweeps, dtype, e_b=None):
+    """x_0 = D^-1 b, x_{m+1} = D^-1 (b - T_s x_m), `sweeps` times.  With e_b (a bound on the error already in
+    b) also returns the running componentwise bound of a float64 evaluation: every pass adds (k + 2) u times
+    the magnitudes that enter the row (k products and subtractions, the reciprocal diagonal, the final
+    product) and propagates the previous pass's error through |D^-1| |T_s|."""
+    val = np.asarray(T.val64, dtype=dtype)
+    dinv = 1 / val[T.dpos]
+    strict = val.copy()
+    strict[T.dpos] = 0
+    b = np.asarray(b, dtype=dtype)
+    x = dinv * b
+    if e_b is None:
+        for _ in range(sweeps):
+            x = dinv * (b - spmv(T.rp, T.col, strict, x, dtype))
+        return x
+    ku = LD(T.longest + 2) * LD(U64)
+    adinv, astrict = np.abs(dinv), np.abs(strict)
+    e = adinv * e_b + 2 * LD(U64) * np.abs(x)
+    for _ in range(sweeps):
+        mag = np.abs(b) + spmv(T.rp, T.col, astrict, np.abs(x), dtype)
+        e = adinv * (e_b + spmv(T.rp, T.col, astrict, e, dtype) + ku * mag)
+        x = dinv * (b - spmv(T.rp, T.col, strict, x, dtype))
+    return x, e
+
+
+def jacobi_sweep_solve(L, U, b, sweeps, dtype=LD, bound=False):
+    """y = U^-1 L^-1 b with each factor applied by the truncated Neumann series of trs_jacobi_kernel.
+    bound: also the derived componentwise error bound of a float64 evaluation (see _jacobi_factor)."""
+    _guard(dtype)
+    if not bound:
+        return _jacobi_factor(U, _jacobi_factor(L, b, sweeps, dtype), sweeps, dtype)
+    zero = np.zeros(L.n, dtype=dtype)
+    r, e_r = _jacobi_factor(L, b, sweeps, dtype, zero)
+    return _jacobi_factor(U, r, sweeps, dtype, e_r)
+
+
+# ---- preconditioner applications --------------------------------------------------------------------------
+
+def precond_none(dtype=LD):
+    return lambda v: np.array(v, dtype=dtype)
+
+
+def precond_jacobi(rp, col, val, dtype=LD):
+    rp = np.asarray(rp, dtype=np.int64)
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    on = np.asarray(col) == rows
+    d = np.zeros(len(rp) - 1, dtype=dtype)
+    d[rows[on]] = np.asarray(val, dtype=dtype)[on]
+    return lambda v: np.asarray(v, dtype=dtype) / d
+
+
+def precond_block_jacobi(rp, col, val, block_ptr, dtype=LD):
+    """Dense inverses of the diagonal blocks block_ptr[k]:block_ptr[k+1], formed in longdouble by Gauss-Jordan
+    elimination with partial pivoting (numpy.linalg has no longdouble; all blocks of one size are eliminated
+    together), applied in `dtype`."""
+    _guard(LD)
+    rp = np.asarray(rp, dtype=np.int64)
+    col = np.asarray(col, dtype=np.int64)
+    n = len(rp) - 1
+    block_ptr = np.asarray(block_ptr, dtype=np.int64)
+    sizes = np.diff(block_ptr)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    blk = np.searchsorted(block_ptr, rows, side="right") - 1
+    inside = (col >= block_ptr[blk]) & (col < block_ptr[blk + 1])
+    groups = []
+    for s in np.unique(sizes):
+        ks = np.nonzero(sizes == s)[0]
+        slot = np.full(len(sizes), -1, dtype=np.int64)
+        slot[ks] = np.arange(len(ks))
+        e = np.nonzero(inside & (slot[blk] >= 0))[0]
+        dense = np.zeros((len(ks), s, s), dtype=LD)
+        dense[slot[blk[e]], rows[e] - block_ptr[blk[e]], col[e] - block_ptr[blk[e]]] = np.asarray(val, dtype=LD)[e]
+        idx = block_ptr[ks][:, None] + np.arange(s)[None, :]
+        groups.append((idx, _dense_inverse(dense).astype(dtype)))
+
+    def apply(v):
+        v = np.asarray(v, dtype=dtype)
+        out = np.empty(n, dtype=dtype)
+        for idx, inv in groups:
+            out[idx] = np.einsum("kij,kj->ki", inv, v[idx])
+        return out
+    return apply
+
+
+def _dense_inverse(a):
+    """Inverses of a stack of square matrices (K, s, s), or of one (s, s), in longdouble."""
+    single = a.ndim == 2
+    w = np.asarray(a, dtype=LD).reshape((-1,) + a.shape[-2:])
+    K, s = w.shape[0], w.shape[1]
+    w = np.concatenate([w, np.broadcast_to(np.eye(s, dtype=LD), (K, s, s))], axis=2)
+    ar = np.arange(K)
+    for c in range(s):
+        p = c + np.argmax(np.abs(w[:, c:, c]), axis=1)
+        rc, rp_ = w[ar, c].copy(), w[ar, p].copy()
+        w[ar, p], w[ar, c] = rc, rp_
+        w[:, c] /= w[:, c, c][:, None]
+        f = w[:, :, c].copy()
+        f[:, c] = 0
+        w -= f[:, :, None] * w[:, c][:, None, :]
+    inv = w[:, :, s:]
+    return inv[0] if single else inv
+
+
+def precond_ilu(f, dtype=LD):
+    """z = U^-1 L^-1 v by substitution on given factors (schwz.ilu0's)."""
+    L, U = factors(f)
+    return lambda v: U.solve(L.solve(v, dtype), dtype)
+
+
+def make_precond(schwz, oracle, rp, col, val, precond, bs, dtype):
+    """The preconditioner codes of the library (0 none, 1 Jacobi, 2 block-Jacobi, 3 ILU) as hp_reference
+    applications; the block partition is the oracle's (structure only), the ILU(0) factors the library's."""
+    if precond == 0:
+        return precond_none(dtype)
+    if precond == 1 or (precond == 2 and bs == 1):
+        return precond_jacobi(rp, col, val, dtype)
+    if precond == 2:
+        return precond_block_jacobi(rp, col, val, oracle.jacobi_blocks(rp, col, bs), dtype)
+    assert precond == 3
+    return precond_ilu(schwz.ilu0(rp, col, val), dtype)
+
+
+# ---- GMRES ----------------------------------------------------------------------------------------------------
+
+def gmres(rp, col, val, b, x0, precond_apply, iters, restart, rtol=0.0, dtype=LD):
+    """Restarted GMRES(restart), right preconditioned, modified Gram-Schmidt, Givens rotations (Saad &
+    Schultz 1986), at most `iters` Krylov vectors, with the structure of schwz_gmres_solve: the stop tests at
+    the top of a cycle use the true residual, inside a cycle the rotated right-hand side.
+
+    Returns (x, hist): hist[0] is the initial residual norm, hist[k] the residual norm reported after k
+    Krylov vectors (if a cycle top stops the solve, its true residual norm replaces the last entry).
+    len(hist) - 1 is the iteration count."""
+    _guard(dtype)
+    m = max(int(restart), 1)
+    n = len(rp) - 1
+    b = np.asarray(b, dtype=dtype)
+    x = np.array(x0, dtype=dtype) if x0 is not None else np.zeros(n, dtype=dtype)
+    V = np.zeros((m + 1, n), dtype=dtype)
+    H = np.zeros((m + 1, m), dtype=dtype)
+    cs, sn = np.zeros(m, dtype=dtype), np.zeros(m, dtype=dtype)
+    hist = []
+    it, r0 = 0, None
+    while True:
+        r = b - spmv(rp, col, val, x, dtype)
+        beta = np.sqrt(np.dot(r, r))
+        if r0 is None:
+            r0 = beta
+            hist.append(beta)
+        else:
+            hist[-1] = beta
+        if it >= iters or beta <= rtol * r0 or beta == 0:
+            break
+        V[0] = r / beta
+        g = np.zeros(m + 1, dtype=dtype)
+        g[0] = beta
+        k = 0
+        resn = beta
+        for j in range(m):
+            if it >= iters:
+                break
+            w = spmv(rp, col, val, precond_apply(V[j]), dtype)
+            for i in range(j + 1):
+                H[i, j] = np.dot(w, V[i])
+                w = w - H[i, j] * V[i]
+            hn = np.sqrt(np.dot(w, w))
+            H[j + 1, j] = hn
+            V[j + 1] = w / hn if hn != 0 else 0
+            for i in range(j):
+                t = cs[i] * H[i, j] + sn[i] * H[i + 1, j]
+                H[i + 1, j] = -sn[i] * H[i, j] + cs[i] * H[i + 1, j]
+                H[i, j] = t
+            if H[j + 1, j] == 0:
+                cs[j], sn[j] = 1, 0
+            else:
+                rr = np.hypot(H[j, j], H[j + 1, j])
+                cs[j], sn[j] = H[j, j] / rr, H[j + 1, j] / rr
+            H[j, j] = cs[j] * H[j, j] + sn[j] * H[j + 1, j]
+            H[j + 1, j] = 0
+            g[j + 1] = -sn[j] * g[j]
+            g[j] = cs[j] * g[j]
+            it += 1
+            k = j + 1
+            resn = abs(g[j + 1])
+            hist.append(resn)
+            if resn <= rtol * r0:
+                break
+        y = np.zeros(k, dtype=dtype)
+        for i in range(k - 1, -1, -1):
+            y[i] = (g[i] - np.dot(H[i, i + 1:k], y[i + 1:k])) / H[i, i]
+        t = np.zeros(n, dtype=dtype)
+        for i in range(k):
+            t = t + y[i] * V[i]
+        x = x + precond_apply(t)
+        if resn <= rtol * r0 or it >= iters:
+            break
+    return x, hist
+
+
+# ---- synchronous ParILU sweeps (schwz.parilu) ---------------------------------------------------------------
+
+class Pattern:
+    """The ILU(0) pattern of A in the library's layout (L: strict lower + unit diagonal LAST, U: upper with
+    its diagonal FIRST) and, for every entry of A, the (L index, U index) pairs of its ParILU sum."""
+
+    def __init__(self, rp, col):
+        n = len(rp) - 1
+        self.n = n
+        rows = [dict((int(col[j]), j) for j in range(rp[i], rp[i + 1])) for i in range(n)]
+        l_rp, u_rp, l_col, u_col = [0], [0], [], []
+        self.where = np.zeros(rp[-1], dtype=np.int64)   # target index in L (>= 0 below the diagonal) or U
+        self.is_l = np.zeros(rp[-1], dtype=bool)
+        for i in range(n):
+            for j in range(rp[i], rp[i + 1]):
+                c = int(col[j])
+                if c < i:
+                    self.where[j], self.is_l[j] = len(l_col), True
+                    l_col.append(c)
+                else:
+                    self.where[j] = len(u_col)
+                    u_col.append(c)
+            l_col.append(i)
+            l_rp.append(len(l_col))
+            u_rp.append(len(u_col))
+        self.l_rp, self.l_col = np.array(l_rp), np.array(l_col)
+        self.u_rp, self.u_col = np.array(u_rp), np.array(u_col)
+        self.pairs = []
+        self.pivot = np.zeros(rp[-1], dtype=np.int64)
+        for i in range(n):
+            for j in range(rp[i], rp[i + 1]):
+                c = int(col[j])
+                ps = []
+                for k in sorted(rows[i]):
+                    if k >= min(i, c):
+                        break
+                    q = rows[k].get(c)
+                    if q is not None:
+                        ps.append((self.where[rows[i][k]], self.where[q]))
+                self.pairs.append(ps)
+                if c < i:
+                    self.pivot[j] = self.where[rows[c][c]]
+        self.rp = np.asarray(rp)
+
+    def depth(self):
+        """Longest dependency chain among the entries (row-major order lists dependencies first)."""
+        d = np.zeros(len(self.pairs), dtype=np.int64)
+        l_of = {}
+        u_of = {}
+        for e in range(len(self.pairs)):
+            (l_of if self.is_l[e] else u_of)[self.where[e]] = e
+        for e, ps in enumerate(self.pairs):
+            m = 0
+            for li, ui in ps:
+                m = max(m, d[l_of[li]], d[u_of[ui]])
+            if self.is_l[e]:
+                m = max(m, d[u_of[self.pivot[e]]])
+            d[e] = m + 1
+        return int(d.max())
+
+
+def parilu_numpy(pat, val, sweeps):
+    """Synchronous ParILU sweeps from L0 = strict lower part of A + unit diagonal, U0 = upper part."""
+    lv = np.ones(len(pat.l_col))
+    uv = np.zeros(len(pat.u_col))
+    lv[pat.where[pat.is_l]] = val[pat.is_l]
+    uv[pat.where[~pat.is_l]] = val[~pat.is_l]
+    for _ in range(sweeps):
+        ln, un = lv.copy(), uv.copy()
+        for e, ps in enumerate(pat.pairs):
+            s = val[e]
+            for li, ui in ps:
+                s -= lv[li] * uv[ui]
+            if pat.is_l[e]:
+                ln[pat.where[e]] = s / uv[pat.pivot[e]]
+            else:
+                un[pat.where[e]] = s
+        lv, uv = ln, un
+    return lv, uv
+
+
+# ---- triangular factors built in numpy (inputs of the triangular-solve tests) -----------------------------------
+
+def _values(n, rp, col, lower, rng, rho):
+    """Values for a triangular pattern (diagonal last in a lower, first in an upper row): off-diagonal entries
+    random with sum_j |t_ij| = rho |t_ii| (row diagonally dominant: M(T) is well conditioned), diagonals in
+    +-[1, 2]."""
+    ln = np.diff(rp)
+    val = rng.uniform(0.25, 1.0, rp[-1]) * rng.choice([-1.0, 1.0], rp[-1])
+    dpos = rp[1:] - 1 if lower else rp[:-1]
+    strict = np.ones(rp[-1], dtype=bool)
+    strict[dpos] = False
+    d = rng.uniform(1.0, 2.0, n) * rng.choice([-1.0, 1.0], n)
+    rowid = np.repeat(np.arange(n), ln)
+    tot = np.bincount(rowid[strict], weights=np.abs(val[strict]), minlength=n)
+    val[strict] *= (rho * np.abs(d) / np.maximum(tot, 1e-300))[rowid[strict]]
+    val[dpos] = d
+    return val
+
+
+def _assemble(n, rows_l, rows_u, rng, rho):
+    """Factors in the library's layout from per-row strict column lists."""
+    out = {}
+    for name, rows, lower in (("l", rows_l, True), ("u", rows_u, False)):
+        ln = np.array([len(r) for r in rows], dtype=np.int64) + 1
+        rp = np.concatenate([[0], np.cumsum(ln)])
+        col = np.empty(rp[-1], dtype=np.int64)
+        dpos = rp[1:] - 1 if lower else rp[:-1]
+        strict = np.ones(rp[-1], dtype=bool)
+        strict[dpos] = False
+        col[dpos] = np.arange(n)
+        if strict.any():
+            col[strict] = np.concatenate([np.sort(np.asarray(r, dtype=np.int64)) for r in rows])
+        out[name + "_rp"], out[name + "_col"] = rp.astype(np.int32), col.astype(np.int32)
+        out[name + "_val"] = _values(n, rp, col, lower, rng, rho)
+    return out
+
+
+def five_point_factors(n, nx, rng, rho=0.4):
+    """The pattern of the ILU(0) of a five-point stencil on a grid nx wide (natural order, the last grid line
+    may be incomplete): L holds south and west, U east and north."""
+    i = np.arange(n, dtype=np.int64)
+    south, west = i >= nx, (i % nx) > 0
+    east, north = ((i % nx) < nx - 1) & (i + 1 < n), i + nx < n
+    out = {}
+    l_rp = np.concatenate([[0], np.cumsum(south.astype(np.int64) + west + 1)])
+    l_col = np.empty(l_rp[-1], dtype=np.int64)
+    l_col[l_rp[:-1][south]] = i[south] - nx
+    l_col[(l_rp[:-1] + south)[west]] = i[west] - 1
+    l_col[l_rp[1:] - 1] = i
+    u_rp = np.concatenate([[0], np.cumsum(1 + east.astype(np.int64) + north)])
+    u_col = np.empty(u_rp[-1], dtype=np.int64)
+    u_col[u_rp[:-1]] = i
+    u_col[(u_rp[:-1] + 1)[east]] = i[east] + 1
+    u_col[(u_rp[:-1] + 1 + east)[north]] = i[north] + nx
+    for name, rp, col, lower in (("l", l_rp, l_col, True), ("u", u_rp, u_col, False)):
+        out[name + "_rp"], out[name + "_col"] = rp.astype(np.int32), col.astype(np.int32)
+        out[name + "_val"] = _values(n, rp, col, lower, rng, rho)
+    return out
+
+
+def diagonal_factors(n, rng):
+    return _assemble(n, [[]] * n, [[]] * n, rng, 0.0)
+
+
+def bidiagonal_factors(n, rng, rho=0.4):
+    """One dependency chain: row i of L needs row i - 1, row i of U row i + 1."""
+    return _assemble(n, [[k - 1] if k else [] for k in range(n)], [[k + 1] if k + 1 < n else [] for k in range(n)],
+                     rng, rho)
+
+
+def layered_rows(widths, rng, deps=2, long_row=None):
+    """Strict lower rows whose dependency levels have exactly the given widths: a row of layer q > 0 takes one
+    column in layer q - 1 and up to deps - 1 more among all earlier rows.  long_row = (layer, count): the first
+    row of that layer takes `count` distinct earlier columns instead."""
+    start = np.concatenate([[0], np.cumsum(widths)])
+    rows = []
+    for q, w in enumerate(widths):
+        for k in range(w):
+            if q == 0:
+                rows.append([])
+                continue
+            cols = {int(rng.integers(start[q - 1], start[q]))}
+            want = deps
+            if long_row is not None and long_row[0] == q and k == 0:
+                want = long_row[1]
+            while len(cols) < min(want, start[q]):
+                cols.add(int(rng.integers(0, start[q])))
+            rows.append(sorted(cols))
+    return rows
+
+
+def layered_factors(widths, rng, deps=2, long_row=None, rho=0.4):
+    """L with the level widths given; U the same kind of structure mirrored (row i -> n - 1 - i), so that its
+    levels, counted from the last row, have the same widths."""
+    n = int(np.sum(widths))
+    rows_l = layered_rows(widths, rng, deps, long_row)
+    mirrored = layered_rows(widths, rng, deps, long_row)
+    rows_u = [[n - 1 - c for c in mirrored[n - 1 - i]] for i in range(n)]
+    return _assemble(n, rows_l, rows_u, rng, rho)
+
+
+def banded_factors(n, lo, hi, rng, rho=0.4):
+    """Dense-ish banded factors: row i of L takes column i - 1 and, in all, between lo and hi of the columns
+    [i - hi - 40, i) (as many as exist near the corner), U is the mirror image: one row per level, rows far
+    longer than a wave."""
+    def rows():
+        out = []
+        for i in range(n):
+            first = max(0, i - hi - 40)
+            cnt = min(int(rng.integers(lo, hi + 1)), i - first)
+            picks = first + rng.choice(i - 1 - first, size=cnt - 1, replace=False) if cnt > 1 else []
+            out.append(np.append(picks, i - 1).astype(np.int64) if cnt else [])
+        return out
+    rows_l, m = rows(), rows()
+    rows_u = [n - 1 - np.asarray(m[n - 1 - i], dtype=np.int64) for i in range(n)]
+    return _assemble(n, rows_l, rows_u, rng, rho)
+
+
+def rescale(f, rng, span=20):
+    """Row and column scalings by signed powers of two, T -> D1 T D2 with |d| in [2^-span, 2^span] on the
+    diagonal of the result: non-unit, negative, badly scaled pivots, while M(T) = |D1| M(T0) |D2| keeps the
+    conditioning of the comparison matrix that the componentwise bound depends on.  Exact in float64."""
+    n = len(f["l_rp"]) - 1
+    out = dict(f)
+    for name in ("l", "u"):
+        rp, col = f[name + "_rp"].astype(np.int64), f[name + "_col"].astype(np.int64)
+        e1, e2 = rng.integers(-span // 2, span // 2 + 1, n), rng.integers(-span // 2, span // 2 + 1, n)
+        d1 = np.ldexp(rng.choice([-1.0, 1.0], n), e1)
+        d2 = np.ldexp(1.0, e2)
+        rowid = np.repeat(np.arange(n), np.diff(rp))
+        out[name + "_val"] = f[name + "_val"] * d1[rowid] * d2[col]
+    return out

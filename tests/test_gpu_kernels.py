@@ -20,7 +20,7 @@ def _dev(torch, a):
 
 
 @pytest.mark.parametrize("op", [0, 1, 2, 3])
-@pytest.mark.parametrize("n", [0, 1, 63, 1000, 100003])
+@pytest.mark.parametrize("n", [0, 1, 63, 1000, 100003, 524289, 1500001])   # the last two: past the launch cap, grid stride
 def test_gather_scatter_ops(schwz, oracle, torch_cuda, op, n):
     torch = torch_cuda
     rng = np.random.default_rng(n + op)
@@ -341,6 +341,30 @@ def test_pcg_block_jacobi_and_ilu_match_oracle(schwz, oracle, torch_cuda, case, 
     it_g, rn_g = cg.solve(d_b.data_ptr(), d_x.data_ptr(), 1e-10, n)
     assert abs(it_g - it_o) <= 1, (it_g, it_o)
     assert np.abs(d_x.cpu().numpy() - exp).max() <= 1e-7 * np.abs(exp).max()
+
+
+@pytest.mark.parametrize("pc", [(2, 7), (2, 32), (4, 1)])
+def test_pcg_block_jacobi_and_isai_past_the_grid_cap(schwz, oracle, torch_cuda, pc):
+    """Block-Jacobi (block sizes 7 and 32) and ISAI applications on n = 725^2 = 525 625 > 524 288 rows: the
+    preconditioner kernels run with a capped grid and stride.  Three fixed iterations against the oracle's
+    recurrence, at the tolerance of test_pcg_block_jacobi_and_ilu_match_oracle."""
+    torch = torch_cuda
+    precond, bs = pc
+    rp, col, val = oracle.laplacian2d(725)
+    n = len(rp) - 1
+    assert n > 2048 * 256
+    rng = np.random.default_rng(19)
+    b = rng.standard_normal(n)
+    x0 = rng.standard_normal(n) * 0.1
+    A = schwz.Csr(rp, col, val)
+    cg = schwz.Pcg(A, precond, bs)
+    exp, it_o, rn_o = oracle.pcg(rp, col, val, b, x0, precond, 0.0, 3, block_size=bs)
+    d_b, d_x = _dev(torch, b), _dev(torch, x0)
+    it_g, rn_g = cg.solve(d_b.data_ptr(), d_x.data_ptr(), 0.0, 3)
+    got = d_x.cpu().numpy()
+    assert it_g == it_o == 3
+    assert np.abs(got - exp).max() <= RTOL_CG * np.abs(exp).max()
+    assert abs(rn_g - rn_o) <= 1e-8 * max(rn_o, 1e-300) + 1e-14
 
 
 @pytest.mark.parametrize("pc", [(0, 1), (1, 1), (2, 8), (3, 1), (4, 1)])
@@ -1033,12 +1057,22 @@ def test_canonical_stencil_layout_variants(schwz, oracle, torch_cuda, monkeypatc
 @pytest.mark.parametrize("vt", ["float32", "float64", "int32", "int64"])
 @pytest.mark.parametrize("it", ["int32", "int64"])
 def test_gather_scatter_every_reference_instantiation(schwz, torch_cuda, vt, it):
+    _gather_scatter_typed(schwz, torch_cuda, vt, it, 5000, 7000)
+
+
+@pytest.mark.parametrize("vt", ["float32", "float64", "int32", "int64"])
+@pytest.mark.parametrize("it", ["int32", "int64"])
+def test_gather_scatter_every_reference_instantiation_past_the_launch_cap(schwz, torch_cuda, vt, it):
+    """n = 600 001 > 2048 * 256: the typed kernels run with a capped grid and stride."""
+    _gather_scatter_typed(schwz, torch_cuda, vt, it, 600001, 700001)
+
+
+def _gather_scatter_typed(schwz, torch_cuda, vt, it, n, m):
     """Gather / Scatter for the eight (value, index) type pairs the reference instantiates
     (gather_kernel.cu:112-146, scatter_kernel.cu:109-142) and its four ops, against numpy with the
     same element type (bit exact: one operation per element, integer avg = integer division)."""
     torch = torch_cuda
     rng = np.random.default_rng(7)
-    n, m = 5000, 7000
     vcode = {"float32": 0, "float64": 1, "int32": 2, "int64": 3}[vt]
     icode = {"int32": 0, "int64": 1}[it]
     idx = rng.permutation(m)[:n].astype(it)          # distinct targets: the scatter has no collisions

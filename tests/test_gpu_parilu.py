@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from hp_reference import Pattern, parilu_numpy
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,85 +21,6 @@ DRIVER = os.path.join(ROOT, "schwarz-lib_amd", "build", "parilu_driver")
 
 
 # ---- numpy restatements -------------------------------------------------------------------------
-
-class Pattern:
-    """The ILU(0) pattern of A in the library's layout (L: strict lower + unit diagonal LAST, U: upper with
-    its diagonal FIRST) and, for every entry of A, the (L index, U index) pairs of its ParILU sum."""
-
-    def __init__(self, rp, col):
-        n = len(rp) - 1
-        self.n = n
-        rows = [dict((int(col[j]), j) for j in range(rp[i], rp[i + 1])) for i in range(n)]
-        l_rp, u_rp, l_col, u_col = [0], [0], [], []
-        self.where = np.zeros(rp[-1], dtype=np.int64)   # target index in L (>= 0 below the diagonal) or U
-        self.is_l = np.zeros(rp[-1], dtype=bool)
-        for i in range(n):
-            for j in range(rp[i], rp[i + 1]):
-                c = int(col[j])
-                if c < i:
-                    self.where[j], self.is_l[j] = len(l_col), True
-                    l_col.append(c)
-                else:
-                    self.where[j] = len(u_col)
-                    u_col.append(c)
-            l_col.append(i)
-            l_rp.append(len(l_col))
-            u_rp.append(len(u_col))
-        self.l_rp, self.l_col = np.array(l_rp), np.array(l_col)
-        self.u_rp, self.u_col = np.array(u_rp), np.array(u_col)
-        self.pairs = []
-        self.pivot = np.zeros(rp[-1], dtype=np.int64)
-        for i in range(n):
-            for j in range(rp[i], rp[i + 1]):
-                c = int(col[j])
-                ps = []
-                for k in sorted(rows[i]):
-                    if k >= min(i, c):
-                        break
-                    q = rows[k].get(c)
-                    if q is not None:
-                        ps.append((self.where[rows[i][k]], self.where[q]))
-                self.pairs.append(ps)
-                if c < i:
-                    self.pivot[j] = self.where[rows[c][c]]
-        self.rp = np.asarray(rp)
-
-    def depth(self):
-        """Longest dependency chain among the entries (row-major order lists dependencies first)."""
-        d = np.zeros(len(self.pairs), dtype=np.int64)
-        l_of = {}
-        u_of = {}
-        for e in range(len(self.pairs)):
-            (l_of if self.is_l[e] else u_of)[self.where[e]] = e
-        for e, ps in enumerate(self.pairs):
-            m = 0
-            for li, ui in ps:
-                m = max(m, d[l_of[li]], d[u_of[ui]])
-            if self.is_l[e]:
-                m = max(m, d[u_of[self.pivot[e]]])
-            d[e] = m + 1
-        return int(d.max())
-
-
-def parilu_numpy(pat, val, sweeps):
-    """Synchronous ParILU sweeps from L0 = strict lower part of A + unit diagonal, U0 = upper part."""
-    lv = np.ones(len(pat.l_col))
-    uv = np.zeros(len(pat.u_col))
-    lv[pat.where[pat.is_l]] = val[pat.is_l]
-    uv[pat.where[~pat.is_l]] = val[~pat.is_l]
-    for _ in range(sweeps):
-        ln, un = lv.copy(), uv.copy()
-        for e, ps in enumerate(pat.pairs):
-            s = val[e]
-            for li, ui in ps:
-                s -= lv[li] * uv[ui]
-            if pat.is_l[e]:
-                ln[pat.where[e]] = s / uv[pat.pivot[e]]
-            else:
-                un[pat.where[e]] = s
-        lv, uv = ln, un
-    return lv, uv
-
 
 def _tri(rp, col, val, n):
     import scipy.sparse as sp
@@ -145,10 +68,11 @@ def _cases(oracle, convdiff):
         "convdiff_32": convdiff(32),
         "ani4_crop": (g["rp"].astype(np.int32), g["col"].astype(np.int32), g["val"]),
         "lap2d_100": oracle.laplacian2d(100),   # above 8192 rows
+        "lap2d_330": oracle.laplacian2d(330),   # nnz = 543 180 > 524 288: the entry-parallel sweeps stride
     }
 
 
-CASES = ["lap2d_16", "lap3d_12", "convdiff_32", "ani4_crop", "lap2d_100"]
+CASES = ["lap2d_16", "lap3d_12", "convdiff_32", "ani4_crop", "lap2d_100", "lap2d_330"]
 _PAT = {}
 
 
