@@ -280,6 +280,31 @@ struct PRing {
     const double *slot[kDeferDepth];
 };
 
+// what every cg_flush_x_kernel launch of a solve is given alike (filled once per solve)
+struct FlushX {
+    int64_t n = 0;
+    double *x = nullptr;
+    PRing ring;
+    const double *alpha_hist = nullptr;
+    const CgState *st = nullptr;
+    int fused = 0;                        // 1: x = fma(alpha, p, x) (stored-q iteration), 0: product rounded, then added
+    const double *pq_partials = nullptr;  // lazy_it: the partial sums of p.(A p) its update launch would have folded
+    int pq_nparts = 0;
+    const double *x2_src = nullptr;       // rows [x2_rows, x2_total) of x2 are copied from here
+    int64_t x2_total = 0;
+    double p0_scale = 1.0;
+    int dmode = 0;                        // vlast_it: D^-1 of the rebuilt direction (0: none, else the scalar dsc)
+    double dsc = 1.0;
+};
+
+// ... and what only the launches that finish x carry
+struct FlushXLast {
+    int lazy_it = -1, vlast_it = -1;
+    const double *vlast_r = nullptr;  // the current residual
+    double *x2 = nullptr;             // second output, rows [0, x2_rows)
+    int64_t x2_rows = 0;
+};
+
 // The launch covers the pairs [pair0, pair1) (and the odd last row when `tail` is set): the last update of a
 // solve is cut into the caller's priority rows and the rest (schwz_pcg::prio_*).
 // lazy_it >= 0: the update launch of iteration lazy_it was not run (schwz_pcg::LazyLast); its direction counts
@@ -288,18 +313,22 @@ struct PRing {
 // restricted write-back of the RAS step) and the rows [x2_rows, x2_total) are copied from x2_src -- the overlap and
 // halo entries of the current x~ --, so that x2 is the complete x~ after the restriction; with nothing to add the
 // launch only copies.
-__global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(int64_t n, double *__restrict__ x, const PRing ring,
-                                                            const double *__restrict__ alpha_hist,
-                                                            const CgState *st, int b0, int count, int pending,
-                                                            int64_t pair0, int64_t pair1, int tail, int fused,
-                                                            int lazy_it, const double *pq_partials, int pq_nparts,
-                                                            double *__restrict__ x2, int64_t x2_rows,
-                                                            const double *__restrict__ x2_src, int64_t x2_total,
-                                                            double p0_scale, int vlast_it,
-                                                            const double *__restrict__ vlast_r, int vlast_dmode,
-                                                            double vlast_dsc)
+__global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, const FlushXLast l, int b0, int count,
+                                                            int pending, int64_t pair0, int64_t pair1, int tail)
 {
 #pragma clang fp contract(off)
+    // (the structs carry no qualifiers: the no-alias promises are made here)
+    const int64_t n = f.n, x2_rows = l.x2_rows, x2_total = f.x2_total;
+    double *__restrict__ const x = f.x;
+    const PRing &ring = f.ring;
+    const double *__restrict__ const alpha_hist = f.alpha_hist;
+    const CgState *const st = f.st;
+    const int fused = f.fused, lazy_it = l.lazy_it, pq_nparts = f.pq_nparts, vlast_it = l.vlast_it, vlast_dmode = f.dmode;
+    const double *const pq_partials = f.pq_partials;
+    double *__restrict__ const x2 = l.x2;
+    const double *__restrict__ const x2_src = f.x2_src;
+    const double *__restrict__ const vlast_r = l.vlast_r;
+    const double p0_scale = f.p0_scale, vlast_dsc = f.dsc;
     // p0_scale: direction 0 of the solve is p0_scale x (slot 0 of the ring) -- 1.0 for a stored p0 (the product is
     // exact), D^-1's uniform factor when slot 0 is r0 and p0 = D^-1 r0 was never stored (virtual first direction:
     // the same rounded product the first-direction launch formed)
@@ -493,6 +522,22 @@ __global__ __launch_bounds__(kBlock) void dot_rz_kernel(int64_t n, const double 
 }  // namespace schwz
 
 using namespace schwz;
+
+// ---- environment switches: the two idioms in use --------------------------------
+
+// "0" switches off what is on by default
+static bool env_on(const char *name)
+{
+    const char *e = std::getenv(name);
+    return !(e && e[0] == '0');
+}
+
+// integer mode with a default
+static int env_mode(const char *name, int dflt)
+{
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
 
 // ---- profiling hooks (bench.py roofline leg) ------------------------------------
 // HIP-event pairs around the SpMV and the update launch of every CG iteration, on the stream
@@ -768,8 +813,7 @@ static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
         // compact representation for the per-iteration vector kernels (DiagView)
         s->diag.mode = 1;
         s->diag.full = s->dinv;
-        const char *env = std::getenv("SCHWZ_DIAG_DICT");
-        if (s->n && !(env && env[0] == '0')) {
+        if (s->n && env_on("SCHWZ_DIAG_DICT")) {
             std::vector<double> h((size_t)s->n);
             SCHWZ_HIP_TRY(hipMemcpy(h.data(), s->dinv, (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost));
             std::vector<double> dict;
@@ -978,36 +1022,25 @@ static bool pcg_is_general(const schwz_pcg *s)
            s->precond == SCHWZ_PRECOND_ISAI;
 }
 
-// How a solve on this system iterates (decided once per solve, the same way in pcg_begin and pcg_iterate).
-struct CgPlan {
-    bool qfree = false;         // row-pair coded matrix: q = A p is recomputed, never stored
-    int dot_mode = kSpmvDot;    // launch that yields p.(A p)
-    bool sweep_on = false;      // z-sweep walk of the update launch
-    bool sweep_dirdot = false;  // ... and of the fused direction + p.(A p) launch
-    bool fusedir = false;       // two launches per iteration
-    bool deferx = false;        // x += sum alpha_k p_k applied once per kDeferDepth iterations
-    bool sweep_start = false;   // the solve can start in the walk too (INIT / FIRST forms, spmv_pair.hip)
-    int flavour = 0;
-};
+// ---- the plan of a solve (CgPlan, schwz_internal.hpp) -----------------------------------------------------------
+// Every SCHWZ_CG_* switch is read here (env_on / env_mode), each in one place, and nowhere else.
 
-static CgPlan pcg_plan(schwz_pcg *s)
+// What follows from the matrix, the preconditioner and the switches: decided once per solve, by pcg_begin, which
+// keeps it for pcg_iterate.  It only decides -- the buffers the plan needs are pcg_acquire_buffers' business.
+static CgPlan pcg_plan_matrix(const schwz_pcg *s)
 {
     CgPlan pl;
     const CsrView &A = s->A->v;
     const int64_t n = s->n;
-    const int gs = spmv_grid(A, s->variant);
-    const bool general = pcg_is_general(s);
+    const int dmode = s->diag.mode;
+    pl.gs = spmv_grid(A, s->variant);
+    pl.gv = grid_for((n + 1) / 2);
+    pl.general = pcg_is_general(s);
     // SCHWZ_CG_QFREE=0 keeps the stored-q iteration for row-pair coded matrices too (A/B runs)
-    static const bool qfree_on = [] {
-        const char *e = std::getenv("SCHWZ_CG_QFREE");
-        return !(e && e[0] == '0');
-    }();
-    pl.qfree = qfree_on && !general && A.pair_id && s->variant == 0 && s->diag.mode != 2;
+    static const bool qfree_on = env_on("SCHWZ_CG_QFREE");
+    pl.qfree = qfree_on && !pl.general && A.pair_id && s->variant == 0 && dmode != 2;
     // p.(A p) from the upper triangle when the upload found the matrix symmetric (SCHWZ_CG_SYM=0: full rows)
-    static const bool sym_on = [] {
-        const char *e = std::getenv("SCHWZ_CG_SYM");
-        return !(e && e[0] == '0');
-    }();
+    static const bool sym_on = env_on("SCHWZ_CG_SYM");
     pl.dot_mode = !pl.qfree ? kSpmvDot : (sym_on && A.pair_sym_base > 0 ? kSpmvDotSym : kSpmvDotOnly);
     // Two launches per iteration: the direction update and the NEXT iteration's p.(A p) share one
     // launch (kSpmvDirDotSym), p alternating between two buffers (a launch that recomputes its
@@ -1018,23 +1051,15 @@ static CgPlan pcg_plan(schwz_pcg *s)
     // 256^3 cube (+1 % on the bench line), 0.111 vs 0.067 + 0.043 ms on the 512 x 512 x 64 slab of the
     // multi-GPU runs (-1 %) -- so they keep three launches.  SCHWZ_CG_FUSEDIR=0: never, =2: every size
     // (it combines with the deferred x update).
-    static const int fusedir_mode = [] {
-        const char *e = std::getenv("SCHWZ_CG_FUSEDIR");
-        return e ? std::atoi(e) : 1;
-    }();
-    const char *dx_env = std::getenv("SCHWZ_CG_DEFERX");  // read per solve: tests switch it
-    const int dx_mode = dx_env ? std::atoi(dx_env) : 1;
-    // ... unless the matrix takes the z-sweep walk (spmv_pair.hip): there the fused launch loads every
-    // element of r and p once instead of gathering both at every entry, and replaces 32 n bytes of the
-    // two launches by 24 n (SCHWZ_CG_SWEEP=0: chunk-by-chunk launches only).
-    const char *sweep_env = std::getenv("SCHWZ_CG_SWEEP");
-    pl.sweep_on = !(sweep_env && sweep_env[0] == '0') && A.sweep_nslots > 0 && s->variant == 0 &&
-                  A.ncols < (int64_t(1) << 28) && A.sweep_nslots + A.sweep_gen_blocks <= gs;
-    pl.sweep_dirdot = pl.sweep_on && A.canon_sym_val && (s->diag.mode == 0 || s->diag.mode == 3) &&
-                      A.sweep_nslots_dir + A.sweep_gen_blocks <= gs;
+    static const int fusedir_mode = env_mode("SCHWZ_CG_FUSEDIR", 1);
+    // ... unless the matrix takes the z-sweep walk (spmv_pair.hip, which owns the conditions): there the fused
+    // launch loads every element of r and p once instead of gathering both at every entry, and replaces 32 n
+    // bytes of the two launches by 24 n (SCHWZ_CG_SWEEP=0: chunk-by-chunk launches only; read per solve: tests
+    // switch it, like the other switches that are not static here).
+    pl.sweep_on = env_on("SCHWZ_CG_SWEEP") && s->variant == 0 && pair_sweep_update_ok(A, pl.gs, dmode);
+    pl.sweep_dirdot = pl.sweep_on && pair_sweep_dirdot_ok(A, pl.gs, dmode);
     pl.fusedir = pl.dot_mode == kSpmvDotSym &&
                  (fusedir_mode == 2 || (fusedir_mode == 1 && (n <= kGraphRows || pl.sweep_dirdot)));
-    pl.flavour = !pl.qfree ? 0 : (pl.fusedir ? 2 : 1);
     // Large systems: x is not touched inside the iteration.  The search directions of up to
     // kDeferDepth iterations stay in a ring (slots 0 and 1 are s->p and the otherwise unused s->q),
     // the update launch stores alpha_k instead of updating x, and one launch per kDeferDepth
@@ -1043,27 +1068,85 @@ static CgPlan pcg_plan(schwz_pcg *s)
     // SCHWZ_CG_DEFERX=0: never, =2: every size (tests).
     // The stored-q iteration of the scalar-Jacobi / unpreconditioned CG (plain CSR and the other codings)
     // defers x the same way; its ring cannot use s->q (it holds q), so it takes one more vector.
-    pl.deferx = !general && !s->ring_failed && (dx_mode == 2 || (dx_mode == 1 && n > kGraphRows));
-    if (pl.deferx && !s->p_ring) {
-        const size_t nb = (size_t)((n + 1) & ~int64_t(1)) * sizeof(double);
-        s->ring_has_q = pl.qfree;
-        if (hipMalloc((void **)&s->p_ring, nb * (kDeferDepth - (pl.qfree ? 2 : 1))) != hipSuccess ||
-            hipMalloc((void **)&s->alpha_hist, kDeferDepth * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();  // not enough memory for the ring: the plain iteration
-            (void)hipFree(s->p_ring);
-            s->p_ring = nullptr;
-            s->ring_failed = true;
-            pl.deferx = false;
-        }
-    }
+    const int dx_mode = env_mode("SCHWZ_CG_DEFERX", 1);
+    pl.deferx = !pl.general && !s->ring_failed && (dx_mode == 2 || (dx_mode == 1 && n > kGraphRows));
     // A solve whose iterations all run in the walk starts in it as well: the start launch takes the walk
     // (32 n -> 24 n bytes: p is not stored) and the first p.(A p) comes from the FIRST form of the fused
     // direction launch, which builds p = D^-1 r from the r it reads anyway (SCHWZ_CG_SWEEPSTART=0: the
     // chunk-by-chunk start launch + kSpmvDotSym).
-    const char *start_env = std::getenv("SCHWZ_CG_SWEEPSTART");
-    pl.sweep_start = !(start_env && start_env[0] == '0') && pl.deferx && pl.sweep_dirdot && pl.fusedir &&
-                     pair_sweep_start_ok(A, gs);
+    pl.sweep_start = env_on("SCHWZ_CG_SWEEPSTART") && pl.deferx && pl.sweep_dirdot && pl.fusedir &&
+                     pair_sweep_start_ok(A, pl.gs);
     return pl;
+}
+
+// What depends on rtol, max_iters and on whether the start launch left p pending: pcg_iterate, on its copy.
+static void pcg_plan_solve(const schwz_pcg *s, CgPlan &pl, double rtol, int max_iters)
+{
+    // the walks serve every launch of the solve, and D^-1 is a scalar or absent
+    const bool all_walks = pl.fusedir && pl.sweep_start && pl.sweep_on && pl.sweep_dirdot && pl.qfree &&
+                           (s->diag.mode == 0 || s->diag.mode == 3);
+    pl.walk_started = s->p_pending;
+    // Virtual first direction (round 3; SCHWZ_CG_P0VIRTUAL=0: stored as before).  A solve that started in the walk
+    // has p0 = D^-1 r0 with D^-1 uniform or absent, and r0 is in memory: the first-direction launch then stores
+    // nothing (windows and the sums of p0.(A p0) only), the first update walk builds its windows from r0 x D^-1 and
+    // writes r1 to the OTHER residual buffer, and r0 -- intact -- serves as p0 for the first fused direction launch
+    // and for the x update.  16 n bytes per solve less (the p0 store and one p0 read), the same bits: every reader
+    // forms the same rounded product D^-1 r0 the store would have held.
+    pl.p0_virtual = env_on("SCHWZ_CG_P0VIRTUAL") && pl.walk_started && all_walks && pl.deferx && !pl.general &&
+                    max_iters >= 2;
+    // The last iteration of a solve of exactly max_iters iterations (rtol == 0: no stopping test can fire), x
+    // deferred: what its result needs is alpha = rho / (p.Ap) and x += alpha p, and both happen inside the last x
+    // update.  The residual update r -= alpha A p with rho' and ||r||^2, and the state advance, produce nothing
+    // anybody reads -- the next solve starts from b - A y -- unless the caller asks for the iteration count or
+    // the residual norm: they are postponed (schwz_pcg::lazy, pcg_finish_lazy) instead of launched.  Same x bit
+    // for bit.  SCHWZ_CG_LAZYLAST=0: every iteration is launched in full.
+    pl.lazy_last = env_on("SCHWZ_CG_LAZYLAST") && rtol == 0.0 && pl.deferx && !pl.general && max_iters > 0;
+    // ... and the direction of that last iteration is never stored (round 3; SCHWZ_CG_PLASTVIRTUAL=0: stored): its
+    // only readers are the x update -- which rebuilds it from the direction before it, which it reads anyway, and
+    // the current residual: the same fma the fused direction launch performed -- and the postponed update launch,
+    // which gets it rebuilt first (cg_rebuild_direction_kernel).  8 n bytes of stores per solve less.
+    pl.vlast = pl.lazy_last && env_on("SCHWZ_CG_PLASTVIRTUAL") && max_iters >= 2 && all_walks;
+    // Small systems are bound by launches, not bytes (33 k rows: 3 launches of ~3 us work each):
+    // kGraphIters iterations are captured once per (x, rtol, plan) into a hipGraph -- on a private stream,
+    // the caller's may be the legacy default stream -- and replayed.  SCHWZ_CG_GRAPH=0 disables,
+    // =2 uses graphs for every size.
+    static const int graph_mode = env_mode("SCHWZ_CG_GRAPH", 1);
+    pl.graph = graph_mode != 0 && !pl.general && !g_prof.on && !pl.deferx && (graph_mode == 2 || s->n <= kGraphRows) &&
+               max_iters >= kGraphIters;
+}
+
+// the bits of schwz_pcg_flavour (include/schwz_hip.h, schwz_pcg::last_flavour)
+static int pcg_plan_flavour(const CgPlan &pl, int diag_mode)
+{
+    return (!pl.qfree ? 0 : (pl.fusedir ? 2 : 1)) | (pl.deferx ? 4 : 0) |
+           (pl.sweep_on && pl.deferx && diag_mode != 2 ? 8 : 0) | (pl.sweep_dirdot && pl.fusedir ? 16 : 0) |
+           (pl.walk_started ? 32 : 0) | (pl.p0_virtual ? 64 : 0) | (pl.vlast ? 128 : 0);
+}
+
+// The buffers the plan needs beyond those of pcg_build, allocated at their first use: the direction ring with
+// its alphas (deferred x) and the second residual (virtual first direction).  Without room for them the plan
+// falls back: no ring -- false, ring_failed is set and the caller plans again (the plain iteration); no second
+// residual -- the stored first direction.
+static bool pcg_acquire_buffers(schwz_pcg *s, CgPlan &pl)
+{
+    const size_t nb = (size_t)((s->n + 1) & ~int64_t(1)) * sizeof(double);
+    if (pl.deferx && !s->p_ring) {
+        s->ring_has_q = pl.qfree;
+        if (hipMalloc((void **)&s->p_ring, nb * (kDeferDepth - (pl.qfree ? 2 : 1))) != hipSuccess ||
+            hipMalloc((void **)&s->alpha_hist, kDeferDepth * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(s->p_ring);
+            s->p_ring = nullptr;
+            s->ring_failed = true;
+            return false;
+        }
+    }
+    if (pl.p0_virtual && !s->r_alt && hipMalloc((void **)&s->r_alt, nb) != hipSuccess) {
+        (void)hipGetLastError();
+        s->r_alt = nullptr;
+        pl.p0_virtual = false;
+    }
+    return true;
 }
 
 // First half of a solve: r = b - A x, p = M^-1 r, rho, ||r||^2 -> CgState.  With
@@ -1073,7 +1156,10 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
               int64_t row_limit, hipStream_t st)
 {
     const CsrView &A = s->A->v;
-    const int gs = spmv_grid(A, s->variant);
+    s->plan = pcg_plan_matrix(s);
+    if (!pcg_acquire_buffers(s, s->plan)) s->plan = pcg_plan_matrix(s);
+    const CgPlan &pl = s->plan;
+    const int gs = pl.gs;
     s->lazy.pending = false;  // nobody asked for the last solve's final residual: it is recomputed from b - A x now
     SpmvArgs a;
     a.x = d_x;
@@ -1086,27 +1172,23 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
     a.row_limit = row_limit;
     // x2 == x over all rows: the check residual IS the start residual (rr bank)
     const bool same = fused && d_x2 == nullptr && row_limit >= s->n;
-    if (pcg_is_general(s)) a.dinv = nullptr;  // p := r for now, z follows
-    if (!pcg_is_general(s) && A.pair_id && s->variant == 0 && s->diag.mode == 3) {
+    if (pl.general) a.dinv = nullptr;  // p := r for now, z follows
+    if (!pl.general && A.pair_id && s->variant == 0 && s->diag.mode == 3) {
         // row-pair kernel: a uniform Jacobi diagonal travels as a scalar, not as a vector of n equal values
         a.dinv = nullptr;
         a.diag_mode = 3;
         a.diag_uniform = s->diag.uniform;
     }
-    // the start launch in the z-sweep walk where the whole solve runs in it (not with the second product of
-    // the fused check residual, which the walk does not have)
-    s->p_pending = false;
-    // (with the second product of the fused check residual only where the upload built its plane flags)
-    const bool walk_start = !pcg_is_general(s) && (a.diag_mode == 3 || !a.dinv) &&
-                            (!(fused && !same) || pair_sweep_dual_ok(A, gs));
-    if (walk_start && pcg_plan(s).sweep_start) {
+    // the start launch in the z-sweep walk where the whole solve runs in it (with the second product of the
+    // fused check residual only where the upload built its plane flags)
+    s->p_pending = pl.sweep_start && (a.diag_mode == 3 || !a.dinv) && (!(fused && !same) || pair_sweep_dual_ok(A, gs));
+    if (s->p_pending) {
         a.sweep_init = 1;
         a.p = nullptr;
-        s->p_pending = true;
     }
     int rc = launch_spmv(A, (fused && !same) ? kSpmvResidDual : kSpmvResidInit, a, s->variant, st);
     if (rc) return rc;
-    if (pcg_is_general(s)) {
+    if (pl.general) {
         // the check-residual norm (bank 1 or 2 of the SpMV partials) first, then z = M^-1 r,
         // p = z and rho = r.z, ||r||^2 from the vector-kernel partials
         if (fused) {
@@ -1127,349 +1209,376 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
     return SCHWZ_OK;
 }
 
+namespace {
+
+// One launch between a pair of HIP events when this is the live solve and bench.py's roofline leg is
+// listening (schwz_profile_begin); kind: 0 = a launch that yields p.(A p), 1 = an update launch
+template <class Launch>
+int profiled(bool live, int kind, hipStream_t q, Launch &&launch)
+{
+    const bool prof = live && g_prof.on && g_prof.used + 2 <= g_prof.ev.size();
+    if (prof) SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used], q));
+    const int rc = launch();
+    if (rc) return rc;
+    if (prof) {
+        SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used + 1], q));
+        g_prof.kind[g_prof.used / 2] = kind;
+        g_prof.used += 2;
+    }
+    return SCHWZ_OK;
+}
+
+// The launches of one solve: the plan, what pcg_iterate was given, and one function per step.  `live` marks
+// the launches of the solve itself as opposed to those recorded into a graph: only they know which iteration
+// is the last one (recorded graphs replay mid-solve) and only they are profiled.
+struct CgSolve {
+    schwz_pcg *const s;
+    const CgPlan pl;
+    double *const d_x;
+    const double rtol;
+    const int max_iters;
+    const hipStream_t st;  // the caller's stream
+    const CsrView &A;
+    const int64_t n;
+    const int gs, gv;
+    double *const part_spmv;  // [3][gs]
+    double *const part_vec;   // [2][gv]
+    const int lazy_it;        // the iteration whose update launch is postponed, -1: none
+    FlushX fx;
+    double *pbuf[2];          // x updated in the launches: p alternates between these with the fused direction launch
+    bool prio_recorded = false;
+
+    CgSolve(schwz_pcg *s_, const CgPlan &pl_, double *x, double rtol_, int max_iters_, hipStream_t st_)
+        : s(s_), pl(pl_), d_x(x), rtol(rtol_), max_iters(max_iters_), st(st_), A(s_->A->v), n(s_->n), gs(pl_.gs),
+          gv(pl_.gv), part_spmv(s_->partials), part_vec(s_->partials + 3 * kMaxGrid),
+          lazy_it(pl_.lazy_last ? max_iters_ - 1 : -1)
+    {
+        const int64_t n_pad = (n + 1) & ~int64_t(1);
+        for (int k = 0; k < kDeferDepth; ++k)
+            fx.ring.slot[k] = k == 0 ? s->p
+                                     : (!s->p_ring ? s->p
+                                                   : (s->ring_has_q ? (k == 1 ? s->q : s->p_ring + (int64_t)(k - 2) * n_pad)
+                                                                    : s->p_ring + (int64_t)(k - 1) * n_pad));
+        // virtual first direction: p0 = p0_scale x r0, and slot 0 is r0 where the start launch left it (a later
+        // direction 16, 32, ... simply lands there: r0 is done with by then)
+        if (pl.p0_virtual) fx.ring.slot[0] = s->r;
+        fx.n = n;
+        fx.x = d_x;
+        fx.alpha_hist = s->alpha_hist;
+        fx.st = s->state;
+        fx.fused = pl.qfree ? 0 : 1;  // how the in-launch update of this iteration forms x + alpha p
+        fx.pq_partials = part_spmv;   // p.(A p) of the last iteration: SpMV bank 0, gs slots
+        fx.pq_nparts = gs;
+        fx.x2_src = s->x2_src;
+        fx.x2_total = s->x2_total;
+        fx.p0_scale = pl.p0_virtual && s->diag.mode != 0 ? s->diag.uniform : 1.0;
+        fx.dmode = s->diag.mode;
+        fx.dsc = s->diag.uniform;
+        pbuf[0] = s->p;
+        pbuf[1] = pl.fusedir ? s->q : s->p;
+    }
+
+    double *slot(int it) const { return const_cast<double *>(fx.ring.slot[it % kDeferDepth]); }
+
+    // x += sum alpha_k p_k over the iterations [b0, b0 + count) (cg_flush_x_kernel); `last`: this launch finishes x
+    void flush_x(int b0, int count, int pending, hipStream_t q, bool last)
+    {
+        const int64_t n2 = n >> 1;
+        // the second output, the alpha of the postponed update and the never-stored last direction only from the
+        // launches that finish x
+        FlushXLast fl;
+        fl.vlast_r = s->r;
+        if (last) {
+            fl.x2 = s->x2_out;
+            fl.x2_rows = s->x2_rows;
+            fl.lazy_it = lazy_it;
+            fl.vlast_it = pl.vlast ? lazy_it : -1;
+        }
+        auto launch = [&](int grid, int64_t pair0, int64_t pair1, int tail) {
+            hipLaunchKernelGGL(cg_flush_x_kernel, dim3(grid), dim3(kBlock), 0, q, fx, fl, b0, count, pending, pair0, pair1, tail);
+        };
+        if (last && s->prio_on && s->prio_event && q == st && !prio_recorded) {
+            // the caller's priority rows first, the event, then the rest (the same bits: every element is
+            // updated by exactly one lane of exactly one of the launches)
+            const int64_t lo = std::min(s->prio_lo >> 1, n2), hi = std::max(std::min(s->prio_hi >> 1, n2), lo);
+            if (lo > 0) launch(grid_for(lo), 0, lo, 0);
+            // (this launch also copies the entries of x2 beyond the solve's vector -- the halo of x~, two planes of a
+            // slab --, element by element over its whole grid: sized for that too.  With one workgroup, which is what
+            // the upper priority range of a subdomain without an upper neighbour asks for, that copy took 0.44 ms.)
+            const int64_t tail_items = fl.x2 ? std::max<int64_t>(s->x2_total - 2 * n2, 0) : 0;
+            launch(std::max(grid_for(n2 - hi + 1), grid_for(tail_items)), hi, n2, 1);
+            if (hipEventRecord(s->prio_event, q) == hipSuccess) prio_recorded = true;
+            if (hi > lo) launch(grid_for(hi - lo), lo, hi, 0);
+        } else {
+            launch(gv, 0, n2, 1);
+        }
+        if (fl.x2) s->x2_written = true;
+    }
+
+    // the ring is full after iteration `it`: its kDeferDepth increments go into x before slot (it + 1) % depth,
+    // the oldest direction, is overwritten
+    void flush_full_ring(int it, hipStream_t q, bool last)
+    {
+        if ((it + 1) % kDeferDepth == 0) flush_x(it + 1 - kDeferDepth, kDeferDepth, it, q, last);
+    }
+
+    // p.(A p) on its own launch (every iteration without the fused direction launch)
+    int launch_dot(int it, hipStream_t q, bool live)
+    {
+        SpmvArgs a;
+        a.x = pl.deferx ? slot(it) : s->p;
+        a.y = s->q;
+        a.partials = part_spmv;
+        a.stop_iter = &s->state->stop_iter;
+        a.it = it;
+        return profiled(live, 0, q, [&] { return launch_spmv(A, pl.dot_mode, a, s->variant, q); });
+    }
+
+    // q = A p is never stored: the update pass recomputes (A p)_i row by row while it streams x and r
+    // (spmv_pair.hip, kSpmvCgUpdate): 16 B per row less HBM traffic, a third of the stores of these two launches
+    SpmvArgs qfree_update_args(int it, bool first_virtual) const
+    {
+        SpmvArgs u;
+        u.x = pl.deferx ? slot(it) : pbuf[it & 1];
+        u.cg_x = pl.deferx ? nullptr : d_x;
+        u.alpha_out = pl.deferx ? s->alpha_hist + it % kDeferDepth : nullptr;
+        u.cg_r = s->r;
+        u.cg_state = s->state;
+        u.pq_partials = part_spmv;
+        u.pq_nparts = gs;
+        u.diag_mode = s->diag.mode;
+        u.diag_uniform = s->diag.uniform;
+        u.dinv = s->dinv;
+        u.partials = part_vec;
+        u.it = it;
+        u.walk = pl.sweep_on && pl.deferx;
+        if (first_virtual) {
+            u.ring_scale = fx.p0_scale;  // windows = ring_scale x r0 (u.x: slot 0) = p0
+            u.cg_r_out = s->r_alt;
+            u.p0_virtual = 1;
+        }
+        return u;
+    }
+
+    // p' = z + beta p into the other buffer and the partial sums of p'.(A p') for the next iteration
+    int launch_fused_direction(int it, hipStream_t q, bool live, bool first_virtual)
+    {
+        SpmvArgs f;
+        f.x = pl.deferx ? slot(it) : pbuf[it & 1];
+        f.y = pl.deferx ? slot(it + 1) : pbuf[(it + 1) & 1];
+        f.cg_r = s->r;
+        f.cg_state = s->state;
+        f.pq_partials = part_vec;
+        f.pq_nparts = gs;
+        f.diag_mode = s->diag.mode;
+        f.diag_uniform = s->diag.uniform;
+        f.dinv = s->dinv;
+        f.partials = part_spmv;
+        f.it = it;
+        f.cg_rtol = rtol;
+        f.walk = pl.sweep_dirdot;
+        if (first_virtual) {
+            f.p_scale = fx.p0_scale;  // p0 = p_scale x r0 (f.x: slot 0)
+            f.p0_virtual = 1;
+        }
+        if (pl.vlast && live && it + 1 == lazy_it) {
+            f.y = nullptr;     // windows and sums only: nobody reads this direction from memory
+            f.p0_virtual = 1;  // (walk kernels only)
+        }
+        const int mode = s->diag.mode == 1 ? kSpmvDirDotSymVec : kSpmvDirDotSym;
+        return profiled(live, 0, q, [&] { return launch_spmv(A, mode, f, s->variant, q); });
+    }
+
+    // r -= alpha q, alpha to the history, x and p untouched: the update of the stored-q iteration with x deferred
+    void launch_update_deferred(int it, hipStream_t q) const
+    {
+        hipLaunchKernelGGL((cg_update_kernel<1, false, true>), dim3(gv), dim3(kBlock), 0, q, n, (double *)nullptr, s->r,
+                           (const double *)nullptr, s->q, s->diag, part_spmv, gs, s->state, it, part_vec,
+                           s->alpha_hist + it % kDeferDepth);
+    }
+
+    // partial sums per bank the update launch leaves: it ran on the SpMV grid (q-free) or on the vector grid
+    int update_parts() const { return pl.qfree ? gs : gv; }
+
+    // The residual update and the state advance of iteration `it`, the last one, wait until somebody asks
+    // (schwz_pcg::lazy, pcg_finish_lazy).  The postponed launches outlive this object: they carry a copy of it.
+    void postpone_last(int it, hipStream_t q)
+    {
+        s->lazy_run = [*this, it](hipStream_t qq) -> int {
+            if (pl.qfree) {
+                // the update launch reads its direction from memory: one that was never stored is rebuilt first
+                if (pl.vlast)
+                    hipLaunchKernelGGL(cg_rebuild_direction_kernel, dim3(gv), dim3(kBlock), 0, qq, n,
+                                       (const double *)slot(it > 0 ? it - 1 : 0), it == 1 ? fx.p0_scale : 1.0,
+                                       (const double *)s->r, s->diag.mode, s->diag.uniform, (const CgState *)s->state, it,
+                                       slot(it));
+                const int rc = launch_spmv(A, kSpmvCgUpdate, qfree_update_args(it, false), s->variant, qq);
+                if (rc) return rc;
+            } else {
+                launch_update_deferred(it, qq);
+            }
+            hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, qq, part_vec, update_parts(), s->state, it,
+                               rtol);
+            SCHWZ_HIP_TRY(hipGetLastError());
+            return SCHWZ_OK;
+        };
+        s->lazy.pending = true;
+        s->lazy.stream = q;
+    }
+
+    // What follows the update launch of an iteration with x deferred: the x update when the ring is full, then the
+    // new direction into the next ring slot -- after the last iteration of a solve, where nobody reads it, only
+    // the state (cg_state_advance_kernel), and nothing at all when that iteration's update is postponed.
+    void close_deferred(int it, hipStream_t q, bool lazy_now, bool last)
+    {
+        flush_full_ring(it, q, last);
+        if (lazy_now)
+            postpone_last(it, q);
+        else if (last)
+            hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, q, part_vec, update_parts(), s->state, it,
+                               rtol);
+        else
+            hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, slot(it), s->r, s->diag,
+                               part_vec, update_parts(), s->state, it, rtol, slot(it + 1));
+    }
+
+    // q-free iteration (row-pair coded matrices): the update launch, then the fused direction + p.(A p) launch
+    // or the direction kernel
+    int iterate_qfree(int it, hipStream_t q, bool live)
+    {
+        const bool first_virtual = pl.p0_virtual && live && it == 0;
+        const bool lazy_now = live && it == lazy_it, last = live && it == max_iters - 1;
+        const SpmvArgs u = qfree_update_args(it, first_virtual);
+        int rc;
+        if (!lazy_now && (rc = profiled(live, 1, q, [&] { return launch_spmv(A, kSpmvCgUpdate, u, s->variant, q); })))
+            return rc;
+        if (first_virtual) std::swap(s->r, s->r_alt);  // r1 (and every later residual) lives in the other buffer
+        if (pl.fusedir && !last) {
+            // (the last iteration of a solve only needs the direction kernel's state update)
+            if (pl.deferx) flush_full_ring(it, q, false);
+            return launch_fused_direction(it, q, live, first_virtual);
+        }
+        if (pl.deferx)
+            close_deferred(it, q, lazy_now, last);
+        else
+            hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, pbuf[it & 1], s->r,
+                               s->diag, part_vec, gs, s->state, it, rtol);
+        return SCHWZ_OK;
+    }
+
+    // stored q, x deferred: r -= alpha q (24 n bytes instead of 48-56 n), alpha to the history, the new
+    // direction into the next ring slot
+    int iterate_stored_deferred(int it, hipStream_t q, bool live)
+    {
+        const bool lazy_now = live && it == lazy_it;
+        if (!lazy_now) launch_update_deferred(it, q);
+        close_deferred(it, q, lazy_now, live && it == max_iters - 1);
+        return SCHWZ_OK;
+    }
+
+    // stored q, x updated in the launch.  Scalar Jacobi or no preconditioner: z = D^-1 r inside the vector kernels.
+    // General preconditioner: x, r update without one; z = M^-1 r; rho' = r.z; p = z + beta p.
+    int iterate_stored(int it, hipStream_t q)
+    {
+        const DiagView none;
+        const DiagView &dg = pl.general ? none : s->diag;
+        hipLaunchKernelGGL((cg_update_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, d_x, s->r, s->p, s->q, dg,
+                           part_spmv, gs, s->state, it, part_vec);
+        const int gz = pl.general ? grid_for(n) : gv;
+        if (pl.general) {
+            const int rc = pcg_apply_general(s, q);
+            if (rc) return rc;
+            hipLaunchKernelGGL(dot_rz_kernel, dim3(gz), dim3(kBlock), 0, q, n, s->r, s->z, (double *)nullptr, s->state, it,
+                               part_vec);
+        }
+        hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, s->p, pl.general ? s->z : s->r,
+                           dg, part_vec, gz, s->state, it, rtol);
+        return SCHWZ_OK;
+    }
+
+    // one CG iteration on stream `q`; `it` only enters through its parity (rho slot) and through
+    // "it >= stop_iter", and stop_iter is 0 once the tolerance test has fired: a recorded sequence
+    // of an even number of iterations can therefore be replayed as a hipGraph
+    int iterate(int it, hipStream_t q, bool live)
+    {
+        int rc;
+        if (!pl.fusedir && (rc = launch_dot(it, q, live))) return rc;
+        if (pl.qfree) return iterate_qfree(it, q, live);
+        return pl.deferx ? iterate_stored_deferred(it, q, live) : iterate_stored(it, q);
+    }
+
+    // the recorded run of kGraphIters iterations for this (x, rtol, plan): found, or captured now; *out stays
+    // null where capture or instantiation is refused (the solve then launches one by one)
+    int graph_for_solve(hipGraphExec_t *out)
+    {
+        for (const auto &g : s->graphs)
+            if (g.x == d_x && g.rtol == rtol && g.variant == s->variant && g.flavour == pl.flavour) *out = g.exec;
+        if (*out || s->graphs.size() >= 4) return SCHWZ_OK;
+        if (!s->capture_stream) SCHWZ_HIP_TRY(hipStreamCreateWithFlags(&s->capture_stream, hipStreamNonBlocking));
+        if (hipStreamBeginCapture(s->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            int rc = SCHWZ_OK;
+            for (int k = 0; k < kGraphIters && !rc; ++k) rc = iterate(k, s->capture_stream, false);
+            hipGraph_t graph = nullptr;
+            const hipError_t e1 = hipStreamEndCapture(s->capture_stream, &graph);
+            if (rc) {
+                if (graph) (void)hipGraphDestroy(graph);
+                return rc;
+            }
+            if (e1 == hipSuccess && hipGraphInstantiate(out, graph, nullptr, nullptr, 0) == hipSuccess)
+                s->graphs.push_back({d_x, rtol, s->variant, pl.flavour, *out});
+            else
+                *out = nullptr;
+            if (graph) (void)hipGraphDestroy(graph);
+        }
+        (void)hipGetLastError();
+        return SCHWZ_OK;
+    }
+
+    // p0.(A p0): every later p.(A p) comes out of the fused direction launch
+    int first_dot()
+    {
+        SpmvArgs a;
+        a.partials = part_spmv;
+        a.it = 0;
+        if (!pl.walk_started) {
+            a.x = s->p;
+            a.stop_iter = &s->state->stop_iter;
+            return launch_spmv(A, kSpmvDotSym, a, s->variant, st);
+        }
+        // z-sweep start: p0 = D^-1 r0 is built here, from the r the launch reads anyway
+        a.y = pl.p0_virtual ? nullptr : slot(0);
+        a.cg_r = s->r;
+        a.cg_state = s->state;
+        a.diag_mode = s->diag.mode;
+        a.diag_uniform = s->diag.uniform;
+        a.sweep_first = 1;
+        return launch_spmv(A, kSpmvDirDotSym, a, s->variant, st);
+    }
+};
+
+}  // namespace
+
 // Second half: up to max_iters CG updates.  With a positive tolerance the host
 // looks at the state every `chunk` iterations, one chunk behind the launches, so
 // the queue never drains.
 int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream_t st)
 {
-    const CsrView &A = s->A->v;
-    const int64_t n = s->n;
-    const int gs = spmv_grid(A, s->variant);
-    const int gv = grid_for((n + 1) / 2);
-    double *part_spmv = s->partials;                // [3][gs]
-    double *part_vec = s->partials + 3 * kMaxGrid;  // [2][gv]
-    const bool poll = rtol > 0.0;
-    const bool general = pcg_is_general(s);
-    const CgPlan plan = pcg_plan(s);
-    const bool qfree = plan.qfree, sweep_on = plan.sweep_on, sweep_dirdot = plan.sweep_dirdot, fusedir = plan.fusedir;
-    const bool deferx = plan.deferx;
-    const int dot_mode = plan.dot_mode, flavour = plan.flavour;
-    s->last_flavour = flavour | (deferx ? 4 : 0) | (sweep_on && deferx && s->diag.mode != 2 ? 8 : 0) |
-                      (sweep_dirdot && fusedir ? 16 : 0) | (s->p_pending ? 32 : 0);
-    // Virtual first direction (round 3; SCHWZ_CG_P0VIRTUAL=0: stored as before).  A solve that started in the walk
-    // has p0 = D^-1 r0 with D^-1 uniform or absent, and r0 is in memory: the first-direction launch then stores
-    // nothing (windows and the sums of p0.(A p0) only), the first update walk builds its windows from r0 x D^-1 and
-    // writes r1 to the OTHER residual buffer, and r0 -- intact -- serves as p0 for the first fused direction launch
-    // and for the x update.  16 n bytes per solve less (the p0 store and one p0 read), the same bits: every reader
-    // forms the same rounded product D^-1 r0 the store would have held.
-    const char *p0_env = std::getenv("SCHWZ_CG_P0VIRTUAL");  // read per solve: tests switch it
-    bool p0_virtual = !(p0_env && p0_env[0] == '0') && s->p_pending && fusedir && plan.sweep_start && sweep_on &&
-                      sweep_dirdot && qfree && deferx && !general && max_iters >= 2 &&
-                      (s->diag.mode == 0 || s->diag.mode == 3);
-    if (p0_virtual && !s->r_alt) {
-        const size_t nb = (size_t)((n + 1) & ~int64_t(1)) * sizeof(double);
-        if (hipMalloc((void **)&s->r_alt, nb) != hipSuccess) {
-            (void)hipGetLastError();
-            s->r_alt = nullptr;
-            p0_virtual = false;  // no room for the second residual: the stored form
-        }
-    }
-    const double p0_scale = p0_virtual && s->diag.mode != 0 ? s->diag.uniform : 1.0;
-    if (p0_virtual) s->last_flavour |= 64;
-    double *const r0_vec = s->r;  // where the start launch left r0
-    PRing ring;
-    const int64_t n_pad = (n + 1) & ~int64_t(1);
-    for (int k = 0; k < kDeferDepth; ++k)
-        ring.slot[k] = k == 0 ? s->p
-                                : (!s->p_ring ? s->p
-                                              : (s->ring_has_q ? (k == 1 ? s->q : s->p_ring + (int64_t)(k - 2) * n_pad)
-                                                               : s->p_ring + (int64_t)(k - 1) * n_pad));
-    if (p0_virtual) ring.slot[0] = r0_vec;  // (a later direction 16, 32, ... simply lands there: r0 is done with by then)
-    auto slot = [&](int it) -> double * { return const_cast<double *>(ring.slot[it % kDeferDepth]); };
-    bool prio_recorded = false;
-    const int fused_x = qfree ? 0 : 1;  // how the in-launch update of this iteration forms x + alpha p
-    // The last iteration of a solve of exactly max_iters iterations (rtol == 0: no stopping test can fire), x
-    // deferred: what its result needs is alpha = rho / (p.Ap) and x += alpha p, and both happen inside the last x
-    // update.  The residual update r -= alpha A p with rho' and ||r||^2, and the state advance, produce nothing
-    // anybody reads -- the next solve starts from b - A y -- unless the caller asks for the iteration count or
-    // the residual norm: they are postponed (schwz_pcg::lazy, pcg_finish_lazy) instead of launched.  Same x bit
-    // for bit.  SCHWZ_CG_LAZYLAST=0: every iteration is launched in full.
-    const char *lazy_env = std::getenv("SCHWZ_CG_LAZYLAST");  // read per solve: tests switch it
-    const bool lazy_on = !(lazy_env && lazy_env[0] == '0');
-    const char *ld_env0 = std::getenv("SCHWZ_CG_LASTDIR");
-    const bool lazy_last = lazy_on && rtol == 0.0 && deferx && !general && max_iters > 0 && !(ld_env0 && ld_env0[0] == '1');
-    const int lazy_it = lazy_last ? max_iters - 1 : -1;
-    const double *const lazy_pq = part_spmv;  // p.(A p) of the last iteration: SpMV bank 0, gs slots
-    // ... and the direction of that last iteration is never stored (round 3; SCHWZ_CG_PLASTVIRTUAL=0: stored): its
-    // only readers are the x update -- which rebuilds it from the direction before it, which it reads anyway, and
-    // the current residual: the same fma the fused direction launch performed -- and the postponed update launch,
-    // which gets it rebuilt first (cg_rebuild_direction_kernel).  8 n bytes of stores per solve less.
-    const char *pl_env = std::getenv("SCHWZ_CG_PLASTVIRTUAL");
-    const bool vlast_on = lazy_last && !(pl_env && pl_env[0] == '0') && max_iters >= 2 && fusedir && sweep_dirdot &&
-                          sweep_on && qfree && plan.sweep_start && (s->diag.mode == 0 || s->diag.mode == 3);
-    if (vlast_on) s->last_flavour |= 128;
-    s->x2_written = false;
-    auto flush_x = [&](int b0, int count, int pending, hipStream_t q, bool last = false) {
-        const int64_t n2 = n >> 1;
-        // the second output only from the launches that finish x (`last`)
-        double *const x2 = last ? s->x2_out : nullptr;
-        const int64_t x2_rows = last ? s->x2_rows : 0;
-        const int lz = last ? lazy_it : -1;
-        const int vl = last && vlast_on ? lazy_it : -1;  // the never-stored last direction (see vlast_on)
-        const double *const vlast_r = s->r;
-        if (last && s->prio_on && s->prio_event && q == st && !prio_recorded) {
-            // the caller's priority rows first, the event, then the rest (the same bits: every element is
-            // updated by exactly one lane of exactly one of the launches)
-            const int64_t lo = std::min(s->prio_lo >> 1, n2), hi = std::max(std::min(s->prio_hi >> 1, n2), lo);
-            if (lo > 0)
-                hipLaunchKernelGGL(cg_flush_x_kernel, dim3(grid_for(lo)), dim3(kBlock), 0, q, n, d_x, ring, s->alpha_hist,
-                                   s->state, b0, count, pending, (int64_t)0, lo, 0, fused_x, lz, lazy_pq, gs, x2, x2_rows, s->x2_src, s->x2_total, p0_scale, vl, vlast_r, s->diag.mode, s->diag.uniform);
-            // (this launch also copies the entries of x2 beyond the solve's vector -- the halo of x~, two planes of a
-            // slab --, element by element over its whole grid: sized for that too.  With one workgroup, which is what
-            // the upper priority range of a subdomain without an upper neighbour asks for, that copy took 0.44 ms.)
-            const int64_t tail_items = x2 ? std::max<int64_t>(s->x2_total - 2 * n2, 0) : 0;
-            hipLaunchKernelGGL(cg_flush_x_kernel, dim3(std::max(grid_for(n2 - hi + 1), grid_for(tail_items))), dim3(kBlock), 0, q, n, d_x, ring,
-                               s->alpha_hist, s->state, b0, count, pending, hi, n2, 1, fused_x, lz, lazy_pq, gs, x2, x2_rows, s->x2_src, s->x2_total, p0_scale, vl, vlast_r, s->diag.mode, s->diag.uniform);
-            if (hipEventRecord(s->prio_event, q) == hipSuccess) prio_recorded = true;
-            if (hi > lo)
-                hipLaunchKernelGGL(cg_flush_x_kernel, dim3(grid_for(hi - lo)), dim3(kBlock), 0, q, n, d_x, ring,
-                                   s->alpha_hist, s->state, b0, count, pending, lo, hi, 0, fused_x, lz, lazy_pq, gs, x2, x2_rows, s->x2_src, s->x2_total, p0_scale, vl, vlast_r, s->diag.mode, s->diag.uniform);
-            if (x2) s->x2_written = true;
-            return;
-        }
-        hipLaunchKernelGGL(cg_flush_x_kernel, dim3(gv), dim3(kBlock), 0, q, n, d_x, ring, s->alpha_hist, s->state, b0,
-                           count, pending, (int64_t)0, n2, 1, fused_x, lz, lazy_pq, gs, x2, x2_rows, s->x2_src, s->x2_total, p0_scale, vl, vlast_r, s->diag.mode, s->diag.uniform);
-        if (x2) s->x2_written = true;
-    };
-    double *const pbuf[2] = {s->p, fusedir ? s->q : s->p};
-    // SCHWZ_CG_LASTDIR=1: the last iteration of a solve updates the search direction like every other one
-    const char *ld_env = std::getenv("SCHWZ_CG_LASTDIR");
-    const bool last_state_only = !(ld_env && ld_env[0] == '1');
-    // one CG iteration on stream `q`; `it` only enters through its parity (rho slot) and through
-    // "it >= stop_iter", and stop_iter is 0 once the tolerance test has fired: a recorded sequence
-    // of an even number of iterations can therefore be replayed as a hipGraph
-    auto launch_iteration = [&](int it, hipStream_t q, bool instrument) -> int {
-        SpmvArgs a;
-        a.x = deferx ? slot(it) : s->p;
-        a.y = s->q;
-        a.partials = part_spmv;
-        a.stop_iter = &s->state->stop_iter;
-        a.it = it;
-        const bool prof = instrument && g_prof.on && g_prof.used + 2 <= g_prof.ev.size();
-        int rc = SCHWZ_OK;
-        if (!fusedir) {
-            if (prof) SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used], q));
-            if ((rc = launch_spmv(A, dot_mode, a, s->variant, q))) return rc;
-            if (prof) {
-                SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used + 1], q));
-                g_prof.kind[g_prof.used / 2] = 0;
-                g_prof.used += 2;
-            }
-        }
-        if (qfree) {
-            // q = A p is never stored: the update pass recomputes (A p)_i row by row while it
-            // streams x and r (spmv_pair.hip, kSpmvCgUpdate): 16 B per row less HBM traffic, a
-            // third of the stores of these two launches
-            SpmvArgs u;
-            u.x = deferx ? slot(it) : pbuf[it & 1];
-            u.cg_x = deferx ? nullptr : d_x;
-            u.alpha_out = deferx ? s->alpha_hist + it % kDeferDepth : nullptr;
-            u.cg_r = s->r;
-            u.cg_state = s->state;
-            u.pq_partials = part_spmv;
-            u.pq_nparts = gs;
-            u.diag_mode = s->diag.mode;
-            u.diag_uniform = s->diag.uniform;
-            u.dinv = s->dinv;
-            u.partials = part_vec;
-            u.it = it;
-            const bool first_virtual = p0_virtual && instrument && it == 0;
-            if (first_virtual) {
-                u.x = r0_vec;  // windows = ring_scale x r0 = p0
-                u.ring_scale = p0_scale;
-                u.cg_r_out = s->r_alt;
-                u.p0_virtual = 1;
-            }
-            const bool lazy_now = instrument && it == lazy_it;
-            const bool prof2 = !lazy_now && instrument && g_prof.on && g_prof.used + 2 <= g_prof.ev.size();
-            if (prof2) SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used], q));
-            if (!lazy_now && (rc = launch_spmv(A, kSpmvCgUpdate, u, s->variant, q))) return rc;
-            if (first_virtual) std::swap(s->r, s->r_alt);  // r1 (and every later residual) lives in the other buffer
-            if (prof2) {
-                SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used + 1], q));
-                g_prof.kind[g_prof.used / 2] = 1;
-                g_prof.used += 2;
-            }
-            if (fusedir && !(instrument && it == max_iters - 1)) {
-                // p' = z + beta p into the other buffer and the partial sums of p'.(A p') for the next
-                // iteration (the last iteration of a solve only needs the direction kernel's state
-                // update; recorded graphs replay mid-solve, so they keep the fused launch)
-                if (deferx && (it + 1) % kDeferDepth == 0) flush_x(it + 1 - kDeferDepth, kDeferDepth, it, q);
-                SpmvArgs f;
-                f.x = deferx ? slot(it) : pbuf[it & 1];
-                f.y = deferx ? slot(it + 1) : pbuf[(it + 1) & 1];
-                f.cg_r = s->r;
-                f.cg_state = s->state;
-                f.pq_partials = part_vec;
-                f.pq_nparts = gs;
-                f.diag_mode = s->diag.mode;
-                f.diag_uniform = s->diag.uniform;
-                f.dinv = s->dinv;
-                f.partials = part_spmv;
-                f.it = it;
-                f.cg_rtol = rtol;
-                if (first_virtual) {
-                    f.x = r0_vec;  // p0 = p_scale x r0
-                    f.p_scale = p0_scale;
-                    f.p0_virtual = 1;
-                }
-                if (vlast_on && instrument && it + 1 == lazy_it) {
-                    f.y = nullptr;     // windows and sums only: nobody reads this direction from memory
-                    f.p0_virtual = 1;  // (walk kernels only)
-                }
-                const bool prof3 = instrument && g_prof.on && g_prof.used + 2 <= g_prof.ev.size();
-                if (prof3) SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used], q));
-                if ((rc = launch_spmv(A, s->diag.mode == 1 ? kSpmvDirDotSymVec : kSpmvDirDotSym, f, s->variant, q)))
-                    return rc;
-                if (prof3) {
-                    SCHWZ_HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used + 1], q));
-                    g_prof.kind[g_prof.used / 2] = 0;
-                    g_prof.used += 2;
-                }
-            } else if (deferx) {
-                // the ring is full: apply its kDeferDepth increments before slot (it + 1) % depth,
-                // the oldest direction, is overwritten
-                if ((it + 1) % kDeferDepth == 0) flush_x(it + 1 - kDeferDepth, kDeferDepth, it, q, instrument && it == max_iters - 1);
-                if (lazy_now) {
-                    // the residual update and the state advance of this iteration wait until somebody asks
-                    const CsrView Av = A;
-                    const int variant = s->variant;
-                    double *const pv = part_vec;
-                    const bool rebuild = vlast_on;
-                    const double *const p_prev = slot(it - 1 >= 0 ? it - 1 : 0);
-                    const double prev_scale = it == 1 ? p0_scale : 1.0;
-                    double *const p_last = slot(it);
-                    const int gvv = gv;
-                    const int64_t nn = n;
-                    s->lazy_run = [Av, u, variant, pv, gs, s, it, rtol, rebuild, p_prev, prev_scale, p_last, gvv, nn](hipStream_t qq) -> int {
-                        if (rebuild)
-                            hipLaunchKernelGGL(cg_rebuild_direction_kernel, dim3(gvv), dim3(kBlock), 0, qq, nn, p_prev, prev_scale,
-                                               (const double *)s->r, s->diag.mode, s->diag.uniform, (const CgState *)s->state, it, p_last);
-                        const int rc2 = launch_spmv(Av, kSpmvCgUpdate, u, variant, qq);
-                        if (rc2) return rc2;
-                        hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, qq, pv, gs, s->state, it, rtol);
-                        SCHWZ_HIP_TRY(hipGetLastError());
-                        return SCHWZ_OK;
-                    };
-                    s->lazy.pending = true;
-                    s->lazy.it = it;
-                    s->lazy.rtol = rtol;
-                    s->lazy.stream = q;
-                } else if (instrument && it == max_iters - 1 && last_state_only)  // nobody reads the direction after the last iteration
-                    hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, q, part_vec, gs, s->state, it, rtol);
-                else
-                    hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, slot(it), s->r,
-                                       s->diag, part_vec, gs, s->state, it, rtol, slot(it + 1));
-            } else {
-                hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, pbuf[it & 1], s->r,
-                                   s->diag, part_vec, gs, s->state, it, rtol);
-            }
-        } else if (!general && deferx) {
-            // stored q, x deferred: r -= alpha q (24 n bytes instead of 48-56 n), alpha to the history, the new
-            // direction into the next ring slot; the last iteration of a solve only advances the state
-            const bool lazy_now = instrument && it == lazy_it;
-            if (!lazy_now)
-                hipLaunchKernelGGL((cg_update_kernel<1, false, true>), dim3(gv), dim3(kBlock), 0, q, n, (double *)nullptr, s->r,
-                                   (const double *)nullptr, s->q, s->diag, part_spmv, gs, s->state, it, part_vec,
-                                   s->alpha_hist + it % kDeferDepth);
-            if ((it + 1) % kDeferDepth == 0) flush_x(it + 1 - kDeferDepth, kDeferDepth, it, q, instrument && it == max_iters - 1);
-            if (lazy_now) {
-                double *const ps = part_spmv, *const pv = part_vec;
-                s->lazy_run = [s, n, gv, gs, ps, pv, it, rtol](hipStream_t qq) -> int {
-                    hipLaunchKernelGGL((cg_update_kernel<1, false, true>), dim3(gv), dim3(kBlock), 0, qq, n, (double *)nullptr,
-                                       s->r, (const double *)nullptr, s->q, s->diag, ps, gs, s->state, it, pv,
-                                       s->alpha_hist + it % kDeferDepth);
-                    hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, qq, pv, gv, s->state, it, rtol);
-                    SCHWZ_HIP_TRY(hipGetLastError());
-                    return SCHWZ_OK;
-                };
-                s->lazy.pending = true;
-                s->lazy.it = it;
-                s->lazy.rtol = rtol;
-                s->lazy.stream = q;
-            } else if (instrument && it == max_iters - 1 && last_state_only)
-                hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, q, part_vec, gv, s->state, it, rtol);
-            else
-                hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, slot(it), s->r,
-                                   s->diag, part_vec, gv, s->state, it, rtol, slot(it + 1));
-        } else if (!general) {
-            hipLaunchKernelGGL((cg_update_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, d_x, s->r, s->p, s->q,
-                               s->diag, part_spmv, gs, s->state, it, part_vec);
-            hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, s->p, s->r, s->diag,
-                               part_vec, gv, s->state, it, rtol);
-        } else {
-            // x, r update without a preconditioner; z = M^-1 r; rho' = r.z; p = z + beta p
-            const DiagView none;
-            const int gz = grid_for(n);
-            hipLaunchKernelGGL((cg_update_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, d_x, s->r, s->p, s->q,
-                               none, part_spmv, gs, s->state, it, part_vec);
-            if ((rc = pcg_apply_general(s, q))) return rc;
-            hipLaunchKernelGGL(dot_rz_kernel, dim3(gz), dim3(kBlock), 0, q, n, s->r, s->z, (double *)nullptr, s->state,
-                               it, part_vec);
-            hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, s->p, s->z, none,
-                               part_vec, gz, s->state, it, rtol);
-        }
-        return SCHWZ_OK;
-    };
-    // Small systems are bound by launches, not bytes (33 k rows: 3 launches of ~3 us work each):
-    // kGraphIters iterations are captured once per (x, rtol) into a hipGraph -- on a private stream,
-    // the caller's may be the legacy default stream -- and replayed.  SCHWZ_CG_GRAPH=0 disables,
-    // =2 uses graphs for every size.
-    static const int graph_mode = [] {
-        const char *e = std::getenv("SCHWZ_CG_GRAPH");
-        return e ? std::atoi(e) : 1;
-    }();
-    const bool graphable = graph_mode != 0 && !general && !g_prof.on && !deferx && (graph_mode == 2 || n <= kGraphRows);
-    hipGraphExec_t replay = nullptr;
-    if (graphable && max_iters >= kGraphIters) {
-        for (const auto &g : s->graphs)
-            if (g.x == d_x && g.rtol == rtol && g.variant == s->variant && g.qfree == flavour) replay = g.exec;
-        if (!replay && s->graphs.size() < 4) {
-            if (!s->capture_stream) SCHWZ_HIP_TRY(hipStreamCreateWithFlags(&s->capture_stream, hipStreamNonBlocking));
-            if (hipStreamBeginCapture(s->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                int rc = SCHWZ_OK;
-                for (int k = 0; k < kGraphIters && !rc; ++k) rc = launch_iteration(k, s->capture_stream, false);
-                hipGraph_t graph = nullptr;
-                const hipError_t e1 = hipStreamEndCapture(s->capture_stream, &graph);
-                if (rc) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    return rc;
-                }
-                if (e1 == hipSuccess && hipGraphInstantiate(&replay, graph, nullptr, nullptr, 0) == hipSuccess)
-                    s->graphs.push_back({d_x, rtol, s->variant, flavour, replay});
-                else
-                    replay = nullptr;
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();
-        }
-    }
-    if (s->p_pending && !(fusedir && plan.sweep_start)) {
+    CgPlan pl = s->plan;
+    pcg_plan_solve(s, pl, rtol, max_iters);
+    (void)pcg_acquire_buffers(s, pl);  // (the ring is pcg_begin's; here: the second residual)
+    pl.flavour = pcg_plan_flavour(pl, s->diag.mode);
+    s->last_flavour = pl.flavour;
+    if (pl.walk_started && !(pl.fusedir && pl.sweep_start)) {
         set_error("pcg_iterate: the start launch left p to a first-direction launch this solve does not run");
         return SCHWZ_ERR_INVALID;
     }
-    if (fusedir && max_iters > 0) {
-        // p0.(A p0): every later p.(A p) comes out of the fused direction launch
-        SpmvArgs a;
-        a.partials = part_spmv;
-        a.it = 0;
-        int rc;
-        if (s->p_pending) {
-            // z-sweep start: p0 = D^-1 r0 is built here, from the r the launch reads anyway
-            a.y = p0_virtual ? nullptr : slot(0);
-            a.cg_r = s->r;
-            a.cg_state = s->state;
-            a.diag_mode = s->diag.mode;
-            a.diag_uniform = s->diag.uniform;
-            a.sweep_first = 1;
-            rc = launch_spmv(A, kSpmvDirDotSym, a, s->variant, st);
-        } else {
-            a.x = s->p;
-            a.stop_iter = &s->state->stop_iter;
-            rc = launch_spmv(A, kSpmvDotSym, a, s->variant, st);
-        }
-        if (rc) return rc;
-    }
+    CgSolve cg(s, pl, d_x, rtol, max_iters, st);
+    const bool poll = rtol > 0.0;
+    s->x2_written = false;
+    int rc;
+    hipGraphExec_t replay = nullptr;
+    if (pl.graph && (rc = cg.graph_for_solve(&replay))) return rc;
+    if (pl.fusedir && max_iters > 0 && (rc = cg.first_dot())) return rc;
     s->p_pending = false;
     int chunk = 16;
     int it = 0, pending = -1, bank = 0;
@@ -1482,8 +1591,7 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
                 it += kGraphIters;
                 continue;
             }
-            int rc = launch_iteration(it, st, true);
-            if (rc) return rc;
+            if ((rc = cg.iterate(it, st, true))) return rc;
             ++it;
         }
         SCHWZ_HIP_TRY(hipGetLastError());
@@ -1501,19 +1609,19 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
     }
     // the increments of the last, partly filled ring (iterations past a tolerance stop are not
     // counted by CgState::iters and add nothing)
-    if (deferx && it % kDeferDepth != 0) {
-        flush_x(it - it % kDeferDepth, it % kDeferDepth, -1, st, true);
+    if (pl.deferx && it % kDeferDepth != 0) {
+        cg.flush_x(it - it % kDeferDepth, it % kDeferDepth, -1, st, true);
         SCHWZ_HIP_TRY(hipGetLastError());
     }
     // second output asked for, but no launch above was the last x update (ring just emptied, a stop between two
     // rings, no iteration at all): a launch that adds nothing and copies
-    if (deferx && s->x2_out && !s->x2_written) {
-        flush_x(it, 0, -1, st, true);
+    if (pl.deferx && s->x2_out && !s->x2_written) {
+        cg.flush_x(it, 0, -1, st, true);
         SCHWZ_HIP_TRY(hipGetLastError());
     }
     // priority rows without a split update (x updated inside the iteration, or no iteration at all): final
     // behind the last launch
-    if (s->prio_on && s->prio_event && !prio_recorded) SCHWZ_HIP_TRY(hipEventRecord(s->prio_event, st));
+    if (s->prio_on && s->prio_event && !cg.prio_recorded) SCHWZ_HIP_TRY(hipEventRecord(s->prio_event, st));
     return SCHWZ_OK;
 }
 

@@ -376,6 +376,9 @@ struct SpmvArgs {
     double ring_scale = 1.0;
     double *cg_r_out = nullptr;
     double p_scale = 1.0;
+    // kSpmvCgUpdate / kSpmvDirDotSym: whoever planned the launch wants the z-sweep walk (cg.hip's plan, from
+    // pair_sweep_update_ok / pair_sweep_dirdot_ok); launch_spmv_pair reads no switch of its own
+    int walk = 0;
 };
 
 // launch grid of the streaming vector kernels: one lane per element up to kMaxGrid workgroups
@@ -404,8 +407,11 @@ int launch_spmv_stream_ablate(const CsrView &A, const SpmvArgs &a, int abl, hipS
 // the measurement variants of schwz_csr_spmv (tools/probes/spmv_variants.hip): null in the product library
 typedef int (*SpmvProbeHook)(const CsrView &A, int mode, const SpmvArgs &a, int variant, int grid, hipStream_t s);
 extern SpmvProbeHook g_spmv_probe_hook;
-bool pair_sweep_start_ok(const CsrView &A, int grid);
-bool pair_sweep_dual_ok(const CsrView &A, int grid);
+// who may take the z-sweep walk (spmv_pair.hip): asked by launch_spmv_pair and by the plan of a CG solve
+bool pair_sweep_update_ok(const CsrView &A, int grid, int diag_mode);  // kSpmvCgUpdate that leaves x alone
+bool pair_sweep_dirdot_ok(const CsrView &A, int grid, int diag_mode);  // kSpmvDirDotSym
+bool pair_sweep_start_ok(const CsrView &A, int grid);                  // start launch + first direction
+bool pair_sweep_dual_ok(const CsrView &A, int grid);                   // ... with the fused check residual
 
 // Jacobi scaling as the CG vector kernels see it.  The full 1/diag vector costs 8 B per row and
 // per kernel; matrices with few distinct diagonal values (every stencil) get a 1-byte code per
@@ -450,6 +456,27 @@ int csr_set_dual_split(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_c
 
 struct schwz_pcg;
 namespace schwz {
+// How a CG solve runs, every decision of it (cg.hip).  pcg_begin fills the part that follows from the matrix,
+// the preconditioner and the switches and keeps it in schwz_pcg::plan; pcg_iterate completes its copy once
+// rtol, max_iters and the outcome of the start launch are known.
+struct CgPlan {
+    bool general = false;       // block-Jacobi / ILU / ISAI: z = M^-1 r is an operator of its own
+    bool qfree = false;         // row-pair coded matrix: q = A p is recomputed, never stored
+    int dot_mode = kSpmvDot;    // launch that yields p.(A p)
+    bool sweep_on = false;      // z-sweep walk of the update launch (where x is deferred)
+    bool sweep_dirdot = false;  // ... and of the fused direction + p.(A p) launch
+    bool fusedir = false;       // two launches per iteration
+    bool deferx = false;        // x += sum alpha_k p_k applied once per kDeferDepth iterations
+    bool sweep_start = false;   // the solve can start in the walk too (INIT / FIRST forms, spmv_pair.hip)
+    int gs = 0, gv = 0;         // grids of the SpMV launches and of the vector kernels
+    // completed by pcg_iterate
+    bool walk_started = false;  // the start launch ran in the walk and left p to the first-direction launch
+    bool p0_virtual = false;    // the first direction is never stored
+    bool lazy_last = false;     // the update launch of the last iteration is postponed
+    bool vlast = false;         // ... and its direction never stored
+    bool graph = false;         // runs of kGraphIters iterations are replayed as a hipGraph
+    int flavour = 0;            // what schwz_pcg_flavour reports (bits: schwz_pcg::last_flavour)
+};
 int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fused, const double *d_x2,
               int64_t row_limit, hipStream_t st);
 int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream_t st);
@@ -523,7 +550,7 @@ struct schwz_pcg {
         double *x;
         double rtol;
         int variant;
-        int qfree;  // 0 stored q, 1 q-free (3 launches), 2 q-free with the fused direction + dot launch
+        int flavour;  // CgPlan::flavour of the solve that recorded it (which launches the graph holds)
         hipGraphExec_t exec;
     };
     std::vector<Captured> graphs;
@@ -535,6 +562,7 @@ struct schwz_pcg {
     bool ring_has_q = true;  // slot 1 of the ring is s->q (q-free iteration); false: the stored-q iteration's ring
     // the start launch of the running solve left p to the first fused direction launch (z-sweep start)
     bool p_pending = false;
+    schwz::CgPlan plan;  // of the running solve, as far as pcg_begin decides it
     // Rows the caller wants final FIRST (a subdomain's boundary rows, which its neighbours wait for): the
     // last x update of a solve takes [0, prio_lo) and [prio_hi, n) ahead of the rest and records prio_event
     // in between, so that the halo pack + send can run beside the remaining update (schwz_ras_pack_early).
@@ -555,8 +583,6 @@ struct schwz_pcg {
     // drops them.
     struct LazyLast {
         bool pending = false;
-        int it = 0;
-        double rtol = 0.0;
         hipStream_t stream = nullptr;
     } lazy;
     std::function<int(hipStream_t)> lazy_run;
@@ -564,7 +590,7 @@ struct schwz_pcg {
     hipEvent_t prio_event = nullptr;
     // how the last solve iterated: bits 0-1: 0 stored q, 1 q-free (three launches), 2 q-free with the fused
     // direction + p.(A p) launch; 4: deferred x update; 8: z-sweep walk of the update launch; 16: of the fused launch;
-    // 32: of the start launch and the first direction as well
+    // 32: of the start launch and the first direction as well; 64 / 128: first / last direction never stored
     int last_flavour = 0;
 };
 

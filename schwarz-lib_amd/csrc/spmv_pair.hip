@@ -1205,18 +1205,52 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     }
 }
 
+// ---- who may take the z-sweep walk: one definition per launch, asked by launch_spmv_pair and by the CG plan ----
+
+// what the launches raise the walk kernels' dynamic-LDS limit to
+constexpr size_t kSweepLdsLimit = 96 << 10;
+
+// dynamic LDS of the update / start walk on bands of T rows: the ring (4 T own + 4 NX halo doubles) and the
+// nine-slot tables of every pattern
+static size_t sweep_update_lds(int64_t T, int64_t nx, int npat)
+{
+    return (size_t)(4 * T + 4 * nx) * sizeof(double) + (size_t)npat * (9 * 16 + 4);
+}
+
+// ... of the fused direction walk: its window carries the halo of r and p, its tables the upper triangle's five slots
+static size_t sweep_dirdot_lds(int64_t T_dir, int64_t nx, int npat)
+{
+    return (size_t)(4 * T_dir + ((SCHWZ_DD & 2) ? 3 : 2) * nx) * sizeof(double) + (size_t)npat * (5 * 16 + 4);
+}
+
+// whether a kSpmvCgUpdate launch that leaves x alone (cg_x == nullptr) can take the walk: single-table coding,
+// 32-bit byte offsets of x, the Jacobi diagonal absent, a scalar or a full vector, segments and companion
+// workgroups within the partial-sum slots, an instantiation for the pieces per lane (own: T / 512, halo:
+// NX / 256) and its LDS within the limit
+bool pair_sweep_update_ok(const CsrView &A, int grid, int diag_mode)
+{
+    const int nh = A.sweep_T / kPairRows, nhl = (A.sweep_nx + kBlock - 1) / kBlock;
+    return A.pair_single && A.sweep_nslots > 0 && A.ncols < (int64_t(1) << 28) && diag_mode != 2 &&
+           A.sweep_nslots + A.sweep_gen_blocks <= grid && (nh == 1 || nh == 2) && nhl <= 4 &&
+           sweep_update_lds(A.sweep_T, A.sweep_nx, A.canon_npat) <= kSweepLdsLimit;
+}
+
+// ... and the fused direction + p.(A p) launch (kSpmvDirDotSym): a matrix whose update launch walks, symmetric
+// tables, the diagonal absent or a scalar, the direction table within the slots, its own instantiations and LDS
+bool pair_sweep_dirdot_ok(const CsrView &A, int grid, int diag_mode)
+{
+    const int nh = A.sweep_T_dir / kPairRows, nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock;
+    return pair_sweep_update_ok(A, grid, diag_mode) && A.canon_sym_val && diag_mode != 1 &&
+           A.sweep_nslots_dir + A.sweep_gen_blocks <= grid && (nh == 1 || nh == 2 || nh == 4) && nhl <= 2 &&
+           sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat) <= kSweepLdsLimit;
+}
+
 // whether a solve on this matrix can START in the z-sweep walk: the INIT form of the update walk and the
-// FIRST form of the fused direction walk exist for the shapes below, and only where the walk covers
-// every row (no companion launch: cubes and z-slab subdomains)
+// FIRST form of the fused direction walk exist for the shapes both walks take, and only where the walk covers
+// every row (no companion launch: cubes and z-slab subdomains); the caller checks the diagonal
 bool pair_sweep_start_ok(const CsrView &A, int grid)
 {
-    if (!(A.pair_single && A.sweep_nslots > 0 && A.canon_sym_val && A.sweep_gen_blocks == 0 && A.sweep_nslots <= grid &&
-          A.ncols < (int64_t(1) << 28)))
-        return false;
-    const int nh = A.sweep_T / kPairRows, nh_dir = A.sweep_T_dir / kPairRows;
-    const int nhl_upd = (A.sweep_nx + kBlock - 1) / kBlock, nhl_dir = (A.sweep_nx / 2 + kBlock - 1) / kBlock;
-    return (nh == 1 || nh == 2) && (nh_dir == 1 || nh_dir == 2 || nh_dir == 4) && nhl_upd <= 4 && nhl_dir <= 2 &&
-           A.sweep_nslots_dir <= grid;
+    return A.sweep_gen_blocks == 0 && pair_sweep_dirdot_ok(A, grid, 0);
 }
 
 // ... and with the fused dual residual: the flagged planes' chunk list exists and its launch fits the
@@ -1227,34 +1261,74 @@ bool pair_sweep_dual_ok(const CsrView &A, int grid)
            A.sweep_nslots + A.dual_blocks <= grid;
 }
 
-// One instantiation of the z-sweep update / start walk: raises its dynamic-LDS limit once, launches it.
-// false: the device does not grant 96 KiB of dynamic LDS to the kernel (nothing was launched).
-template <int L_, int H_, bool DV, bool INIT, bool DUAL, int RUNS>
-static bool launch_sweep_instance(const CsrView &A, const SpmvArgs &b, size_t lds, hipStream_t s)
+// One instantiation of a z-sweep walk kernel, one workgroup per segment slot: raises its dynamic-LDS limit once,
+// launches it.  false: the device does not grant 96 KiB of dynamic LDS to the kernel (nothing was launched).
+template <void (*KERNEL)(CsrView, SpmvArgs)>
+static bool launch_walk_kernel(int nslots, const CsrView &A, const SpmvArgs &b, size_t lds, hipStream_t s)
 {
-    static const hipError_t e = hipFuncSetAttribute((const void *)spmv_pair_sweep_kernel<L_, H_, DV, INIT, DUAL, RUNS>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);
-    if (e != hipSuccess || lds > (size_t)(96 << 10)) return false;
-    hipLaunchKernelGGL((spmv_pair_sweep_kernel<L_, H_, DV, INIT, DUAL, RUNS>), dim3(A.sweep_nslots), dim3(kBlock), lds, s, A, b);
+    static const hipError_t e = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                    kSweepLdsLimit);
+    if (e != hipSuccess || lds > kSweepLdsLimit) return false;
+    hipLaunchKernelGGL(KERNEL, dim3(nslots), dim3(kBlock), lds, s, A, b);
     return true;
 }
 
-// ... chosen by the run-length record of the matrix (8 / 16 runs per chunk)
+// The update / start walk: the instantiation by the run-length record of the matrix (8 / 16 runs per chunk)
 template <int L_, int H_, bool DV, bool INIT, bool DUAL>
 static bool launch_sweep_variant(const CsrView &A, const SpmvArgs &b, size_t lds, hipStream_t s)
 {
     if (A.sweep_gen_mode) {
         // planes that are not whole chunks (byte ids, partial last band); no dual form there
         if (DUAL) return false;
-        return launch_sweep_instance<L_, H_, DV, INIT, false, 0>(A, b, lds, s);
+        return launch_walk_kernel<spmv_pair_sweep_kernel<L_, H_, DV, INIT, false, 0>>(A.sweep_nslots, A, b, lds, s);
     }
-    return A.pair_rle_runs == 16 ? launch_sweep_instance<L_, H_, DV, INIT, DUAL, 16>(A, b, lds, s)
-                                 : launch_sweep_instance<L_, H_, DV, INIT, DUAL, 8>(A, b, lds, s);
+    return A.pair_rle_runs == 16
+               ? launch_walk_kernel<spmv_pair_sweep_kernel<L_, H_, DV, INIT, DUAL, 16>>(A.sweep_nslots, A, b, lds, s)
+               : launch_walk_kernel<spmv_pair_sweep_kernel<L_, H_, DV, INIT, DUAL, 8>>(A.sweep_nslots, A, b, lds, s);
+}
+
+// ... and by the halo / own pieces per lane (pair_sweep_update_ok has checked that the instantiation exists)
+template <bool DV, bool INIT, bool DUAL>
+static bool launch_update_walk(const CsrView &A, const SpmvArgs &b, hipStream_t s)
+{
+    const int nhl = (A.sweep_nx + kBlock - 1) / kBlock, nh = A.sweep_T / kPairRows;
+    const size_t lds = sweep_update_lds(A.sweep_T, A.sweep_nx, A.canon_npat);
+    if (nh == 1)
+        return nhl == 1   ? launch_sweep_variant<1, 1, DV, INIT, DUAL>(A, b, lds, s)
+               : nhl == 2 ? launch_sweep_variant<2, 1, DV, INIT, DUAL>(A, b, lds, s)
+                          : launch_sweep_variant<4, 1, DV, INIT, DUAL>(A, b, lds, s);
+    return nhl == 1   ? launch_sweep_variant<1, 2, DV, INIT, DUAL>(A, b, lds, s)
+           : nhl == 2 ? launch_sweep_variant<2, 2, DV, INIT, DUAL>(A, b, lds, s)
+                      : launch_sweep_variant<4, 2, DV, INIT, DUAL>(A, b, lds, s);
+}
+
+// The same two steps for the fused direction walk (FIRST: the first direction of a solve that started in
+// the walk) over the direction table of the view it is given.
+template <int L_, int H_, bool FIRST>
+static bool launch_dirdot_variant(const CsrView &A, const SpmvArgs &b, size_t lds, hipStream_t s)
+{
+    const int nslots = A.sweep_nslots_dir;
+    if (A.sweep_gen_mode) return launch_walk_kernel<spmv_pair_dirdot_sweep_kernel<L_, H_, FIRST, 0>>(nslots, A, b, lds, s);
+    return A.pair_rle_runs == 16 ? launch_walk_kernel<spmv_pair_dirdot_sweep_kernel<L_, H_, FIRST, 16>>(nslots, A, b, lds, s)
+                                 : launch_walk_kernel<spmv_pair_dirdot_sweep_kernel<L_, H_, FIRST, 8>>(nslots, A, b, lds, s);
+}
+
+template <bool FIRST>
+static bool launch_dirdot_walk(const CsrView &A, const SpmvArgs &b, hipStream_t s)
+{
+    const int nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock, nh = A.sweep_T_dir / kPairRows;
+    const size_t lds = sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat);
+    if (nh == 1)
+        return nhl == 1 ? launch_dirdot_variant<1, 1, FIRST>(A, b, lds, s) : launch_dirdot_variant<2, 1, FIRST>(A, b, lds, s);
+    if (nh == 2)
+        return nhl == 1 ? launch_dirdot_variant<1, 2, FIRST>(A, b, lds, s) : launch_dirdot_variant<2, 2, FIRST>(A, b, lds, s);
+    return nhl == 1 ? launch_dirdot_variant<1, 4, FIRST>(A, b, lds, s) : launch_dirdot_variant<2, 4, FIRST>(A, b, lds, s);
 }
 
 int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hipStream_t s)
 {
     const bool wide = A.ncols >= (int64_t(1) << 28);  // byte offsets of x beyond 32 bits
+    const char *const no_lds = "launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device";
     if ((mode == kSpmvResidInit || mode == kSpmvResidDual) && a.sweep_init) {
         // CG start in the z-sweep walk (pcg_begin asks for it only where pair_sweep_start_ok holds and the
         // Jacobi diagonal is a scalar or absent): r = b - A x to a.y, partial r.z and r.r; p is not written
@@ -1262,8 +1336,6 @@ int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
             set_error("launch_spmv_pair: the z-sweep start launch does not apply to this matrix");
             return SCHWZ_ERR_INVALID;
         }
-        const int nhl = (A.sweep_nx + kBlock - 1) / kBlock, nh = A.sweep_T / kPairRows;
-        const size_t lds = (size_t)(4 * A.sweep_T + 4 * A.sweep_nx) * sizeof(double) + (size_t)A.canon_npat * (9 * 16 + 4);
         SpmvArgs b = a;
         b.part_stride = grid;
         b.part_offset = 0;
@@ -1274,21 +1346,10 @@ int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
             set_error("launch_spmv_pair: the z-sweep dual start launch does not apply to this matrix");
             return SCHWZ_ERR_INVALID;
         }
-#define SCHWZ_SWEEP_INIT(L_, H_)                                                                              \
-    ok = with_dual ? launch_sweep_variant<L_, H_, false, true, true>(A, b, lds, s)                            \
-                   : launch_sweep_variant<L_, H_, false, true, false>(A, b, lds, s);
-        bool ok = false;
-        if (nh == 1 && nhl == 1) SCHWZ_SWEEP_INIT(1, 1)
-        else if (nh == 1 && nhl == 2) SCHWZ_SWEEP_INIT(2, 1)
-        else if (nh == 2 && nhl == 1) SCHWZ_SWEEP_INIT(1, 2)
-        else if (nh == 2 && nhl == 2) SCHWZ_SWEEP_INIT(2, 2)
-        else if (nh == 1) SCHWZ_SWEEP_INIT(4, 1)
-        else SCHWZ_SWEEP_INIT(4, 2)
-        if (!ok) {
-            set_error("launch_spmv_pair: the z-sweep kernels cannot have their dynamic LDS on this device");
+        if (!(with_dual ? launch_update_walk<false, true, true>(A, b, s) : launch_update_walk<false, true, false>(A, b, s))) {
+            set_error(no_lds);
             return SCHWZ_ERR_HIP;
         }
-#undef SCHWZ_SWEEP_INIT
         SCHWZ_HIP_TRY(hipGetLastError());
         if (with_dual) {
             // ||b - A x2||^2 over the flagged planes: chunk by chunk on x2, partial sums into the third bank
@@ -1309,159 +1370,76 @@ int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
     }
     if (mode == kSpmvDirDotSym && a.sweep_first) {
         // first direction of such a solve: p' = D^-1 r and the partial sums of p'.(A p'), CgState untouched
-        const CsrView &A_in = A;
         if (!pair_sweep_start_ok(A, grid) || a.diag_mode == 1 || a.diag_mode == 2) {
             set_error("launch_spmv_pair: the z-sweep first-direction launch does not apply to this matrix");
             return SCHWZ_ERR_INVALID;
         }
         // (the kernel reads its segments from sweep_seg_dir: this launch gets a view whose direction table IS the
         // first-direction table)
-        CsrView Af = A_in;
-        if (A_in.sweep_seg_first && A_in.sweep_nslots_first <= grid) {
-            Af.sweep_T_dir = A_in.sweep_T_first;
-            Af.sweep_seg_dir = A_in.sweep_seg_first;
-            Af.sweep_nslots_dir = A_in.sweep_nslots_first;
+        CsrView Af = A;
+        if (A.sweep_seg_first && A.sweep_nslots_first <= grid) {
+            Af.sweep_T_dir = A.sweep_T_first;
+            Af.sweep_seg_dir = A.sweep_seg_first;
+            Af.sweep_nslots_dir = A.sweep_nslots_first;
         }
-        const CsrView &A = Af;
-        const int nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock, nh = A.sweep_T_dir / kPairRows;
-        const size_t lds = (size_t)(4 * A.sweep_T_dir + ((SCHWZ_DD & 2) ? 3 : 2) * A.sweep_nx) * sizeof(double) + (size_t)A.canon_npat * (5 * 16 + 4);
         SpmvArgs b = a;
         b.part_stride = grid;
         b.part_offset = 0;
-#define SCHWZ_DIRDOT_FIRST(L_, H_)                                                                                        \
-    {                                                                                                                    \
-        static const hipError_t e0 = hipFuncSetAttribute((const void *)spmv_pair_dirdot_sweep_kernel<L_, H_, true>,      \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);          \
-        if (e0 != hipSuccess) {                                                                                          \
-            set_error("launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device");         \
-            return SCHWZ_ERR_HIP;                                                                                        \
-        }                                                                                                                \
-        if (A.sweep_gen_mode) {                                                                                          \
-            static const hipError_t e3 = hipFuncSetAttribute((const void *)spmv_pair_dirdot_sweep_kernel<L_, H_, true, 0>, \
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);      \
-            if (e3 != hipSuccess) {                                                                                      \
-                set_error("launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device");     \
-                return SCHWZ_ERR_HIP;                                                                                    \
-            }                                                                                                            \
-            hipLaunchKernelGGL((spmv_pair_dirdot_sweep_kernel<L_, H_, true, 0>), dim3(A.sweep_nslots_dir), dim3(kBlock), lds, s, A, b); \
-        } else if (A.pair_rle_runs == 16) {                                                                              \
-            static const hipError_t e2 = hipFuncSetAttribute((const void *)spmv_pair_dirdot_sweep_kernel<L_, H_, true, 16>, \
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);      \
-            if (e2 != hipSuccess) {                                                                                      \
-                set_error("launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device");     \
-                return SCHWZ_ERR_HIP;                                                                                    \
-            }                                                                                                            \
-            hipLaunchKernelGGL((spmv_pair_dirdot_sweep_kernel<L_, H_, true, 16>), dim3(A.sweep_nslots_dir), dim3(kBlock), lds, s, A, b); \
-        } else                                                                                                           \
-            hipLaunchKernelGGL((spmv_pair_dirdot_sweep_kernel<L_, H_, true>), dim3(A.sweep_nslots_dir), dim3(kBlock), lds, s, A, b); \
-    }
-        if (nh == 1 && nhl == 1) SCHWZ_DIRDOT_FIRST(1, 1)
-        else if (nh == 1) SCHWZ_DIRDOT_FIRST(2, 1)
-        else if (nh == 2 && nhl == 1) SCHWZ_DIRDOT_FIRST(1, 2)
-        else if (nh == 2) SCHWZ_DIRDOT_FIRST(2, 2)
-        else if (nhl == 1) SCHWZ_DIRDOT_FIRST(1, 4)
-        else SCHWZ_DIRDOT_FIRST(2, 4)
-#undef SCHWZ_DIRDOT_FIRST
+        if (!launch_dirdot_walk<true>(Af, b, s)) {
+            set_error(no_lds);
+            return SCHWZ_ERR_HIP;
+        }
         SCHWZ_HIP_TRY(hipGetLastError());
         return SCHWZ_OK;
     }
-    if (mode == kSpmvCgUpdate && !wide && A.pair_single && A.sweep_nslots > 0 && !a.cg_x && a.diag_mode != 2 &&
-        A.sweep_nslots + A.sweep_gen_blocks <= grid) {
-        const char *sweep_env = std::getenv("SCHWZ_CG_SWEEP");  // read per launch: tests switch it
-        if (!(sweep_env && sweep_env[0] == '0')) {
-            // z-sweep walk + (where boundary planes or overlap rows exist) the listed walk of the chunks it
-            // leaves out; the consumer folds `grid` partial sums per bank, as after a chunk-by-chunk launch
-            const int nhl = (A.sweep_nx + kBlock - 1) / kBlock, nh = A.sweep_T / kPairRows;  // halo / own pieces per lane
-            const size_t lds = (size_t)(4 * A.sweep_T + 4 * A.sweep_nx) * sizeof(double) + (size_t)A.canon_npat * (9 * 16 + 4);
-            SpmvArgs b = a;
-            b.part_stride = grid;
-            b.part_offset = A.sweep_gen_blocks;  // slots of the companion launch follow this one's
-            const bool dv = a.diag_mode == 1;
-#define SCHWZ_SWEEP_LAUNCH(L_, H_)                                                                   \
-    launched = dv ? launch_sweep_variant<L_, H_, true, false, false>(A, b, lds, s)                 \
-                  : launch_sweep_variant<L_, H_, false, false, false>(A, b, lds, s);
-            bool launched = true;  // false: no such instantiation, or no LDS for it -- chunk by chunk then
-            if (nh == 1 && nhl == 1) SCHWZ_SWEEP_LAUNCH(1, 1)
-            else if (nh == 1 && nhl == 2) SCHWZ_SWEEP_LAUNCH(2, 1)
-            else if (nh == 2 && nhl == 1) SCHWZ_SWEEP_LAUNCH(1, 2)
-            else if (nh == 2 && nhl == 2) SCHWZ_SWEEP_LAUNCH(2, 2)
-            else if (nh == 1 && nhl <= 4) SCHWZ_SWEEP_LAUNCH(4, 1)
-            else if (nh == 2 && nhl <= 4) SCHWZ_SWEEP_LAUNCH(4, 2)
-            else launched = false;
-#undef SCHWZ_SWEEP_LAUNCH
-            if (launched) {
+    // a.walk: whoever planned the launch (the plan of a CG solve in cg.hip, from the same predicates) wants the walk.  A plan the matrix
+    // cannot serve is an error; the one thing only this function can find out is the device refusing the LDS.
+    if ((mode == kSpmvCgUpdate && a.walk && (a.cg_x || !pair_sweep_update_ok(A, grid, a.diag_mode))) ||
+        (mode == kSpmvDirDotSym && a.walk && !pair_sweep_dirdot_ok(A, grid, a.diag_mode))) {
+        set_error("launch_spmv_pair: a launch planned for the z-sweep walk cannot take it on this matrix");
+        return SCHWZ_ERR_INVALID;
+    }
+    if (mode == kSpmvCgUpdate && a.walk) {
+        // z-sweep walk + (where boundary planes or overlap rows exist) the listed walk of the chunks it
+        // leaves out; the consumer folds `grid` partial sums per bank, as after a chunk-by-chunk launch
+        SpmvArgs b = a;
+        b.part_stride = grid;
+        b.part_offset = A.sweep_gen_blocks;  // slots of the companion launch follow this one's
+        // false: no LDS for the instantiation -- chunk by chunk then
+        if (a.diag_mode == 1 ? launch_update_walk<true, false, false>(A, b, s) : launch_update_walk<false, false, false>(A, b, s)) {
+            SCHWZ_HIP_TRY(hipGetLastError());
+            if (A.sweep_gen_blocks > 0) {
+                SpmvArgs c = a;
+                c.sweep = 1;
+                c.part_stride = grid;
+                c.part_offset = A.sweep_nslots;
+                hipLaunchKernelGGL((spmv_pair_kernel<kSpmvCgUpdate, false, true>), dim3(A.sweep_gen_blocks), dim3(kBlock),
+                                   kPairTableLds, s, A, c);
                 SCHWZ_HIP_TRY(hipGetLastError());
-                if (A.sweep_gen_blocks > 0) {
-                    SpmvArgs c = a;
-                    c.sweep = 1;
-                    c.part_stride = grid;
-                    c.part_offset = A.sweep_nslots;
-                    hipLaunchKernelGGL((spmv_pair_kernel<kSpmvCgUpdate, false, true>), dim3(A.sweep_gen_blocks), dim3(kBlock),
-                                       kPairTableLds, s, A, c);
-                    SCHWZ_HIP_TRY(hipGetLastError());
-                }
-                return SCHWZ_OK;
             }
+            return SCHWZ_OK;
         }
     }
-    if (mode == kSpmvDirDotSym && !wide && A.pair_single && A.sweep_nslots > 0 && A.canon_sym_val && a.diag_mode != 1 &&
-        a.diag_mode != 2 && A.sweep_nslots_dir + A.sweep_gen_blocks <= grid) {
-        const char *sweep_env = std::getenv("SCHWZ_CG_SWEEP");
-        if (!(sweep_env && sweep_env[0] == '0')) {
-            const int nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock, nh = A.sweep_T_dir / kPairRows;
-            const size_t lds = (size_t)(4 * A.sweep_T_dir + ((SCHWZ_DD & 2) ? 3 : 2) * A.sweep_nx) * sizeof(double) + (size_t)A.canon_npat * (5 * 16 + 4);
-            if (nhl <= 2) {
-                // the companion first: the z-sweep kernel's workgroup 0 advances CgState for both
-                if (A.sweep_gen_blocks > 0) {
-                    SpmvArgs c = a;
-                    c.sweep = 1;
-                    c.part_stride = grid;
-                    c.part_offset = A.sweep_nslots_dir;
-                    hipLaunchKernelGGL((spmv_pair_kernel<kSpmvDirDotSym, false, true>), dim3(A.sweep_gen_blocks), dim3(kBlock),
-                                       kPairTableLds, s, A, c);
-                    SCHWZ_HIP_TRY(hipGetLastError());
-                }
-                SpmvArgs b = a;
-                b.part_stride = grid;
-                b.part_offset = A.sweep_gen_blocks;
-#define SCHWZ_DIRDOT_LAUNCH(L_, H_)                                                                                      \
-    {                                                                                                                    \
-        static const hipError_t e0 = hipFuncSetAttribute((const void *)spmv_pair_dirdot_sweep_kernel<L_, H_>,            \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);          \
-        if (e0 != hipSuccess) {                                                                                          \
-            set_error("launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device");         \
-            return SCHWZ_ERR_HIP;                                                                                        \
-        }                                                                                                                \
-        if (A.sweep_gen_mode) {                                                                                          \
-            static const hipError_t e3 = hipFuncSetAttribute((const void *)spmv_pair_dirdot_sweep_kernel<L_, H_, false, 0>, \
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);      \
-            if (e3 != hipSuccess) {                                                                                      \
-                set_error("launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device");     \
-                return SCHWZ_ERR_HIP;                                                                                    \
-            }                                                                                                            \
-            hipLaunchKernelGGL((spmv_pair_dirdot_sweep_kernel<L_, H_, false, 0>), dim3(A.sweep_nslots_dir), dim3(kBlock), lds, s, A, b); \
-        } else if (A.pair_rle_runs == 16) {                                                                              \
-            static const hipError_t e2 = hipFuncSetAttribute((const void *)spmv_pair_dirdot_sweep_kernel<L_, H_, false, 16>, \
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 << 10);      \
-            if (e2 != hipSuccess) {                                                                                      \
-                set_error("launch_spmv_pair: the z-sweep kernels cannot have 96 KiB of dynamic LDS on this device");     \
-                return SCHWZ_ERR_HIP;                                                                                    \
-            }                                                                                                            \
-            hipLaunchKernelGGL((spmv_pair_dirdot_sweep_kernel<L_, H_, false, 16>), dim3(A.sweep_nslots_dir), dim3(kBlock), lds, s, A, b); \
-        } else                                                                                                           \
-            hipLaunchKernelGGL((spmv_pair_dirdot_sweep_kernel<L_, H_>), dim3(A.sweep_nslots_dir), dim3(kBlock), lds, s, A, b); \
-    }
-                if (nh == 1 && nhl == 1) SCHWZ_DIRDOT_LAUNCH(1, 1)
-                else if (nh == 1) SCHWZ_DIRDOT_LAUNCH(2, 1)
-                else if (nh == 2 && nhl == 1) SCHWZ_DIRDOT_LAUNCH(1, 2)
-                else if (nh == 2) SCHWZ_DIRDOT_LAUNCH(2, 2)
-                else if (nhl == 1) SCHWZ_DIRDOT_LAUNCH(1, 4)
-                else SCHWZ_DIRDOT_LAUNCH(2, 4)
-#undef SCHWZ_DIRDOT_LAUNCH
-                SCHWZ_HIP_TRY(hipGetLastError());
-                return SCHWZ_OK;
-            }
+    if (mode == kSpmvDirDotSym && a.walk) {
+        // the companion first: the z-sweep kernel's workgroup 0 advances CgState for both
+        if (A.sweep_gen_blocks > 0) {
+            SpmvArgs c = a;
+            c.sweep = 1;
+            c.part_stride = grid;
+            c.part_offset = A.sweep_nslots_dir;
+            hipLaunchKernelGGL((spmv_pair_kernel<kSpmvDirDotSym, false, true>), dim3(A.sweep_gen_blocks), dim3(kBlock),
+                               kPairTableLds, s, A, c);
+            SCHWZ_HIP_TRY(hipGetLastError());
         }
+        SpmvArgs b = a;
+        b.part_stride = grid;
+        b.part_offset = A.sweep_gen_blocks;
+        if (!launch_dirdot_walk<false>(A, b, s)) {
+            set_error(no_lds);
+            return SCHWZ_ERR_HIP;
+        }
+        SCHWZ_HIP_TRY(hipGetLastError());
+        return SCHWZ_OK;
     }
     if (a.p0_virtual) {
         // (the chunk-by-chunk kernels read a stored p0; pcg_iterate only asks for the virtual one where the walks apply)
@@ -1753,9 +1731,9 @@ static int build_sweep(schwz_csr *A, int64_t nrows, const PairTable &tb, const P
     // dynamic LDS of the update / start walk: the ring (4 T own + 4 NX halo doubles) and the nine-slot tables of
     // every pattern; the launches raise the kernels' limit to 96 KiB.  Too many patterns for the tall band: the
     // short one; still too much: no walk (the chunk-by-chunk launches take the matrix).
-    auto walk_lds = [&](int t) { return (size_t)(4 * t + 4 * NX) * sizeof(double) + (size_t)tb.npat * (9 * 16 + 4); };
-    if (walk_lds(T) > (size_t)(96 << 10) && T == 1024 && PL % 512 == 0) T = 512;
-    if (walk_lds(T) > (size_t)(96 << 10)) return no_walk("ring and pattern tables exceed 96 KiB of LDS");
+    auto walk_lds = [&](int t) { return sweep_update_lds(t, NX, tb.npat); };
+    if (walk_lds(T) > kSweepLdsLimit && T == 1024 && PL % 512 == 0) T = 512;
+    if (walk_lds(T) > kSweepLdsLimit) return no_walk("ring and pattern tables exceed 96 KiB of LDS");
     if (NX > T) return no_walk("x line longer than a band");  // the halo of a band is NX rows either side: a band holds at least one x line
     const int bands = (int)((PL + T - 1) / T);  // (gen mode: the last band of a plane is partial)
     const int grid = (int)((std::min<int64_t>(ntiles, kMaxGrid) + kXcds - 1) / kXcds) * kXcds;
@@ -1869,7 +1847,7 @@ static int build_sweep(schwz_csr *A, int64_t nrows, const PairTable &tb, const P
     const char *td_env = std::getenv("SCHWZ_SWEEP_TDIR");
     int T_dir = td_env ? std::atoi(td_env) : (T == 512 ? 1024 : T);
     if ((T_dir != 512 && T_dir != 1024 && T_dir != 2048) || (PL % T_dir && !gen_mode) || (gen_mode && PL < T_dir) ||
-        (size_t)(4 * T_dir + ((SCHWZ_DD & 2) ? 3 : 2) * NX) * sizeof(double) + (size_t)tb.npat * 84 > (size_t)(96 << 10))
+        sweep_dirdot_lds(T_dir, NX, tb.npat) > kSweepLdsLimit)
         T_dir = T;
     std::vector<int4> slots_dir;
     if (T_dir != T) {

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Step time of the fixed-work RAS iteration on a large 2-D 5-point Laplacian (the reference's own generator,
 initialization.cpp:214-265), one subdomain: z-sweep walk with the x line as the plane against the chunk-by-chunk
-launches (SCHWZ_CG_SWEEP=0 is read per launch).
+launches (SCHWZ_CG_SWEEP=0 is read per solve).
 
     python tools/walk2d_probe.py [n1d ...]
 """
