@@ -1,8 +1,8 @@
 """Extended-precision references for the GPU tests, in plain numpy.
 
 Everything here is written from the textbook statement of the operation (CSR row sums, forward / backward
-substitution, right-preconditioned MGS-GMRES with Givens rotations, truncated Neumann series, synchronous
-ParILU sweeps) and runs in `np.longdouble`, which has a 64-bit mantissa on x86 (eps = 1.08e-19): 11 bits
+substitution, right-preconditioned MGS-GMRES with Givens rotations, preconditioned CG, truncated Neumann series,
+synchronous ParILU sweeps) and runs in `np.longdouble`, which has a 64-bit mantissa on x86 (eps = 1.08e-19): 11 bits
 more than the float64 the kernels compute in, so a kernel's summation-order error of a few hundred ulp is
 visible against it.  Where `np.longdouble` is no wider than float64 the functions call `pytest.skip`
 instead of quietly comparing float64 with float64.
@@ -252,10 +252,20 @@ def precond_block_jacobi(rp, col, val, block_ptr, dtype=LD):
         slot = np.full(len(sizes), -1, dtype=np.int64)
         slot[ks] = np.arange(len(ks))
         e = np.nonzero(inside & (slot[blk] >= 0))[0]
-        dense = np.zeros((len(ks), s, s), dtype=LD)
-        dense[slot[blk[e]], rows[e] - block_ptr[blk[e]], col[e] - block_ptr[blk[e]]] = np.asarray(val, dtype=LD)[e]
+        exact64 = np.asarray(val).dtype == np.float64
+        dense = np.zeros((len(ks), s, s), dtype=np.float64 if exact64 else LD)
+        dense[slot[blk[e]], rows[e] - block_ptr[blk[e]], col[e] - block_ptr[blk[e]]] = np.asarray(val)[e]
         idx = block_ptr[ks][:, None] + np.arange(s)[None, :]
-        groups.append((idx, _dense_inverse(dense).astype(dtype)))
+        if exact64:   # equal blocks (a stencil matrix has a handful) are eliminated once: the same operations per block
+            seen, back = {}, np.empty(len(ks), dtype=np.int64)
+            for k, blk_k in enumerate(dense):
+                back[k] = seen.setdefault(blk_k.tobytes(), len(seen))
+            first = np.full(len(seen), -1, dtype=np.int64)
+            first[back[::-1]] = np.arange(len(ks))[::-1]
+            inv = _dense_inverse(dense[first].astype(LD)).reshape(-1, s, s)[back]
+        else:
+            inv = _dense_inverse(dense).reshape(-1, s, s)
+        groups.append((idx, inv.astype(dtype)))
 
     def apply(v):
         v = np.asarray(v, dtype=dtype)
@@ -291,17 +301,117 @@ def precond_ilu(f, dtype=LD):
     return lambda v: U.solve(L.solve(v, dtype), dtype)
 
 
+def precond_isai(schwz, f, dtype=LD):
+    """z = W_U (W_L v): the incomplete sparse approximate inverses of given factors on the factors' own patterns,
+    two CSR products."""
+    wl = schwz.isai(f["l_rp"], f["l_col"], f["l_val"], True)
+    wu = schwz.isai(f["u_rp"], f["u_col"], f["u_val"], False)
+    return lambda v: spmv(f["u_rp"], f["u_col"], wu, spmv(f["l_rp"], f["l_col"], wl, v, dtype), dtype)
+
+
 def make_precond(schwz, oracle, rp, col, val, precond, bs, dtype):
-    """The preconditioner codes of the library (0 none, 1 Jacobi, 2 block-Jacobi, 3 ILU) as hp_reference
-    applications; the block partition is the oracle's (structure only), the ILU(0) factors the library's."""
+    """The preconditioner codes of the library (0 none, 1 Jacobi, 2 block-Jacobi, 3 ILU, 4 ISAI) as hp_reference
+    applications; the block partition is the oracle's (structure only), the ILU(0) factors and the ISAI values on
+    their patterns the library's (host code: schwz.ilu0, schwz.isai)."""
     if precond == 0:
         return precond_none(dtype)
     if precond == 1 or (precond == 2 and bs == 1):
         return precond_jacobi(rp, col, val, dtype)
     if precond == 2:
         return precond_block_jacobi(rp, col, val, oracle.jacobi_blocks(rp, col, bs), dtype)
+    if precond == 4:
+        return precond_isai(schwz, schwz.ilu0(rp, col, val), dtype)
     assert precond == 3
     return precond_ilu(schwz.ilu0(rp, col, val), dtype)
+
+
+# ---- the Dirichlet Laplacian by array slicing, dot products, preconditioned CG ---------------------------------
+
+def stencil_apply(x, shape, dtype=LD):
+    """y = A x for the 5- / 7-point Laplacian with Dirichlet boundaries on a grid of shape (nx, ny[, nz]) in natural
+    order, x fastest (diagonal 2 * dim, off-diagonals -1), by array slicing.  The terms of a row are added in
+    ascending column order, as spmv adds them from a CSR with sorted columns: in float64 the two agree bit for
+    bit.  A tenth of the time of the row passes of spmv, which is what makes references at 2^24 rows affordable."""
+    _guard(dtype)
+    dims = tuple(int(s) for s in shape)[::-1]          # slowest axis first
+    v = np.asarray(x, dtype=dtype).reshape(dims)
+    nd = len(dims)
+    y = np.zeros(dims, dtype=dtype)
+
+    def cut(ax, a, b):
+        return tuple(slice(a, b) if k == ax else slice(None) for k in range(nd))
+    for ax in range(nd):                                # columns below the diagonal: the farthest first
+        y[cut(ax, 1, None)] -= v[cut(ax, None, -1)]
+    y += np.dtype(dtype).type(2 * nd) * v
+    for ax in range(nd - 1, -1, -1):                    # columns above it: the nearest first
+        y[cut(ax, None, -1)] -= v[cut(ax, 1, None)]
+    return y.reshape(-1)
+
+
+def slab_operator(local_to_global, nx, ny, dtype=LD):
+    """v -> A_loc v for the local matrix of a z-slab subdomain of the 7-point Laplacian on an nx x ny x nz grid: the
+    rows of the subdomain (interior and overlap, local_to_global[:local_size_x]) fill a box of whole x-y planes,
+    A_loc is the Dirichlet Laplacian of that box in the subdomain's numbering.  The vector is put into natural
+    order, the slicing stencil applied, the result brought back."""
+    g = np.asarray(local_to_global, dtype=np.int64)
+    plane = int(nx) * int(ny)
+    lo = int(g.min())
+    nz, rem = divmod(int(g.max()) + 1 - lo, plane)
+    assert lo % plane == 0 and rem == 0 and len(g) == nz * plane and len(np.unique(g)) == len(g), "not a box of planes"
+    pos = g - lo
+
+    def apply(v):
+        w = np.empty(len(pos), dtype=dtype)
+        w[pos] = v
+        return stencil_apply(w, (nx, ny, nz), dtype)[pos]
+    return apply
+
+
+def dot(x, y):
+    """sum_i x_i y_i by numpy's pairwise summation (np.sum), in the type of the operands.  Not `@` / np.dot: for
+    longdouble those accumulate in sequence, and at 2^24 terms lose the digits the CG tests are about."""
+    return np.sum(x * y)
+
+
+def pcg(rp, col, val, b, x0, precond_apply, iters, rtol=0.0, dtype=LD, keep=None):
+    """Preconditioned conjugate gradients (Hestenes & Stiefel 1952; Saad, Iterative Methods, Alg. 9.1) with the
+    stopping rule schwz_pcg_solve documents: before every update the recurred residual norm is tested against
+    rtol times the start residual norm, at most `iters` updates; rtol <= 0 runs exactly `iters` updates (a residual
+    of exactly zero ends the solve all the same: there is no direction left).
+
+    `rp` is a CSR row pointer (with col, val) or a callable v -> A v in `dtype` (col and val are then ignored).
+    Returns (x, hist): hist[k] = ||r_k||_2 from the recurrence r_{k+1} = r_k - alpha_k A p_k, len(hist) - 1 the
+    number of updates.  keep: a dict whose keys are update counts; x after that many updates is stored in it."""
+    _guard(dtype)
+    A = rp if callable(rp) else (lambda v: spmv(rp, col, val, v, dtype))
+    b = np.asarray(b, dtype=dtype)
+    x = np.array(x0, dtype=dtype) if x0 is not None else np.zeros(len(b), dtype=dtype)
+    r = b - A(x)
+    rr = dot(r, r)
+    r0 = np.sqrt(rr)
+    hist = [r0]
+    z = precond_apply(r)
+    p = np.array(z, dtype=dtype)
+    rho = dot(r, z)
+    if keep is not None and 0 in keep:
+        keep[0] = x.copy()
+    for k in range(iters):
+        if np.sqrt(rr) <= np.dtype(dtype).type(rtol) * r0:
+            break
+        q = A(p)
+        alpha = rho / dot(p, q)
+        x += alpha * p
+        r -= alpha * q
+        z = precond_apply(r)
+        rho_new = dot(r, z)
+        rr = dot(r, r)
+        p *= rho_new / rho
+        p += z
+        rho = rho_new
+        hist.append(np.sqrt(rr))
+        if keep is not None and k + 1 in keep:
+            keep[k + 1] = x.copy()
+    return x, hist
 
 
 # ---- GMRES ----------------------------------------------------------------------------------------------------

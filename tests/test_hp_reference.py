@@ -1,6 +1,8 @@
 """The extended-precision references of hp_reference.py, pinned on the CPU: against scipy, against the C
 oracle, against a dense solve, and the componentwise substitution bound against a float64 run of the same
 substitution (it must hold, and it must not be slack by orders of magnitude)."""
+import math
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -175,3 +177,139 @@ def test_parilu_restatement_reaches_ilu0(oracle):
     f = oracle.ilu0(rp, col, val)
     assert np.array_equal(pat.l_col, f["l_col"]) and np.array_equal(pat.u_col, f["u_col"])
     assert np.abs(lv - f["l_val"]).max() <= 1e-14 and np.abs(uv - f["u_val"]).max() <= 1e-14
+
+
+# ---- preconditioned CG, the slicing stencil, pairwise dot products ------------------------------------------------
+
+@pytest.mark.parametrize("pc", [(0, 1), (1, 1), (2, 8), (3, 1)])
+def test_pcg_float64_matches_the_oracle(schwz, oracle, pc):
+    """Two float64 statements of one recurrence on a system of condition ~ 700: they differ by rounding only, so
+    1e-11 (not the 1e-9 the device CG is held to against the oracle)."""
+    precond, bs = pc
+    rp, col, val = oracle.laplacian2d(40)
+    n = len(rp) - 1
+    rng = np.random.default_rng(29)
+    b = rng.standard_normal(n)
+    x0 = rng.standard_normal(n) * 0.1
+    M = hp.make_precond(schwz, oracle, rp, col, val, precond, bs, np.float64)
+    keep = {1: None, 5: None, 23: None}
+    got, hist = hp.pcg(rp, col, val, b, x0, M, 23, dtype=np.float64, keep=keep)
+    assert got.dtype == np.float64 and np.array_equal(keep[23], got)
+    for iters in (1, 5, 23):
+        exp, it_o, rn_o = oracle.pcg(rp, col, val, b, x0, precond, 0.0, iters, block_size=bs)
+        assert it_o == iters
+        assert np.abs(keep[iters] - exp).max() <= 1e-11 * np.abs(exp).max()
+        assert abs(hist[iters] - rn_o) <= 1e-11 * rn_o
+    # the stopping rule: the same iteration count, the same iterate
+    exp, it_o, rn_o = oracle.pcg(rp, col, val, b, None, precond, 1e-9, 4000, block_size=bs)
+    got, hist = hp.pcg(rp, col, val, b, None, M, 4000, rtol=1e-9, dtype=np.float64)
+    assert len(hist) - 1 == it_o and hist[-1] <= 1e-9 * hist[0] < hist[-2]
+    assert np.abs(got - exp).max() <= 1e-9 * np.abs(exp).max()
+    # max_iters = 0 and a start vector that solves the system exactly (small integers: b = A x0 without rounding)
+    got, hist = hp.pcg(rp, col, val, b, x0, M, 0, dtype=np.float64)
+    assert len(hist) == 1 and np.array_equal(got, x0)
+    xi = rng.integers(-8, 9, n).astype(np.float64)
+    got, hist = hp.pcg(rp, col, val, hp.spmv(rp, col, val, xi, np.float64), xi, M, 20, dtype=np.float64)
+    assert len(hist) == 1 and hist[0] == 0.0 and np.array_equal(got, xi)
+
+
+def test_pcg_isai_application_matches_the_oracle(schwz, oracle):
+    """precond 4 of make_precond: W_U (W_L v) with the library's host ISAI values, against the oracle's values on
+    the oracle's ILU(0) factors."""
+    rp, col, val = oracle.laplacian2d(12)
+    n = len(rp) - 1
+    v = np.random.default_rng(5).standard_normal(n)
+    f = oracle.ilu0(rp, col, val)
+    wl, wu = oracle.isai(f["l_rp"], f["l_col"], f["l_val"], True), oracle.isai(f["u_rp"], f["u_col"], f["u_val"], False)
+    exp = _csr(dict(u_val=wu, u_col=f["u_col"], u_rp=f["u_rp"]), "u", n) @ (
+        _csr(dict(l_val=wl, l_col=f["l_col"], l_rp=f["l_rp"]), "l", n) @ v)
+    got = hp.make_precond(schwz, oracle, rp, col, val, 4, 1, np.float64)(v)
+    assert np.abs(got - exp).max() <= 1e-13 * np.abs(exp).max()
+
+
+def test_pcg_longdouble_reaches_the_dense_solution(oracle):
+    rng = np.random.default_rng(2)
+    rp, col, val = oracle.laplacian2d(6)
+    n = len(rp) - 1
+    a = sp.csr_matrix((val, col, rp), shape=(n, n)).toarray()
+    b = rng.standard_normal(n)
+    exp = np.linalg.solve(a, b)
+    for M in (hp.precond_none(), hp.precond_jacobi(rp, col, val),
+              hp.precond_block_jacobi(rp, col, val, np.arange(0, n + 1, 6))):
+        x, hist = hp.pcg(rp, col, val, b, None, M, 10 * n, rtol=1e-17)
+        assert x.dtype == np.dtype(LD) and len(hist) - 1 <= n
+        assert hist[-1] <= 1e-17 * hist[0]
+        assert np.abs(x.astype(np.float64) - exp).max() <= 1e-14 * np.abs(exp).max()
+        # the recurred residual norm is the true one while rounding is far away
+        x5, h5 = hp.pcg(rp, col, val, b, None, M, 5)
+        true = b.astype(LD) - hp.spmv(rp, col, val, x5)
+        assert abs(float(h5[-1]) - float(np.sqrt(hp.dot(true, true)))) <= 1e-17 * float(h5[0])
+
+
+@pytest.mark.parametrize("shape", [(7, 5, 4), (2, 1, 3), (9, 9), (6, 11)])
+def test_slicing_stencil_is_the_csr_laplacian_bit_for_bit(oracle, shape):
+    if len(shape) == 3:
+        rp, col, val = oracle.laplacian3d(*shape)
+    elif shape[0] == shape[1]:
+        rp, col, val = oracle.laplacian2d(shape[0])
+    else:   # a 2-D grid that is not square: the 3-D generator with one plane, its diagonal set to 4
+        rp, col, val = oracle.laplacian3d(shape[0], shape[1], 1)
+        val = np.where(val > 0, 4.0, val)
+    n = len(rp) - 1
+    assert n == int(np.prod(shape))
+    x = np.random.default_rng(n).standard_normal(n)
+    for dtype in (np.float64, LD):
+        got = hp.stencil_apply(x.astype(dtype), shape, dtype)
+        assert got.dtype == np.dtype(dtype)
+        assert np.array_equal(got, hp.spmv(rp, col, val, x, dtype))
+    # pcg takes the operator in place of the CSR triple: the same bits
+    M = hp.precond_jacobi(rp, col, val, np.float64)
+    x_a, h_a = hp.pcg(rp, col, val, x, None, M, 7, dtype=np.float64)
+    x_b, h_b = hp.pcg(lambda v: hp.stencil_apply(v, shape, np.float64), None, None, x, None, M, 7, dtype=np.float64)
+    assert np.array_equal(x_a, x_b) and h_a == h_b
+
+
+@pytest.mark.parametrize("me", [0, 1, 2])
+def test_slab_operator_is_the_local_matrix(schwz, me):
+    """hp.slab_operator with the subdomain's own index set against spmv on its local_matrix: first, middle and last
+    slab of 16 x 6 x 18 in three, overlap planes appended behind the interior.  On small integers, where no sum
+    rounds, the two are the same bits: the index sets are right.  On random data they are two summation orders of
+    the same seven terms (an appended plane has high column numbers, so the CSR row takes it last): within
+    7 eps |A| |x| row by row."""
+    nx, ny, nz = 16, 6, 18
+    prob = schwz.Problem.laplacian(3, nx, ny, nz)
+    sd = schwz.Subdomain(prob, 3, me, 2, schwz.partition_regular(prob.N, 3))
+    rp, col, val = sd.local_matrix()
+    n = len(rp) - 1
+    assert n == sd.local_size_x > sd.local_size
+    rng = np.random.default_rng(me)
+    xi, x = rng.integers(-99, 100, n).astype(np.float64), rng.standard_normal(n)
+    for dtype in (np.float64, LD):
+        op = hp.slab_operator(sd.local_to_global[:n], nx, ny, dtype)
+        assert np.array_equal(op(xi.astype(dtype)), hp.spmv(rp, col, val, xi, dtype))
+        mag = hp.spmv(rp, col, np.abs(val), np.abs(x), LD)
+        diff = np.abs(op(x.astype(dtype)).astype(LD) - hp.spmv(rp, col, val, x, dtype))
+        assert (diff <= 7 * np.finfo(dtype).eps * mag).all()
+
+
+def test_longdouble_dot_of_2_to_24_terms_against_fsum():
+    """The operands are float32 values, so every product is exact in float64 and math.fsum returns the correctly
+    rounded sum; fsum of the products and minus that sum gives the rest, hence the exact sum to ~ 2^-106.  The
+    pairwise longdouble sum must be within a few longdouble eps of sum |x_i y_i| of it (bound of pairwise summation:
+    (log2 n + block) eps; measured here 0.002 eps), where a float64 accumulation is three orders of magnitude off."""
+    hp.require_extended_precision()
+    n = 1 << 24
+    rng = np.random.default_rng(24)
+    x = rng.standard_normal(n).astype(np.float32).astype(np.float64)
+    y = rng.standard_normal(n).astype(np.float32).astype(np.float64)
+    prod = x * y
+    assert np.array_equal(prod.astype(LD), x.astype(LD) * y.astype(LD))   # exact products
+    s = math.fsum(prod)
+    rest = math.fsum(np.append(prod, -s))
+    exact = LD(s) + LD(rest)
+    mag = LD(np.abs(prod).sum())
+    eps = np.finfo(LD).eps
+    err = abs(hp.dot(x.astype(LD), y.astype(LD)) - exact)
+    print("longdouble pairwise dot: %.3f eps sum|xy|; float64 pairwise: %.1f eps" %
+          (float(err / (eps * mag)), float(abs(LD(hp.dot(x, y)) - exact) / (eps * mag))))
+    assert err <= 4 * eps * mag
