@@ -525,7 +525,12 @@ int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream);
 
 /* device pointers of the state vectors (for tests and host layers):
  * which: 0 = x~ (local_size_x+halo), 1 = b~ / local_solution (local_size_x),
- *        2 = y / init_guess (local_size_x), 3 = local_rhs (local_size_x) */
+ *        2 = y / init_guess (local_size_x), 3 = local_rhs (local_size_x)
+ * The pointers of ids 0 and 2 are valid only until the next local solve or restriction of this subdomain: the
+ * restriction swaps the two x~ buffers, and on a subdomain without overlap and halo whose local solver is CG the
+ * vector y lives in one of them (the one x~ itself occupies after a restriction and before the first solve, the
+ * other one after a solve).  Ask again after either call.  Ids 1 and 3 never move.  Where y is the x~ buffer
+ * itself (schwz_ras_y_form 1), writing through the pointer of id 2 writes x~ too: the two are one vector there. */
 int schwz_ras_vector(schwz_subdomain *sd, int which, double **d_ptr, int64_t *len);
 /* the HBM-resident local_matrix of the subdomain (borrowed handle, owned by sd) */
 int schwz_ras_local_csr(schwz_subdomain *sd, schwz_csr **out);
@@ -536,6 +541,10 @@ int schwz_ras_local_csr(schwz_subdomain *sd, schwz_csr **out);
 int schwz_ras_jacobi_form(const schwz_subdomain *sd);
 /* schwz_pcg_flavour of the subdomain's local CG (0 for the other local solvers) */
 int schwz_ras_cg_flavour(const schwz_subdomain *sd);
+/* where the vector y (schwz_ras_vector id 2) lives: 0 a buffer of its own; 1 the x~ buffer itself, 2 the other x~
+ * buffer (a solve that has not been restricted) -- the latter two only on a subdomain without overlap and halo whose
+ * CG defers the x update, where the solve then stores its result once instead of twice */
+int schwz_ras_y_form(const schwz_subdomain *sd);
 /* copy x~[0:local_size] to the host (synchronous) -- the rank's piece of the
  * solution assembled in Solve::compute_residual_norm (solve.cpp:1025-1085) */
 int schwz_ras_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stream);

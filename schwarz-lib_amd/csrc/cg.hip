@@ -23,24 +23,7 @@ __global__ void cg_init_finalize_kernel(CgState *st, const double *partials, int
                                         double *norm_sq_out, int norm_bank)
 {
     __shared__ double red[4];
-    const double rho = fold_partials(partials, nparts, red);
-    const double rr = fold_partials(partials + nparts, nparts, red);
-    if (norm_sq_out) {
-        const double n2 = fold_partials(partials + norm_bank * nparts, nparts, red);
-        if (threadIdx.x == 0) {
-            norm_sq_out[0] = n2;  // may be mapped host memory
-            __threadfence_system();
-        }
-    }
-    if (threadIdx.x == 0) {
-        st->rho[0] = rho;
-        st->rho[1] = 0.0;
-        st->rr = rr;
-        st->r0 = sqrt(rr);
-        st->iters = 0;
-        // loop-top test of iteration 0: ||r|| <= rtol*||r_initial||
-        st->stop_iter = (sqrt(rr) <= rtol * sqrt(rr)) ? 0 : INT_MAX;
-    }
+    cg_init_state(st, partials, nparts, rtol, norm_sq_out, norm_bank, red);  // (device_utils.hpp)
 }
 
 typedef double vd2 __attribute__((ext_vector_type(2)));
@@ -283,7 +266,7 @@ struct PRing {
 // what every cg_flush_x_kernel launch of a solve is given alike (filled once per solve)
 struct FlushX {
     int64_t n = 0;
-    double *x = nullptr;
+    double *x = nullptr;                  // where x is stored (and, in place, read)
     PRing ring;
     const double *alpha_hist = nullptr;
     const CgState *st = nullptr;
@@ -297,12 +280,13 @@ struct FlushX {
     double dsc = 1.0;
 };
 
-// ... and what only the launches that finish x carry
+// ... and what differs between them: what only the launches that finish x carry, and x_in
 struct FlushXLast {
     int lazy_it = -1, vlast_it = -1;
     const double *vlast_r = nullptr;  // the current residual
     double *x2 = nullptr;             // second output, rows [0, x2_rows)
     int64_t x2_rows = 0;
+    const double *x_in = nullptr;     // out-of-place form (OOP): x is read from here and stored to FlushX::x
 };
 
 // The launch covers the pairs [pair0, pair1) (and the odd last row when `tail` is set): the last update of a
@@ -313,6 +297,10 @@ struct FlushXLast {
 // restricted write-back of the RAS step) and the rows [x2_rows, x2_total) are copied from x2_src -- the overlap and
 // halo entries of the current x~ --, so that x2 is the complete x~ after the restriction; with nothing to add the
 // launch only copies.
+// OOP, the out-of-place form (schwz_pcg::x_out): x is read from l.x_in, a vector the launch leaves untouched, and
+// stored to f.x whether or not anything was added -- so f.x holds the whole of x after ONE such launch, and the
+// later x updates of the solve run in place on it.  The arithmetic is the in-place form's.
+template <bool OOP>
 __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, const FlushXLast l, int b0, int count,
                                                             int pending, int64_t pair0, int64_t pair1, int tail)
 {
@@ -320,6 +308,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, cons
     // (the structs carry no qualifiers: the no-alias promises are made here)
     const int64_t n = f.n, x2_rows = l.x2_rows, x2_total = f.x2_total;
     double *__restrict__ const x = f.x;
+    const double *__restrict__ const x_in = OOP ? l.x_in : nullptr;
     const PRing &ring = f.ring;
     const double *__restrict__ const alpha_hist = f.alpha_hist;
     const CgState *const st = f.st;
@@ -342,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, cons
     int done = st->iters + ((pending >= 0 && pending < stop) ? 1 : 0);
     if (lazy_it >= 0 && lazy_it < stop && done <= lazy_it) done = lazy_it + 1;
     const int kmax = min(count, done - b0);
-    if (kmax <= 0 && !x2) return;
+    if (kmax <= 0 && !x2 && !OOP) return;
     double lazy_alpha = 0.0;
     if (kmax > 0 && lazy_it >= b0 && lazy_it < b0 + kmax)  // workgroup-uniform
         lazy_alpha = st->rho[lazy_it & 1] / fold_partials(pq_partials, pq_nparts, red);
@@ -357,7 +346,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, cons
     const double *const vprev_slot = ring.slot[(vlast_it + kDeferDepth - 1) % kDeferDepth];
     const double vprev_scale = vlast_it == 1 ? p0_scale : 1.0;
     for (int64_t i = pair0 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
-        vd2 xv = __builtin_nontemporal_load(x2v + i);
+        vd2 xv = __builtin_nontemporal_load(OOP ? reinterpret_cast<const vd2 *>(x_in) + i : x2v + i);
         vd2 carry = {0.0, 0.0};  // direction of the iteration before the current group of four
         for (int k0 = 0; k0 < kmax; k0 += 4) {
             vd2 pv[4];
@@ -397,7 +386,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, cons
                 }
             carry = pv[3];
         }
-        if (kmax > 0) __builtin_nontemporal_store(xv, x2v + i);
+        if (OOP || kmax > 0) __builtin_nontemporal_store(xv, x2v + i);
         if (x2) {
             if (2 * i + 1 < x2_rows) {
                 __builtin_nontemporal_store(xv, reinterpret_cast<vd2 *>(x2) + i);
@@ -415,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, cons
         for (int64_t j = 2 * pair1 + (int64_t)blockIdx.x * kBlock + threadIdx.x; j < x2_total; j += stride)
             if (!((n & 1) && j == n - 1)) x2[j] = x2_src[j];
     if (tail && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        double xv = x[n - 1];
+        double xv = OOP ? x_in[n - 1] : x[n - 1];
         double pprev = vlast ? vprev_scale * vprev_slot[n - 1] : 0.0;
         for (int k = 0; k < kmax; ++k) {
             double pk;
@@ -435,7 +424,7 @@ __global__ __launch_bounds__(kBlock) void cg_flush_x_kernel(const FlushX f, cons
                 xv = xv + inc;
             }
         }
-        if (kmax > 0) x[n - 1] = xv;
+        if (OOP || kmax > 0) x[n - 1] = xv;
         if (x2) x2[n - 1] = n - 1 < x2_rows ? xv : x2_src[n - 1];
     }
 }
@@ -797,7 +786,7 @@ static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->r, nb));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->p, nb));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->q, nb));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->partials, sizeof(double) * 5 * kMaxGrid));
+    SCHWZ_HIP_TRY(hipMalloc((void **)&s->partials, sizeof(double) * 8 * kMaxGrid));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->d_norm_sq, sizeof(double) * 2));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->state, sizeof(CgState)));
     SCHWZ_HIP_TRY(hipHostMalloc((void **)&s->h_state, 2 * sizeof(CgState), hipHostMallocDefault));
@@ -1076,6 +1065,11 @@ static CgPlan pcg_plan_matrix(const schwz_pcg *s)
     // chunk-by-chunk start launch + kSpmvDotSym).
     pl.sweep_start = env_on("SCHWZ_CG_SWEEPSTART") && pl.deferx && pl.sweep_dirdot && pl.fusedir &&
                      pair_sweep_start_ok(A, pl.gs);
+    // A start in the walk leaves the partial sums of rho, ||r||^2 and the check norm to workgroup 0 of the
+    // first-direction launch, which folds them into CgState behind its first window requests -- the separate
+    // one-workgroup launch between two full-grid ones (8 us and a launch boundary at 256^3) is gone, the same
+    // folds in the same order (cg_init_state).  SCHWZ_CG_INITFOLD=0: cg_init_finalize_kernel as for every other start.
+    pl.initfold = env_on("SCHWZ_CG_INITFOLD");
     return pl;
 }
 
@@ -1182,9 +1176,21 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
     // the start launch in the z-sweep walk where the whole solve runs in it (with the second product of the
     // fused check residual only where the upload built its plane flags)
     s->p_pending = pl.sweep_start && (a.diag_mode == 3 || !a.dinv) && (!(fused && !same) || pair_sweep_dual_ok(A, gs));
+    s->init = schwz_pcg::InitFold();
     if (s->p_pending) {
         a.sweep_init = 1;
         a.p = nullptr;
+        if (pl.initfold) {
+            // banks of their own: other workgroups of the launch that folds them may already be writing their partial
+            // sums of p0.(A p0) into the SpMV banks while its workgroup 0 still reads these
+            a.partials = s->partials + 5 * kMaxGrid;
+            s->init.pending = true;
+            s->init.partials = a.partials;
+            s->init.nparts = gs;
+            s->init.rtol = rtol;
+            s->init.norm_sq_out = fused ? s->d_norm_sq : nullptr;
+            s->init.norm_bank = same ? 1 : 2;
+        }
     }
     int rc = launch_spmv(A, (fused && !same) ? kSpmvResidDual : kSpmvResidInit, a, s->variant, st);
     if (rc) return rc;
@@ -1203,10 +1209,20 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
         SCHWZ_HIP_TRY(hipGetLastError());
         return SCHWZ_OK;
     }
+    if (s->init.pending) return SCHWZ_OK;  // pcg_iterate: the first-direction launch (or, without one, this kernel there)
     hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state, s->partials, gs, rtol,
                        fused ? s->d_norm_sq : nullptr, same ? 1 : 2);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
+}
+
+// whether a solve of `s` would defer x as things stand (the ring is acquired on the way, like in pcg_begin): who
+// hands the solve an x_out asks first
+bool pcg_defers_x(schwz_pcg *s)
+{
+    CgPlan pl = pcg_plan_matrix(s);
+    if (!pcg_acquire_buffers(s, pl)) pl = pcg_plan_matrix(s);
+    return pl.deferx;
 }
 
 namespace {
@@ -1247,6 +1263,7 @@ struct CgSolve {
     FlushX fx;
     double *pbuf[2];          // x updated in the launches: p alternates between these with the fused direction launch
     bool prio_recorded = false;
+    bool x_moved = false;     // schwz_pcg::x_out: an x update has run, x lives in x_out from here on
 
     CgSolve(schwz_pcg *s_, const CgPlan &pl_, double *x, double rtol_, int max_iters_, hipStream_t st_)
         : s(s_), pl(pl_), d_x(x), rtol(rtol_), max_iters(max_iters_), st(st_), A(s_->A->v), n(s_->n), gs(pl_.gs),
@@ -1263,7 +1280,7 @@ struct CgSolve {
         // direction 16, 32, ... simply lands there: r0 is done with by then)
         if (pl.p0_virtual) fx.ring.slot[0] = s->r;
         fx.n = n;
-        fx.x = d_x;
+        fx.x = s->x_out ? s->x_out : d_x;
         fx.alpha_hist = s->alpha_hist;
         fx.st = s->state;
         fx.fused = pl.qfree ? 0 : 1;  // how the in-launch update of this iteration forms x + alpha p
@@ -1294,8 +1311,15 @@ struct CgSolve {
             fl.lazy_it = lazy_it;
             fl.vlast_it = pl.vlast ? lazy_it : -1;
         }
+        // the first x update of a solve with an x_out reads the caller's vector (and leaves it alone), every later
+        // one runs in place on x_out
+        const bool oop = s->x_out && !x_moved;
+        if (oop) fl.x_in = d_x;
         auto launch = [&](int grid, int64_t pair0, int64_t pair1, int tail) {
-            hipLaunchKernelGGL(cg_flush_x_kernel, dim3(grid), dim3(kBlock), 0, q, fx, fl, b0, count, pending, pair0, pair1, tail);
+            if (oop)
+                hipLaunchKernelGGL(cg_flush_x_kernel<true>, dim3(grid), dim3(kBlock), 0, q, fx, fl, b0, count, pending, pair0, pair1, tail);
+            else
+                hipLaunchKernelGGL(cg_flush_x_kernel<false>, dim3(grid), dim3(kBlock), 0, q, fx, fl, b0, count, pending, pair0, pair1, tail);
         };
         if (last && s->prio_on && s->prio_event && q == st && !prio_recorded) {
             // the caller's priority rows first, the event, then the rest (the same bits: every element is
@@ -1313,6 +1337,7 @@ struct CgSolve {
             launch(gv, 0, n2, 1);
         }
         if (fl.x2) s->x2_written = true;
+        x_moved = true;
     }
 
     // the ring is full after iteration `it`: its kDeferDepth increments go into x before slot (it + 1) % depth,
@@ -1552,6 +1577,15 @@ struct CgSolve {
         a.diag_mode = s->diag.mode;
         a.diag_uniform = s->diag.uniform;
         a.sweep_first = 1;
+        if (s->init.pending) {
+            // ... and its workgroup 0 folds the start launch's partial sums into CgState (and the check norm)
+            a.init_fold = 1;
+            a.pq_partials = s->init.partials;
+            a.pq_nparts = s->init.nparts;
+            a.cg_rtol = s->init.rtol;
+            a.norm_sq_out = s->init.norm_sq_out;
+            a.norm_bank = s->init.norm_bank;
+        }
         return launch_spmv(A, kSpmvDirDotSym, a, s->variant, st);
     }
 };
@@ -1572,6 +1606,10 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
         set_error("pcg_iterate: the start launch left p to a first-direction launch this solve does not run");
         return SCHWZ_ERR_INVALID;
     }
+    if (s->x_out && !pl.deferx) {
+        set_error("pcg_iterate: a result vector of its own (x_out) needs the deferred x update");
+        return SCHWZ_ERR_INVALID;
+    }
     CgSolve cg(s, pl, d_x, rtol, max_iters, st);
     const bool poll = rtol > 0.0;
     s->x2_written = false;
@@ -1579,6 +1617,18 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
     hipGraphExec_t replay = nullptr;
     if (pl.graph && (rc = cg.graph_for_solve(&replay))) return rc;
     if (pl.fusedir && max_iters > 0 && (rc = cg.first_dot())) return rc;
+    if (s->init.pending && !(pl.fusedir && max_iters > 0 && pl.walk_started)) {
+        // no first-direction launch took the fold of the start launch's partial sums along: the kernel of its own
+        hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state, s->init.partials, s->init.nparts,
+                           s->init.rtol, s->init.norm_sq_out, s->init.norm_bank);
+        SCHWZ_HIP_TRY(hipGetLastError());
+    }
+    s->init.pending = false;
+    if (s->init_event) {
+        // CgState and the check norm are final behind this point of the stream, wherever they were folded
+        SCHWZ_HIP_TRY(hipEventRecord(s->init_event, st));
+        s->init_event = nullptr;
+    }
     s->p_pending = false;
     int chunk = 16;
     int it = 0, pending = -1, bank = 0;
@@ -1615,7 +1665,8 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
     }
     // second output asked for, but no launch above was the last x update (ring just emptied, a stop between two
     // rings, no iteration at all): a launch that adds nothing and copies
-    if (pl.deferx && s->x2_out && !s->x2_written) {
+    // ... likewise for a result vector of its own that no x update has filled yet
+    if (pl.deferx && ((s->x2_out && !s->x2_written) || (s->x_out && !cg.x_moved))) {
         cg.flush_x(it, 0, -1, st, true);
         SCHWZ_HIP_TRY(hipGetLastError());
     }

@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "schwz_internal.hpp"
 
 namespace schwz {
@@ -47,6 +49,32 @@ __device__ __forceinline__ double fold_partials(const double *part, int count, d
     double s = 0.0;
     for (int i = threadIdx.x; i < count; i += kBlock) s += part[i];
     return block_sum(s, red);
+}
+
+// Start of a CG solve: the partial sums its start launch left (banks of nparts slots: rho = r.z, ||r||^2 and, for
+// norm_sq_out, bank norm_bank: the check norm) folded into CgState.  One workgroup: cg_init_finalize_kernel, or
+// workgroup 0 of the first-direction walk (spmv_pair.hip) -- the same folds in the same order, the same stores.
+__device__ __forceinline__ void cg_init_state(CgState *st, const double *partials, int nparts, double rtol,
+                                              double *norm_sq_out, int norm_bank, double *red)
+{
+    const double rho = fold_partials(partials, nparts, red);
+    const double rr = fold_partials(partials + nparts, nparts, red);
+    if (norm_sq_out) {
+        const double n2 = fold_partials(partials + norm_bank * nparts, nparts, red);
+        if (threadIdx.x == 0) {
+            norm_sq_out[0] = n2;  // may be mapped host memory
+            __threadfence_system();
+        }
+    }
+    if (threadIdx.x == 0) {
+        st->rho[0] = rho;
+        st->rho[1] = 0.0;
+        st->rr = rr;
+        st->r0 = sqrt(rr);
+        st->iters = 0;
+        // loop-top test of iteration 0: ||r|| <= rtol*||r_initial||
+        st->stop_iter = (sqrt(rr) <= rtol * sqrt(rr)) ? 0 : INT_MAX;
+    }
 }
 
 // Tile dealt to XCD `xcd` as its j-th one.  Tiles go to the eight XCDs (blockIdx % 8) in runs

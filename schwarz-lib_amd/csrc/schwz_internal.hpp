@@ -379,6 +379,13 @@ struct SpmvArgs {
     // kSpmvCgUpdate / kSpmvDirDotSym: whoever planned the launch wants the z-sweep walk (cg.hip's plan, from
     // pair_sweep_update_ok / pair_sweep_dirdot_ok); launch_spmv_pair reads no switch of its own
     int walk = 0;
+    // first-direction launch of a solve that started in the walk (sweep_first): workgroup 0 also folds the start
+    // launch's partial sums -- pq_partials, pq_nparts slots per bank; banks 0 and 1: rho and ||r||^2 -- into
+    // cg_state with the stopping test of cg_rtol, and bank norm_bank into norm_sq_out (nullptr: no check norm):
+    // what cg_init_finalize_kernel does (cg.hip, CgPlan::initfold)
+    int init_fold = 0;
+    int norm_bank = 1;
+    double *norm_sq_out = nullptr;
 };
 
 // launch grid of the streaming vector kernels: one lane per element up to kMaxGrid workgroups
@@ -468,6 +475,7 @@ struct CgPlan {
     bool fusedir = false;       // two launches per iteration
     bool deferx = false;        // x += sum alpha_k p_k applied once per kDeferDepth iterations
     bool sweep_start = false;   // the solve can start in the walk too (INIT / FIRST forms, spmv_pair.hip)
+    bool initfold = false;      // ... and the FIRST launch then initialises CgState (no cg_init_finalize_kernel)
     int gs = 0, gv = 0;         // grids of the SpMV launches and of the vector kernels
     // completed by pcg_iterate
     bool walk_started = false;  // the start launch ran in the walk and left p to the first-direction launch
@@ -480,6 +488,7 @@ struct CgPlan {
 int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fused, const double *d_x2,
               int64_t row_limit, hipStream_t st);
 int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream_t st);
+bool pcg_defers_x(schwz_pcg *s);  // the next solve would defer x (what schwz_pcg::x_out needs)
 int precond_apply(schwz_pcg *s, const double *in, double *out, hipStream_t st);
 int pcg_last_stats(schwz_pcg *s, int *h_iters, double *h_resnorm);  // device sync + state copy
 int pcg_take_trs_error(schwz_pcg *s);
@@ -539,7 +548,7 @@ struct schwz_pcg {
     double *isai_tmp = nullptr;
     schwz::DiagView diag;
     void *d_dcode = nullptr, *d_ddict = nullptr;
-    double *partials = nullptr;  // 3 * kMaxGrid (SpMV banks) + 2 * kMaxGrid (vector banks)
+    double *partials = nullptr;  // 3 * kMaxGrid (SpMV banks) + 2 * kMaxGrid (vector banks) + 3 * kMaxGrid (start banks, InitFold)
     double *d_norm_sq = nullptr; // kSpmvResidDual result
     schwz::CgState *state = nullptr;
     schwz::CgState *h_state = nullptr;  // pinned
@@ -576,6 +585,23 @@ struct schwz_pcg {
     const double *x2_src = nullptr;  // rows [x2_rows, x2_total) of x2_out are copied from here (overlap / halo of x~)
     int64_t x2_total = 0;
     bool x2_written = false;
+    // A result vector of its own: the solve reads its start vector d_x, leaves it untouched and stores the result
+    // here (the first x update of the solve runs out of place, the later ones in place on x_out).  Only with the
+    // deferred x update -- pcg_iterate refuses otherwise, pcg_defers_x tells beforehand -- and not together with the
+    // priority-row split, which exists only on subdomains with neighbours, where nobody sets it.
+    double *x_out = nullptr;
+    // The start launch of the running solve left its partial sums to the first-direction launch (CgPlan::initfold):
+    // what that launch -- or, where none follows, cg_init_finalize_kernel from pcg_iterate -- folds, and the
+    // event pcg_iterate records once CgState and the check norm are final (the caller sets it, one solve at a time).
+    struct InitFold {
+        bool pending = false;
+        const double *partials = nullptr;
+        int nparts = 0;
+        double rtol = 0.0;
+        double *norm_sq_out = nullptr;
+        int norm_bank = 1;
+    } init;
+    hipEvent_t init_event = nullptr;
     // A solve of exactly max_iters iterations (rtol == 0) whose last iteration was cut down to what its result
     // needs: alpha of that iteration is formed inside the x update, and the residual update + state advance --
     // whose results nothing reads unless the caller asks for the iteration count / residual norm -- wait in
@@ -712,7 +738,14 @@ struct schwz_subdomain {
     double *d_x_alt = nullptr;   // the other x~ buffer: the last x update of a CG solve writes its interior, the restriction swaps the two
     double *d_rhs = nullptr;     // b_loc
     double *d_btilde = nullptr;  // b~ = local_solution on entry of the solve
-    double *d_y = nullptr;       // init_guess / solve result
+    double *d_y = nullptr;       // init_guess / solve result of the separate form (allocated at first need)
+    // Unified form (subdomain.hip, use_unified): no overlap, no halo, CG with x deferred -- y and x~ are the same n
+    // values, and y lives in one of the two x~ buffers.  State A: y IS x~ (d_x).  State B (y_in_alt): y is d_x_alt,
+    // after a solve that has not been restricted.
+    bool unified = false;
+    bool y_in_alt = false;
+    // separate form: a solve has run since the last restriction (y is ahead of x~)
+    bool y_ahead = false;
     double *d_partials = nullptr;
     double *h_scalar = nullptr;  // pinned, mapped
     double *d_h_scalar = nullptr;  // device alias of h_scalar

@@ -950,9 +950,18 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     PairVal *const cpv = reinterpret_cast<PairVal *>(halo_ring + kHaloSlots * NX);
     int *const cmask = reinterpret_cast<int *>(cpv + A.canon_npat * 5);
     __shared__ double red[4];
-    if (a.it >= a.cg_state->stop_iter) return;
+    // (FIRST reads nothing of CgState: with init_fold its own workgroup 0 is still to write it.  After a zero start
+    // residual the launch is needless; the update launch behind it sees stop_iter == 0 and leaves.)
+    if (!FIRST && a.it >= a.cg_state->stop_iter) return;
     double cg_rho_new = 0.0, cg_rr = 0.0, cg_beta = 0.0;
     const int tid = threadIdx.x;
+    // FIRST, workgroup 0: CgState and the check norm from the start walk's partial sums, which the kernel boundary
+    // behind that walk made visible (cg_init_finalize_kernel's work; nobody in this launch reads the state)
+    auto init_fold = [&]() {
+        if (FIRST && a.init_fold && blockIdx.x == 0)
+            cg_init_state(const_cast<CgState *>(a.cg_state), a.pq_partials, a.pq_nparts, a.cg_rtol, a.norm_sq_out,
+                          a.norm_bank, red);
+    };
     // the slot tables and beta (folded from the previous launch's partial sums by every workgroup): fetched after
     // the first windows have been requested, like in the update walk above
     auto tables_and_beta = [&]() {
@@ -970,6 +979,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             cg_rr = fold_partials(a.pq_partials + a.pq_nparts, a.pq_nparts, red);
             cg_beta = cg_rho_new / a.cg_state->rho[a.it & 1];
         }
+        init_fold();
         lds_barrier();
     };
     if (blockIdx.x == 0)
@@ -1189,6 +1199,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         if (z < z1) step(z, own_b, rle_a, hreg);
     } else if (!FIRST && blockIdx.x == 0) {
         tables_and_beta();  // (an empty first slot still advances the CG state below)
+    } else {
+        init_fold();  // (... or initialises it)
     }
     const double s0 = block_sum(acc0, red);
     if (tid == 0) {

@@ -7,6 +7,7 @@
 //   A_loc   CSR over [interior|overlap] rows and columns, int32 indices
 //   A_Gamma CSR over the overlap rows only, columns index x~ directly
 //   b_loc, b~, y (CG warm start), r, p, q, 1/diag : local_size_x doubles each
+//           (y: a vector of its own, or -- unified form, below -- one of the two x~ buffers)
 //   put / get lists: int32 local ids, packed in neighbour order
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,69 @@ static int dev_zeros(int64_t n, double **d)
     *d = nullptr;
     SCHWZ_HIP_TRY(hipMalloc((void **)d, (size_t)(n ? n : 1) * sizeof(double)));
     SCHWZ_HIP_TRY(hipMemset(*d, 0, (size_t)(n ? n : 1) * sizeof(double)));
+    return SCHWZ_OK;
+}
+
+// ---- where the solver's vector y lives -----------------------------------------------------------------------
+// On a subdomain without overlap and without halo (one subdomain) y and x~ are the same local_size_x values: the
+// check residual is the CG start residual, and the restriction copies all of y.  When the local solver is CG with
+// the deferred x update, y then needs no memory of its own (UNIFIED form):
+//   state A  y IS x~ (d_x): after the upload and after every restriction.  A solve reads its start vector from d_x,
+//            leaves d_x untouched -- a discarded solve must not change x~ -- and stores its result to d_x_alt
+//            (schwz_pcg::x_out: one store of the solution instead of two) -> state B
+//   state B  y is d_x_alt.  The restriction swaps the buffers -> state A.  Another solve first (a discarded one
+//            before it, or schwz_ras_local_solve twice) runs in place on y, and its check residual, on x~, is no
+//            longer its start residual: the separate launches.
+// Everything else is the SEPARATE form: y = d_y, the restriction swaps (schwz_pcg::x2_out) or copies.  The form is
+// chosen per solve (the switches are read per solve); a change of form carries y over with one copy.  With
+// neighbours (overlap or halo entries, the priority-row split of the last x update) the form is always separate.
+static bool want_unified(schwz_subdomain *sd)
+{
+    const char *e = std::getenv("SCHWZ_RESTRICT_FUSE");
+    if (e && e[0] == '0') return false;
+    return sd->cg && sd->overlap_size == 0 && sd->halo_size == 0 && sd->local_size > 0 && !sd->cg->prio_on &&
+           pcg_defers_x(sd->cg);
+}
+
+// the second x~ buffer, allocated at first need (zeroed); false: no room
+static bool ensure_x_alt(schwz_subdomain *sd)
+{
+    if (sd->d_x_alt) return true;
+    const size_t nx = (size_t)std::max<int64_t>(sd->local_size_x + sd->halo_size, 1);
+    if (hipMalloc((void **)&sd->d_x_alt, nx * sizeof(double)) != hipSuccess ||
+        hipMemset(sd->d_x_alt, 0, nx * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(sd->d_x_alt);
+        sd->d_x_alt = nullptr;
+        return false;
+    }
+    return true;
+}
+
+static double *y_of(const schwz_subdomain *sd)
+{
+    return sd->unified ? (sd->y_in_alt ? sd->d_x_alt : sd->d_x) : sd->d_y;
+}
+
+// the form of the solve about to be launched; y moves with one copy where it differs from the current one
+static int choose_form(schwz_subdomain *sd, hipStream_t st)
+{
+    const bool uni = want_unified(sd) && ensure_x_alt(sd);
+    if (uni == sd->unified) return SCHWZ_OK;
+    const int64_t n = sd->local_size_x;
+    int rc;
+    if (uni) {
+        // y ahead of x~ (a solve that was not restricted): state B.  Otherwise state A, where y is x~: the copy makes
+        // it so even where the caller wrote into y -- which the separate form, too, takes for x~ in its check residual.
+        if ((rc = launch_copy(n, sd->d_y, sd->y_ahead ? sd->d_x_alt : sd->d_x, st))) return rc;
+        sd->y_in_alt = sd->y_ahead;
+    } else {
+        if (!sd->d_y && (rc = dev_zeros(n, &sd->d_y))) return rc;
+        if ((rc = launch_copy(n, y_of(sd), sd->d_y, st))) return rc;
+        sd->y_ahead = sd->y_in_alt;
+        sd->y_in_alt = false;
+    }
+    sd->unified = uni;
     return SCHWZ_OK;
 }
 
@@ -111,7 +175,7 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
         (rc = dev_upload(sd->i_val, &sd->d_i_val)) || (rc = dev_upload(put_idx, &sd->d_put_idx)) ||
         (rc = dev_upload(get_idx, &sd->d_get_idx)))
         return rc;
-    if ((rc = dev_zeros(nx, &sd->d_x)) || (rc = dev_zeros(n, &sd->d_y))) return rc;
+    if ((rc = dev_zeros(nx, &sd->d_x))) return rc;  // (y: at the end, once the solver is known)
     std::vector<double> rhs(h_local_rhs, h_local_rhs + n);
     if ((rc = dev_upload(rhs, &sd->d_rhs)) || (rc = dev_upload(rhs, &sd->d_btilde))) return rc;
     SCHWZ_HIP_TRY(hipMalloc((void **)&sd->d_partials, sizeof(double) * (2 * kMaxGrid + 2)));
@@ -194,6 +258,9 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
         schwz_free(perm);
         if (rc) return rc;
     }
+    // y: inside the x~ buffers where the two coincide (state A), else a vector of its own
+    sd->unified = want_unified(sd) && ensure_x_alt(sd);
+    if (!sd->unified && (rc = dev_zeros(n, &sd->d_y))) return rc;
     SCHWZ_HIP_TRY(hipDeviceSynchronize());
     return SCHWZ_OK;
 }
@@ -249,8 +316,8 @@ int schwz_ras_pack_early(schwz_subdomain *sd, void *d_send, int single, schwz_st
     if (sd->num_send == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_send, "schwz_ras_pack_early: null send buffer");
     SCHWZ_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, sd->cg->prio_event, 0));
-    if (single) return launch_gather_f32(sd->num_send, sd->d_put_idx, sd->d_y, (float *)d_send, (hipStream_t)stream);
-    return schwz_gather(sd->num_send, sd->d_put_idx, sd->d_y, (double *)d_send, SCHWZ_OP_COPY, stream);
+    if (single) return launch_gather_f32(sd->num_send, sd->d_put_idx, y_of(sd), (float *)d_send, (hipStream_t)stream);
+    return schwz_gather(sd->num_send, sd->d_put_idx, y_of(sd), (double *)d_send, SCHWZ_OP_COPY, stream);
 }
 
 // One neighbour's part of the halo, to / from ANY device address -- the receiver's window in the
@@ -457,16 +524,7 @@ static void restrict_by_solver(schwz_subdomain *sd)
     const bool on = !(e && e[0] == '0');
     if (sd->cg) sd->cg->x2_out = nullptr;
     if (!on || !sd->cg || sd->local_size == 0) return;
-    if (!sd->d_x_alt) {
-        const size_t nx = (size_t)std::max<int64_t>(sd->local_size_x + sd->halo_size, 1);
-        if (hipMalloc((void **)&sd->d_x_alt, nx * sizeof(double)) != hipSuccess ||
-            hipMemset(sd->d_x_alt, 0, nx * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(sd->d_x_alt);
-            sd->d_x_alt = nullptr;
-            return;
-        }
-    }
+    if (!ensure_x_alt(sd)) return;
     sd->cg->x2_out = sd->d_x_alt;
     sd->cg->x2_rows = sd->local_size;
     sd->cg->x2_src = sd->d_x;
@@ -485,7 +543,19 @@ int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream 
     if (sd->gmres)
         return schwz_gmres_solve(sd->gmres, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
                                  stream);
+    int rc = choose_form(sd, (hipStream_t)stream);
+    if (rc) return rc;
+    if (sd->unified) {
+        // state A: out of place, d_x -> d_x_alt; state B: in place on d_x_alt
+        sd->cg->x2_out = nullptr;
+        sd->cg->x_out = sd->y_in_alt ? nullptr : sd->d_x_alt;
+        rc = schwz_pcg_solve(sd->cg, sd->d_btilde, y_of(sd), sd->opt.local_tol, maxit, h_inner_iters, nullptr, stream);
+        sd->cg->x_out = nullptr;
+        if (!rc) sd->y_in_alt = true;
+        return rc;
+    }
     restrict_by_solver(sd);
+    sd->y_ahead = true;
     return schwz_pcg_solve(sd->cg, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
                            stream);
 }
@@ -502,24 +572,59 @@ int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
         if (rc) return rc;
         return schwz_ras_local_solve(sd, nullptr, stream);
     }
+    int rc = choose_form(sd, st);
+    if (rc) return rc;
     // x~ and y coincide on [interior|overlap] when there is no overlap at all
-    // (single subdomain): the check residual is then the CG start residual.
+    // (single subdomain): the check residual is then the CG start residual ...
     const double *x2 = (sd->overlap_size == 0) ? nullptr : sd->d_x;
+    // ... unless a solve has run since the last restriction (a discarded solve, x~ kept): y has moved on and the
+    // check residual, which belongs to x~, gets its own launch
+    if (!x2 && (sd->unified ? sd->y_in_alt : sd->y_ahead)) {
+        if ((rc = schwz_ras_local_residual_launch(sd, stream))) return rc;
+        return schwz_ras_local_solve(sd, nullptr, stream);
+    }
     const int maxit = sd->opt.local_max_iters == -1 ? (int)n : sd->opt.local_max_iters;
-    restrict_by_solver(sd);
+    double *const y = y_of(sd);
+    if (sd->unified) {
+        sd->cg->x2_out = nullptr;
+        sd->cg->x_out = sd->d_x_alt;  // (state A: d_x is read, and stays x~)
+    } else {
+        restrict_by_solver(sd);
+        sd->y_ahead = true;
+    }
     double *keep = sd->cg->d_norm_sq;
     sd->cg->d_norm_sq = sd->d_h_scalar;  // mapped pinned host memory, written by the kernel
-    int rc = pcg_begin(sd->cg, sd->d_btilde, sd->d_y, sd->opt.local_tol, true, x2, n, st);
+    rc = pcg_begin(sd->cg, sd->d_btilde, y, sd->opt.local_tol, true, x2, n, st);
     sd->cg->d_norm_sq = keep;
-    if (rc) return rc;
-    SCHWZ_HIP_TRY(hipEventRecord(sd->ev_scalar, st));
-    return pcg_iterate(sd->cg, sd->d_y, sd->opt.local_tol, maxit, st);
+    if (!rc) {
+        // the norm is final behind the start launch's fold: a kernel of pcg_begin, or the first launch of pcg_iterate,
+        // which then records the event (nothing on the device waits for it earlier: schwz_ras_norm_sq_to_device
+        // is enqueued after this function)
+        if (sd->cg->init.pending)
+            sd->cg->init_event = sd->ev_scalar;
+        else if (hipEventRecord(sd->ev_scalar, st) != hipSuccess)
+            rc = SCHWZ_ERR_HIP;
+    }
+    if (!rc) rc = pcg_iterate(sd->cg, y, sd->opt.local_tol, maxit, st);
+    sd->cg->init_event = nullptr;
+    if (sd->unified) {
+        sd->cg->x_out = nullptr;
+        if (!rc) sd->y_in_alt = true;
+    }
+    return rc;
 }
 
 int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_restrict");
     if (sd->local_size == 0) return SCHWZ_OK;
+    if (sd->unified) {
+        // state B: the buffer the solve filled becomes x~ (and y stays where it is: state A).  State A: y is x~.
+        if (sd->y_in_alt) std::swap(sd->d_x, sd->d_x_alt);
+        sd->y_in_alt = false;
+        return SCHWZ_OK;
+    }
+    sd->y_ahead = false;
     if (sd->cg && sd->cg->x2_written && sd->d_x_alt && sd->cg->x2_out == sd->d_x_alt) {
         // the solve's last x update wrote y[interior] into the other buffer: it becomes x~
         std::swap(sd->d_x, sd->d_x_alt);
@@ -537,7 +642,7 @@ int schwz_ras_vector(schwz_subdomain *sd, int which, double **d_ptr, int64_t *le
     switch (which) {
     case 0: *d_ptr = sd->d_x; *len = sd->local_size_x + sd->halo_size; break;
     case 1: *d_ptr = sd->d_btilde; *len = sd->local_size_x; break;
-    case 2: *d_ptr = sd->d_y; *len = sd->local_size_x; break;
+    case 2: *d_ptr = y_of(sd); *len = sd->local_size_x; break;
     case 3: *d_ptr = sd->d_rhs; *len = sd->local_size_x; break;
     default: set_error("schwz_ras_vector: unknown vector id"); return SCHWZ_ERR_INVALID;
     }
@@ -554,6 +659,8 @@ int schwz_ras_local_csr(schwz_subdomain *sd, schwz_csr **out)
 
 // 0 none, 1 full 1/diag vector, 2 one-byte codes into a dictionary, 3 one scalar (schwz::DiagView)
 int schwz_ras_jacobi_form(const schwz_subdomain *sd) { return sd && sd->cg ? sd->cg->diag.mode : 0; }
+
+int schwz_ras_y_form(const schwz_subdomain *sd) { return sd && sd->on_device && sd->unified ? (sd->y_in_alt ? 2 : 1) : 0; }
 
 int schwz_ras_cg_flavour(const schwz_subdomain *sd) { return sd && sd->cg ? schwz_pcg_flavour(sd->cg) : 0; }
 

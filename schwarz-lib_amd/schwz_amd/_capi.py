@@ -57,7 +57,7 @@ SYMBOLS = [
     "schwz_ras_last_inner_stats",
     "schwz_ras_check_and_solve_launch",
     "schwz_ras_norm_sq_to_device",
-    "schwz_ras_restrict", "schwz_ras_vector", "schwz_ras_local_csr", "schwz_ras_jacobi_form", "schwz_ras_cg_flavour", "schwz_ras_get_interior",
+    "schwz_ras_restrict", "schwz_ras_vector", "schwz_ras_local_csr", "schwz_ras_jacobi_form", "schwz_ras_cg_flavour", "schwz_ras_y_form", "schwz_ras_get_interior",
     "schwz_ras_true_residual_sq", "schwz_ras_algorithmic_bytes",
 ]
 
@@ -211,6 +211,7 @@ _sig("schwz_ras_vector", i32, [vp, i32, pvp, C.POINTER(i64)])
 _sig("schwz_ras_local_csr", i32, [vp, pvp])
 _sig("schwz_ras_jacobi_form", i32, [vp])
 _sig("schwz_ras_cg_flavour", i32, [vp])
+_sig("schwz_ras_y_form", i32, [vp])
 _sig("schwz_ras_get_interior", i32, [vp, vp, vp])
 _sig("schwz_ras_true_residual_sq", i32, [vp, C.POINTER(dbl), vp])
 _sig("schwz_ras_algorithmic_bytes", i64, [vp, i32])

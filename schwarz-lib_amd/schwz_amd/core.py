@@ -637,6 +637,10 @@ class Subdomain:
         4 deferred x update, 8 / 16 z-sweep walk of the update / fused direction launch, 32 of the start)."""
         return int(lib.schwz_ras_cg_flavour(self.h))
 
+    def y_form(self):
+        """Where y lives (schwz_ras_y_form): 0 a buffer of its own, 1 the x~ buffer, 2 the other x~ buffer."""
+        return int(lib.schwz_ras_y_form(self.h))
+
     def vector(self, which):
         p = C.c_void_p()
         n = C.c_int64(0)
