@@ -350,6 +350,8 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
                   "schwz_csr_create: row_ptr not monotone or column index out of range");
     // row tiles: consecutive rows, <= kTileRows rows and <= kTileNnz nonzeros; a
     // row longer than kTileNnz forms a tile of its own.
+    // (tests/drivers/coding_plan_driver.cpp repeats this loop and the pair_deal_shift arithmetic below to plan
+    // without a GPU: change them together)
     timer_chk.stop();
     StageTimer timer_tiles("csr_create: tiles, orders, column check");
     std::vector<schwz_idx> tiles;

@@ -190,6 +190,44 @@ void set_error(const std::string &msg);
         }                                             \
     } while (0)
 
+// host vector -> fresh device allocation; `pad` extra zeroed elements follow the data (the 16-byte
+// SpMV loads may touch them)
+template <typename T>
+inline int upload(const T *h, size_t count, void **d, size_t pad = 0)
+{
+    *d = nullptr;
+    SCHWZ_HIP_TRY(hipMalloc(d, (count + pad ? count + pad : 1) * sizeof(T)));
+    if (count) SCHWZ_HIP_TRY(hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice));
+    if (pad) SCHWZ_HIP_TRY(hipMemset((char *)*d + count * sizeof(T), 0, pad * sizeof(T)));
+    return SCHWZ_OK;
+}
+
+// A device allocation that frees itself.  The buffers of the matrix codings live in structs of these
+// (schwz_csr::coding): releasing a coding is assigning a fresh struct, and no pointer can be forgotten.
+struct DevBuf {
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    // replaces the allocation by a copy of h (plus `pad` zeroed elements)
+    template <typename T>
+    int put(const std::vector<T> &h, size_t pad = 0)
+    {
+        *this = DevBuf();
+        return upload(h.data(), h.size(), &p, pad);
+    }
+    template <typename T>
+    const T *as() const { return static_cast<const T *>(p); }
+};
+
 // ---- SpMV tiling constants (see DESIGN.md "CSR SpMV") ------------------------
 constexpr int kBlock = 256;      // threads per workgroup = 4 waves of 64
 constexpr int kTileNnz = 2048;   // products staged in LDS per tile (16 KiB fp64)
@@ -295,7 +333,7 @@ struct CsrView {
     // far after 1], 5 PairVal
     const double *canon_sym_val = nullptr;
     const int *canon_sym_mask = nullptr;
-    // chains of planes (see build_sweep): plane index per chain position (-1: none) and, per position, which
+    // chains of planes (see plan_walk, coding_plan.cpp): plane index per chain position (-1: none) and, per position, which
     // window each far slot reads (2 bits per slot B0, B1, A0, A1: 0 none, 1 previous position, 2 next)
     const int *chain_plane = nullptr;
     const int *chain_far = nullptr;
@@ -445,12 +483,14 @@ struct CgState {
 
 struct schwz_csr;
 namespace schwz {
-// builds the dictionary coding on the host and uploads it (no-op + SCHWZ_OK when it does not pay)
+// plans the codings of the matrix (coding_plan.hpp: row patterns, then row pairs and the z-sweep walk, then the
+// per-entry dictionaries), uploads what was accepted and binds it to A->v; the switches are read here, once
 int build_spmv_dict(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_col, const double *h_val,
                     const std::vector<schwz_idx> &tiles);
 void free_spmv_dict(schwz_csr *A);
-int build_spmv_pair(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_col, const double *h_val,
-                    const std::vector<schwz_idx> &tiles);
+struct CodingOptions;
+struct HostCsr;
+int build_spmv_pair(schwz_csr *A, const CodingOptions &opt, const HostCsr &M);
 void free_spmv_pair(schwz_csr *A);
 int pair_set_dual_split(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_col, int64_t split);
 // marks the tiles whose rows or columns reach index >= split (see CsrView::tile_dual)
@@ -508,18 +548,19 @@ struct schwz_csr {
     void *d_tile_nz = nullptr;
     void *d_stream_part = nullptr;
     void *d_stream_order = nullptr;
-    void *d_code = nullptr, *d_vptr = nullptr, *d_dptr = nullptr, *d_vdict = nullptr, *d_ddict = nullptr;
-    void *d_pat_id = nullptr, *d_tile_table = nullptr, *d_tbl_desc = nullptr, *d_tbl_len = nullptr, *d_tbl_val = nullptr,
-         *d_tbl_delta = nullptr;
-    void *d_pair_rle = nullptr;
-    void *d_sweep_seg_dir = nullptr;
-    void *d_sweep_seg_first = nullptr;
-    void *d_sweep_seg = nullptr, *d_sweep_gen = nullptr, *d_canon_val = nullptr, *d_canon_mask = nullptr,
-         *d_canon_sym_val = nullptr, *d_canon_sym_mask = nullptr, *d_chain_plane = nullptr, *d_chain_far = nullptr;
-    void *d_pair_id = nullptr, *d_tile_ptable = nullptr, *d_ptbl_desc = nullptr, *d_ptbl_len = nullptr,
-         *d_ptbl_val = nullptr, *d_ptbl_meta = nullptr, *d_chunk_dual = nullptr;
+    // device arrays of the codings, one struct per plan of coding_plan.hpp (uploaded and bound to `v` by
+    // spmv_dict.hip / spmv_pair.hip)
+    struct Coding {
+        struct { schwz::DevBuf pat_id, tile_table, tbl_desc, tbl_len, tbl_val, tbl_delta; } pattern;
+        struct { schwz::DevBuf code, vptr, dptr, vdict, ddict; } dict;
+        struct { schwz::DevBuf pair_id, rle, chunk_ptable, ptbl_desc, ptbl_len, ptbl_val, ptbl_meta; } pair;
+        struct {
+            schwz::DevBuf seg, seg_dir, seg_first, gen, canon_val, canon_mask, canon_sym_val, canon_sym_mask, chain_plane,
+                chain_far;
+        } walk;
+        struct { schwz::DevBuf chunk_dual, chain_dual, dual_chunks; } dual;
+    } coding;
     void *d_tile_dual = nullptr;
-    void *d_chain_dual = nullptr, *d_dual_chunks = nullptr;
     std::vector<int> h_chain_plane;  // host copy of CsrView::chain_plane (z-sweep walk built)
     std::vector<schwz_idx> h_tiles;  // host copy of the tile boundaries
     int pair_deal_shift = 0;         // log2 of the run length (in tiles) of the XCD deal the pair kernels derive theirs from
@@ -755,17 +796,3 @@ struct schwz_subdomain {
 namespace schwz {
 int trs_take_error(schwz_trs *t);  // trs.hip: SCHWZ_ERR_HIP (and the reason) if a flag-driven sweep timed out
 }
-
-namespace schwz {
-// host vector -> fresh device allocation; `pad` extra zeroed elements follow the data (the 16-byte
-// SpMV loads may touch them)
-template <typename T>
-inline int upload(const T *h, size_t count, void **d, size_t pad = 0)
-{
-    *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc(d, (count + pad ? count + pad : 1) * sizeof(T)));
-    if (count) SCHWZ_HIP_TRY(hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice));
-    if (pad) SCHWZ_HIP_TRY(hipMemset((char *)*d + count * sizeof(T), 0, pad * sizeof(T)));
-    return SCHWZ_OK;
-}
-}  // namespace schwz

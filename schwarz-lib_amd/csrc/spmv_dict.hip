@@ -18,16 +18,12 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <unordered_map>
 
+#include "coding_plan.hpp"
 #include "device_utils.hpp"
 #include "schwz_internal.hpp"
 
 namespace schwz {
-
-constexpr int kDictMax = 256;
-constexpr int kChunk = 8;  // gathers issued back to back per lane
 
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void spmv_dict_kernel(CsrView A, SpmvArgs a)
@@ -192,53 +188,6 @@ int launch_spmv_dict(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
     return SCHWZ_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// host: build the coding
-// ---------------------------------------------------------------------------------------------
-
-namespace {
-
-template <typename T>
-int up(const std::vector<T> &h, void **d, size_t pad = 0)
-{
-    *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc(d, (h.size() + pad ? h.size() + pad : 1) * sizeof(T)));
-    if (!h.empty()) SCHWZ_HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    if (pad) SCHWZ_HIP_TRY(hipMemset((char *)*d + h.size() * sizeof(T), 0, pad * sizeof(T)));
-    return SCHWZ_OK;
-}
-
-// small open-addressing map from a 64-bit key to a code < 256, reset per tile
-struct TinyMap {
-    uint64_t key[512];
-    int16_t code[512];
-    int used[256];
-    int n = 0;
-    TinyMap() { std::memset(code, -1, sizeof(code)); }
-    void reset()
-    {
-        for (int i = 0; i < n; ++i) code[used[i]] = -1;
-        n = 0;
-    }
-    // returns the code, or -1 when a 257th distinct key arrives
-    int get(uint64_t k)
-    {
-        uint64_t h = k * 0x9E3779B97F4A7C15ull;
-        int slot = (int)(h >> 55);  // 9 bits
-        while (code[slot] >= 0) {
-            if (key[slot] == k) return code[slot];
-            slot = (slot + 1) & 511;
-        }
-        if (n == kDictMax) return -1;
-        key[slot] = k;
-        code[slot] = (int16_t)n;
-        used[n] = slot;
-        return n++;
-    }
-};
-
-}  // namespace
-
 // =============================================================================================
 // Row-pattern coding: the second level of the same idea.  In a stencil-like matrix almost every
 // row of a tile is one of a few (values, col - row offsets) sequences; coding the SEQUENCE costs
@@ -249,8 +198,7 @@ struct TinyMap {
 // row's entry order, products rounded individually: bit-identical to the CSR kernels again.
 // =============================================================================================
 
-constexpr int kPatMax = 64;       // patterns per table
-constexpr int kPatEntries = 1024;  // entries per table (npat * lmax)
+// (kPatMax, kPatEntries, kChunk, pat_stride: coding_plan.hpp, shared with the plan)
 
 // One staged table entry: the value and the BYTE offset of the column relative to the row
 // (col - row) * 8 (WIDE: col - row), read together by one ds_read_b128.  Pattern p starts at entry p * ls with
@@ -261,8 +209,6 @@ struct __attribute__((aligned(16))) PatEntry {
     int off8;
     int pad;
 };
-
-__host__ __device__ inline int pat_stride(int lmax) { return (lmax + kChunk - 1) / kChunk * kChunk; }
 
 // NT: tiles a workgroup works on at a time (NT rows per lane; 2 was measured and is slower: the
 // registers cost occupancy).  WIDE: x needs 64-bit offsets (>= 2^28 columns); otherwise the
@@ -509,257 +455,83 @@ int launch_spmv_pattern(const CsrView &A, int mode, const SpmvArgs &a, int grid,
     return SCHWZ_OK;
 }
 
-namespace {
+// ---- uploads: the plans of coding_plan.hpp become device arrays bound to CsrView; nothing is decided here ----
 
-struct RowPat {
-    std::vector<uint64_t> bits;
-    std::vector<schwz_idx> delta;
-    bool operator==(const RowPat &o) const { return bits == o.bits && delta == o.delta; }
-};
-
-struct Table {
-    int npat = 0, lmax = 0;
-    std::vector<uint8_t> len;
-    std::vector<double> val;       // [npat][lmax]
-    std::vector<schwz_idx> delta;  // [npat][lmax]
-    uint64_t hash = 0;
-    bool same(const Table &o) const
-    {
-        return npat == o.npat && lmax == o.lmax && len == o.len && delta == o.delta &&
-               std::memcmp(val.data(), o.val.data(), val.size() * sizeof(double)) == 0;
-    }
-};
-
-}  // namespace
-
-// Returns SCHWZ_OK; leaves A->v.pat_id null when the coding does not cover >= 90 % of the
-// nonzeros (SCHWZ_SPMV_PATTERN=0 disables, =2 forces whatever the coverage).
-static int build_spmv_pattern(schwz_csr *A, const schwz_idx *rp, const schwz_idx *col, const double *val,
-                              const std::vector<schwz_idx> &tiles)
+// the row-pattern fields of A->v from a plan and the arrays uploaded for it (no arrays: not pattern coded)
+static void bind_pattern(schwz_csr *A, const PatternPlan &P)
 {
-    const char *env = std::getenv("SCHWZ_SPMV_PATTERN");
-    if (env && env[0] == '0') return SCHWZ_OK;
-    const int ntiles = (int)tiles.size() - 1;
-    const int64_t nrows = tiles.back(), nnz = rp[nrows];
-    if (ntiles == 0 || nnz == 0) return SCHWZ_OK;
-    std::vector<uint8_t> pat_id((size_t)nrows, 0);
-    std::vector<schwz_idx> tile_table((size_t)ntiles, -1);
-    std::vector<Table> tables;
-    std::unordered_multimap<uint64_t, int> by_hash;
-    int64_t coded = 0;
-    // every tile's table by all threads (a tile's rows, ids and table depend on that tile alone), then the tables
-    // are de-duplicated in tile order -- the ids a sequential pass would give
-    std::vector<Table> tile_tb((size_t)ntiles);
-    std::vector<char> tile_ok((size_t)ntiles, 0);
-    parallel_blocks(ntiles, 256, [&](int, int, int64_t t_begin, int64_t t_end) {
-        std::vector<RowPat> pats;
-        for (int t = (int)t_begin; t < (int)t_end; ++t) {
-            const schwz_idx r0 = tiles[(size_t)t], r1 = tiles[(size_t)t + 1];
-            if (rp[r1] == rp[r0] || (r1 - r0 == 1 && rp[r1] - rp[r0] > kTileNnz - 2)) continue;
-            pats.clear();
-            int lmax = 0;
-            bool ok = true;
-            RowPat p;
-            for (schwz_idx r = r0; r < r1 && ok; ++r) {
-                const int len = rp[r + 1] - rp[r];
-                if (len > 255) {
-                    ok = false;
-                    break;
-                }
-                p.bits.resize((size_t)len);
-                p.delta.resize((size_t)len);
-                for (int k = 0; k < len; ++k) {
-                    std::memcpy(&p.bits[(size_t)k], &val[rp[r] + k], 8);
-                    p.delta[(size_t)k] = col[rp[r] + k] - r;
-                }
-                int id = -1;
-                for (size_t q = 0; q < pats.size(); ++q)
-                    if (pats[q] == p) {
-                        id = (int)q;
-                        break;
-                    }
-                if (id < 0) {
-                    if ((int)pats.size() == kPatMax) {
-                        ok = false;
-                        break;
-                    }
-                    id = (int)pats.size();
-                    lmax = std::max(lmax, len);
-                    pats.push_back(p);
-                }
-                pat_id[(size_t)r] = (uint8_t)id;
-            }
-            if (!ok || (int64_t)pats.size() * pat_stride(std::max(lmax, 1)) > kPatEntries) continue;
-            Table &tb = tile_tb[(size_t)t];
-            tb.npat = (int)pats.size();
-            tb.lmax = std::max(lmax, 1);
-            tb.len.resize((size_t)tb.npat);
-            tb.val.assign((size_t)tb.npat * tb.lmax, 0.0);
-            tb.delta.assign((size_t)tb.npat * tb.lmax, 0);
-            uint64_t h = 1469598103934665603ull;
-            for (int q = 0; q < tb.npat; ++q) {
-                tb.len[(size_t)q] = (uint8_t)pats[(size_t)q].bits.size();
-                for (size_t k = 0; k < pats[(size_t)q].bits.size(); ++k) {
-                    std::memcpy(&tb.val[(size_t)q * tb.lmax + k], &pats[(size_t)q].bits[k], 8);
-                    tb.delta[(size_t)q * tb.lmax + k] = pats[(size_t)q].delta[k];
-                    h = (h ^ pats[(size_t)q].bits[k]) * 1099511628211ull;
-                    h = (h ^ (uint64_t)(int64_t)pats[(size_t)q].delta[k]) * 1099511628211ull;
-                }
-                h = (h ^ 0xffull ^ (uint64_t)tb.len[(size_t)q]) * 1099511628211ull;
-            }
-            tb.hash = h;
-            tile_ok[(size_t)t] = 1;
-        }
-    });
-    for (int t = 0; t < ntiles; ++t) {
-        if (!tile_ok[(size_t)t]) continue;
-        Table &tb = tile_tb[(size_t)t];
-        int id = -1;
-        auto range = by_hash.equal_range(tb.hash);
-        for (auto it = range.first; it != range.second; ++it)
-            if (tables[(size_t)it->second].same(tb)) {
-                id = it->second;
-                break;
-            }
-        if (id < 0) {
-            id = (int)tables.size();
-            by_hash.emplace(tb.hash, id);
-            tables.push_back(std::move(tb));
-        }
-        tile_table[(size_t)t] = id;
-        coded += rp[tiles[(size_t)t + 1]] - rp[tiles[(size_t)t]];
-    }
-    tile_tb.clear();
-    tile_tb.shrink_to_fit();
-    A->pattern_fraction = (double)coded / (double)nnz;
-    if (A->pattern_fraction < 0.9 && !(env && env[0] == '2')) return SCHWZ_OK;
-    // a table pays off only when it is shared: with one table per tile the "coding" is just the
-    // raw data in another layout
-    if (tables.size() * 4 > (size_t)ntiles && !(env && env[0] == '2')) return SCHWZ_OK;
-    std::vector<schwz_idx> desc;
-    std::vector<uint8_t> lens;
-    std::vector<double> vals;
-    std::vector<schwz_idx> deltas;
-    for (const Table &tb : tables) {
-        desc.push_back((schwz_idx)vals.size());
-        desc.push_back((schwz_idx)lens.size());
-        desc.push_back(tb.npat);
-        desc.push_back(tb.lmax);
-        lens.insert(lens.end(), tb.len.begin(), tb.len.end());
-        vals.insert(vals.end(), tb.val.begin(), tb.val.end());
-        deltas.insert(deltas.end(), tb.delta.begin(), tb.delta.end());
-    }
-    int rc;
-    if ((rc = up(pat_id, &A->d_pat_id)) || (rc = up(tile_table, &A->d_tile_table)) || (rc = up(desc, &A->d_tbl_desc)) ||
-        (rc = up(lens, &A->d_tbl_len)) || (rc = up(vals, &A->d_tbl_val)) || (rc = up(deltas, &A->d_tbl_delta)))
+    const auto &b = A->coding.pattern;
+    A->v.pat_id = b.pat_id.as<uint8_t>();
+    A->v.tile_table = b.tile_table.as<schwz_idx>();
+    A->v.tbl_desc = b.tbl_desc.as<schwz_idx>();
+    A->v.tbl_len = b.tbl_len.as<uint8_t>();
+    A->v.tbl_val = b.tbl_val.as<double>();
+    A->v.tbl_delta = b.tbl_delta.as<schwz_idx>();
+    A->pattern_fraction = P.fraction;
+}
+
+static void bind_dict(schwz_csr *A, const DictPlan &P)
+{
+    const auto &b = A->coding.dict;
+    A->v.code = b.code.as<uint16_t>();
+    A->v.vdict_ptr = b.vptr.as<schwz_idx>();
+    A->v.ddict_ptr = b.dptr.as<schwz_idx>();
+    A->v.vdict = b.vdict.as<double>();
+    A->v.ddict = b.ddict.as<schwz_idx>();
+    A->dict_fraction = P.fraction;
+}
+
+static int upload_pattern(schwz_csr *A, const PatternPlan &P)
+{
+    auto &b = A->coding.pattern;
+    int rc = SCHWZ_OK;
+    if (P.built && ((rc = b.pat_id.put(P.pat_id)) || (rc = b.tile_table.put(P.tile_table)) || (rc = b.tbl_desc.put(P.tbl_desc)) ||
+                    (rc = b.tbl_len.put(P.tbl_len)) || (rc = b.tbl_val.put(P.tbl_val)) || (rc = b.tbl_delta.put(P.tbl_delta))))
         return rc;
-    A->v.pat_id = (const uint8_t *)A->d_pat_id;
-    A->v.tile_table = (const schwz_idx *)A->d_tile_table;
-    A->v.tbl_desc = (const schwz_idx *)A->d_tbl_desc;
-    A->v.tbl_len = (const uint8_t *)A->d_tbl_len;
-    A->v.tbl_val = (const double *)A->d_tbl_val;
-    A->v.tbl_delta = (const schwz_idx *)A->d_tbl_delta;
+    bind_pattern(A, P);
     return SCHWZ_OK;
 }
 
+static int upload_dict(schwz_csr *A, const DictPlan &P)
+{
+    auto &b = A->coding.dict;
+    int rc = SCHWZ_OK;
+    if (P.built && ((rc = b.code.put(P.code, 8)) || (rc = b.vptr.put(P.vptr)) || (rc = b.dptr.put(P.dptr)) ||
+                    (rc = b.vdict.put(P.vdict)) || (rc = b.ddict.put(P.ddict))))
+        return rc;
+    bind_dict(A, P);
+    return SCHWZ_OK;
+}
+
+// Row patterns; row pairs and the walk only over accepted patterns (stencil-like matrices); per-entry dictionaries
+// only without patterns or when forced.  A coding that is not accepted leaves its fields null and its fraction
+// known.  If an upload fails, everything uploaded so far is released and the error returned.
 int build_spmv_dict(schwz_csr *A, const schwz_idx *rp, const schwz_idx *col, const double *val,
                     const std::vector<schwz_idx> &tiles)
 {
-    {
-        int rc;
-        {
-            StageTimer t("codings: row patterns");
-            rc = build_spmv_pattern(A, rp, col, val, tiles);
-        }
-        if (!rc && A->v.pat_id) {
-            StageTimer t("codings: row pairs + walk tables");
-            rc = build_spmv_pair(A, rp, col, val, tiles);  // stencil-like: pairs too
-        }
-        if (rc) {
-            free_spmv_dict(A);
-            return rc;
-        }
-    }
-    const char *env = std::getenv("SCHWZ_SPMV_DICT");
-    if (env && env[0] == '0') return SCHWZ_OK;
-    // the row-pattern coding supersedes the per-entry one unless that is forced too
-    if (A->v.pat_id && !(env && env[0] == '2')) return SCHWZ_OK;
-    const int ntiles = (int)tiles.size() - 1;
-    const int64_t nnz = rp[tiles.back()];
-    if (ntiles == 0 || nnz == 0) return SCHWZ_OK;
-    std::vector<uint16_t> code((size_t)nnz, 0);
-    std::vector<schwz_idx> vptr((size_t)ntiles + 1, 0), dptr((size_t)ntiles + 1, 0);
-    std::vector<double> vdata;
-    std::vector<schwz_idx> ddata;
-    std::vector<double> tv;
-    std::vector<schwz_idx> td;
-    TinyMap vm, dm;
-    int64_t coded = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const schwz_idx r0 = tiles[(size_t)t], r1 = tiles[(size_t)t + 1];
-        const int64_t s = rp[r0], e = rp[r1];
-        // the kernel stages the codes of the 8-byte aligned window [s & ~3, e) : 2048 at most
-        bool ok = e > s && (s & 3) + (e - s) <= kTileNnz;
-        vm.reset();
-        dm.reset();
-        tv.clear();
-        td.clear();
-        if (ok) {
-            for (schwz_idx r = r0; r < r1 && ok; ++r) {
-                for (int64_t j = rp[r]; j < rp[r + 1]; ++j) {
-                    uint64_t bits;
-                    std::memcpy(&bits, &val[j], 8);
-                    const int before_v = vm.n, before_d = dm.n;
-                    const int cv = vm.get(bits);
-                    const int cdv = dm.get((uint64_t)(int64_t)(col[j] - r));
-                    if (cv < 0 || cdv < 0) {
-                        ok = false;
-                        break;
-                    }
-                    if (vm.n > before_v) tv.push_back(val[j]);
-                    if (dm.n > before_d) td.push_back(col[j] - r);
-                    code[(size_t)j] = (uint16_t)(cv | (cdv << 8));
-                }
-            }
-        }
-        if (!ok) {
-            vptr[(size_t)t + 1] = vptr[(size_t)t];
-            dptr[(size_t)t + 1] = dptr[(size_t)t];
-            continue;
-        }
-        coded += e - s;
-        vdata.insert(vdata.end(), tv.begin(), tv.end());
-        ddata.insert(ddata.end(), td.begin(), td.end());
-        vptr[(size_t)t + 1] = (schwz_idx)vdata.size();
-        dptr[(size_t)t + 1] = (schwz_idx)ddata.size();
-    }
-    A->dict_fraction = (double)coded / (double)nnz;
-    // worth it only when (nearly) the whole matrix is coded; SCHWZ_SPMV_DICT=2 forces it (tests)
-    if (A->dict_fraction < 0.9 && !(env && env[0] == '2')) return SCHWZ_OK;
+    const CodingOptions opt = coding_options_from_env();
+    const HostCsr M{A->v.nrows, A->v.ncols, rp, col, val, tiles};
     int rc;
-    if ((rc = up(code, &A->d_code, 8)) || (rc = up(vptr, &A->d_vptr)) || (rc = up(dptr, &A->d_dptr)) ||
-        (rc = up(vdata, &A->d_vdict)) || (rc = up(ddata, &A->d_ddict))) {
-        free_spmv_dict(A);
-        return rc;
+    {
+        StageTimer t("codings: row patterns");
+        rc = upload_pattern(A, plan_patterns(opt, M));
     }
-    A->v.code = (const uint16_t *)A->d_code;
-    A->v.vdict_ptr = (const schwz_idx *)A->d_vptr;
-    A->v.ddict_ptr = (const schwz_idx *)A->d_dptr;
-    A->v.vdict = (const double *)A->d_vdict;
-    A->v.ddict = (const schwz_idx *)A->d_ddict;
-    return SCHWZ_OK;
+    if (!rc && A->v.pat_id) {
+        StageTimer t("codings: row pairs + walk tables");
+        rc = build_spmv_pair(A, opt, M);
+    }
+    if (!rc) rc = upload_dict(A, plan_dict(opt, M, A->v.pat_id != nullptr));
+    if (rc) free_spmv_dict(A);
+    return rc;
 }
 
 void free_spmv_dict(schwz_csr *A)
 {
-    void *ptrs[] = {A->d_code, A->d_vptr, A->d_dptr, A->d_vdict, A->d_ddict, A->d_pat_id, A->d_tile_table,
-                    A->d_tbl_desc, A->d_tbl_len, A->d_tbl_val, A->d_tbl_delta};
-    for (void *p : ptrs) (void)hipFree(p);
+    A->coding.pattern = {};
+    A->coding.dict = {};
+    bind_pattern(A, PatternPlan());
+    bind_dict(A, DictPlan());
     free_spmv_pair(A);
-    A->d_code = A->d_vptr = A->d_dptr = A->d_vdict = A->d_ddict = nullptr;
-    A->d_pat_id = A->d_tile_table = A->d_tbl_desc = A->d_tbl_len = A->d_tbl_val = A->d_tbl_delta = nullptr;
-    A->v.code = nullptr;
-    A->v.pat_id = nullptr;
 }
 
 }  // namespace schwz

@@ -19,23 +19,18 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <unordered_map>
 #include <vector>
 
+#include "coding_plan.hpp"
 #include "device_utils.hpp"
 #include "schwz_hip.h"
 #include "schwz_internal.hpp"
 
 namespace schwz {
 
-constexpr int kPairPats = 64;      // patterns per table
-constexpr int kPairEntries = 512;  // staged entries per table (npat * stride)
-constexpr int kPairChunk = 8;      // gathers issued back to back per lane
+// (kPairPats, kPairEntries, kPairChunk, kPairRows, pair_stride: coding_plan.hpp, shared with the plan)
 // dynamic shared memory of every launch: values (16 B), offsets (4 B) per staged entry, group masks
 constexpr int kPairTableLds = kPairEntries * 16 + kPairEntries * 4 + (kPairEntries / 4) * 4;
-
-__host__ __device__ inline int pair_stride(int lmax, int ch = kPairChunk) { return (lmax + ch - 1) / ch * ch; }
 
 struct __attribute__((aligned(16))) PairVal {
     double a, b;
@@ -46,8 +41,6 @@ struct __attribute__((aligned(8))) PairMeta {
 };
 
 typedef double pvd2 __attribute__((ext_vector_type(2)));
-
-constexpr int kPairRows = 2 * kBlock;  // rows per chunk: one pair per lane
 
 // chunk dealt to XCD `xcd` as its j-th one (block-cyclic in runs of 1 << sh), -1 past the end
 __device__ __forceinline__ int xcd_chunk(int nchunks, int sh, int xcd, int j)
@@ -934,9 +927,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
 // bytes: exactly the halo, fetched twice.  All three together, in-box (profiles/r03_dd_ab.txt): launch 0.0789 ->
 // 0.0740 ms on the cube, 0.0861 -> 0.0729 ms on the 512 x 512 x 64 slab (0.585 -> 0.69 of peak; the step
 // 1.95 -> 1.82 ms), the same bits.  0 restores the round-2 schedule.
-#ifndef SCHWZ_DD
-#define SCHWZ_DD 7
-#endif
+// (default: 7, set in coding_plan.hpp together with the halo-line count kDirdotHaloLines that follows from it)
 template <int NHL, int NH, bool FIRST = false, int RUNS = 8>
 __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView A, SpmvArgs a)
 {
@@ -1219,21 +1210,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
 
 // ---- who may take the z-sweep walk: one definition per launch, asked by launch_spmv_pair and by the CG plan ----
 
-// what the launches raise the walk kernels' dynamic-LDS limit to
-constexpr size_t kSweepLdsLimit = 96 << 10;
-
-// dynamic LDS of the update / start walk on bands of T rows: the ring (4 T own + 4 NX halo doubles) and the
-// nine-slot tables of every pattern
-static size_t sweep_update_lds(int64_t T, int64_t nx, int npat)
-{
-    return (size_t)(4 * T + 4 * nx) * sizeof(double) + (size_t)npat * (9 * 16 + 4);
-}
-
-// ... of the fused direction walk: its window carries the halo of r and p, its tables the upper triangle's five slots
-static size_t sweep_dirdot_lds(int64_t T_dir, int64_t nx, int npat)
-{
-    return (size_t)(4 * T_dir + ((SCHWZ_DD & 2) ? 3 : 2) * nx) * sizeof(double) + (size_t)npat * (5 * 16 + 4);
-}
+// (dynamic LDS of the walks: sweep_update_lds / sweep_dirdot_lds of coding_plan.hpp, which the plan of the segment
+// tables uses too, with this translation unit's kDirdotHaloLines)
 
 // whether a kSpmvCgUpdate launch that leaves x alone (cg_x == nullptr) can take the walk: single-table coding,
 // 32-bit byte offsets of x, the Jacobi diagonal absent, a scalar or a full vector, segments and companion
@@ -1254,7 +1232,7 @@ bool pair_sweep_dirdot_ok(const CsrView &A, int grid, int diag_mode)
     const int nh = A.sweep_T_dir / kPairRows, nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock;
     return pair_sweep_update_ok(A, grid, diag_mode) && A.canon_sym_val && diag_mode != 1 &&
            A.sweep_nslots_dir + A.sweep_gen_blocks <= grid && (nh == 1 || nh == 2 || nh == 4) && nhl <= 2 &&
-           sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat) <= kSweepLdsLimit;
+           sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat, kDirdotHaloLines) <= kSweepLdsLimit;
 }
 
 // whether a solve on this matrix can START in the z-sweep walk: the INIT form of the update walk and the
@@ -1329,7 +1307,7 @@ template <bool FIRST>
 static bool launch_dirdot_walk(const CsrView &A, const SpmvArgs &b, hipStream_t s)
 {
     const int nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock, nh = A.sweep_T_dir / kPairRows;
-    const size_t lds = sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat);
+    const size_t lds = sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat, kDirdotHaloLines);
     if (nh == 1)
         return nhl == 1 ? launch_dirdot_variant<1, 1, FIRST>(A, b, lds, s) : launch_dirdot_variant<2, 1, FIRST>(A, b, lds, s);
     if (nh == 2)
@@ -1482,1003 +1460,139 @@ int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
     return SCHWZ_OK;
 }
 
-namespace {
+// ---- uploads: the plans of coding_plan.hpp become device arrays bound to CsrView; nothing is decided here ----
 
-struct PairEntryH {
-    schwz_idx off;
-    int flags;
-    uint64_t va, vb;
-    bool operator==(const PairEntryH &o) const { return off == o.off && flags == o.flags && va == o.va && vb == o.vb; }
-};
-
-struct PairTable {
-    int npat = 0, lmax = 0;
-    std::vector<uint8_t> len;
-    std::vector<PairEntryH> ent;  // [npat][lmax], padded with {0,0,0,0}
-    uint64_t hash = 0;
-    bool same(const PairTable &o) const { return npat == o.npat && lmax == o.lmax && len == o.len && ent == o.ent; }
-};
-
-template <typename T>
-int upv(const std::vector<T> &h, void **d)
+// the pair fields of A->v from a plan and the arrays uploaded for it (a fresh plan, no arrays: not pair coded)
+static void bind_pair(schwz_csr *A, const PairPlan &P)
 {
-    *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc(d, (h.empty() ? 1 : h.size()) * sizeof(T)));
-    if (!h.empty()) SCHWZ_HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    CsrView &v = A->v;
+    const auto &b = A->coding.pair;
+    v.pair_id = b.pair_id.as<uint8_t>();
+    v.pair_rle = b.rle.as<uint4>();
+    v.pair_rle_runs = P.rle_runs;
+    v.chunk_ptable = b.chunk_ptable.as<schwz_idx>();
+    v.ptbl_desc = b.ptbl_desc.as<schwz_idx>();
+    v.ptbl_len = b.ptbl_len.as<uint8_t>();
+    v.ptbl_val = b.ptbl_val.as<double>();
+    v.ptbl_meta = b.ptbl_meta.as<schwz_idx>();
+    v.pair_single = P.single;
+    std::copy(P.canon, P.canon + 8, v.pair_canon);
+    v.pair_sym_base = P.sym_base;
+    v.pair_shift = P.shift;
+    A->pair_fraction = P.fraction;
+    A->pair_code_bytes = P.code_bytes;
+}
+
+// ... the z-sweep walk's; a launch without a segment table of its own reads the table before it
+static void bind_walk(schwz_csr *A, const WalkPlan &W)
+{
+    CsrView &v = A->v;
+    const auto &b = A->coding.walk;
+    v.sweep_gen_mode = W.gen_mode;
+    v.sweep_T = W.T;
+    v.sweep_nx = W.nx;
+    v.sweep_pl = W.pl;
+    v.sweep_nslots = W.nslots();
+    v.sweep_ngen = (int)W.gen.size();
+    v.sweep_gen_blocks = W.gen_blocks;
+    v.sweep_seg = b.seg.as<int4>();
+    v.sweep_gen = b.gen.as<schwz_idx>();
+    v.sweep_T_dir = W.T_dir;
+    v.sweep_nslots_dir = W.nslots_dir();
+    v.sweep_seg_dir = b.seg_dir.p ? b.seg_dir.as<int4>() : v.sweep_seg;
+    v.sweep_T_first = W.T_first;
+    v.sweep_nslots_first = W.nslots_first();
+    v.sweep_seg_first = b.seg_first.p ? b.seg_first.as<int4>() : v.sweep_seg_dir;
+    v.canon_val = b.canon_val.as<double>();
+    v.canon_mask = b.canon_mask.as<int>();
+    v.canon_npat = W.npat;
+    v.canon_sym_val = b.canon_sym_val.as<double>();
+    v.canon_sym_mask = b.canon_sym_mask.as<int>();
+    v.chain_plane = b.chain_plane.as<int>();
+    v.chain_far = b.chain_far.as<int>();
+    A->h_chain_plane = W.chain_plane;
+}
+
+// ... and the fused dual residual's
+static void bind_dual(schwz_csr *A, const DualPlan &D)
+{
+    const auto &b = A->coding.dual;
+    A->v.chunk_dual = b.chunk_dual.as<uint8_t>();
+    A->v.chain_dual = b.chain_dual.as<int>();
+    A->v.dual_chunks = b.dual_chunks.as<schwz_idx>();
+    A->v.dual_nchunks = (int)D.dual_chunks.size();
+    A->v.dual_blocks = D.dual_blocks;
+}
+
+static int upload_walk(schwz_csr *A, const WalkPlan &W)
+{
+    if (!W.built()) return SCHWZ_OK;
+    auto &b = A->coding.walk;
+    int rc = SCHWZ_OK;
+    if ((!W.seg_dir.empty() && (rc = b.seg_dir.put(W.seg_dir))) || (!W.seg_first.empty() && (rc = b.seg_first.put(W.seg_first))) ||
+        (rc = b.seg.put(W.seg)) || (rc = b.gen.put(W.gen)) || (rc = b.canon_val.put(W.canon_val)) ||
+        (rc = b.canon_mask.put(W.canon_mask)) || (rc = b.chain_plane.put(W.chain_plane)) ||
+        (rc = b.chain_far.put(W.chain_far)) ||
+        (!W.canon_sym_val.empty() && ((rc = b.canon_sym_val.put(W.canon_sym_val)) || (rc = b.canon_sym_mask.put(W.canon_sym_mask)))))
+        return rc;
     return SCHWZ_OK;
 }
 
-}  // namespace
-
-// The z-sweep walk (spmv_pair_sweep_kernel, spmv_pair_dirdot_sweep_kernel): host side.
-//
-// Geometry.  The matrix is cut into PLANES of PL consecutive rows (PL = the dominant far offset of the
-// canonical layout, NX its in-plane line offset).  A row of plane k may couple to {-NX, -1, 0, +1, +NX}
-// inside its plane and to the row at the SAME in-plane position of at most two other planes: for the
-// interior of a grid in natural order those are k - 1 and k + 1; for a subdomain whose overlap planes are
-// appended behind its interior the first interior plane couples to the plane PL rows on and
-// to the lower overlap plane far behind it, and so on.  Planes linked like that form CHAINS; a workgroup
-// sweeps a band of rows along a chain and keeps the windows of three consecutive chain positions in LDS,
-// so every far operand of a row is in the window before or after its own -- wherever the numbering put
-// that plane.  Slots of a row pair, in the order the entries are summed (= ascending column, the CSR
-// order): [far before 0, far before 1, -NX, -1, 0, +1, +NX, far after 0, far after 1]; which window
-// (previous / next chain position) a far slot reads is a property of the plane (sweep_far).
-// A plane takes part when all its chunks are full, run-length coded, and every pattern in them fits those
-// slots; the rest of the matrix is left to the companion launch (sweep_gen).
-static int build_sweep(schwz_csr *A, int64_t nrows, const PairTable &tb, const PairTable *ts,
-                       const std::vector<uint8_t> &pair_id, const std::vector<uint16_t> &rle, int64_t ntiles)
+// Row pairs and, over a single-table coding, the z-sweep walk.  On an error the caller releases the codings.
+int build_spmv_pair(schwz_csr *A, const CodingOptions &opt, const HostCsr &M)
 {
-    // SCHWZ_SWEEP_WHY=1: says on stderr why a matrix gets no z-sweep walk
-    auto no_walk = [](const char *why) {
-        static const bool say = [] {
-            const char *e = std::getenv("SCHWZ_SWEEP_WHY");
-            return e && e[0] == '1';
-        }();
-        if (say) std::fprintf(stderr, "[schwz] no z-sweep walk: %s\n", why);
+    PairPlan P;
+    if (!plan_pair_tables(opt, M, P)) {
+        A->pair_fraction = P.fraction;
         return SCHWZ_OK;
-    };
-    const char *sw_env = std::getenv("SCHWZ_SPMV_SWEEP");
-    const int sw_mode = sw_env ? std::atoi(sw_env) : 1;
-    const int *cn = A->v.pair_canon;
-    // A 5-point (2-D) stencil {-N, -1, 0, +1, +N} in natural order is the same walk with the x LINE in the role of the
-    // plane: the canonical layout then repeats its outer offsets (cn[0] == cn[1] == -N, cn[5] == cn[6] == N), the
-    // +-N neighbours sit at the same position of the previous / next line (the far slots), and nothing couples rows
-    // +-NX apart inside a "plane" -- NX is only the width of the halo the kernels load around a band, 2 rows: the
-    // band's left and right neighbour.
-    const bool two_d = cn[7] && cn[5] == cn[6] && cn[0] == cn[1] && cn[6] > 2;
-    const int64_t NX = two_d ? 2 : cn[5], PL = cn[6];
-    // Planes of whole 512-row chunks: a band's sub-bands ARE chunks and the pattern ids come from the chunk's
-    // run-length record.  Any other even plane size (200 x 200, 300 x 300, ...; round 3): "gen mode" -- byte ids, a
-    // partial last band per plane, and the walk must cover the whole matrix (no companion launch: its unit is the
-    // chunk, and chunks straddle planes there).  SCHWZ_SWEEP_GEN=0: whole-chunk planes only.
-    const char *gen_env = std::getenv("SCHWZ_SWEEP_GEN");
-    const bool gen_mode = PL % kPairRows != 0;
-    const bool shape_ok = cn[7] && cn[0] == -PL && (two_d || cn[1] == -NX) && NX >= 2 && PL > NX && NX % 2 == 0 && PL % 2 == 0 &&
-                          NX <= 1024 && (!gen_mode || (!(gen_env && gen_env[0] == '0') && nrows % PL == 0 && PL >= kPairRows));
-    if (sw_mode == 0) return no_walk("switched off (SCHWZ_SPMV_SWEEP=0)");
-    if (!cn[7]) return no_walk("no canonical stencil layout (the patterns do not share one set of offsets)");
-    if (!shape_ok) return no_walk("offsets are not those of an x-y-z (or x-y) numbering with even line and plane sizes");
-    if (!(nrows >= (int64_t(1) << 20) || sw_mode == 2)) return no_walk("below 2^20 rows (SCHWZ_SPMV_SWEEP=2 walks anyway)");
-    if (nrows < 3 * PL || nrows % 2 || A->v.ncols != nrows) return no_walk("fewer than three planes, or not square");
-    if (rle.empty()) return no_walk("chunks have no run-length records");
-    const int nchunks = (int)((nrows + kPairRows - 1) / kPairRows);
-    const int nplanes = (int)(nrows / PL), cpp = (int)(PL / kPairRows);
-    // ---- per plane: the far offsets its rows use -------------------------------------------------
-    auto in_plane = [&](schwz_idx off) { return off == 0 || off == 1 || off == -1 || off == NX || off == -NX; };
-    std::vector<std::vector<schwz_idx>> pat_far((size_t)tb.npat);
-    std::vector<uint8_t> pat_bad((size_t)tb.npat, 0);
-    for (int q = 0; q < tb.npat; ++q) {
-        if ((int)tb.len[(size_t)q] > 9) pat_bad[(size_t)q] = 1;
-        for (int k = 0; k < (int)tb.len[(size_t)q]; ++k) {
-            const schwz_idx off = tb.ent[(size_t)q * tb.lmax + k].off;
-            if (in_plane(off)) continue;
-            if (off % PL != 0) pat_bad[(size_t)q] = 1;  // a far entry must keep the in-plane position
-            pat_far[(size_t)q].push_back(off);
-        }
     }
-    std::vector<uint8_t> plane_ok((size_t)nplanes, 1);
-    std::vector<std::vector<schwz_idx>> plane_far((size_t)nplanes);  // sorted ascending
-    std::vector<std::vector<int>> plane_pats((size_t)nplanes);
-    for (int k = 0; k < nplanes; ++k) {
-        std::vector<uint8_t> used((size_t)tb.npat, 0);
-        if (gen_mode)  // the patterns of the plane's pairs, from the byte ids
-            for (int64_t pr = (int64_t)k * PL / 2; pr < (int64_t)(k + 1) * PL / 2; ++pr) used[(size_t)pair_id[(size_t)pr]] = 1;
-        for (int c = k * cpp; !gen_mode && c < (k + 1) * cpp && plane_ok[(size_t)k]; ++c) {
-            const int R = A->v.pair_rle_runs;
-            if (rle[(size_t)c * R] == 0xffffu) {  // ids must run-length code (scalar loads only)
-                plane_ok[(size_t)k] = 0;
-                break;
-            }
-            // the patterns of a chunk are the ids of its runs
-            for (int r = 0; r < R; ++r) used[(size_t)(rle[(size_t)c * R + r] >> 8)] = 1;
-        }
-        if (!plane_ok[(size_t)k]) continue;
-        std::vector<schwz_idx> far;
-        for (int q = 0; q < tb.npat; ++q) {
-            if (!used[(size_t)q]) continue;
-            plane_pats[(size_t)k].push_back(q);
-            if (pat_bad[(size_t)q]) plane_ok[(size_t)k] = 0;
-            for (schwz_idx f : pat_far[(size_t)q]) far.push_back(f);
-        }
-        std::sort(far.begin(), far.end());
-        far.erase(std::unique(far.begin(), far.end()), far.end());
-        int nb = 0, na = 0;
-        for (schwz_idx f : far) {
-            const int64_t j = k + f / PL;
-            if (j < 0 || j >= nplanes) plane_ok[(size_t)k] = 0;
-            (f < 0 ? nb : na)++;
-        }
-        if (far.size() > 2 || nb > 2 || na > 2) plane_ok[(size_t)k] = 0;
-        if (plane_ok[(size_t)k]) plane_far[(size_t)k] = far;
-    }
-    // ---- chains: planes linked by their far couplings (degree <= 2: paths) ------------------------
-    std::vector<std::vector<int>> adj((size_t)nplanes);
-    auto link = [&](int x, int y) {
-        if (std::find(adj[(size_t)x].begin(), adj[(size_t)x].end(), y) == adj[(size_t)x].end()) adj[(size_t)x].push_back(y);
-    };
-    for (int k = 0; k < nplanes; ++k)
-        for (schwz_idx f : plane_far[(size_t)k]) {
-            link(k, (int)(k + f / PL));
-            link((int)(k + f / PL), k);
-        }
-    for (int k = 0; k < nplanes; ++k)
-        if (adj[(size_t)k].size() > 2) {  // a plane somebody else points at as a third neighbour: not a path
-            plane_ok[(size_t)k] = 0;
-            for (int j : adj[(size_t)k]) plane_ok[(size_t)j] = 0;
-        }
-    std::vector<int> chain_plane;   // concatenated chains, -1 between them and at both ends
-    std::vector<int> pos_of((size_t)nplanes, -1);
-    chain_plane.push_back(-1);
-    std::vector<uint8_t> seen((size_t)nplanes, 0);
-    for (int pass = 0; pass < 2; ++pass)   // paths from their ends first, then whatever is left (rings: cut anywhere)
-        for (int k0 = 0; k0 < nplanes; ++k0) {
-            if (seen[(size_t)k0] || adj[(size_t)k0].size() > 2) continue;
-            if (pass == 0 && adj[(size_t)k0].size() != 1 && !adj[(size_t)k0].empty()) continue;
-            int prev = -1, k = k0;
-            while (k >= 0 && !seen[(size_t)k] && adj[(size_t)k].size() <= 2) {
-                seen[(size_t)k] = 1;
-                pos_of[(size_t)k] = (int)chain_plane.size();
-                chain_plane.push_back(k);
-                int next = -1;
-                for (int j : adj[(size_t)k])
-                    if (j != prev && !seen[(size_t)j]) next = j;
-                prev = k;
-                k = next;
-            }
-            chain_plane.push_back(-1);
-        }
-    const int npos = (int)chain_plane.size();
-    for (int k = 0; k < 4; ++k) chain_plane.push_back(-1);  // the kernels look up to four positions ahead
-    // ---- per chain position: which window each far slot reads; per pattern: its nine slots --------
-    // far code: 2 bits per far slot (B0, B1, A0, A1): 0 none, 1 previous chain position, 2 next
-    std::vector<int> chain_far((size_t)npos + 4, 0);
-    std::vector<double> cval((size_t)tb.npat * 18, 0.0), sval((size_t)tb.npat * 10, 0.0);
-    std::vector<int> cmsk((size_t)tb.npat, 0), smsk((size_t)tb.npat, 0);
-    std::vector<int8_t> pat_slot_set((size_t)tb.npat, 0);
-    std::vector<std::vector<int8_t>> pat_slots((size_t)tb.npat);
-    bool sym_ok = ts != nullptr && ts->npat == tb.npat;
-    for (int p = 0; p < npos; ++p) {
-        const int k = chain_plane[(size_t)p];
-        if (k < 0 || !plane_ok[(size_t)k]) continue;
-        const std::vector<schwz_idx> &far = plane_far[(size_t)k];
-        std::vector<schwz_idx> fb, fa;
-        for (schwz_idx f : far) (f < 0 ? fb : fa).push_back(f);
-        int code = 0;
-        bool ok = true;
-        auto src_of = [&](schwz_idx f) -> int {
-            const int j = (int)(k + f / PL);
-            if (pos_of[(size_t)j] == p - 1) return 1;
-            if (pos_of[(size_t)j] == p + 1) return 2;
-            ok = false;
-            return 0;
-        };
-        for (size_t i = 0; i < fb.size(); ++i) code |= src_of(fb[i]) << (2 * (int)i);
-        for (size_t i = 0; i < fa.size(); ++i) code |= src_of(fa[i]) << (4 + 2 * (int)i);
-        // slots of every pattern of the plane; a pattern shared with another plane must get the same ones
-        for (int q : plane_pats[(size_t)k]) {
-            std::vector<int8_t> slots;
-            for (int e = 0; e < (int)tb.len[(size_t)q] && ok; ++e) {
-                const schwz_idx off = tb.ent[(size_t)q * tb.lmax + e].off;
-                int slot = -1;
-                if (off == -NX) slot = 2;
-                else if (off == -1) slot = 3;
-                else if (off == 0) slot = 4;
-                else if (off == 1) slot = 5;
-                else if (off == NX) slot = 6;
-                else {
-                    for (size_t i = 0; i < fb.size(); ++i)
-                        if (fb[i] == off) slot = (int)i;
-                    for (size_t i = 0; i < fa.size(); ++i)
-                        if (fa[i] == off) slot = 7 + (int)i;
-                }
-                if (slot < 0) ok = false;
-                slots.push_back((int8_t)slot);
-            }
-            if (!ok) break;
-            if (pat_slot_set[(size_t)q] && pat_slots[(size_t)q] != slots) ok = false;
-            if (!ok) break;
-            pat_slot_set[(size_t)q] = 1;
-            pat_slots[(size_t)q] = slots;
-        }
-        if (!ok) {
-            plane_ok[(size_t)k] = 0;
-            continue;
-        }
-        chain_far[(size_t)p] = code;
-    }
-    for (int q = 0; q < tb.npat; ++q) {
-        if (!pat_slot_set[(size_t)q]) continue;
-        for (int e = 0; e < (int)tb.len[(size_t)q]; ++e) {
-            const PairEntryH &en = tb.ent[(size_t)q * tb.lmax + e];
-            const int slot = pat_slots[(size_t)q][(size_t)e];
-            std::memcpy(&cval[((size_t)q * 9 + slot) * 2], &en.va, 8);
-            std::memcpy(&cval[((size_t)q * 9 + slot) * 2 + 1], &en.vb, 8);
-            cmsk[(size_t)q] |= (en.flags & 1) << slot;
-            cmsk[(size_t)q] |= ((en.flags >> 1) & 1) << (16 + slot);
-        }
-        if (sym_ok) {
-            // upper-triangle twin: slots [0, +1, +NX, far after 0, far after 1] = slots 4 .. 8 of the full form
-            for (int e = 0; e < (int)ts->len[(size_t)q]; ++e) {
-                const PairEntryH &en = ts->ent[(size_t)q * ts->lmax + e];
-                int slot = -1;
-                for (int f = 0; f < (int)tb.len[(size_t)q]; ++f)
-                    if (tb.ent[(size_t)q * tb.lmax + f].off == en.off) slot = pat_slots[(size_t)q][(size_t)f] - 4;
-                if (slot < 0 || slot > 4) {
-                    sym_ok = false;
-                    break;
-                }
-                std::memcpy(&sval[((size_t)q * 5 + slot) * 2], &en.va, 8);
-                std::memcpy(&sval[((size_t)q * 5 + slot) * 2 + 1], &en.vb, 8);
-                smsk[(size_t)q] |= (en.flags & 1) << slot;
-                smsk[(size_t)q] |= ((en.flags >> 1) & 1) << (16 + slot);
-            }
-        }
-    }
-    // ---- segments -----------------------------------------------------------------------------------
-    const char *t_env = std::getenv("SCHWZ_SWEEP_T"), *l_env = std::getenv("SCHWZ_SWEEP_L");
-    int T = t_env ? std::atoi(t_env) : ((NX >= 512 || (two_d && PL % 1024 == 0)) ? 1024 : 512);
-    if (T != 512 && T != 1024) T = 512;
-    if (PL % T && !gen_mode) T = 512;
-    if (gen_mode && PL < T) T = 512;
-    // dynamic LDS of the update / start walk: the ring (4 T own + 4 NX halo doubles) and the nine-slot tables of
-    // every pattern; the launches raise the kernels' limit to 96 KiB.  Too many patterns for the tall band: the
-    // short one; still too much: no walk (the chunk-by-chunk launches take the matrix).
-    auto walk_lds = [&](int t) { return sweep_update_lds(t, NX, tb.npat); };
-    if (walk_lds(T) > kSweepLdsLimit && T == 1024 && PL % 512 == 0) T = 512;
-    if (walk_lds(T) > kSweepLdsLimit) return no_walk("ring and pattern tables exceed 96 KiB of LDS");
-    if (NX > T) return no_walk("x line longer than a band");  // the halo of a band is NX rows either side: a band holds at least one x line
-    const int bands = (int)((PL + T - 1) / T);  // (gen mode: the last band of a plane is partial)
-    const int grid = (int)((std::min<int64_t>(ntiles, kMaxGrid) + kXcds - 1) / kXcds) * kXcds;
-    struct Run { int p0, p1; };
-    std::vector<Run> runs;
-    int64_t steps = 0;
-    for (int p = 0; p < npos;) {
-        const int k = chain_plane[(size_t)p];
-        if (k < 0 || !plane_ok[(size_t)k]) {
-            ++p;
-            continue;
-        }
-        int e = p;
-        while (e < npos && chain_plane[(size_t)e] >= 0 && plane_ok[(size_t)chain_plane[(size_t)e]]) ++e;
-        if (e - p >= 2) {
-            runs.push_back({p, e});
-            steps += (int64_t)(e - p) * bands;
-        }
-        p = e;
-    }
-    if (runs.empty()) return no_walk("no chain of two or more walkable planes");
-    std::vector<uint8_t> covered((size_t)nchunks, 0);
-    std::vector<schwz_idx> gen;
-    if (gen_mode) {
-        // every plane must be walked: nothing can be left to the chunk-by-chunk companion launch
-        int64_t walked = 0;
-        for (const Run &r : runs) walked += r.p1 - r.p0;
-        if (walked != nplanes) return no_walk("planes that are not whole chunks: some plane cannot be walked (and nothing can be left to the chunk launches)");
-    } else {
-        for (const Run &r : runs)
-            for (int p = r.p0; p < r.p1; ++p)
-                for (int c = 0; c < cpp; ++c) covered[(size_t)chain_plane[(size_t)p] * cpp + c] = 1;
-        for (int c = 0; c < nchunks; ++c)
-            if (!covered[(size_t)c]) gen.push_back(c);
-    }
-    // segment length: about three segments per CU (two for bands of 1024 rows, which keep twice the loads
-    // in flight) in ONE round of workgroups (measured on MI355X, 256^3 and 512 x 512 x 64; tools/sweep_ab.sh)
-    int cus = 256;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-    }
-    const int per_cu = T == 1024 ? 2 : 3;
-    int L = l_env ? std::atoi(l_env) : (int)std::max<int64_t>(8, (steps + per_cu * cus - 1) / (per_cu * cus));
-    if (L < 2) L = 16;
-    auto count = [&](int len) {
-        int64_t n = 0;
-        for (const Run &r : runs) n += (int64_t)((r.p1 - r.p0 + len - 1) / len) * bands;
-        return n;
-    };
-    // the companion launch walks its chunks with one gather round trip after the other: as many workgroups
-    // as the partial-sum slots next to the segments allow (up to one per chunk)
-    const int seg_slots = (int)((count(L) + kXcds - 1) / kXcds * kXcds) + kXcds;
-    const int gen_blocks = (int)std::min<int64_t>((int64_t)gen.size(), std::max(256, std::min(1024, grid - seg_slots)));
-    while (count(L) + kXcds > grid - gen_blocks && L < (1 << 20)) L += 4;
-    struct Seg { int band, p0, p1; };
-    // workgroup slots for bands of Tq rows and segments of about Lq chain positions
-    auto make_slots = [&](int Tq, int Lq) -> std::vector<int4> {
-        const int bands_q = (int)((PL + Tq - 1) / Tq);
-        std::vector<Seg> segs;
-        for (const Run &r : runs) {
-            const int nseg = (r.p1 - r.p0 + Lq - 1) / Lq, len = (r.p1 - r.p0 + nseg - 1) / nseg;
-            for (int b = 0; b < bands_q; ++b)
-                for (int p = r.p0; p < r.p1; p += len) segs.push_back({b, p, std::min(p + len, r.p1)});
-        }
-        // deal: XCD x takes the bands [x * bands / 8, (x + 1) * bands / 8) (a band's window shares its NX-row
-        // halos with the neighbouring bands: the same L2), segment by segment along the chain
-        std::stable_sort(segs.begin(), segs.end(), [](const Seg &x, const Seg &y) { return x.p0 != y.p0 ? x.p0 < y.p0 : x.band < y.band; });
-        std::vector<std::vector<int4>> per_xcd(kXcds);
-        for (const Seg &sgm : segs) {
-            int4 v;
-            v.x = sgm.band;
-            v.y = sgm.p0;
-            v.z = sgm.p1;
-            v.w = (int)std::min<int64_t>(Tq, PL - (int64_t)sgm.band * Tq);  // rows of the band inside the plane
-            size_t x;
-            if (bands_q >= 2 * kXcds) {
-                x = (size_t)((int64_t)sgm.band * kXcds / bands_q);
-            } else {  // few bands: round robin
-                x = 0;
-                for (size_t k = 1; k < (size_t)kXcds; ++k)
-                    if (per_xcd[k].size() < per_xcd[x].size()) x = k;
-            }
-            per_xcd[x].push_back(v);
-        }
-        size_t depth = 0;
-        for (const auto &l : per_xcd) depth = std::max(depth, l.size());
-        std::vector<int4> out(depth * kXcds);
-        for (size_t q = 0; q < depth; ++q)
-            for (int x = 0; x < kXcds; ++x) {
-                int4 v;
-                v.x = v.y = v.z = v.w = 0;
-                if (q < per_xcd[(size_t)x].size()) v = per_xcd[(size_t)x][q];
-                out[q * kXcds + x] = v;
-            }
-        return out;
-    };
-    const std::vector<int4> slots_v = make_slots(T, L);
-    // The fused direction launch may take taller bands than the update launch (SCHWZ_SWEEP_TDIR=512|1024|2048):
-    // its window carries an NX-row halo of r AND p per band, so a band of twice the rows halves that share,
-    // while the update launch keeps four halo lines per window and prefers the shorter band.  A table of its
-    // own; equal to the update launch's when the band heights coincide.
-    // Measured in-box (tools/tdir_ab.sh): 256-wide planes, update bands of 512 rows: 1024-row bands for the fused
-    // launch -3 % per step (2048: +5 %); 512-wide planes, 1024 / 2048: +3 % (two workgroups per CU); 1024-wide
-    // planes, where a 1024-row band is a single x line, 2048: fused launch 0.773 -> 0.696 ms, -4 % per step -- in
-    // round 2.  With the halo schedule of round 3 (SCHWZ_DD) the halo lines hit L2 and what counts on 1024-wide
-    // planes is the second workgroup per CU a 1024-row band leaves room for: 1024 x 1024 x 128 slab, fused launch
-    // 0.681 ms with 2048-row bands, 0.640 ms with 1024 (step 16.5 -> 16.0 ms; profiles/r03_c5slab_ab.txt).
-    const char *td_env = std::getenv("SCHWZ_SWEEP_TDIR");
-    int T_dir = td_env ? std::atoi(td_env) : (T == 512 ? 1024 : T);
-    if ((T_dir != 512 && T_dir != 1024 && T_dir != 2048) || (PL % T_dir && !gen_mode) || (gen_mode && PL < T_dir) ||
-        sweep_dirdot_lds(T_dir, NX, tb.npat) > kSweepLdsLimit)
-        T_dir = T;
-    std::vector<int4> slots_dir;
-    if (T_dir != T) {
-        const int bands_d = (int)((PL + T_dir - 1) / T_dir);
-        int64_t steps_d = 0;
-        for (const Run &r : runs) steps_d += (int64_t)(r.p1 - r.p0) * bands_d;
-        const int per_cu_d = T_dir >= 2048 ? 1 : (T_dir == 1024 ? 2 : 3);
-        const char *ld_env = std::getenv("SCHWZ_SWEEP_LDIR");
-        int Ld = ld_env ? std::atoi(ld_env) : (int)std::max<int64_t>(8, (steps_d + per_cu_d * cus - 1) / (per_cu_d * cus));
-        if (Ld < 2) Ld = 16;
-        auto count_d = [&](int len) {
-            int64_t nq = 0;
-            for (const Run &r : runs) nq += (int64_t)((r.p1 - r.p0 + len - 1) / len) * bands_d;
-            return nq;
-        };
-        while (count_d(Ld) + kXcds > grid - gen_blocks && Ld < (1 << 20)) Ld += 4;
-        slots_dir = make_slots(T_dir, Ld);
-        if ((int64_t)slots_dir.size() + gen_blocks > grid) {
-            slots_dir.clear();
-            T_dir = T;
-        }
-    }
-    // Rows the walk leaves out cost a companion launch per CG launch: measured with 256 x 256 planes, 8 / 4 / 1
-    // slabs on one GPU when the boundary planes of a slab were still left out (tools/sweep_sizes.sh, bench.py
-    // --ttr-subdomains): +13 % time at 2.2 M rows, +2 % at 4.3 M, -18 % at 16.8 M; without left-out rows the
-    // walk wins from 1 M rows on.
-    const bool worth = gen.empty() || nrows >= 6000000 || sw_mode == 2;
-    if (!worth || (int64_t)slots_v.size() + gen_blocks > grid || steps * T * 2 < nrows)
-        return no_walk("rows left to the companion launch on a small matrix, more segments than partial-sum slots, or less than half of the rows walkable");
-    // A table of its own for the first-direction launch of a solve (round 3).  That launch reads ONE vector and does
-    // little per row: its time is the latency of a workgroup's steps times the bytes it keeps in flight, and the
-    // fused launch's table gives it two workgroups per CU.  Bands of the update launch's height (512 rows where the
-    // plane allows) and about SCHWZ_SWEEP_FIRSTPERCU (6; 0: the fused launch's table) workgroups per CU.
-    std::vector<int4> slots_first;
-    int T_first = 0;
-    {
-        const char *fe = std::getenv("SCHWZ_SWEEP_FIRSTPERCU");
-        const int per_cu_f = fe ? std::atoi(fe) : 6;
-        const int Tf = T;  // (a height both walks have instantiations for)
-        if (per_cu_f > 0 && Tf <= (slots_dir.empty() ? T : T_dir)) {
-            const int bands_f = (int)((PL + Tf - 1) / Tf);
-            int64_t steps_f = 0;
-            for (const Run &r : runs) steps_f += (int64_t)(r.p1 - r.p0) * bands_f;
-            int Lf = (int)std::max<int64_t>(6, (steps_f + (int64_t)per_cu_f * cus - 1) / ((int64_t)per_cu_f * cus));
-            auto count_f = [&](int len) {
-                int64_t nq = 0;
-                for (const Run &r : runs) nq += (int64_t)((r.p1 - r.p0 + len - 1) / len) * bands_f;
-                return nq;
-            };
-            while (count_f(Lf) + kXcds > grid - gen_blocks && Lf < (1 << 20)) Lf += 2;
-            slots_first = make_slots(Tf, Lf);
-            if ((int64_t)slots_first.size() + gen_blocks > grid) slots_first.clear();
-            T_first = Tf;
-        }
-    }
-    int rc;
-    if (!slots_dir.empty() && (rc = upv(slots_dir, &A->d_sweep_seg_dir))) return rc;
-    if (!slots_first.empty() && (rc = upv(slots_first, &A->d_sweep_seg_first))) return rc;
-    if ((rc = upv(slots_v, &A->d_sweep_seg)) || (rc = upv(gen, &A->d_sweep_gen)) || (rc = upv(cval, &A->d_canon_val)) ||
-        (rc = upv(cmsk, &A->d_canon_mask)) || (rc = upv(chain_plane, &A->d_chain_plane)) ||
-        (rc = upv(chain_far, &A->d_chain_far)))
-        return rc;
-    A->v.canon_val = (const double *)A->d_canon_val;
-    A->v.canon_mask = (const int *)A->d_canon_mask;
-    A->v.canon_npat = tb.npat;
-    A->v.chain_plane = (const int *)A->d_chain_plane;
-    A->h_chain_plane = chain_plane;
-    A->v.chain_far = (const int *)A->d_chain_far;
-    if (sym_ok) {
-        if ((rc = upv(sval, &A->d_canon_sym_val)) || (rc = upv(smsk, &A->d_canon_sym_mask))) return rc;
-        A->v.canon_sym_val = (const double *)A->d_canon_sym_val;
-        A->v.canon_sym_mask = (const int *)A->d_canon_sym_mask;
-    }
-    A->v.sweep_gen_mode = gen_mode ? 1 : 0;
-    A->v.sweep_T = T;
-    A->v.sweep_nx = (int)NX;
-    A->v.sweep_pl = PL;
-    A->v.sweep_nslots = (int)slots_v.size();
-    A->v.sweep_ngen = (int)gen.size();
-    A->v.sweep_gen_blocks = gen_blocks;
-    A->v.sweep_seg = (const int4 *)A->d_sweep_seg;
-    A->v.sweep_gen = (const schwz_idx *)A->d_sweep_gen;
-    A->v.sweep_T_dir = slots_dir.empty() ? T : T_dir;
-    A->v.sweep_nslots_dir = slots_dir.empty() ? (int)slots_v.size() : (int)slots_dir.size();
-    A->v.sweep_seg_dir = slots_dir.empty() ? A->v.sweep_seg : (const int4 *)A->d_sweep_seg_dir;
-    A->v.sweep_T_first = slots_first.empty() ? A->v.sweep_T_dir : T_first;
-    A->v.sweep_nslots_first = slots_first.empty() ? A->v.sweep_nslots_dir : (int)slots_first.size();
-    A->v.sweep_seg_first = slots_first.empty() ? A->v.sweep_seg_dir : (const int4 *)A->d_sweep_seg_first;
-    return SCHWZ_OK;
-}
-
-// Leaves A->v.pair_id null when fewer than 90 % of the nonzeros sit in pair-coded chunks
-// (SCHWZ_SPMV_PAIR=0 disables, =2 forces whatever the coverage).
-int build_spmv_pair(schwz_csr *A, const schwz_idx *rp, const schwz_idx *col, const double *val,
-                    const std::vector<schwz_idx> &tiles)
-{
-    const char *env = std::getenv("SCHWZ_SPMV_PAIR");
-    if (env && env[0] == '0') return SCHWZ_OK;
-    if (tiles.size() < 2) return SCHWZ_OK;
-    const int64_t nrows = tiles.back(), nnz = rp[nrows];
-    if (nnz == 0 || A->v.ncols < 2 || A->v.ncols >= INT32_MAX || nrows >= INT32_MAX - kPairRows) return SCHWZ_OK;
-    const int nchunks = (int)((nrows + kPairRows - 1) / kPairRows);
-    std::vector<uint8_t> pair_id((size_t)(nrows + 1) / 2, 0);
-    std::vector<schwz_idx> chunk_ptable((size_t)nchunks, -1);
-    std::vector<PairTable> tables;
-    std::unordered_multimap<uint64_t, int> by_hash;
-    std::vector<std::vector<PairEntryH>> pats;
-    std::vector<PairEntryH> cur;
-    int64_t coded = 0;
-    // merged (offset, values, presence) sequence of the pair starting at row ra
-    auto merge_pair = [&](int64_t ra, bool has_b) {
-        cur.clear();
-        schwz_idx ja = rp[ra], ea = rp[ra + 1];
-        schwz_idx jb = has_b ? rp[ra + 1] : 0, eb = has_b ? rp[ra + 2] : 0;
-        while (ja < ea || jb < eb) {
-            const int64_t da = ja < ea ? (int64_t)col[ja] - ra : INT64_MAX;
-            const int64_t db = jb < eb ? (int64_t)col[jb] - (ra + 1) : INT64_MAX;
-            PairEntryH e = {0, 0, 0, 0};
-            const int64_t d = std::min(da, db);
-            e.off = (schwz_idx)d;
-            if (da == d) {
-                e.flags |= 1;
-                std::memcpy(&e.va, &val[ja], 8);
-                ++ja;
-            }
-            if (db == d) {
-                e.flags |= 2;
-                std::memcpy(&e.vb, &val[jb], 8);
-                ++jb;
-            }
-            cur.push_back(e);
-        }
-    };
-    // First choice: ONE table for the whole matrix (a constant-coefficient stencil has a few dozen
-    // distinct pairs in total); the kernel then stages it once and looks nothing up per chunk.
-    bool single = !(env && env[0] == '3');  // SCHWZ_SPMV_PAIR=3: per-chunk tables even if one would do
-    {
-        StageTimer t_single("  pairs: one table for the whole matrix");
-        std::vector<char> unsorted(64, 0);
-        parallel_blocks(nrows, 1 << 16, [&](int t, int, int64_t a, int64_t b) {
-            bool bad = false;
-            for (int64_t r = a; r < b && !bad; ++r) {
-                if (rp[r + 1] - rp[r] > 127) bad = true;
-                for (schwz_idx j = rp[r] + 1; j < rp[r + 1] && !bad; ++j)
-                    if (col[j] <= col[j - 1]) bad = true;
-            }
-            unsorted[(size_t)t] = bad;
-        });
-        bool sorted = true;
-        for (char u : unsorted) sorted = sorted && !u;
-        single = single && sorted;
-        int lmax = 1;
-        if (single) {
-            // Every thread codes a contiguous block of pairs against a dictionary of its own (ids in ITS order of
-            // first appearance); the dictionaries are then merged in block order, which numbers the patterns in
-            // the order a sequential pass meets them, and the ids are renumbered.
-            const int64_t npairs = (nrows + 1) / 2;
-            std::vector<std::vector<std::vector<PairEntryH>>> tpats(64);
-            std::vector<char> tfail(64, 0);
-            const int nthreads = parallel_blocks(npairs, 1 << 15, [&](int t, int, int64_t a, int64_t b) {
-                auto &mine = tpats[(size_t)t];
-                std::unordered_multimap<uint64_t, int> seen;
-                std::vector<PairEntryH> cur_t;
-                for (int64_t pi = a; pi < b && !tfail[(size_t)t]; ++pi) {
-                    const int64_t ra = 2 * pi;
-                    // (merge_pair on a thread-private sequence)
-                    cur_t.clear();
-                    {
-                        const bool has_b = ra + 1 < nrows;
-                        schwz_idx ja = rp[ra], ea = rp[ra + 1];
-                        schwz_idx jb = has_b ? rp[ra + 1] : 0, eb = has_b ? rp[ra + 2] : 0;
-                        while (ja < ea || jb < eb) {
-                            const int64_t da = ja < ea ? (int64_t)col[ja] - ra : INT64_MAX;
-                            const int64_t db = jb < eb ? (int64_t)col[jb] - (ra + 1) : INT64_MAX;
-                            PairEntryH e = {0, 0, 0, 0};
-                            const int64_t d = std::min(da, db);
-                            e.off = (schwz_idx)d;
-                            if (da == d) {
-                                e.flags |= 1;
-                                std::memcpy(&e.va, &val[ja], 8);
-                                ++ja;
-                            }
-                            if (db == d) {
-                                e.flags |= 2;
-                                std::memcpy(&e.vb, &val[jb], 8);
-                                ++jb;
-                            }
-                            cur_t.push_back(e);
-                        }
-                    }
-                    uint64_t h = 1469598103934665603ull;
-                    for (const PairEntryH &e : cur_t) {
-                        h = (h ^ e.va) * 1099511628211ull;
-                        h = (h ^ e.vb) * 1099511628211ull;
-                        h = (h ^ (uint64_t)(int64_t)e.off) * 1099511628211ull;
-                        h = (h ^ (uint64_t)e.flags) * 1099511628211ull;
-                    }
-                    int id = -1;
-                    auto range = seen.equal_range(h);
-                    for (auto it = range.first; it != range.second; ++it)
-                        if (mine[(size_t)it->second] == cur_t) {
-                            id = it->second;
-                            break;
-                        }
-                    if (id < 0) {
-                        id = (int)mine.size();
-                        if (id == kPairPats) {
-                            tfail[(size_t)t] = 1;
-                            break;
-                        }
-                        seen.emplace(h, id);
-                        mine.push_back(cur_t);
-                    }
-                    pair_id[(size_t)pi] = (uint8_t)id;
-                }
-            });
-            std::vector<std::vector<int>> remap((size_t)nthreads);
-            for (int t = 0; t < nthreads && single; ++t) {
-                if (tfail[(size_t)t]) single = false;
-                for (const auto &pt : tpats[(size_t)t]) {
-                    if (!single) break;
-                    int id = -1;
-                    for (size_t q = 0; q < pats.size(); ++q)
-                        if (pats[q] == pt) {
-                            id = (int)q;
-                            break;
-                        }
-                    if (id < 0) {
-                        id = (int)pats.size();
-                        lmax = std::max(lmax, (int)pt.size());
-                        if (id == kPairPats || (int64_t)(id + 1) * pair_stride(lmax) > kPairEntries) {
-                            single = false;
-                            break;
-                        }
-                        pats.push_back(pt);
-                    }
-                    remap[(size_t)t].push_back(id);
-                }
-            }
-            if (single) {
-                // the same blocks again (parallel_blocks cuts [0, npairs) the same way for the same n and grain)
-                parallel_blocks(npairs, 1 << 15, [&](int t, int, int64_t a, int64_t b) {
-                    const auto &mp = remap[(size_t)t];
-                    for (int64_t pi = a; pi < b; ++pi) pair_id[(size_t)pi] = (uint8_t)mp[(size_t)pair_id[(size_t)pi]];
-                });
-            } else {
-                pats.clear();
-            }
-        }
-        if (single) {
-            PairTable tb;
-            tb.npat = (int)pats.size();
-            tb.lmax = lmax;
-            tb.len.resize((size_t)tb.npat);
-            tb.ent.assign((size_t)tb.npat * lmax, PairEntryH{0, 0, 0, 0});
-            for (int q = 0; q < tb.npat; ++q) {
-                tb.len[(size_t)q] = (uint8_t)pats[(size_t)q].size();
-                for (size_t k = 0; k < pats[(size_t)q].size(); ++k) tb.ent[(size_t)q * lmax + k] = pats[(size_t)q][k];
-            }
-            tables.push_back(std::move(tb));
-            std::fill(chunk_ptable.begin(), chunk_ptable.end(), 0);
-            coded = nnz;
-        }
-    }
-    for (int c = 0; c < nchunks && !single; ++c) {
-        const int64_t r0 = (int64_t)c * kPairRows, r1 = std::min<int64_t>(r0 + kPairRows, nrows);
-        if (rp[r1] == rp[r0]) continue;
-        bool ok = true;
-        for (int64_t r = r0; r < r1 && ok; ++r) {
-            if (rp[r + 1] - rp[r] > 127) ok = false;
-            for (schwz_idx j = rp[r] + 1; j < rp[r + 1] && ok; ++j)
-                if (col[j] <= col[j - 1]) ok = false;  // merged order == each row's order needs sorted rows
-        }
-        if (!ok) continue;
-        pats.clear();
-        int lmax = 0;
-        for (int64_t ra = r0; ra < r1 && ok; ra += 2) {
-            merge_pair(ra, ra + 1 < r1);
-            int id = -1;
-            for (size_t q = 0; q < pats.size(); ++q)
-                if (pats[q] == cur) {
-                    id = (int)q;
-                    break;
-                }
-            if (id < 0) {
-                if ((int)pats.size() == kPairPats) {
-                    ok = false;
-                    break;
-                }
-                id = (int)pats.size();
-                lmax = std::max(lmax, (int)cur.size());
-                pats.push_back(cur);
-            }
-            pair_id[(size_t)(ra >> 1)] = (uint8_t)id;
-        }
-        lmax = std::max(lmax, 1);
-        if (!ok || (int64_t)pats.size() * pair_stride(lmax) > kPairEntries) continue;
-        PairTable tb;
-        tb.npat = (int)pats.size();
-        tb.lmax = lmax;
-        tb.len.resize((size_t)tb.npat);
-        tb.ent.assign((size_t)tb.npat * lmax, PairEntryH{0, 0, 0, 0});
-        uint64_t h = 1469598103934665603ull;
-        for (int q = 0; q < tb.npat; ++q) {
-            tb.len[(size_t)q] = (uint8_t)pats[(size_t)q].size();
-            for (size_t k = 0; k < pats[(size_t)q].size(); ++k) {
-                const PairEntryH &e = pats[(size_t)q][k];
-                tb.ent[(size_t)q * lmax + k] = e;
-                h = (h ^ e.va) * 1099511628211ull;
-                h = (h ^ e.vb) * 1099511628211ull;
-                h = (h ^ (uint64_t)(int64_t)e.off) * 1099511628211ull;
-                h = (h ^ (uint64_t)e.flags) * 1099511628211ull;
-            }
-            h = (h ^ 0xffull ^ (uint64_t)tb.len[(size_t)q]) * 1099511628211ull;
-        }
-        tb.hash = h;
-        int id = -1;
-        auto range = by_hash.equal_range(h);
-        for (auto it = range.first; it != range.second; ++it)
-            if (tables[(size_t)it->second].same(tb)) {
-                id = it->second;
-                break;
-            }
-        if (id < 0) {
-            id = (int)tables.size();
-            by_hash.emplace(h, id);
-            tables.push_back(std::move(tb));
-        }
-        chunk_ptable[(size_t)c] = id;
-        coded += rp[r1] - rp[r0];
-    }
-    A->pair_fraction = (double)coded / (double)nnz;
-    const bool force = env && env[0] == '2';
-    if (A->pair_fraction < 0.9 && !force) return SCHWZ_OK;
-    if (!single && tables.size() * 4 > (size_t)nchunks && !force) return SCHWZ_OK;  // tables must be shared to pay off
-    // Symmetric matrix (checked bit for bit): a second set of tables with the entries on and above the
-    // diagonal only, the strictly upper ones doubled (exact), for kSpmvDotSym.  SCHWZ_SPMV_SYM=0 skips it.
-    StageTimer t_sym("  pairs: symmetry check, upper-triangle twins");
-    int sym_base = 0;
-    const char *sym_env = std::getenv("SCHWZ_SPMV_SYM");
-    if (!(sym_env && sym_env[0] == '0') && csr_is_symmetric(nrows, A->v.ncols, rp, col, val)) {
-        sym_base = (int)tables.size();
-        std::vector<PairTable> upper((size_t)sym_base);
-        for (int t = 0; t < sym_base; ++t) {
-            const PairTable &src = tables[(size_t)t];
-            PairTable &u = upper[(size_t)t];
-            u.npat = src.npat;
-            u.len.assign((size_t)u.npat, 0);
-            u.lmax = 1;
-            for (int q = 0; q < src.npat; ++q) {
-                int cnt = 0;
-                for (int k = 0; k < (int)src.len[(size_t)q]; ++k) cnt += src.ent[(size_t)q * src.lmax + k].off >= 0;
-                u.len[(size_t)q] = (uint8_t)cnt;
-                u.lmax = std::max(u.lmax, cnt);
-            }
-            u.ent.assign((size_t)u.npat * u.lmax, PairEntryH{0, 0, 0, 0});
-            for (int q = 0; q < src.npat; ++q) {
-                int w = 0;
-                for (int k = 0; k < (int)src.len[(size_t)q]; ++k) {
-                    PairEntryH e = src.ent[(size_t)q * src.lmax + k];
-                    if (e.off < 0) continue;
-                    if (e.off > 0) {
-                        double va, vb;
-                        std::memcpy(&va, &e.va, 8);
-                        std::memcpy(&vb, &e.vb, 8);
-                        va *= 2.0;
-                        vb *= 2.0;
-                        std::memcpy(&e.va, &va, 8);
-                        std::memcpy(&e.vb, &vb, 8);
-                    }
-                    u.ent[(size_t)q * u.lmax + w++] = e;
-                }
-            }
-        }
-        for (PairTable &u : upper) tables.push_back(std::move(u));
-    }
-    t_sym.stop();
     StageTimer t_rest("  pairs: tables, records, canonical layout, walk tables, uploads");
-    std::vector<schwz_idx> desc, meta;
-    std::vector<uint8_t> lens;
-    std::vector<double> vals;
-    for (const PairTable &tb : tables) {
-        desc.push_back((schwz_idx)(vals.size() / 2));
-        desc.push_back((schwz_idx)lens.size());
-        desc.push_back(tb.npat);
-        desc.push_back(tb.lmax);
-        schwz_idx reach = 0;
-        for (const PairEntryH &e : tb.ent) reach = std::max<schwz_idx>(reach, e.off < 0 ? -e.off : e.off);
-        desc.push_back(reach);
-        lens.insert(lens.end(), tb.len.begin(), tb.len.end());
-        for (const PairEntryH &e : tb.ent) {
-            double va, vb;
-            std::memcpy(&va, &e.va, 8);
-            std::memcpy(&vb, &e.vb, 8);
-            vals.push_back(va);
-            vals.push_back(vb);
-            meta.push_back(e.off);
-            meta.push_back(e.flags);
-        }
-    }
-    int rc;
-    if ((rc = upv(pair_id, &A->d_pair_id)) || (rc = upv(chunk_ptable, &A->d_tile_ptable)) ||
-        (rc = upv(desc, &A->d_ptbl_desc)) || (rc = upv(lens, &A->d_ptbl_len)) || (rc = upv(vals, &A->d_ptbl_val)) ||
-        (rc = upv(meta, &A->d_ptbl_meta)))
+    plan_pair_records(opt, M, A->pair_deal_shift, P);
+    // the segment lengths follow the number of CUs: asked here, the plan takes it as a number -- and only where the
+    // plan can get as far as its segments (a canonical layout, run-length records, the walk not switched off)
+    int cus = 256, dev = 0;
+    hipDeviceProp_t prop;
+    if (P.single && P.canon[7] && !P.rle.empty() && opt.sweep != 0 && hipGetDevice(&dev) == hipSuccess &&
+        hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        cus = prop.multiProcessorCount;
+    const WalkPlan W = plan_walk(opt, P, M.nrows, M.ncols, walk_grid((int64_t)M.tiles.size() - 1), cus, kDirdotHaloLines);
+    // SCHWZ_SWEEP_WHY=1: says on stderr why a matrix gets no z-sweep walk
+    if (opt.sweep_why && !W.why.empty()) std::fprintf(stderr, "[schwz] no z-sweep walk: %s\n", W.why.c_str());
+    auto &b = A->coding.pair;
+    int rc = SCHWZ_OK;
+    if ((rc = b.pair_id.put(P.pair_id)) || (rc = b.chunk_ptable.put(P.chunk_ptable)) || (rc = b.ptbl_desc.put(P.ptbl_desc)) ||
+        (rc = b.ptbl_len.put(P.ptbl_len)) || (rc = b.ptbl_val.put(P.ptbl_val)) || (rc = b.ptbl_meta.put(P.ptbl_meta)) ||
+        (!P.rle.empty() && (rc = b.rle.put(P.rle))) || (rc = upload_walk(A, W)))
         return rc;
-    A->v.pair_id = (const uint8_t *)A->d_pair_id;
-    // run-length form of the ids, chunk by chunk (SCHWZ_SPMV_RLE=0: byte ids only)
-    // Records of 8 runs (16 bytes per chunk) serve x lines of ~170 entries and more; a matrix some of whose
-    // chunks need up to 16 runs (a 512-row chunk of a 192 x 192 plane crosses three line ends: ten runs) gets
-    // records of 16 runs (32 bytes per chunk) throughout -- SCHWZ_SPMV_RLE=8 keeps the short records.
-    const char *rle_env = std::getenv("SCHWZ_SPMV_RLE");
-    std::vector<uint16_t> rle;
-    int rle_runs = 8;
-    if (!(rle_env && rle_env[0] == '0')) {
-        auto build_rle = [&](int R, int64_t *coded_out) {
-            std::vector<uint16_t> out((size_t)nchunks * R, 0xffffu);
-            std::vector<int64_t> coded_t(64, 0);
-            parallel_blocks(nchunks, 2048, [&](int t, int, int64_t c_begin, int64_t c_end) {
-                int64_t mine = 0;
-                for (int64_t c = c_begin; c < c_end; ++c) {
-                    if (chunk_ptable[(size_t)c] < 0) continue;
-                    const int64_t p0 = c * (kPairRows / 2), p1 = std::min<int64_t>(p0 + kPairRows / 2, (nrows + 1) / 2);
-                    uint16_t runs[16];
-                    int nr = 0;
-                    bool fits = true;
-                    for (int64_t p = p0; p < p1 && fits; ++p) {
-                        if (nr == 0 || pair_id[(size_t)p] != (uint8_t)(runs[nr - 1] >> 8)) {
-                            if (nr == R) {
-                                fits = false;
-                                break;
-                            }
-                            runs[nr++] = (uint16_t)((p - p0) | ((int)pair_id[(size_t)p] << 8));
-                        }
-                    }
-                    if (!fits || nr == 0) continue;
-                    for (int k = nr; k < R; ++k) runs[k] = runs[nr - 1];
-                    if (runs[0] == 0xffffu) continue;  // would read as the "not coded" marker
-                    std::copy(runs, runs + R, out.begin() + (size_t)c * R);
-                    ++mine;
-                }
-                coded_t[(size_t)t] = mine;
-            });
-            int64_t coded = 0;
-            for (int64_t v : coded_t) coded += v;
-            *coded_out = coded;
-            return out;
-        };
-        int64_t coded8 = 0, coded16 = 0;
-        rle = build_rle(8, &coded8);
-        if (!(rle_env && rle_env[0] == '8')) {
-            std::vector<uint16_t> wide = build_rle(16, &coded16);
-            if (coded16 > coded8) {
-                rle.swap(wide);
-                rle_runs = 16;
-            }
-        }
-        if ((rc = upv(rle, &A->d_pair_rle))) return rc;
-        A->v.pair_rle = (const uint4 *)A->d_pair_rle;
-        A->v.pair_rle_runs = rle_runs;
-    }
-    A->v.chunk_ptable = (const schwz_idx *)A->d_tile_ptable;
-    A->v.ptbl_desc = (const schwz_idx *)A->d_ptbl_desc;
-    A->v.ptbl_len = (const uint8_t *)A->d_ptbl_len;
-    A->v.ptbl_val = (const double *)A->d_ptbl_val;
-    A->v.ptbl_meta = (const schwz_idx *)A->d_ptbl_meta;
-    A->v.pair_single = single ? 1 : 0;
-    // canonical stencil layout of a single-table matrix (SCHWZ_SPMV_CANON=0: off): the offsets of its
-    // commonest pattern when they read {<= 2 below -1, -1, 0, +1, <= 2 above +1}; missing outer slots
-    // repeat their neighbour outwards, so an entry always lands in the lowest slot with its offset and
-    // the slots stay in ascending entry order
-    for (int k = 0; k < 8; ++k) A->v.pair_canon[k] = 0;
-    const char *canon_env = std::getenv("SCHWZ_SPMV_CANON");
-    if (single && !(canon_env && canon_env[0] == '0')) {
-        const PairTable &tb = tables[0];
-        std::vector<int64_t> freq((size_t)tb.npat, 0);
-        for (uint8_t id : pair_id) ++freq[(size_t)id];
-        const int best = (int)(std::max_element(freq.begin(), freq.end()) - freq.begin());
-        std::vector<schwz_idx> neg, pos;
-        bool has_m1 = false, has_0 = false, has_p1 = false, ok = true;
-        for (int k = 0; k < (int)tb.len[(size_t)best]; ++k) {
-            const schwz_idx off = tb.ent[(size_t)best * tb.lmax + k].off;
-            if (off == -1) has_m1 = true;
-            else if (off == 0) has_0 = true;
-            else if (off == 1) has_p1 = true;
-            else if (off < 0) neg.push_back(off);
-            else pos.push_back(off);
-        }
-        ok = has_m1 && has_0 && has_p1 && neg.size() <= 2 && pos.size() <= 2;
-        if (ok) {
-            std::sort(neg.begin(), neg.end());  // most negative first
-            std::sort(pos.begin(), pos.end());
-            const schwz_idx n2 = neg.size() >= 1 ? neg[0] : -1;
-            const schwz_idx n1 = neg.size() == 2 ? neg[1] : n2;
-            const schwz_idx p2 = pos.size() >= 1 ? pos.back() : 1;
-            const schwz_idx p1 = pos.size() == 2 ? pos[0] : p2;
-            const schwz_idx lay[7] = {n2, n1, -1, 0, 1, p1, p2};
-            for (int k = 0; k < 7; ++k) A->v.pair_canon[k] = lay[k];
-            A->v.pair_canon[7] = 1;
-        }
-    }
-    A->v.pair_sym_base = sym_base;
-    // z-sweep segments (CsrView::sweep_*): SCHWZ_SPMV_SWEEP=0 off, =2 also below a million rows (tests);
-    // SCHWZ_SWEEP_T (512 / 1024 rows per band), SCHWZ_SWEEP_L (planes per segment) override the defaults.
-    if (single && (rc = build_sweep(A, nrows, tables[0], sym_base > 0 ? &tables[(size_t)sym_base] : nullptr, pair_id, rle,
-                                    (int64_t)tiles.size() - 1)))
-        return rc;
-    {
-        // what a pass over the coded matrix reads: per chunk its 16-byte run-length record, or one byte per
-        // pair where the ids do not run-length code; the chunk's table id unless one table serves the whole
-        // matrix; the tables themselves (one set; the upper-triangle twins are read INSTEAD by kSpmvDotSym)
-        int64_t bytes = 0;
-        const uint16_t *rle_h = rle.empty() ? nullptr : rle.data();
-        for (int c = 0; c < nchunks; ++c) {
-            if (chunk_ptable[(size_t)c] < 0) continue;
-            const bool runs = rle_h && rle_h[(size_t)c * rle_runs] != 0xffffu;
-            bytes += runs ? 2 * rle_runs : (rle_h ? 2 * rle_runs : 0) + kPairRows / 2;
-            if (!single) bytes += 4;
-        }
-        const size_t ntab = sym_base ? (size_t)sym_base : tables.size();
-        for (size_t t = 0; t < ntab; ++t) bytes += (int64_t)tables[t].ent.size() * 24 + tables[t].npat;
-        A->pair_code_bytes = bytes;
-    }
-    // the XCD deal of the chunks: the tile deal's run length in rows, in chunks (a power of two)
-    int sh = A->pair_deal_shift;
-    const int64_t rows_per_tile = std::max<int64_t>(1, nrows / std::max<int64_t>(1, (int64_t)tiles.size() - 1));
-    for (int64_t f = kPairRows / std::max<int64_t>(1, rows_per_tile); f > 1 && sh > 0; f >>= 1) --sh;
-    A->v.pair_shift = sh;
+    bind_pair(A, P);
+    bind_walk(A, W);
     return SCHWZ_OK;
 }
 
-// chunks whose rows or columns reach `split` need the second product of the fused dual residual
+// chunks whose rows or columns reach `split` need the second product of the fused dual residual: planned
+// again on every call, the three arrays replaced
 int pair_set_dual_split(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_col, int64_t split)
 {
     if (!A->v.pair_id) return SCHWZ_OK;
-    const int64_t nrows = A->v.nrows;
-    const int nchunks = (int)((nrows + kPairRows - 1) / kPairRows);
-    std::vector<uint8_t> flag((size_t)nchunks, 0);
-    for (int c = 0; c < nchunks; ++c) {
-        const int64_t r0 = (int64_t)c * kPairRows, r1 = std::min<int64_t>(r0 + kPairRows, nrows);
-        bool f = r1 > split;
-        for (int64_t j = h_rp[r0]; j < h_rp[r1] && !f; ++j) f = h_col[j] >= split;
-        flag[(size_t)c] = f ? 1 : 0;
-    }
-    (void)hipFree(A->d_chunk_dual);
-    A->d_chunk_dual = nullptr;
-    int rc = upv(flag, &A->d_chunk_dual);
-    if (rc) return rc;
-    A->v.chunk_dual = (const uint8_t *)A->d_chunk_dual;
-    // the same for the z-sweep walk: chain positions whose plane has a flagged chunk, and the list of those
-    // planes' chunks for the listed kSpmvResidNorm launch (launch_spmv_pair, dual start in the walk)
-    (void)hipFree(A->d_chain_dual);
-    (void)hipFree(A->d_dual_chunks);
-    A->d_chain_dual = A->d_dual_chunks = nullptr;
-    A->v.chain_dual = nullptr;
-    A->v.dual_chunks = nullptr;
-    A->v.dual_nchunks = A->v.dual_blocks = 0;
-    if (A->v.sweep_nslots > 0 && !A->h_chain_plane.empty() && A->v.sweep_pl > 0 && !A->v.sweep_gen_mode) {
-        const int cpp = (int)(A->v.sweep_pl / kPairRows);
-        std::vector<int> cdual(A->h_chain_plane.size(), 0);
-        std::vector<schwz_idx> list;
-        for (size_t p = 0; p < A->h_chain_plane.size(); ++p) {
-            const int k = A->h_chain_plane[p];
-            if (k < 0) continue;
-            bool f = false;
-            for (int c = k * cpp; c < (k + 1) * cpp && c < nchunks; ++c) f = f || flag[(size_t)c];
-            if (!f) continue;
-            cdual[p] = 1;
-            for (int c = k * cpp; c < (k + 1) * cpp && c < nchunks; ++c) list.push_back(c);
-        }
-        if (!list.empty()) {
-            if ((rc = upv(cdual, &A->d_chain_dual)) || (rc = upv(list, &A->d_dual_chunks))) return rc;
-            A->v.chain_dual = (const int *)A->d_chain_dual;
-            A->v.dual_chunks = (const schwz_idx *)A->d_dual_chunks;
-            A->v.dual_nchunks = (int)list.size();
-            A->v.dual_blocks = (int)std::min<size_t>(list.size(), 512);
-        }
-    }
-    return SCHWZ_OK;
+    const bool whole_chunk_walk = A->v.sweep_nslots > 0 && !A->v.sweep_gen_mode;
+    const DualPlan D = plan_dual_split(A->v.nrows, h_rp, h_col, split, A->h_chain_plane, whole_chunk_walk ? A->v.sweep_pl : 0);
+    auto &b = A->coding.dual;
+    b = {};
+    int rc = b.chunk_dual.put(D.chunk_dual);
+    if (!rc && !D.dual_chunks.empty() && !(rc = b.chain_dual.put(D.chain_dual))) rc = b.dual_chunks.put(D.dual_chunks);
+    if (rc) b = {};
+    bind_dual(A, rc ? DualPlan() : D);
+    return rc;
 }
 
 void free_spmv_pair(schwz_csr *A)
 {
-    (void)hipFree(A->d_sweep_seg);
-    (void)hipFree(A->d_sweep_seg_dir);
-    A->d_sweep_seg_dir = nullptr;
-    (void)hipFree(A->d_sweep_seg_first);
-    A->d_sweep_seg_first = nullptr;
-    A->v.sweep_seg_first = nullptr;
-    A->v.sweep_T_first = A->v.sweep_nslots_first = 0;
-    A->v.sweep_seg_dir = nullptr;
-    A->v.sweep_T_dir = A->v.sweep_nslots_dir = 0;
-    (void)hipFree(A->d_sweep_gen);
-    (void)hipFree(A->d_canon_val);
-    (void)hipFree(A->d_canon_mask);
-    (void)hipFree(A->d_canon_sym_val);
-    (void)hipFree(A->d_canon_sym_mask);
-    (void)hipFree(A->d_chain_plane);
-    (void)hipFree(A->d_chain_far);
-    (void)hipFree(A->d_chain_dual);
-    (void)hipFree(A->d_dual_chunks);
-    A->d_chain_plane = A->d_chain_far = A->d_chain_dual = A->d_dual_chunks = nullptr;
-    A->v.chain_dual = nullptr;
-    A->v.dual_chunks = nullptr;
-    A->v.dual_nchunks = A->v.dual_blocks = 0;
-    A->h_chain_plane.clear();
-    A->d_sweep_seg = A->d_sweep_gen = A->d_canon_val = A->d_canon_mask = A->d_canon_sym_val = A->d_canon_sym_mask = nullptr;
-    A->v.canon_sym_val = nullptr;
-    A->v.sweep_nslots = 0;
-    (void)hipFree(A->d_pair_rle);
-    A->d_pair_rle = nullptr;
-    A->v.pair_rle = nullptr;
-    void *ptrs[] = {A->d_pair_id, A->d_tile_ptable, A->d_ptbl_desc, A->d_ptbl_len, A->d_ptbl_val, A->d_ptbl_meta,
-                    A->d_chunk_dual};
-    for (void *p : ptrs) (void)hipFree(p);
-    A->d_pair_id = A->d_tile_ptable = A->d_ptbl_desc = A->d_ptbl_len = A->d_ptbl_val = A->d_ptbl_meta = nullptr;
-    A->d_chunk_dual = nullptr;
-    A->v.pair_id = nullptr;
-    A->v.chunk_dual = nullptr;
-    A->v.pair_sym_base = 0;
+    A->coding.pair = {};
+    A->coding.walk = {};
+    A->coding.dual = {};
+    bind_pair(A, PairPlan());
+    bind_walk(A, WalkPlan());
+    bind_dual(A, DualPlan());
 }
 
 }  // namespace schwz
