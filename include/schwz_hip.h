@@ -176,6 +176,34 @@ int schwz_pcg_solve(schwz_pcg *s, const double *d_b, double *d_x, double rtol,
                     int max_iters, int *h_iters, double *h_resnorm,
                     schwz_stream stream);
 
+/* Mixed-precision CG (an extension: the reference's only mixed-precision feature is the fp32 halo): the solve runs
+ * in residual-correction form,
+ *   1. r0 = b - A x in fp64, through the matrix's best fp64 coding, nu = ||r0||_2;
+ *   2. nu == 0: x is untouched, 0 iterations;
+ *   3. PCG on A32 e = fl32(r0 / nu) from e = 0, with fp32 matrix values (a copy of 4 nnz bytes built at creation,
+ *      round to nearest) and fp32 vectors; dot products and norms are accumulated in fp64, in a fixed order (the
+ *      same input gives the same bits); the stop rule is schwz_pcg_solve's, on the recurred residual relative to
+ *      the norm of the scaled start residual;
+ *   4. x += nu e in fp64.
+ * One step of iterative refinement: a caller that recomputes the residual in fp64 and calls again (the RAS
+ * iteration does) reaches fp64 accuracy.  h_resnorm is nu times the recurred norm.  precond: SCHWZ_PRECOND_NONE
+ * or SCHWZ_PRECOND_JACOBI; another known code: SCHWZ_ERR_NOT_IMPLEMENTED; an unknown code or a null `out`:
+ * SCHWZ_ERR_INVALID (both checked before the matrix is looked at).  A finite matrix value that rounds to
+ * +-inf in fp32: SCHWZ_ERR_NOT_IMPLEMENTED, the message names the entry.  Plain CSR only (csrc/cg_f32.hip): the
+ * codings and the z-sweep walk have no fp32 form, so on a stencil matrix this solver moves MORE bytes than
+ * schwz_pcg does. */
+typedef struct schwz_pcg_f32 schwz_pcg_f32;
+int schwz_pcg_f32_create(const schwz_csr *A, int precond, schwz_pcg_f32 **out);
+void schwz_pcg_f32_destroy(schwz_pcg_f32 *s);
+int schwz_pcg_f32_solve(schwz_pcg_f32 *s, const double *d_b, double *d_x, double rtol, int max_iters,
+                        int *h_iters, double *h_resnorm, schwz_stream stream);
+/* q = A32 p and, through *h_pq (may be NULL), p.q as the iteration accumulates it, by the launch the iteration
+ * uses: for tests and probes.  d_p, d_q: n floats in HBM.  Synchronises `stream`; not to be called between the
+ * launch of a solve on another stream and its end. */
+int schwz_pcg_f32_spmv(schwz_pcg_f32 *s, const float *d_p, float *d_q, double *h_pq, schwz_stream stream);
+/* iterations and residual norm of the last solve (device synchronisation) */
+int schwz_pcg_f32_last_stats(schwz_pcg_f32 *s, int *h_iters, double *h_resnorm);
+
 /* Restarted GMRES(restart) with right preconditioning, device resident like the CG.
  * Replaces gko::solver::Gmres with krylov_dim = settings.restart_iter and the same
  * Combined(Iteration, ResidualNormReduction) criterion, the local solver of
@@ -505,6 +533,17 @@ int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream 
  * iteration cap once iter_count > settings.reset_local_crit_iter (source/solve.cpp:723-742);
  * max_iters = -1 means local_size_x.  Takes effect from the next local solve. */
 int schwz_ras_set_local_max_iters(schwz_subdomain *sd, int max_iters);
+/* Precision of the iterative local solve (an extension; schwz_solver_options keeps its layout, so the precision
+ * travels through this setter).  Call after schwz_subdomain_to_device; takes effect from the next local solve.
+ * SCHWZ_PRECISION_F32: the local solve is schwz_pcg_f32_solve on (b~, y), the solver created on the local matrix
+ * at first use; SCHWZ_ERR_NOT_IMPLEMENTED for a direct local solver, for GMRES (non_symmetric) and for a
+ * preconditioner other than none or scalar Jacobi (block-jacobi with block size 1 included).  While it is set
+ * schwz_ras_check_and_solve_launch runs its two steps back to back, schwz_ras_early_pack_ok, schwz_ras_cg_flavour
+ * and schwz_ras_y_form return 0, the restriction is the copy launch, and schwz_ras_algorithmic_bytes(sd, 1) prices
+ * the fp32 iteration.  SCHWZ_PRECISION_F64 restores the fp64 path exactly. */
+enum schwz_precision { SCHWZ_PRECISION_F64 = 0, SCHWZ_PRECISION_F32 = 1 };
+int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision);
+int schwz_ras_local_precision(const schwz_subdomain *sd);
 /* settings.enable_logging (source/solve.cpp:751-771): inner iterations and final residual norm of the
  * last local solve (0 and 0.0 for the direct path).  Synchronises the solver's stream. */
 int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resnorm);

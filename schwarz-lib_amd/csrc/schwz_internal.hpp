@@ -738,6 +738,8 @@ struct schwz_problem {
     int max_row_nnz = 0;
 };
 
+struct schwz_pcg_f32;  // cg_f32.hip
+
 struct schwz_subdomain {
     // ---- host index sets -------------------------------------------------
     int P = 0, me = 0, overlap = 0;
@@ -769,6 +771,10 @@ struct schwz_subdomain {
     schwz_csr *A = nullptr;  // local_matrix
     schwz_pcg *cg = nullptr;
     schwz_gmres *gmres = nullptr;  // non-symmetric local matrix
+    // mixed-precision local solve (schwz_ras_set_local_precision, csrc/cg_f32.hip): created at first use, used while
+    // `precision` is SCHWZ_PRECISION_F32; `cg` stays what it is, so that F64 restores the fp64 path exactly
+    schwz_pcg_f32 *cg32 = nullptr;
+    int precision = 0;
     schwz_trs *trs = nullptr;
     // interface rows: only overlap rows are non-empty; stored compactly
     schwz_idx *d_i_rp = nullptr, *d_i_col = nullptr;  // cols index x~ directly

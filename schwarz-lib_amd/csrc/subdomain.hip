@@ -53,6 +53,7 @@ static bool want_unified(schwz_subdomain *sd)
 {
     const char *e = std::getenv("SCHWZ_RESTRICT_FUSE");
     if (e && e[0] == '0') return false;
+    if (sd->precision == SCHWZ_PRECISION_F32) return false;  // the fp32 solver updates y in place
     return sd->cg && sd->overlap_size == 0 && sd->halo_size == 0 && sd->local_size > 0 && !sd->cg->prio_on &&
            pcg_defers_x(sd->cg);
 }
@@ -106,6 +107,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
     if (!sd) return;
     if (sd->on_device) {
         schwz_pcg_destroy(sd->cg);
+        schwz_pcg_f32_destroy(sd->cg32);
         schwz_gmres_destroy(sd->gmres);
         schwz_trs_destroy(sd->trs);
         schwz_csr_destroy(sd->A);
@@ -306,6 +308,7 @@ int schwz_ras_unpack_f32(schwz_subdomain *sd, const float *d_recv, schwz_stream 
 // schwz_ras_pack would read after schwz_ras_restrict.
 int schwz_ras_early_pack_ok(const schwz_subdomain *sd)
 {
+    if (sd && sd->precision == SCHWZ_PRECISION_F32) return 0;  // the fp32 solver records no boundary event
     return sd && sd->on_device && sd->cg && sd->cg->prio_on && sd->cg->prio_event ? 1 : 0;
 }
 
@@ -508,6 +511,7 @@ int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resn
     *h_iters = 0;
     *h_resnorm = 0.0;
     if (sd->local_size_x == 0) return SCHWZ_OK;
+    if (sd->precision == SCHWZ_PRECISION_F32) return schwz_pcg_f32_last_stats(sd->cg32, h_iters, h_resnorm);
     if (sd->cg) return pcg_last_stats(sd->cg, h_iters, h_resnorm);
     if (sd->gmres) return schwz_gmres_last_stats(sd->gmres, h_iters, h_resnorm);
     return SCHWZ_OK;
@@ -545,6 +549,14 @@ int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream 
                                  stream);
     int rc = choose_form(sd, (hipStream_t)stream);
     if (rc) return rc;
+    if (sd->precision == SCHWZ_PRECISION_F32) {
+        // separate form (want_unified), y updated in place; the restriction is the copy launch
+        sd->cg->x2_out = nullptr;
+        sd->cg->x2_written = false;
+        sd->y_ahead = true;
+        return schwz_pcg_f32_solve(sd->cg32, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
+                                   stream);
+    }
     if (sd->unified) {
         // state A: out of place, d_x -> d_x_alt; state B: in place on d_x_alt
         sd->cg->x2_out = nullptr;
@@ -566,7 +578,7 @@ int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = sd->local_size_x;
     if (n == 0) return SCHWZ_OK;
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || sd->precision == SCHWZ_PRECISION_F32 || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
         // no fused kernel for this configuration: the two steps back to back
         int rc = schwz_ras_local_residual_launch(sd, stream);
         if (rc) return rc;
@@ -662,7 +674,44 @@ int schwz_ras_jacobi_form(const schwz_subdomain *sd) { return sd && sd->cg ? sd-
 
 int schwz_ras_y_form(const schwz_subdomain *sd) { return sd && sd->on_device && sd->unified ? (sd->y_in_alt ? 2 : 1) : 0; }
 
-int schwz_ras_cg_flavour(const schwz_subdomain *sd) { return sd && sd->cg ? schwz_pcg_flavour(sd->cg) : 0; }
+int schwz_ras_cg_flavour(const schwz_subdomain *sd)
+{
+    if (sd && sd->precision == SCHWZ_PRECISION_F32) return 0;
+    return sd && sd->cg ? schwz_pcg_flavour(sd->cg) : 0;
+}
+
+int schwz_ras_local_precision(const schwz_subdomain *sd) { return sd ? sd->precision : SCHWZ_PRECISION_F64; }
+
+int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
+{
+    REQUIRE_DEVICE(sd, "schwz_ras_set_local_precision");
+    SCHWZ_REQUIRE(precision == SCHWZ_PRECISION_F64 || precision == SCHWZ_PRECISION_F32,
+                  "schwz_ras_set_local_precision: unknown precision");
+    if (precision == SCHWZ_PRECISION_F64) {
+        sd->precision = precision;  // (the next solve chooses its form again: choose_form)
+        return SCHWZ_OK;
+    }
+    const schwz_solver_options &o = sd->opt;
+    const bool jacobi = o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1);
+    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->cg ||
+        !(o.precond == SCHWZ_PRECOND_NONE || jacobi)) {
+        set_error("schwz_ras_set_local_precision: the fp32 local solve exists for the iterative solver of a symmetric "
+                  "matrix (CG) without a preconditioner or with scalar Jacobi only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (!sd->cg32) {
+        const int rc = schwz_pcg_f32_create(sd->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, &sd->cg32);
+        if (rc) return rc;
+    }
+    // a solve still in flight on a stream the null stream does not wait for must not race with the copy below
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    sd->precision = precision;
+    // y gets a vector of its own now (schwz_ras_y_form answers 0 from here on)
+    const int rc = choose_form(sd, nullptr);
+    if (rc) return rc;
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    return SCHWZ_OK;
+}
 
 int schwz_ras_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stream)
 {
@@ -681,6 +730,9 @@ int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which)
     if (!sd) return 0;
     const int64_t n = sd->local_size_x, nnz = (int64_t)sd->l_col.size();
     const int64_t spmv = 12 * nnz + 4 * (n + 1) + 16 * n;
+    // the fp32 iteration (cg_f32.hip): 8 B per nonzero, p gathered and q stored in fp32, then e, r read and written,
+    // p, q, 1/diag read (update launch) and p read and written, r, 1/diag read (direction launch): 44 B per row
+    if (which == 1 && sd->precision == SCHWZ_PRECISION_F32) return 8 * nnz + 4 * (n + 1) + 8 * n + 44 * n;
     return which == 0 ? spmv : spmv + 136 * n;
 }
 

@@ -121,6 +121,9 @@ struct Metadata {
     // (ilu); 0 = the exact ILU(0) and exact triangular solves
     int par_ilu_sweeps = 0;
     int trisolve_sweeps = 0;
+    // extension: "single" runs the iterative local solve as fp32 CG on the fp64 start residual, the correction
+    // added in fp64 (schwz_ras_set_local_precision); CG without a preconditioner or with scalar Jacobi only
+    std::string local_solver_precision = "double";
     ValueType current_residual_norm = -1.0;
     ValueType min_residual_norm = -1.0;
 

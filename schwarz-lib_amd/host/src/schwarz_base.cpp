@@ -252,6 +252,18 @@ void SchwarzBase<V, I, M>::initialize()
         throw ::NotImplemented(__FILE__, __LINE__, "trisolve_sweeps with local_precond '" + m.local_precond + "'");
     opt.par_ilu_sweeps = m.par_ilu_sweeps;
     opt.trisolve_sweeps = m.trisolve_sweeps;
+    // extension: fp32 CG on the fp64 start residual (schwz_ras_set_local_precision)
+    if (m.local_solver_precision != "double" && m.local_solver_precision != "single")
+        throw ::BadDimension(__FILE__, __LINE__, "initialize", "local_solver_precision must be 'double' or 'single'");
+    const bool single_local = m.local_solver_precision == "single";
+    if (single_local && opt.local_solver != SCHWZ_SOLVER_ITERATIVE)
+        throw ::NotImplemented(__FILE__, __LINE__, "local_solver_precision 'single' with a direct local solver");
+    if (single_local && s.non_symmetric_matrix)
+        throw ::NotImplemented(__FILE__, __LINE__, "local_solver_precision 'single' with non_symmetric_matrix (GMRES)");
+    if (single_local && opt.precond != SCHWZ_PRECOND_NONE && opt.precond != SCHWZ_PRECOND_JACOBI)
+        throw ::NotImplemented(__FILE__, __LINE__,
+                               "local_solver_precision 'single' with local_precond '" + m.local_precond +
+                                   "' (available: null, block-jacobi with precond_max_block_size 1)");
 
     // ---- Initialize::setup_global_matrix (initialization.cpp:197-272) ----------------------
     // extension: "--matrix_filename=poisson3d:NX[xNYxNZ]" or SCHWZ_LAPLACIAN_DIM=3 select the 3-D
@@ -403,6 +415,7 @@ void SchwarzBase<V, I, M>::initialize()
     for (gko::size_type i = 0; i < m.local_size; ++i) im.rhs_sq_interior += rhs[i] * rhs[i];
     for (size_t i = 0; i < rhs.size(); ++i) local_rhs->at(i) = (V)rhs[i];
     SCHWZ_CALL(schwz_subdomain_to_device(im.sd, rhs.data(), &opt));
+    if (single_local) SCHWZ_CALL(schwz_ras_set_local_precision(im.sd, SCHWZ_PRECISION_F32));
 
     im.f32_wire = s.use_mixed_precision && std::is_same<M, float>::value;
     const size_t nsend = (size_t)std::max<int64_t>(im.sizes[9], 1), nrecv = (size_t)std::max<int64_t>(im.sizes[8], 1);

@@ -112,6 +112,44 @@ class Pcg:
         self.close()
 
 
+class PcgF32:
+    """Mixed-precision CG (schwz_pcg_f32): fp32 PCG on the fp64 start residual, the correction added in fp64.
+    precond: PRECOND_NONE or PRECOND_JACOBI."""
+
+    def __init__(self, csr, precond=capi.PRECOND_NONE):
+        self.csr = csr
+        h = C.c_void_p()
+        check(lib.schwz_pcg_f32_create(csr.h, precond, C.byref(h)))
+        self.h = h
+
+    def solve(self, d_b, d_x, rtol, max_iters, stream=0, want_stats=True):
+        it = C.c_int(0)
+        rn = C.c_double(0.0)
+        check(lib.schwz_pcg_f32_solve(self.h, ptr(d_b), ptr(d_x), rtol, max_iters,
+                                      C.byref(it) if want_stats else None,
+                                      C.byref(rn) if want_stats else None, _stream_arg(stream)))
+        return it.value, rn.value
+
+    def spmv(self, d_p, d_q, stream=0):
+        """q = A32 p by the launch of the iteration (fp32 device vectors); returns p.q as that launch sums it."""
+        pq = C.c_double(0.0)
+        check(lib.schwz_pcg_f32_spmv(self.h, ptr(d_p), ptr(d_q), C.byref(pq), _stream_arg(stream)))
+        return pq.value
+
+    def last_stats(self):
+        it, rn = C.c_int(0), C.c_double(0.0)
+        check(lib.schwz_pcg_f32_last_stats(self.h, C.byref(it), C.byref(rn)))
+        return it.value, rn.value
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.schwz_pcg_f32_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class Gmres:
     """Device-resident restarted GMRES, right preconditioned (gko::solver::Gmres with
     krylov_dim = restart; solve.cpp:486-520)."""
@@ -622,6 +660,14 @@ class Subdomain:
     def set_local_max_iters(self, max_iters):
         """Inner iteration cap of later local solves (two-stage criterion, solve.cpp:723-742)."""
         check(lib.schwz_ras_set_local_max_iters(self.h, int(max_iters)))
+
+    def set_local_precision(self, precision):
+        """Precision of the iterative local solve from the next one on (schwz_ras_set_local_precision):
+        capi.PRECISION_F64, or capi.PRECISION_F32 for the fp32 CG on the fp64 start residual."""
+        check(lib.schwz_ras_set_local_precision(self.h, int(precision)))
+
+    def local_precision(self):
+        return int(lib.schwz_ras_local_precision(self.h))
 
     def local_solve(self, stream=0, want_iters=False):
         it = C.c_int(0)

@@ -123,6 +123,10 @@ class Metadata:
     # triangular solves (ilu).  0 = today's exact paths.
     par_ilu_sweeps: int = 0
     trisolve_sweeps: int = 0
+    # extension (no field of the reference's Metadata): "single" runs the iterative local solve as fp32 CG on the
+    # fp64 start residual, the correction added in fp64 (schwz_pcg_f32); the outer iteration, which recomputes the
+    # residual in fp64, is the refinement loop.  CG without a preconditioner or with block-jacobi of block size 1.
+    local_solver_precision: str = "double"
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
@@ -235,6 +239,29 @@ def _precond_code(metadata):
         raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
                                        "trisolve_sweeps applies to local_precond 'ilu' only")
     return code
+
+
+def _precision_code(settings, metadata):
+    """capi.PRECISION_* of metadata.local_solver_precision; "single" exists for the iterative local solver of a
+    symmetric matrix (CG) without a preconditioner or with scalar Jacobi.  Runs before any device call."""
+    name = getattr(metadata, "local_solver_precision", "double")
+    if name == "double":
+        return capi.PRECISION_F64
+    if name != "single":
+        raise capi.SchwzError(capi.ERR_INVALID,
+                              "local_solver_precision must be 'double' or 'single', not %r" % (name,))
+    if _local_solver_code(settings) != capi.SOLVER_ITERATIVE:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "local_solver_precision 'single' applies to the iterative local solver only")
+    if settings.non_symmetric_matrix:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "local_solver_precision 'single' is not implemented for GMRES "
+                                       "(non_symmetric_matrix)")
+    if _precond_name_code(metadata) not in (capi.PRECOND_NONE, capi.PRECOND_JACOBI):
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "local_solver_precision 'single' is implemented for local_precond 'null' and "
+                                       "'block-jacobi' with precond_max_block_size 1 only")
+    return capi.PRECISION_F32
 
 
 def _precond_name_code(metadata):
@@ -431,6 +458,7 @@ class SolverRAS:
         self._user_rhs = None if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
         solver_code = _factor_solver_code(s, m)
         precond_code = _precond_code(m)
+        precision_code = _precision_code(s, m)
         if self._distributed_ingest():
             prob = self._ingest_distributed()
         else:
@@ -454,6 +482,8 @@ class SolverRAS:
                          natural_factor_ordering=s.naturally_ordered_factor,
                          spmv_variant=s.spmv_variant, precond_block_size=m.precond_max_block_size,
                          non_symmetric=s.non_symmetric_matrix, restart_iter=s.restart_iter, **sweeps)
+            if precision_code != capi.PRECISION_F64:  # (a backend without the setter keeps working in double)
+                sd.set_local_precision(precision_code)
             # use_mixed_precision (MixedValueType = float): halos travel as fp32
             self.send_buf[me] = be.empty(sd.num_send, s.use_mixed_precision)
             self.recv_buf[me] = be.empty(sd.num_recv, s.use_mixed_precision)
