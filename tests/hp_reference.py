@@ -703,3 +703,344 @@ def rescale(f, rng, span=20):
         rowid = np.repeat(np.arange(n), np.diff(rp))
         out[name + "_val"] = f[name + "_val"] * d1[rowid] * d2[col]
     return out
+
+
+# ---- row-wise bounds of CSR row sums evaluated in float64 ------------------------------------------------------------
+# Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., section 3.1: a sum of k products evaluated in
+# floating point with unit roundoff u, in ANY order of the additions, with or without FMA, is
+#     s^ = sum_j a_j x_j (1 + theta_j),   |theta_j| <= gamma(k) = k u / (1 - k u)
+# (every product is rounded at most once and then takes part in at most k - 1 rounded additions; an FMA rounds once
+# where a product and an addition round twice).  Each further rounded operation on the result raises the index of
+# gamma by one (Lemma 3.3).  Nothing below is measured on a kernel.  The bounds assume that no product underflows.
+#
+# The references are longdouble evaluations of the same sums, themselves rounded: by the same argument with
+# u_ld = 2^-64 their error is at most (k + 2) u_ld times the same magnitudes (to first order, which at 2^-64 leaves
+# a factor 1 + 1e-15 that the "+ 2" absorbs for every k used here).  Every bound below carries that term.
+
+U_LD = 2.0 ** -64   # unit roundoff of the x87 extended format
+
+
+def gamma(k, u=U64):
+    """gamma(k) = k u / (1 - k u), in longdouble; k a number or an array."""
+    ku = np.asarray(k, dtype=LD) * LD(u)
+    return ku / (1 - ku)
+
+
+def abs_row_sums(rp, col, val, x):
+    """m_i = sum_j |a_ij| |x_j| in longdouble."""
+    return spmv(rp, col, np.abs(np.asarray(val, dtype=LD)), np.abs(np.asarray(x, dtype=LD)), LD)
+
+
+def axpby(rp, col, val, x, alpha, beta, y0, dtype=LD):
+    """y = alpha A x + beta y0, rows summed in CSR order, in `dtype`.  beta == 0: y0 is not looked at (it may hold
+    NaN), which is what BLAS and schwz_csr_spmv document."""
+    t = np.dtype(dtype).type
+    y = t(alpha) * spmv(rp, col, val, x, dtype)
+    if beta != 0:
+        y = y + t(beta) * np.asarray(y0, dtype=dtype)
+    return y
+
+
+def axpby_bound(rp, col, val, x, alpha, beta, y0):
+    """Row-wise bound of a float64 evaluation of y = alpha A x + beta y0 against axpby(...) in longdouble:
+
+        |y^_i - y_i| <= gamma(k_i + 2) (|alpha| m_i + |beta| |y0_i|)  +  (k_i + 2) 2^-64 (the same magnitudes),
+
+    k_i the stored entries of row i.  Derivation: s^_i carries gamma(k_i) (above); alpha s^_i, beta y0_i and their
+    sum are three more rounded operations, of which a term passes through two: gamma(k_i + 2) on the first term,
+    gamma(2) <= gamma(k_i + 2) on the second.  Valid for any order of the k_i additions, with or without FMA."""
+    k = np.diff(np.asarray(rp, dtype=np.int64))
+    mag = abs(LD(alpha)) * abs_row_sums(rp, col, val, x)
+    if beta != 0:
+        mag = mag + abs(LD(beta)) * np.abs(np.asarray(y0, dtype=LD))
+    return (gamma(k + 2) + (k + 2) * LD(U_LD)) * mag
+
+
+def residual(rp, col, val, x, b, dtype=LD):
+    """r = b - A x, rows summed in CSR order, in `dtype`."""
+    return np.asarray(b, dtype=dtype) - spmv(rp, col, val, x, dtype)
+
+
+def residual_bound(rp, col, val, x, b):
+    """e_i with |r^_i - r_i| <= e_i for a float64 evaluation of r_i = b_i - (A x)_i against residual(...) in
+    longdouble:  e_i = gamma(k_i + 1) (|b_i| + m_i) + (k_i + 2) 2^-64 (|b_i| + m_i): the k_i roundings of the row sum
+    and the subtraction.  The interface update b~_i = b_i - (A_Gamma x~)_i is the same expression."""
+    k = np.diff(np.asarray(rp, dtype=np.int64))
+    mag = np.abs(np.asarray(b, dtype=LD)) + abs_row_sums(rp, col, val, x)
+    return (gamma(k + 1) + (k + 2) * LD(U_LD)) * mag
+
+
+def norm_sq_bound(r, e, L, root=False):
+    """B with |S^ - rho^2| <= B, where rho^2 = sum_{i<L} r_i^2 in longdouble (np.sum) and S^ is that sum formed in
+    float64 from computed residuals r^_i with |r^_i - r_i| <= e_i, in ANY order -- per-workgroup partial sums folded
+    by another kernel included:
+
+        B = sum_{i<L} (2 |r_i| e_i + e_i^2)  +  (gamma(L + 1) + (L + 1) 2^-64) sum_{i<L} (|r_i| + e_i)^2.
+
+    First term: |r^_i^2 - r_i^2| = |r^_i - r_i| |r^_i + r_i| <= e_i (2 |r_i| + e_i).  Second: each square is rounded
+    once and passes through at most L - 1 rounded additions (a sum with an exact zero, the rows past L, rounds
+    nothing), so S^ = sum r^_i^2 (1 + theta_i) with |theta_i| <= gamma(L) <= gamma(L + 1), and r^_i^2 <=
+    (|r_i| + e_i)^2; the reference's own sum adds (L + 1) 2^-64 of the same.  (e from residual_bound already holds
+    the rounding of the reference residuals.)
+
+    root: the API returned v = fl(sqrt(S^)) and the test compares v^2 (squared in longdouble) with rho^2: v^2 =
+    S^ (1 + d)^2, |d| <= u, so 4 u rho^2 is added (it covers (2 u + u^2) (rho^2 + B) as long as B < rho^2 / 2,
+    which the callers assert)."""
+    r = np.abs(np.asarray(r, dtype=LD)[:L])
+    e = np.asarray(e, dtype=LD)[:L]
+    B = np.sum(2 * r * e + e * e) + (gamma(L + 1) + (L + 1) * LD(U_LD)) * np.sum((r + e) ** 2)
+    if root:
+        rho2 = np.sum(r * r)
+        assert B < rho2 / 2
+        B = B + 4 * LD(U64) * rho2
+    return B
+
+
+# ---- the tile rule of schwz_csr_create, and which branch of spmv_tiled2_kernel a tile takes -----------------------------
+
+TILE_ROWS, TILE_NNZ = 256, 2048   # kTileRows, kTileNnz
+
+
+def tiles_of(rp):
+    """Row boundaries of the tiles: consecutive rows, at most 256 of them, at most 2046 entries; a longer row forms a
+    tile of its own (the loop of schwz_csr_create)."""
+    rp = np.asarray(rp, dtype=np.int64)
+    n = len(rp) - 1
+    out, r = [0], 0
+    while r < n:
+        e = r
+        while e < n and e - r < TILE_ROWS and rp[e + 1] - rp[r] <= TILE_NNZ - 2:
+            e += 1
+        e = max(e, r + 1)
+        out.append(e)
+        r = e
+    return np.asarray(out, dtype=np.int64)
+
+
+def tile_branches(rp):
+    """Per tile "a" (16-byte aligned window), "b" (fits the tile but not the aligned window: unaligned staging) or
+    "c" (one long row reduced by the workgroup), by the conditions of spmv_tiled2_kernel."""
+    rp = np.asarray(rp, dtype=np.int64)
+    t = tiles_of(rp)
+    out = []
+    for r0, r1 in zip(t[:-1], t[1:]):
+        s, cnt = rp[r0], rp[r1] - rp[r0]
+        out.append("a" if (s & 3) + cnt <= TILE_NNZ else ("b" if r1 - r0 > 1 else "c"))
+    return out
+
+
+def stream_cap(rp):
+    """The masked-add form of the straight-line kernel of spmv_stream.hip (8, 16 or 32 entries per row), 0 where it
+    does not apply: a row of more than 32 entries or a tile outside the aligned window."""
+    longest = int(np.diff(np.asarray(rp, dtype=np.int64)).max()) if len(rp) > 1 else 0
+    if len(rp) < 2 or longest > 32 or any(b != "a" for b in tile_branches(rp)):
+        return 0
+    return 32 if longest > 16 else (16 if longest > 8 else 8)
+
+
+# ---- seeded matrices of the row-sum tests --------------------------------------------------------------------------
+
+def csr_from_lengths(lens, ncols, rng):
+    """Random CSR with the given row lengths: distinct sorted columns, standard normal values."""
+    lens = np.asarray(lens, dtype=np.int64)
+    rp = np.concatenate([[0], np.cumsum(lens)])
+    col = np.empty(rp[-1], dtype=np.int32)
+    for i, ln in enumerate(lens):
+        if ln:
+            col[rp[i]:rp[i + 1]] = np.sort(rng.choice(ncols, size=ln, replace=False))
+    return rp.astype(np.int32), col, rng.standard_normal(rp[-1])
+
+
+def short_lengths(n, max_len, rng):
+    lens = rng.integers(0, max_len + 1, size=n)
+    lens[rng.integers(0, n, size=max(n // 10, 1))] = 0
+    return lens
+
+
+def laplacian(shape):
+    """The 5- / 7-point Dirichlet Laplacian of stencil_apply as CSR with sorted columns (natural order, x fastest)."""
+    import scipy.sparse as sp
+    a = None
+    for k, m in enumerate(shape):
+        t = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(m, m), format="csr")
+        term = t
+        for q, mq in enumerate(shape):
+            if q < k:
+                term = sp.kron(term, sp.identity(mq, format="csr"), format="csr")
+            elif q > k:
+                term = sp.kron(sp.identity(mq, format="csr"), term, format="csr")
+        a = term if a is None else a + term
+    a = a.tocsr()
+    a.sort_indices()
+    return a.indptr.astype(np.int32), a.indices.astype(np.int32), a.data.astype(np.float64)
+
+
+def window2049_lengths(rng, tail=300, tail_len=6):
+    """Row 0 has 1027 entries and rows 1 and 2 have 1023 each: row 1 does not fit behind row 0 (2050 > 2046), so
+    tile 1 starts at entry 1027 = 3 mod 4 and holds rows 1 and 2, 2046 entries: (s & 3) + cnt = 2049 > 2048, the
+    unaligned staging branch with two rows.  (With 3 entries in row 0 the greedy rule would take row 1 into tile 0.)
+    Then `tail` short rows, the first of them not empty (it ends tile 1), some of the others empty."""
+    tail_lens = short_lengths(tail, tail_len, rng)
+    tail_lens[0] = max(tail_lens[0], 1)
+    return np.concatenate([[1027, 1023, 1023], tail_lens])
+
+
+def scaled_matrix(n, max_len, rng, span=40, band=None):
+    """Ragged rows of at most max_len entries (some empty), row i scaled by 2^s_i and column j by 2^t_j, s and t in
+    [-span, span]: exact in float64.  Returns (rp, col, val, s, t).  band: columns within that distance of the row."""
+    lens = short_lengths(n, max_len, rng)
+    rp = np.concatenate([[0], np.cumsum(lens)])
+    col = np.empty(rp[-1], dtype=np.int32)
+    for i, ln in enumerate(lens):
+        if ln:
+            if band is None:
+                col[rp[i]:rp[i + 1]] = np.sort(rng.choice(n, size=ln, replace=False))
+            else:
+                lo, hi = max(0, i - band), min(n, i + band + 1)
+                col[rp[i]:rp[i + 1]] = lo + np.sort(rng.choice(hi - lo, size=ln, replace=False))
+    s, t = rng.integers(-span, span + 1, n), rng.integers(-span, span + 1, n)
+    rowid = np.repeat(np.arange(n), lens)
+    val = np.ldexp(rng.standard_normal(rp[-1]), s[rowid] + t[col])
+    return rp.astype(np.int32), col, val, s, t
+
+
+def rowsum_case(name):
+    """The stand-alone SpMV cases: dict(rp, col, val, ncols, x, y0, branches), seeded by name.  `branches`: the
+    branches of spmv_tiled2_kernel the matrix is built to reach (asserted by the tests through tile_branches)."""
+    rng = np.random.default_rng(sum(name.encode()) + 1000)
+    want, y_exp = set("a"), None
+    if name == "window2049":
+        ncols = 1100
+        rp, col, val = csr_from_lengths(window2049_lengths(rng), ncols, rng)
+        want = {"a", "b"}
+    elif name == "longrows":
+        # long rows between short ones; the pad row in front of each long row sets its start modulo 4 (2047 fits the
+        # aligned window from 0 or 1, 2048 from 0 only; a second row of 2047 starts at 3 and takes branch c)
+        ncols = 5200
+        lens = []
+        for ln, mod in ((5000, 0), (2046, None), (2047, 1), (2048, 0), (2049, 2), (2047, 3), (2500, None)):
+            if lens:
+                lens += list(rng.integers(1, 9, size=5))
+                if mod is not None:
+                    lens.append(1 + (mod - (sum(lens) + 1)) % 4)
+            lens.append(ln)
+        rp, col, val = csr_from_lengths(lens, ncols, rng)
+        want = {"a", "c"}
+    elif name in ("scaled8", "scaled16", "scaled32"):
+        n = 1501
+        rp, col, val, s, _ = scaled_matrix(n, int(name[6:]), rng)
+        ncols, y_exp = n, s
+    elif name == "rect_wide":
+        ncols = 1900
+        rp, col, val = csr_from_lengths(short_lengths(700, 24, rng), ncols, rng)
+    elif name == "rect_tall":
+        ncols = 700
+        rp, col, val = csr_from_lengths(short_lengths(1900, 24, rng), ncols, rng)
+    elif name == "lap3d":
+        rp, col, val = laplacian((23, 17, 11))
+        ncols = len(rp) - 1
+    elif name == "lap2d":
+        rp, col, val = laplacian((97, 97))
+        ncols = len(rp) - 1
+    elif name == "ani4_crop":
+        import os
+        g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ani4_crop.npz"))
+        rp, col, val = g["rp"], g["col"], g["val"]
+        ncols = len(rp) - 1
+    elif name == "one":
+        rp, col, val, ncols = np.array([0, 1], np.int32), np.array([0], np.int32), np.array([-1.75]), 1
+    elif name == "three":
+        rp, col, val, ncols = np.array([0, 2, 2, 3], np.int32), np.array([0, 2, 1], np.int32), rng.standard_normal(3), 3
+    else:
+        raise KeyError(name)
+    n = len(rp) - 1
+    x = rng.standard_normal(ncols)
+    y0 = rng.standard_normal(n)
+    if y_exp is not None:
+        y0 = np.ldexp(y0, y_exp)      # of the size of its row: an order-1 y0 would hide a small row behind beta y0
+    return dict(name=name, rp=rp, col=col, val=val, ncols=ncols, x=x, y0=y0, branches=want)
+
+
+ROWSUM_CASES = ("window2049", "longrows", "scaled8", "scaled16", "scaled32", "rect_wide", "rect_tall", "lap3d",
+                "lap2d", "ani4_crop", "one", "three")
+ALPHA_BETA = ((1.0, 0.0), (-1.0, 1.0), (0.5, -2.0), (0.0, 1.0))
+
+
+# ---- seeded matrices of the RAS step tests: structurally symmetric, nonzero diagonal ------------------------------------
+
+def sym_band_matrix(n, picks, band, rng, spd=True):
+    """Row i takes up to `picks` columns in (i, i + band], the transposed entries are added, and the diagonal: at
+    most 2 * picks + 1 entries in a row... of which the lower ones depend on the rows above (callers that need a cap
+    assert it).  spd: symmetric values in (-1, 1) with diag = 1 + sum |off-diagonal| (strictly dominant, positive:
+    SPD); otherwise independent standard normal values, a diagonal of magnitude >= 1."""
+    import scipy.sparse as sp
+    rows, cols = [], []
+    for i in range(n - 1):
+        hi = min(n, i + band + 1)
+        k = min(int(rng.integers(0, picks + 1)), hi - i - 1)
+        if k:
+            c = i + 1 + rng.choice(hi - i - 1, size=k, replace=False)
+            rows += [i] * k
+            cols += list(c)
+    rows, cols = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+    if spd:
+        v = rng.uniform(-1.0, 1.0, len(rows))
+        a = sp.csr_matrix((v, (rows, cols)), shape=(n, n))
+        a = a + a.T
+        a = a + sp.diags(1.0 + np.asarray(abs(a).sum(axis=1)).ravel())
+    else:
+        a = sp.csr_matrix((rng.standard_normal(len(rows)), (rows, cols)), shape=(n, n))
+        a = a + sp.csr_matrix((rng.standard_normal(len(rows)), (cols, rows)), shape=(n, n))
+        a = a + sp.diags(rng.choice([-1.0, 1.0], n) * rng.uniform(1.0, 2.0, n))
+    a = a.tocsr()
+    a.sort_indices()
+    assert a.nnz == 2 * len(rows) + n    # no entry cancelled: the structure is symmetric
+    return a.indptr.astype(np.int32), a.indices.astype(np.int32), a.data.astype(np.float64)
+
+
+def rescale_rows_cols(rp, col, val, rng, span=40):
+    """D1 A D2 with powers of two in [2^-span, 2^span]: exact.  Returns (val, s, t)."""
+    n = len(rp) - 1
+    s, t = rng.integers(-span, span + 1, n), rng.integers(-span, span + 1, n)
+    rowid = np.repeat(np.arange(n), np.diff(rp))
+    return np.ldexp(val, s[rowid] + t[col]), s, t
+
+
+def arrow_matrix(n, rng):
+    """Row 0 and column 0 dense, a tridiagonal rest, a dominant diagonal; symmetric."""
+    import scipy.sparse as sp
+    i = np.arange(1, n)
+    v0 = rng.uniform(-1.0, 1.0, n - 1)
+    v1 = rng.uniform(-1.0, 1.0, n - 2)
+    a = sp.csr_matrix((np.concatenate([v0, v1]), (np.concatenate([np.zeros(n - 1, dtype=np.int64), i[:-1]]),
+                                                   np.concatenate([i, i[1:]]))), shape=(n, n))
+    a = a + a.T
+    a = (a + sp.diags(1.0 + np.asarray(abs(a).sum(axis=1)).ravel())).tocsr()
+    a.sort_indices()
+    return a.indptr.astype(np.int32), a.indices.astype(np.int32), a.data.astype(np.float64)
+
+
+def window2049_square(rng, n=1100):
+    """window2049_lengths as a square, structurally symmetric matrix with a nonzero diagonal: rows 0, 1, 2 hold each
+    other, themselves and 1024 / 1020 / 1020 of the columns from 3 on; row j >= 3 holds its diagonal, j - 1 and j + 1
+    (from 3 on) and whichever of 0, 1, 2 hold it: at most 6 entries."""
+    import scipy.sparse as sp
+    rows, cols = [], []
+    for r, cnt in ((0, 1024), (1, 1020), (2, 1020)):
+        c = 3 + np.sort(rng.choice(n - 3, size=cnt, replace=False))
+        rows += [r] * cnt + list(c)
+        cols += list(c) + [r] * cnt
+    for r in range(3):
+        for c in range(3):
+            rows.append(r), cols.append(c)
+    j = np.arange(3, n)
+    rows += list(j) + list(j[:-1]) + list(j[1:])
+    cols += list(j) + list(j[1:]) + list(j[:-1])
+    pat = sp.csr_matrix((np.ones(len(rows)), (rows, cols)), shape=(n, n))
+    pat.sum_duplicates()
+    pat.sort_indices()
+    val = rng.standard_normal(pat.nnz)
+    rowid = np.repeat(np.arange(n), np.diff(pat.indptr))
+    on = pat.indices == rowid
+    val[on] = rng.choice([-1.0, 1.0], n) * rng.uniform(1.0, 2.0, n)
+    return pat.indptr.astype(np.int32), pat.indices.astype(np.int32), val

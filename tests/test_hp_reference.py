@@ -313,3 +313,184 @@ def test_longdouble_dot_of_2_to_24_terms_against_fsum():
     print("longdouble pairwise dot: %.3f eps sum|xy|; float64 pairwise: %.1f eps" %
           (float(err / (eps * mag)), float(abs(LD(hp.dot(x, y)) - exact) / (eps * mag))))
     assert err <= 4 * eps * mag
+
+
+# ---- the row-wise bounds of CSR row sums: they hold for a float64 restatement, and they reject seeded defects ---------
+
+@pytest.fixture(scope="module")
+def rowsum_cases():
+    hp.require_extended_precision()
+    return {name: hp.rowsum_case(name) for name in hp.ROWSUM_CASES}
+
+
+def _norm_case(kind):
+    """An order-1 matrix with x~, b of the RAS norm tests: (rp, col, val, x, b)."""
+    rng = np.random.default_rng(77)
+    if kind == "band":
+        rp, col, val = hp.sym_band_matrix(1500, 6, 40, rng)
+    elif kind == "band7":
+        rp, col, val = hp.sym_band_matrix(1500, 3, 3, rng)
+    else:
+        rp, col, val = hp.sym_band_matrix(1501, 14, 60, rng, spd=False)
+    n = len(rp) - 1
+    return rp, col, val, rng.standard_normal(n), rng.standard_normal(n)
+
+
+def _sum_sq64(r, L):
+    """sum_{i<L} r_i^2 in float64, one term after the other."""
+    s = 0.0
+    for v in np.asarray(r[:L], dtype=np.float64):
+        s += v * v
+    return s
+
+
+def test_the_built_matrices_reach_the_branches_they_are_built_for(rowsum_cases):
+    for name, c in rowsum_cases.items():
+        assert c["branches"] <= set(hp.tile_branches(c["rp"])), name
+    c = rowsum_cases["window2049"]
+    t, br = hp.tiles_of(c["rp"]), hp.tile_branches(c["rp"])
+    assert br[1] == "b" and t[1] == 1 and t[2] == 3 and c["rp"][1] & 3 == 3 and c["rp"][3] - c["rp"][1] == 2046
+    c = rowsum_cases["longrows"]
+    t, br, ln = hp.tiles_of(c["rp"]), hp.tile_branches(c["rp"]), np.diff(c["rp"])
+    single = {(int(ln[r0]), b) for r0, r1, b in zip(t[:-1], t[1:], br) if r1 - r0 == 1 and ln[r0] > 2000}
+    assert single == {(5000, "c"), (2046, "a"), (2047, "a"), (2048, "a"), (2049, "c"), (2047, "c"), (2500, "c")}
+    assert ln[0] == 5000 and ln[-1] == 2500
+    for name, cap in (("scaled8", 8), ("scaled16", 16), ("scaled32", 32)):
+        c = rowsum_cases[name]
+        n = len(c["rp"]) - 1
+        assert hp.stream_cap(c["rp"]) == cap and n % 4 != 0 and (np.diff(c["rp"]) == 0).any()
+        assert np.diff(hp.tiles_of(c["rp"]))[-1] < np.diff(hp.tiles_of(c["rp"]))[0]          # a partial last tile
+    assert np.diff(hp.tiles_of(rowsum_cases["scaled32"]["rp"])).max() < 256                    # nnz-limited tiles
+
+
+def test_row_wise_bounds_hold_for_a_float64_restatement(rowsum_cases):
+    """Products rounded, added in CSR order, the epilogue in float64: inside axpby_bound, residual_bound and
+    norm_sq_bound on every matrix of the stand-alone SpMV tests."""
+    for name, c in rowsum_cases.items():
+        a = (c["rp"], c["col"], c["val"], c["x"])
+        n = len(c["rp"]) - 1
+        for alpha, beta in hp.ALPHA_BETA:
+            ref = hp.axpby(*a, alpha, beta, c["y0"])
+            got = hp.axpby(*a, alpha, beta, c["y0"], np.float64)
+            assert (np.abs(got - ref) <= hp.axpby_bound(*a, alpha, beta, c["y0"])).all(), (name, alpha, beta)
+        r, e = hp.residual(*a, c["y0"]), hp.residual_bound(*a, c["y0"])
+        r64 = hp.residual(*a, c["y0"], np.float64)
+        assert (np.abs(r64 - r) <= e).all(), name
+        for L in {n, max(n - 1, 1), (n + 1) // 2}:
+            rho2 = np.sum(r[:L] * r[:L])
+            assert abs(_sum_sq64(r64, L) - rho2) <= hp.norm_sq_bound(r, e, L), (name, L)
+            assert abs(hp.LD(np.sqrt(_sum_sq64(r64, L))) ** 2 - rho2) <= hp.norm_sq_bound(r, e, L, root=True), (name, L)
+    for kind in ("band", "band7", "ragged"):
+        rp, col, val, x, b = _norm_case(kind)
+        r, e, r64 = hp.residual(rp, col, val, x, b), hp.residual_bound(rp, col, val, x, b), hp.residual(rp, col, val, x, b, np.float64)
+        for L in (1, 255, 256, 257, len(b) - 1, len(b)):
+            assert abs(_sum_sq64(r64, L) - np.sum(r[:L] * r[:L])) <= hp.norm_sq_bound(r, e, L), (kind, L)
+
+
+def _drop_smallest(rp, col, val, x, bound, small=False):
+    """Zero the smallest-magnitude term of one row: the row where that term stands highest above the row's bound, or
+    (small) the row with the smallest such term among those where it stands more than four times above it.  Returns
+    (val', row, term / bound)."""
+    term = np.abs(val * x[col]).astype(hp.LD)
+    rows = np.nonzero(np.diff(rp) >= 2)[0]
+    at = np.array([rp[i] + int(np.argmin(term[rp[i]:rp[i + 1]])) for i in rows])
+    q = term[at] / np.maximum(bound[rows], hp.LD(1e-4000))
+    if small:
+        ok = np.nonzero(q > 4.0)[0]
+        k = ok[int(np.argmin(term[at[ok]]))]
+    else:
+        k = int(np.argmax(q))
+    v = val.copy()
+    v[at[k]] = 0.0
+    return v, rows[k], float(q[k])
+
+
+def _round_one_to_fp32(rp, col, val, x, bound):
+    rowid = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    change = np.abs((val - val.astype(np.float32).astype(np.float64)) * x[col]).astype(hp.LD)
+    q = change / np.maximum(bound[rowid], hp.LD(1e-4000))
+    j = int(np.argmax(q))
+    v = val.copy()
+    v[j] = np.float32(val[j])
+    return v, rowid[j], float(q[j])
+
+
+@pytest.mark.parametrize("name", ["scaled8", "scaled16", "scaled32", "longrows", "window2049"])
+def test_row_wise_bounds_reject_a_dropped_term_and_an_fp32_value(rowsum_cases, name):
+    """The smallest-magnitude term of one badly scaled row dropped; one matrix value rounded to fp32.  Each defect is
+    seeded where it stands more than twice the row's bound high (asserted: the input is chosen, not the bound), and
+    on the scaled matrices where 5e-12 max |y|, the tolerance these bounds replace, does not see the dropped term."""
+    c = rowsum_cases[name]
+    rp, col, val, x, y0 = c["rp"], c["col"], c["val"], c["x"], c["y0"]
+    for alpha, beta in ((1.0, 0.0), (0.5, -2.0)):
+        ref = hp.axpby(rp, col, val, x, alpha, beta, y0)
+        bound = hp.axpby_bound(rp, col, val, x, alpha, beta, y0)
+        for seed in (_drop_smallest, _round_one_to_fp32):
+            v, row, q = seed(rp, col, val, x, bound / abs(alpha))
+            assert q > 2.0, (seed.__name__, q)
+            got = hp.axpby(rp, col, v, x, alpha, beta, y0, np.float64)
+            assert abs(got[row] - ref[row]) > bound[row], seed.__name__
+        if name.startswith("scaled"):
+            v, row, q = _drop_smallest(rp, col, val, x, bound / abs(alpha), small=True)
+            got = hp.axpby(rp, col, v, x, alpha, beta, y0, np.float64)
+            assert q > 4.0 and abs(got[row] - ref[row]) > bound[row]
+            assert abs(got[row] - ref[row]) < 1e-30 * 5e-12 * float(np.abs(ref).max())    # ... and far below
+    r, e = hp.residual(rp, col, val, x, y0), hp.residual_bound(rp, col, val, x, y0)
+    for seed in (_drop_smallest, _round_one_to_fp32):
+        v, row, q = seed(rp, col, val, x, e)
+        assert q > 2.0
+        assert abs(hp.residual(rp, col, v, x, y0, np.float64)[row] - r[row]) > e[row]
+
+
+@pytest.mark.parametrize("kind", ["band", "band7", "ragged"])
+def test_norm_bound_rejects_the_seeded_defects(kind):
+    """On the order-1 matrices of the norm tests: a dropped term, an fp32 value, and a row limit off by one in either
+    direction at 1, 255, 256, 257, n - 1 change the sum of squares by more than norm_sq_bound allows."""
+    hp.require_extended_precision()
+    rp, col, val, x, b = _norm_case(kind)
+    n = len(b)
+    r, e = hp.residual(rp, col, val, x, b), hp.residual_bound(rp, col, val, x, b)
+    r64 = hp.residual(rp, col, val, x, b, np.float64)
+    for L in (1, 255, 256, 257, n - 1):
+        B = hp.norm_sq_bound(r, e, L, root=True)
+        rho2 = np.sum(r[:L] * r[:L])
+        assert r[L - 1] ** 2 > 4 * B and r[L] ** 2 > 4 * B           # the discrimination condition
+        assert abs(_sum_sq64(r64, L) - rho2) <= B
+        assert abs(_sum_sq64(r64, L + 1) - rho2) > B                   # row <= row_limit
+        assert L == 1 or abs(_sum_sq64(r64, L - 1) - rho2) > B         # row < row_limit - 1
+    B, rho2 = hp.norm_sq_bound(r, e, n), np.sum(r * r)
+    # a defect in row i moves the sum by about 2 |r_i| d: seed it where that is largest against B
+    weight = 2 * np.abs(r) / B
+    for seed in (_drop_smallest, _round_one_to_fp32):
+        v, row, q = seed(rp, col, val, x, 1 / np.maximum(weight, hp.LD(1e-300)))
+        assert q > 4.0, (seed.__name__, q)
+        assert abs(_sum_sq64(hp.residual(rp, col, v, x, b, np.float64), n) - rho2) > B, seed.__name__
+
+
+def test_residual_bound_rejects_a_skipped_first_entry_of_an_interface_row():
+    """The interface update b~_i = b_i - (A_Gamma x~)_i on a badly scaled rectangular matrix (the rows 500..999 of a
+    scaled band matrix, the columns outside them): the loop started at rp[i] + 1 in one row."""
+    hp.require_extended_precision()
+    rng = np.random.default_rng(12)
+    rp, col, val = hp.sym_band_matrix(1500, 6, 40, rng, spd=False)
+    val, s, _ = hp.rescale_rows_cols(rp, col, val, rng)
+    a = sp.csr_matrix((val, col, rp), shape=(1500, 1500))[500:1000].tocsc()
+    a = sp.hstack([a[:, :500], a[:, 1000:]]).tocsr()
+    a.sort_indices()
+    irp, icol, ival = a.indptr, a.indices, a.data
+    assert a.nnz > 100 and (np.diff(irp) == 0).any()
+    x = rng.standard_normal(1000)
+    b = np.ldexp(rng.standard_normal(500), s[500:1000])
+    r, e = hp.residual(irp, icol, ival, x, b), hp.residual_bound(irp, icol, ival, x, b)
+    assert (np.abs(hp.residual(irp, icol, ival, x, b, np.float64) - r) <= e).all()
+    first = irp[:-1][np.diff(irp) > 0]
+    rows = np.nonzero(np.diff(irp) > 0)[0]
+    q = np.abs(ival[first] * x[icol[first]]) / e[rows]
+    # (a first entry 2^-60 of its row is rounding noise to any bound; most are not)
+    seen = np.nonzero(q > 2.0)[0]
+    assert len(seen) > len(rows) // 2
+    for k in (seen[0], seen[len(seen) // 2], seen[-1]):
+        v = ival.copy()
+        v[first[k]] = 0.0
+        got = hp.residual(irp, icol, v, x, b, np.float64)
+        assert abs(got[rows[k]] - r[rows[k]]) > e[rows[k]]
