@@ -221,6 +221,29 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
 /* iterations and residual norm of the last solve (device synchronisation) */
 int schwz_gmres_last_stats(schwz_gmres *s, int *h_iters, double *h_resnorm);
 
+/* BiCGSTAB with right preconditioning (van der Vorst 1992), device resident like the CG and GMRES: a second
+ * local solver for non-symmetric matrices, an extension (the reference offers GMRES only).  Two matrix-vector
+ * products and five vector launches per iteration, 8 work vectors whatever the iteration count.  The
+ * preconditioner codes and the ParILU options are those of schwz_gmres_create_ex.  The solve stops before
+ * iteration k when k == max_iters or the recurred residual norm ||r_k|| is <= rtol times the start residual norm
+ * (or exactly zero), and in the middle of an iteration when ||s|| is (the half step is then applied and counts as
+ * an iteration); rtol <= 0 runs exactly max_iters iterations unless a norm is exactly zero or the recurrence
+ * breaks down.  h_resnorm is the recurred norm the stop test saw, not the norm of b - A x.  A breakdown ends the
+ * solve with a finite x and SCHWZ_OK; schwz_bicgstab_breakdown tells which (device synchronisation): 0 none,
+ * 1 rho = 0 at the top, 2 rhat.v = 0 (x untouched by that iteration), 3 t.t = 0 or t.s = 0 (half step applied);
+ * -1 when the device state could not be read (schwz_last_error says why), 0 for a null solver.
+ * The host looks at the device state every SCHWZ_BICGSTAB_POLL_BATCH iterations, one batch behind the launches. */
+#define SCHWZ_BICGSTAB_POLL_BATCH 8
+typedef struct schwz_bicgstab schwz_bicgstab;
+int schwz_bicgstab_create(const schwz_csr *A, int precond, int block_size, int par_ilu_sweeps, int trisolve_sweeps,
+                          schwz_bicgstab **out);
+void schwz_bicgstab_destroy(schwz_bicgstab *s);
+int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, double rtol, int max_iters,
+                         int *h_iters, double *h_resnorm, schwz_stream stream);
+/* iterations and residual norm of the last solve (device synchronisation) */
+int schwz_bicgstab_last_stats(schwz_bicgstab *s, int *h_iters, double *h_resnorm);
+int schwz_bicgstab_breakdown(schwz_bicgstab *s);
+
 /* Profiling hooks for bench.py's roofline leg: between begin and end, every
  * launch of the dominant kernel (the CSR SpMV inside schwz_pcg_solve) is
  * bracketed by a HIP event pair on its launch stream; end synchronises and
@@ -544,6 +567,17 @@ int schwz_ras_set_local_max_iters(schwz_subdomain *sd, int max_iters);
 enum schwz_precision { SCHWZ_PRECISION_F64 = 0, SCHWZ_PRECISION_F32 = 1 };
 int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision);
 int schwz_ras_local_precision(const schwz_subdomain *sd);
+
+/* Which Krylov method solves a non-symmetric local system iteratively (an extension; schwz_solver_options keeps its
+ * layout, so the choice travels through a setter, after schwz_subdomain_to_device).  GMRES(restart_iter) is what
+ * the upload creates.  The setter creates the requested solver around the preconditioner the current one holds and
+ * then destroys the other, so one set of work vectors lives between solves (device synchronisation; if the new
+ * solver cannot be created the subdomain keeps the one it has).  SCHWZ_ERR_INVALID for a null
+ * subdomain or an unknown code, SCHWZ_ERR_NOT_IMPLEMENTED unless the subdomain runs the iterative local solver
+ * with non_symmetric set.  The getter answers SCHWZ_NONSYM_GMRES for a null subdomain. */
+enum schwz_nonsym_solver { SCHWZ_NONSYM_GMRES = 0, SCHWZ_NONSYM_BICGSTAB = 1 };
+int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which);
+int schwz_ras_nonsym_solver(const schwz_subdomain *sd);
 /* settings.enable_logging (source/solve.cpp:751-771): inner iterations and final residual norm of the
  * last local solve (0 and 0.0 for the direct path).  Synchronises the solver's stream. */
 int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resnorm);

@@ -26,40 +26,7 @@ __global__ void cg_init_finalize_kernel(CgState *st, const double *partials, int
     cg_init_state(st, partials, nparts, rtol, norm_sq_out, norm_bank, red);  // (device_utils.hpp)
 }
 
-typedef double vd2 __attribute__((ext_vector_type(2)));
-
-template <bool NT>
-__device__ __forceinline__ void store2(double *base, int64_t i, vd2 v)
-{
-    if (NT)
-        __builtin_nontemporal_store(v, reinterpret_cast<vd2 *>(base) + i);
-    else
-        reinterpret_cast<vd2 *>(base)[i] = v;
-}
-
-// 1/diag of rows 2i and 2i+1 in whichever representation the solver holds
-__device__ __forceinline__ vd2 diag_pair(const DiagView &dg, const vd2 *full2, const uint16_t *code2,
-                                         const double *ddict, int64_t i)
-{
-    vd2 d;
-    if (dg.mode == 1) {
-        d = full2[i];
-    } else if (dg.mode == 2) {
-        const unsigned c = code2[i];
-        d.x = ddict[c & 255u];
-        d.y = ddict[c >> 8];
-    } else {
-        d.x = d.y = dg.uniform;
-    }
-    return d;
-}
-
-__device__ __forceinline__ double diag_one(const DiagView &dg, const double *ddict, int64_t i)
-{
-    if (dg.mode == 1) return dg.full[i];
-    if (dg.mode == 2) return ddict[dg.code[i]];
-    return dg.uniform;
-}
+// (vd2, store2, diag_pair, diag_one: device_utils.hpp, shared with bicgstab.hip)
 
 // x += alpha p ; r -= alpha q ; z = dinv r ; partials: r.z and r.r
 // U: 16-byte elements per lane in flight per trip; NT: non-temporal stores; NOX: x and p are not touched

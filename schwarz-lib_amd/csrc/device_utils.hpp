@@ -77,6 +77,45 @@ __device__ __forceinline__ void cg_init_state(CgState *st, const double *partial
     }
 }
 
+// ---------------------------------------------------------------------------
+// streaming vector kernels (cg.hip, bicgstab.hip): 16-byte accesses, the Jacobi diagonal in its DiagView forms
+// ---------------------------------------------------------------------------
+
+typedef double vd2 __attribute__((ext_vector_type(2)));
+
+template <bool NT>
+__device__ __forceinline__ void store2(double *base, int64_t i, vd2 v)
+{
+    if (NT)
+        __builtin_nontemporal_store(v, reinterpret_cast<vd2 *>(base) + i);
+    else
+        reinterpret_cast<vd2 *>(base)[i] = v;
+}
+
+// 1/diag of rows 2i and 2i+1 in whichever representation the solver holds
+__device__ __forceinline__ vd2 diag_pair(const DiagView &dg, const vd2 *full2, const uint16_t *code2,
+                                         const double *ddict, int64_t i)
+{
+    vd2 d;
+    if (dg.mode == 1) {
+        d = full2[i];
+    } else if (dg.mode == 2) {
+        const unsigned c = code2[i];
+        d.x = ddict[c & 255u];
+        d.y = ddict[c >> 8];
+    } else {
+        d.x = d.y = dg.uniform;
+    }
+    return d;
+}
+
+__device__ __forceinline__ double diag_one(const DiagView &dg, const double *ddict, int64_t i)
+{
+    if (dg.mode == 1) return dg.full[i];
+    if (dg.mode == 2) return ddict[dg.code[i]];
+    return dg.uniform;
+}
+
 // Tile dealt to XCD `xcd` as its j-th one.  Tiles go to the eight XCDs (blockIdx % 8) in runs
 // of A.xcd_block (block-cyclic; a run as long as an eighth of the matrix gives each XCD one
 // contiguous eighth).  The run length was meant to keep the x lines a tile shares with its

@@ -199,34 +199,18 @@ struct schwz_gmres {
     int variant = 0;
 };
 
-extern "C" {
+namespace schwz {
 
-int schwz_gmres_create(const schwz_csr *A, int precond, int block_size, int restart, schwz_gmres **out)
+// the solver around a preconditioner object it takes over (destroyed with it); when this fails `pre` stays the
+// caller's
+int gmres_create_adopt(const schwz_csr *A, int restart, schwz_pcg *pre, schwz_gmres **out)
 {
-    return schwz_gmres_create_ex(A, precond, block_size, restart, 0, 0, out);
-}
-
-int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int restart, int par_ilu_sweeps,
-                          int trisolve_sweeps, schwz_gmres **out)
-{
-    int rc = pcg_check_ilu_sweeps(precond, par_ilu_sweeps, trisolve_sweeps);
-    if (rc) return rc;
-    SCHWZ_REQUIRE(A && out, "schwz_gmres_create: null argument");
-    SCHWZ_REQUIRE(A->v.nrows == A->v.ncols, "schwz_gmres_create: matrix must be square");
-    SCHWZ_REQUIRE(restart >= 1, "schwz_gmres_create: restart (krylov_dim) must be >= 1");
-    SCHWZ_REQUIRE(restart <= 2048, "schwz_gmres_create: restart above 2048 is not supported");
     schwz_gmres *s = new schwz_gmres();
     s->A = A;
     s->n = A->v.nrows;
     s->m = restart;
     s->ldv = (s->n + 1) & ~int64_t(1);  // 16-byte aligned columns
-    rc = par_ilu_sweeps || trisolve_sweeps
-             ? pcg_create_impl(A, precond, block_size, par_ilu_sweeps, trisolve_sweeps, &s->pre)
-             : schwz_pcg_create_ex(A, precond, block_size, &s->pre);
-    if (rc) {
-        delete s;
-        return rc;
-    }
+    s->pre = pre;
     const size_t ld = (size_t)(s->ldv ? s->ldv : 2), m = (size_t)restart;
     hipError_t e = hipSuccess;
     auto alloc = [&](void **p, size_t bytes) {
@@ -247,11 +231,48 @@ int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int r
     if (e == hipSuccess) e = hipMemset(s->H, 0, sizeof(double) * (m + 1) * m);
     if (e != hipSuccess) {
         set_error(std::string("schwz_gmres_create: ") + hipGetErrorString(e));
+        s->pre = nullptr;
         schwz_gmres_destroy(s);
         return SCHWZ_ERR_HIP;
     }
     *out = s;
     return SCHWZ_OK;
+}
+
+schwz_pcg *gmres_precond(schwz_gmres *s) { return s->pre; }
+
+schwz_pcg *gmres_release_precond(schwz_gmres *s)
+{
+    schwz_pcg *pre = s->pre;
+    s->pre = nullptr;
+    return pre;
+}
+
+}  // namespace schwz
+
+extern "C" {
+
+int schwz_gmres_create(const schwz_csr *A, int precond, int block_size, int restart, schwz_gmres **out)
+{
+    return schwz_gmres_create_ex(A, precond, block_size, restart, 0, 0, out);
+}
+
+int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int restart, int par_ilu_sweeps,
+                          int trisolve_sweeps, schwz_gmres **out)
+{
+    int rc = pcg_check_ilu_sweeps(precond, par_ilu_sweeps, trisolve_sweeps);
+    if (rc) return rc;
+    SCHWZ_REQUIRE(A && out, "schwz_gmres_create: null argument");
+    SCHWZ_REQUIRE(A->v.nrows == A->v.ncols, "schwz_gmres_create: matrix must be square");
+    SCHWZ_REQUIRE(restart >= 1, "schwz_gmres_create: restart (krylov_dim) must be >= 1");
+    SCHWZ_REQUIRE(restart <= 2048, "schwz_gmres_create: restart above 2048 is not supported");
+    schwz_pcg *pre = nullptr;
+    rc = par_ilu_sweeps || trisolve_sweeps
+             ? pcg_create_impl(A, precond, block_size, par_ilu_sweeps, trisolve_sweeps, &pre)
+             : schwz_pcg_create_ex(A, precond, block_size, &pre);
+    if (rc) return rc;
+    if ((rc = gmres_create_adopt(A, restart, pre, out))) schwz_pcg_destroy(pre);
+    return rc;
 }
 
 void schwz_gmres_destroy(schwz_gmres *s)

@@ -537,6 +537,15 @@ int pcg_take_trs_error(schwz_pcg *s);
 int pcg_check_ilu_sweeps(int precond, int par_ilu_sweeps, int trisolve_sweeps);
 int pcg_create_impl(const schwz_csr *A, int precond, int block_size, int par_ilu_sweeps, int trisolve_sweeps,
                     schwz_pcg **out);
+// The two Krylov solvers of the non-symmetric branch (gmres.hip, bicgstab.hip) around a preconditioner object they
+// take over (on failure it stays the caller's), the object a solver holds, and giving it up before the solver is
+// destroyed: schwz_ras_set_nonsym_solver hands the preconditioner from one solver to the other.
+int gmres_create_adopt(const schwz_csr *A, int restart, schwz_pcg *pre, schwz_gmres **out);
+schwz_pcg *gmres_precond(schwz_gmres *s);
+schwz_pcg *gmres_release_precond(schwz_gmres *s);
+int bicgstab_create_adopt(const schwz_csr *A, schwz_pcg *pre, schwz_bicgstab **out);
+schwz_pcg *bicgstab_precond(schwz_bicgstab *s);
+schwz_pcg *bicgstab_release_precond(schwz_bicgstab *s);
 int pcg_finish_lazy(schwz_pcg *s);  // the postponed residual update / state advance of the last solve, if any  // ILU(0) sweeps: trs_take_error of the factor solves
 }  // namespace schwz
 
@@ -771,6 +780,7 @@ struct schwz_subdomain {
     schwz_csr *A = nullptr;  // local_matrix
     schwz_pcg *cg = nullptr;
     schwz_gmres *gmres = nullptr;  // non-symmetric local matrix
+    schwz_bicgstab *bicg = nullptr;  // ... once schwz_ras_set_nonsym_solver asked for BiCGSTAB (then gmres is null)
     // mixed-precision local solve (schwz_ras_set_local_precision, csrc/cg_f32.hip): created at first use, used while
     // `precision` is SCHWZ_PRECISION_F32; `cg` stays what it is, so that F64 restores the fp64 path exactly
     schwz_pcg_f32 *cg32 = nullptr;

@@ -109,6 +109,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
         schwz_pcg_destroy(sd->cg);
         schwz_pcg_f32_destroy(sd->cg32);
         schwz_gmres_destroy(sd->gmres);
+        schwz_bicgstab_destroy(sd->bicg);
         schwz_trs_destroy(sd->trs);
         schwz_csr_destroy(sd->A);
         void *ptrs[] = {sd->d_i_rp, sd->d_i_col, sd->d_i_val, sd->d_put_idx, sd->d_get_idx, sd->d_x, sd->d_x_alt,
@@ -514,6 +515,7 @@ int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resn
     if (sd->precision == SCHWZ_PRECISION_F32) return schwz_pcg_f32_last_stats(sd->cg32, h_iters, h_resnorm);
     if (sd->cg) return pcg_last_stats(sd->cg, h_iters, h_resnorm);
     if (sd->gmres) return schwz_gmres_last_stats(sd->gmres, h_iters, h_resnorm);
+    if (sd->bicg) return schwz_bicgstab_last_stats(sd->bicg, h_iters, h_resnorm);
     return SCHWZ_OK;
 }
 
@@ -547,6 +549,11 @@ int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream 
     if (sd->gmres)
         return schwz_gmres_solve(sd->gmres, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
                                  stream);
+    // (a breakdown simply ends this local solve: the next outer iteration starts again from y with a fresh rhat)
+    if (sd->bicg)
+        return schwz_bicgstab_solve(sd->bicg, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
+                                    stream);
+    SCHWZ_REQUIRE(sd->cg, "schwz_ras_local_solve: the subdomain has no iterative solver");
     int rc = choose_form(sd, (hipStream_t)stream);
     if (rc) return rc;
     if (sd->precision == SCHWZ_PRECISION_F32) {
@@ -578,7 +585,7 @@ int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = sd->local_size_x;
     if (n == 0) return SCHWZ_OK;
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || sd->precision == SCHWZ_PRECISION_F32 || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || sd->bicg || sd->precision == SCHWZ_PRECISION_F32 || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
         // no fused kernel for this configuration: the two steps back to back
         int rc = schwz_ras_local_residual_launch(sd, stream);
         if (rc) return rc;
@@ -710,6 +717,42 @@ int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
     const int rc = choose_form(sd, nullptr);
     if (rc) return rc;
     SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    return SCHWZ_OK;
+}
+
+int schwz_ras_nonsym_solver(const schwz_subdomain *sd) { return sd && sd->bicg ? SCHWZ_NONSYM_BICGSTAB : SCHWZ_NONSYM_GMRES; }
+
+int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which)
+{
+    SCHWZ_REQUIRE(sd, "schwz_ras_set_nonsym_solver: null subdomain");
+    SCHWZ_REQUIRE(which == SCHWZ_NONSYM_GMRES || which == SCHWZ_NONSYM_BICGSTAB,
+                  "schwz_ras_set_nonsym_solver: unknown solver");
+    REQUIRE_DEVICE(sd, "schwz_ras_set_nonsym_solver");
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !(sd->gmres || sd->bicg)) {
+        set_error("schwz_ras_set_nonsym_solver: the choice exists for the iterative local solver of a non-symmetric "
+                  "matrix only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (which == schwz_ras_nonsym_solver(sd)) return SCHWZ_OK;
+    // a solve still in flight must not lose its work vectors
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    // The preconditioner object (Jacobi diagonal, block inverses, ILU / ISAI factors, its partial-sum banks) is
+    // handed over: neither solver keeps state of a solve in it.  The new solver is created around it first, while
+    // the old one still owns it; a failure (no memory for the work vectors) leaves the subdomain as it was.
+    int rc;
+    if (which == SCHWZ_NONSYM_BICGSTAB) {
+        if ((rc = bicgstab_create_adopt(sd->A, gmres_precond(sd->gmres), &sd->bicg))) return rc;
+        (void)gmres_release_precond(sd->gmres);
+        schwz_gmres_destroy(sd->gmres);
+        sd->gmres = nullptr;
+        return SCHWZ_OK;
+    }
+    if ((rc = gmres_create_adopt(sd->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, bicgstab_precond(sd->bicg),
+                                 &sd->gmres)))
+        return rc;
+    (void)bicgstab_release_precond(sd->bicg);
+    schwz_bicgstab_destroy(sd->bicg);
+    sd->bicg = nullptr;
     return SCHWZ_OK;
 }
 

@@ -124,6 +124,10 @@ struct Metadata {
     // extension: "single" runs the iterative local solve as fp32 CG on the fp64 start residual, the correction
     // added in fp64 (schwz_ras_set_local_precision); CG without a preconditioner or with scalar Jacobi only
     std::string local_solver_precision = "double";
+    // extension: the Krylov method of the iterative local solve of a non-symmetric matrix: "gmres"
+    // (GMRES(restart_iter), the reference's) or "bicgstab" (schwz_ras_set_nonsym_solver); without
+    // non_symmetric_matrix or with a direct local solver it has no effect, like restart_iter
+    std::string non_symmetric_solver = "gmres";
     ValueType current_residual_norm = -1.0;
     ValueType min_residual_norm = -1.0;
 

@@ -264,6 +264,11 @@ void SchwarzBase<V, I, M>::initialize()
         throw ::NotImplemented(__FILE__, __LINE__,
                                "local_solver_precision 'single' with local_precond '" + m.local_precond +
                                    "' (available: null, block-jacobi with precond_max_block_size 1)");
+    // extension: BiCGSTAB as the iterative local solver of a non-symmetric matrix (schwz_ras_set_nonsym_solver)
+    if (m.non_symmetric_solver != "gmres" && m.non_symmetric_solver != "bicgstab")
+        throw ::BadDimension(__FILE__, __LINE__, "initialize", "non_symmetric_solver must be 'gmres' or 'bicgstab'");
+    const bool bicgstab_local = m.non_symmetric_solver == "bicgstab" && s.non_symmetric_matrix &&
+                                opt.local_solver == SCHWZ_SOLVER_ITERATIVE;
 
     // ---- Initialize::setup_global_matrix (initialization.cpp:197-272) ----------------------
     // extension: "--matrix_filename=poisson3d:NX[xNYxNZ]" or SCHWZ_LAPLACIAN_DIM=3 select the 3-D
@@ -416,6 +421,7 @@ void SchwarzBase<V, I, M>::initialize()
     for (size_t i = 0; i < rhs.size(); ++i) local_rhs->at(i) = (V)rhs[i];
     SCHWZ_CALL(schwz_subdomain_to_device(im.sd, rhs.data(), &opt));
     if (single_local) SCHWZ_CALL(schwz_ras_set_local_precision(im.sd, SCHWZ_PRECISION_F32));
+    if (bicgstab_local) SCHWZ_CALL(schwz_ras_set_nonsym_solver(im.sd, SCHWZ_NONSYM_BICGSTAB));
 
     im.f32_wire = s.use_mixed_precision && std::is_same<M, float>::value;
     const size_t nsend = (size_t)std::max<int64_t>(im.sizes[9], 1), nrecv = (size_t)std::max<int64_t>(im.sizes[8], 1);
@@ -536,7 +542,10 @@ void SchwarzBase<V, I, M>::initialize()
                   << m.local_size << " with overlap rows: " << m.overlap_size << std::endl;
         if (opt.local_solver == SCHWZ_SOLVER_ITERATIVE) {
             const long long lmi = m.local_max_iters == -1 ? (long long)m.local_size_x : (long long)m.local_max_iters;
-            std::cout << " Local max iters " << lmi << " with restart iter " << s.restart_iter << std::endl;
+            if (bicgstab_local)
+                std::cout << " Local max iters " << lmi << " (BiCGSTAB)" << std::endl;
+            else
+                std::cout << " Local max iters " << lmi << " with restart iter " << s.restart_iter << std::endl;
         } else {
             std::cout << " Local direct solve with HIP TRS" << std::endl;
         }

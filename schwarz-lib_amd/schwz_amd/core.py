@@ -150,6 +150,46 @@ class PcgF32:
         self.close()
 
 
+class Bicgstab:
+    """Device-resident BiCGSTAB, right preconditioned (schwz_bicgstab, an extension: the reference's non-symmetric
+    local solver is GMRES).  solve() returns (iterations, recurred residual norm); breakdown() the flag of the last
+    solve: 0 none, 1 rho = 0, 2 rhat.v = 0, 3 t.t = 0 or t.s = 0."""
+
+    def __init__(self, csr, precond=capi.PRECOND_NONE, block_size=1, par_ilu_sweeps=0, trisolve_sweeps=0):
+        self.csr = csr
+        h = C.c_void_p()
+        check(lib.schwz_bicgstab_create(csr.h, precond, block_size, int(par_ilu_sweeps), int(trisolve_sweeps),
+                                        C.byref(h)))
+        self.h = h
+
+    def solve(self, d_b, d_x, rtol, max_iters, stream=0, want_stats=True):
+        it = C.c_int(0)
+        rn = C.c_double(0.0)
+        check(lib.schwz_bicgstab_solve(self.h, ptr(d_b), ptr(d_x), rtol, max_iters,
+                                       C.byref(it) if want_stats else None,
+                                       C.byref(rn) if want_stats else None, _stream_arg(stream)))
+        return it.value, rn.value
+
+    def last_stats(self):
+        it, rn = C.c_int(0), C.c_double(0.0)
+        check(lib.schwz_bicgstab_last_stats(self.h, C.byref(it), C.byref(rn)))
+        return it.value, rn.value
+
+    def breakdown(self):
+        flag = int(lib.schwz_bicgstab_breakdown(self.h))
+        if flag < 0:   # the device state could not be read
+            check(capi.ERR_HIP)
+        return flag
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.schwz_bicgstab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class Gmres:
     """Device-resident restarted GMRES, right preconditioned (gko::solver::Gmres with
     krylov_dim = restart; solve.cpp:486-520)."""
@@ -668,6 +708,14 @@ class Subdomain:
 
     def local_precision(self):
         return int(lib.schwz_ras_local_precision(self.h))
+
+    def set_nonsym_solver(self, which):
+        """Krylov method of the iterative local solve of a non-symmetric matrix from the next solve on
+        (schwz_ras_set_nonsym_solver): capi.NONSYM_GMRES (what to_device creates) or capi.NONSYM_BICGSTAB."""
+        check(lib.schwz_ras_set_nonsym_solver(self.h, int(which)))
+
+    def nonsym_solver(self):
+        return int(lib.schwz_ras_nonsym_solver(self.h))
 
     def local_solve(self, stream=0, want_iters=False):
         it = C.c_int(0)

@@ -127,6 +127,12 @@ class Metadata:
     # fp64 start residual, the correction added in fp64 (schwz_pcg_f32); the outer iteration, which recomputes the
     # residual in fp64, is the refinement loop.  CG without a preconditioner or with block-jacobi of block size 1.
     local_solver_precision: str = "double"
+    # extension (no field of the reference's Metadata): the Krylov method of the iterative local solve when
+    # settings.non_symmetric_matrix is set: "gmres" (GMRES(restart_iter), the reference's) or "bicgstab"
+    # (schwz_bicgstab: two products and five vector passes per iteration, 8 work vectors; it stops on the RECURRED
+    # residual).  Without non_symmetric_matrix, or with a direct local solver, the field has no effect, like
+    # restart_iter; any other name is refused.
+    non_symmetric_solver: str = "gmres"
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
@@ -262,6 +268,19 @@ def _precision_code(settings, metadata):
                                        "local_solver_precision 'single' is implemented for local_precond 'null' and "
                                        "'block-jacobi' with precond_max_block_size 1 only")
     return capi.PRECISION_F32
+
+
+def _nonsym_solver_code(settings, metadata):
+    """capi.NONSYM_* of metadata.non_symmetric_solver.  The name is checked whatever the other settings are; it
+    selects BiCGSTAB only for the iterative local solver of a non-symmetric matrix.  Runs before any device call."""
+    name = getattr(metadata, "non_symmetric_solver", "gmres")
+    if name not in ("gmres", "bicgstab"):
+        raise capi.SchwzError(capi.ERR_INVALID,
+                              "non_symmetric_solver must be 'gmres' or 'bicgstab', not %r" % (name,))
+    if name == "bicgstab" and settings.non_symmetric_matrix \
+            and _local_solver_code(settings) == capi.SOLVER_ITERATIVE:
+        return capi.NONSYM_BICGSTAB
+    return capi.NONSYM_GMRES
 
 
 def _precond_name_code(metadata):
@@ -459,6 +478,7 @@ class SolverRAS:
         solver_code = _factor_solver_code(s, m)
         precond_code = _precond_code(m)
         precision_code = _precision_code(s, m)
+        nonsym_code = _nonsym_solver_code(s, m)
         if self._distributed_ingest():
             prob = self._ingest_distributed()
         else:
@@ -484,6 +504,8 @@ class SolverRAS:
                          non_symmetric=s.non_symmetric_matrix, restart_iter=s.restart_iter, **sweeps)
             if precision_code != capi.PRECISION_F64:  # (a backend without the setter keeps working in double)
                 sd.set_local_precision(precision_code)
+            if nonsym_code != capi.NONSYM_GMRES:  # (GMRES is what to_device creates: the setter is not called)
+                sd.set_nonsym_solver(nonsym_code)
             # use_mixed_precision (MixedValueType = float): halos travel as fp32
             self.send_buf[me] = be.empty(sd.num_send, s.use_mixed_precision)
             self.recv_buf[me] = be.empty(sd.num_recv, s.use_mixed_precision)
@@ -518,7 +540,10 @@ class SolverRAS:
                     (m.global_size, P, comm.rank, m.local_size, m.overlap_size))
         if solver_code == capi.SOLVER_ITERATIVE:
             lmi = m.local_size_x if m.local_max_iters == -1 else m.local_max_iters
-            self._print(" Local max iters %d with restart iter %d" % (lmi, s.restart_iter))
+            if nonsym_code == capi.NONSYM_BICGSTAB:
+                self._print(" Local max iters %d (BiCGSTAB)" % lmi)
+            else:
+                self._print(" Local max iters %d with restart iter %d" % (lmi, s.restart_iter))
         else:
             self._print(" Local direct solve with HIP TRS")
 
