@@ -244,6 +244,49 @@ int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, doub
 int schwz_bicgstab_last_stats(schwz_bicgstab *s, int *h_iters, double *h_resnorm);
 int schwz_bicgstab_breakdown(schwz_bicgstab *s);
 
+/* Chebyshev iteration for SPD matrices (an extension: the reference's symmetric local solver is CG only), device
+ * resident, one reduction-free launch per iteration (csrc/chebyshev.hip).  With M = I (SCHWZ_PRECOND_NONE) or
+ * M = diag(A) (SCHWZ_PRECOND_JACOBI), the spectrum of M^-1 A assumed in [lmin, lmax]:
+ *   theta = (lmax + lmin) / 2 ; delta = (lmax - lmin) / 2 ; sigma = theta / delta
+ *
+ *   r_0 = b - A x_0 ;  rho_0 = 1 / sigma ;  d_0 = (1 / theta) M^-1 r_0
+ *   for k = 0 ... m-1:
+ *       x_{k+1} = x_k + d_k
+ *       r_{k+1} = r_k - A d_k
+ *       rho_{k+1} = 1 / (2 sigma - rho_k)
+ *       d_{k+1} = (rho_{k+1} rho_k) d_k + (2 rho_{k+1} / delta) M^-1 r_{k+1}
+ *
+ * max_iters = m is the number of corrections applied, the polynomial degree.  The scalars are computed on the host in
+ * fp64, in exactly the order written above, and passed to the launches by value.  The iteration converges for any
+ * 0 < lmin < lmax as long as lmax really is an upper bound (eigenvalues below lmin are still damped, only more
+ * slowly); a lmax below the true one makes it DIVERGE.  At creation lmax is the Gershgorin bound
+ * max_i |1 / m_ii| sum_j |a_ij|, which is guaranteed, and lmin = lmax / 30, the conventional default eigenvalue ratio
+ * of Chebyshev smoothers (hypre, Ifpack2, PETSc): a default, not a measurement.  Better bounds are the caller's
+ * responsibility (schwz_cheb_set_bounds: 0 < lmin < lmax, both finite, else SCHWZ_ERR_INVALID; they take effect from
+ * the next solve).
+ * create: precond SCHWZ_PRECOND_NONE or SCHWZ_PRECOND_JACOBI; another known code: SCHWZ_ERR_NOT_IMPLEMENTED; an
+ * unknown code or a null `out`: SCHWZ_ERR_INVALID (both checked before the matrix is looked at).  With Jacobi a row
+ * whose diagonal is missing, zero, negative or not finite: SCHWZ_ERR_NOT_SPD.  The solver reads plain CSR, whatever
+ * coding the upload chose.
+ * solve, rtol <= 0 (fixed work): the start launch, m - 1 iteration launches and one vector launch, m matrix passes;
+ * the host polls nothing and no launch reads device state; m = 0 launches nothing and leaves x untouched.  The norm
+ * ||r_m|| costs one more matrix pass and is computed only when asked for (a non-NULL h_resnorm: on `stream`;
+ * schwz_cheb_last_stats: behind its device synchronisation), once; that pass stores nothing to x or the work
+ * vectors.  After max_iters = 0 without h_resnorm, last_stats reports a NaN norm (b and x are the caller's).
+ * solve, rtol > 0: ||r_k|| is looked at for k = 0 (mod SCHWZ_CHEB_CHECK_EVERY) and for k = m, and the solve returns
+ * x_k for the first such k with ||r_k|| <= rtol ||r_0|| or ||r_k|| = 0 (k = m if none): iterations are reported in
+ * {0, 8, 16, ..., m}.  A zero start residual means 0 iterations and x untouched.  h_resnorm is the recurred norm. */
+#define SCHWZ_CHEB_CHECK_EVERY 8
+typedef struct schwz_cheb schwz_cheb;
+int schwz_cheb_create(const schwz_csr *A, int precond, schwz_cheb **out);
+void schwz_cheb_destroy(schwz_cheb *s);
+int schwz_cheb_bounds(const schwz_cheb *s, double *lmin, double *lmax);
+int schwz_cheb_set_bounds(schwz_cheb *s, double lmin, double lmax);
+int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol, int max_iters,
+                     int *h_iters, double *h_resnorm, schwz_stream stream);
+/* iterations and residual norm of the last solve (device synchronisation) */
+int schwz_cheb_last_stats(schwz_cheb *s, int *h_iters, double *h_resnorm);
+
 /* Profiling hooks for bench.py's roofline leg: between begin and end, every
  * launch of the dominant kernel (the CSR SpMV inside schwz_pcg_solve) is
  * bracketed by a HIP event pair on its launch stream; end synchronises and
@@ -578,6 +621,25 @@ int schwz_ras_local_precision(const schwz_subdomain *sd);
 enum schwz_nonsym_solver { SCHWZ_NONSYM_GMRES = 0, SCHWZ_NONSYM_BICGSTAB = 1 };
 int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which);
 int schwz_ras_nonsym_solver(const schwz_subdomain *sd);
+
+/* Which method solves a symmetric local system iteratively (an extension; schwz_solver_options keeps its layout, so
+ * the choice travels through a setter, after schwz_subdomain_to_device; it takes effect from the next local solve).
+ * SCHWZ_SYM_CG is what the upload creates.  SCHWZ_SYM_CHEBYSHEV: the local solve is schwz_cheb_solve on (b~, y), the
+ * solver created on the local matrix at first use, with the bounds of schwz_cheb_create until
+ * schwz_ras_set_cheb_bounds replaces them; SCHWZ_ERR_NOT_IMPLEMENTED for a direct local solver, for non_symmetric,
+ * for a preconditioner other than none or scalar Jacobi (block-jacobi with block size 1 counts as Jacobi), for nonzero
+ * ParILU options and while SCHWZ_PRECISION_F32 is set (schwz_ras_set_local_precision refuses F32 the same way while
+ * Chebyshev is set).  While it is set schwz_ras_check_and_solve_launch runs its two steps back to back,
+ * schwz_ras_early_pack_ok, schwz_ras_cg_flavour and schwz_ras_y_form return 0, the restriction is the copy launch,
+ * schwz_ras_set_local_max_iters and schwz_ras_last_inner_stats work, and schwz_ras_algorithmic_bytes(sd, 1) prices
+ * the fused launch: 12 nnz + 4 (n + 1) + 56 n (48 n without Jacobi).  SCHWZ_SYM_CG restores the CG path exactly.
+ * The bounds calls return SCHWZ_ERR_INVALID before Chebyshev was first set.  The getter answers SCHWZ_SYM_CG for a
+ * null subdomain. */
+enum schwz_sym_solver { SCHWZ_SYM_CG = 0, SCHWZ_SYM_CHEBYSHEV = 1 };
+int schwz_ras_set_sym_solver(schwz_subdomain *sd, int which);
+int schwz_ras_sym_solver(const schwz_subdomain *sd);
+int schwz_ras_cheb_bounds(const schwz_subdomain *sd, double *lmin, double *lmax);
+int schwz_ras_set_cheb_bounds(schwz_subdomain *sd, double lmin, double lmax);
 /* settings.enable_logging (source/solve.cpp:751-771): inner iterations and final residual norm of the
  * last local solve (0 and 0.0 for the direct path).  Synchronises the solver's stream. */
 int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resnorm);

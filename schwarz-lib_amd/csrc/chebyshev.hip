@@ -1,0 +1,748 @@
+// Chebyshev local solve (schwz_cheb): the Jacobi-preconditioned Chebyshev iteration for SPD matrices, one
+// reduction-free launch per iteration.  An extension: the reference's symmetric local solver is CG only.
+//
+// For SPD A, with M = I or M = diag(A), the spectrum of M^-1 A assumed in [lmin, lmax]:
+//   theta = (lmax + lmin) / 2 ; delta = (lmax - lmin) / 2 ; sigma = theta / delta
+//
+//   r_0 = b - A x_0 ;  rho_0 = 1 / sigma ;  d_0 = (1 / theta) M^-1 r_0
+//   for k = 0 ... m-1:
+//       x_{k+1} = x_k + d_k
+//       r_{k+1} = r_k - A d_k
+//       rho_{k+1} = 1 / (2 sigma - rho_k)
+//       d_{k+1} = (rho_{k+1} rho_k) d_k + (2 rho_{k+1} / delta) M^-1 r_{k+1}
+//
+// max_iters = m is the number of corrections applied, the polynomial degree.  The scalars depend on the bounds and on
+// k alone: the host computes them in fp64, in exactly the order written above, and passes them to the launches by
+// value.  There is no inner product in the iteration, so there are no partial-sum banks to fold, no state struct to
+// read and ONE launch per iteration: launch k (k >= 1) gathers d_{k-1}, and at its own row i
+//   q_i = (A d)_i ;  r_i -= q_i ;  x_i += d_i ;  d'_i = a d_i + c dinv_i r_i   (d' stored to the other d buffer)
+// d ping-pongs because the launch gathers d from neighbouring rows while it produces d'; x and r are touched at the
+// lane's own row only and are updated in place.  Launch 0 (START) gathers x: r = b - A x, d_0 = (1/theta) dinv r.
+//
+// Fixed work (rtol <= 0): START, m - 1 iteration launches, one vector launch x += d_{m-1}: m matrix passes, no host
+// poll, no device state read.  ||r_m|| is computed only when somebody asks (h_resnorm, *_last_stats): one NORM-only
+// launch of ||r_{m-1} - A d_{m-1}||, which stores nothing but its partial sums.
+// With a tolerance: the launches that produce r_k for k = 0 (mod SCHWZ_CHEB_CHECK_EVERY) and for k = m also write one
+// fp64 partial sum of r_i^2 per workgroup, and every workgroup of the NEXT launch folds them itself in a fixed order
+// (fold_partials, as cg_f32.hip has it: no fence, no atomic, no ticket counter) and returns at once when
+// ||r_k|| <= rtol ||r_0|| or the norm is zero; workgroup 0 records the stop in ChebState for the launches behind it
+// and for the host, which polls one chunk behind as schwz_pcg_f32_solve does.
+//
+// The solver reads plain CSR, whatever coding the upload chose: on stencil matrices the fp64 z-sweep walk of CG moves
+// far fewer matrix bytes; there this solver is opt-in and expected to be slower per pass.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <vector>
+
+#include "schwz_internal.hpp"
+#include "device_utils.hpp"
+
+namespace schwz {
+
+constexpr int kChebSeq = 3;  // consecutive tiles per short-lived workgroup (spmv_stream.hip), more where the grid is capped
+
+struct ChebState {
+    double nu2;  // ||r_0||^2
+    double rr;   // ||r_iters||^2
+    int iters;
+    int stop_iter;  // INT_MAX while the solve runs
+};
+
+enum ChebForm {
+    kChebStart = 0,     // r = b - A x ; d' = c dinv r ; x untouched
+    kChebIter = 1,      // r -= A d ; x += d ; d' = a d + c dinv r
+    kChebNormOnly = 2,  // partial sums of ||b - A g||^2, nothing else stored
+};
+
+struct ChebArgs {
+    const double *g = nullptr;     // the gathered vector: d_{k-1}, or x (START)
+    const double *b = nullptr;     // START: the right-hand side; NORM-only: the vector A g is subtracted from
+    double *r = nullptr;           // residual, updated in place at the lane's own row
+    double *x = nullptr;           // iterate, updated in place at the lane's own row
+    double *dn = nullptr;          // d' (never the gathered buffer)
+    const double *dinv = nullptr;  // 1 / diag(A); null: M = I
+    double a = 0.0, c = 0.0;
+    double *part = nullptr;        // NORM forms: one partial sum of r_i^2 per workgroup
+    // with a tolerance only (st != null)
+    ChebState *st = nullptr;
+    const double *chk = nullptr;   // the partial sums of ||r_{k-1}||^2 where k - 1 is a checked iterate
+    int nchk = 0;
+    int k = 0;                     // the iterate this launch produces
+    double rtol = 0.0;
+    int seq = kChebSeq;
+};
+
+// Start of a launch of a solve with a tolerance; true: the workgroup leaves (uniform over the workgroup).
+// Launch k leaves when an earlier launch recorded a stop before k, or when iterate k - 1 was checked and passes.
+// Workgroup 0 records; workgroups that read stop_iter while it is being written see INT_MAX or k - 1 and decide the
+// same either way.
+__device__ __forceinline__ bool cheb_leaves(const ChebArgs &a, double *red)
+{
+    if (!a.st) return false;
+    if (a.st->stop_iter < a.k) return true;
+    if (!a.chk) return false;
+    const double rr = fold_partials(a.chk, a.nchk, red);
+    const double nu2 = a.k == 1 ? rr : a.st->nu2;
+    const bool stop = sqrt(rr) <= a.rtol * sqrt(nu2) || rr == 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (a.k == 1) a.st->nu2 = rr;
+        if (stop) {
+            a.st->rr = rr;
+            a.st->iters = a.k - 1;
+            a.st->stop_iter = a.k - 1;
+        }
+    }
+    return stop;
+}
+
+// The straight-line tile pipeline of spmv_stream_kernel (spmv_stream.hip): the same tiles, tile tables and XCD deal,
+// short-lived workgroups of `seq` consecutive tiles of their XCD's sequence, products staged in LDS, CAP masked adds
+// per row in CSR order, no branch in the tile loop but the one around the stores: a lane past the tile's last row
+// repeats that row's loads and arithmetic and stores nothing, because r and x are updated in place (a second store
+// of the same value would be harmless, a second load after another wave's store would not).
+template <int FORM, bool NORM, int CAP>
+__global__ __launch_bounds__(kBlock) void cheb_stream_kernel(CsrView A, ChebArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) double vals[kTileNnz + 4 + CAP];
+    __shared__ __attribute__((aligned(16))) int cols[kTileNnz + 4 + CAP];
+    __shared__ int rstart[kBlock + 1];
+    __shared__ double red[4];
+    if (FORM == kChebIter && cheb_leaves(a, red)) return;
+    const int tid = threadIdx.x;
+    if (FORM == kChebStart && a.st && blockIdx.x == 0 && tid == 0) {
+        a.st->nu2 = 0.0;
+        a.st->rr = 0.0;
+        a.st->iters = 0;
+        a.st->stop_iter = INT_MAX;
+    }
+    const int xcd = blockIdx.x % kXcds;
+    const int slot = blockIdx.x / kXcds;
+    typedef const int __attribute__((address_space(4))) *const_ints;
+    const const_ints sorder = (const_ints)(uintptr_t)A.stream_order;
+    const int nslots = sorder ? A.stream_nper : xcd_slots(A);
+    const int sh = A.xcd_shift;
+    auto tile_at = [&](int j) -> int {
+        if (sorder) {
+            const int t = sorder[(int64_t)xcd * A.stream_nper + j];
+            return t < 0 ? A.ntiles : t;
+        }
+        return ((j >> sh) << (sh + 3)) + (xcd << sh) + (j & (A.xcd_block - 1));
+    };
+    const int seq = a.seq;
+    auto slot_at = [&](int k) -> int { return slot * seq + k; };
+    int ntw = max(0, min(seq, nslots - slot * seq));
+    while (ntw > 0 && tile_at(slot_at(ntw - 1)) >= A.ntiles) --ntw;
+    // the masked reads of a tile's last rows may run up to CAP entries past the window: finite values, columns
+    // inside the gathered vector (never summed, but gathered)
+    if (tid < 4 + CAP) {
+        vals[kTileNnz + tid] = 0.0;
+        cols[kTileNnz + tid] = 0;
+    }
+    double acc = 0.0;
+    if (ntw > 0) {
+        const const_ints trow = (const_ints)(uintptr_t)A.tile_row;
+        const const_ints tnz = (const_ints)(uintptr_t)A.tile_nz;
+        struct Meta {
+            int r0, r1, s, e;
+        };
+        auto meta = [&](int k) -> Meta {
+            // beyond the workgroup's last tile: loaded (no branch in the loop), never computed
+            const int t = tile_at(slot_at(min(k, ntw - 1)));
+            const bool past = k >= ntw;
+            const int r0 = trow[t], s0 = tnz[t];
+            return Meta{r0, past ? r0 + 1 : trow[t + 1], s0, past ? s0 : tnz[t + 1]};
+        };
+        typedef int vi4 __attribute__((ext_vector_type(4)));
+        const double *const own = FORM == kChebIter ? (const double *)a.r : a.b;  // what A g is subtracted from
+        const double *const dinv = a.dinv ? a.dinv : own;  // a valid address either way (the value is selected away)
+#define SCHWZ_CHEB_ISSUE(M, P)                                                                       \
+    {                                                                                                \
+        const int s2_ = (M).s & ~3;                                                                  \
+        const int last_ = max(((M).e - 1) & ~3, s2_);                                                \
+        const int i0_ = min(s2_ + 4 * tid, last_), i1_ = min(s2_ + 4 * (tid + kBlock), last_);       \
+        P##v0 = *reinterpret_cast<const vd2 *>(A.val + i0_);                                         \
+        P##v1 = *reinterpret_cast<const vd2 *>(A.val + i0_ + 2);                                     \
+        P##c0 = *reinterpret_cast<const vi4 *>(A.col + i0_);                                         \
+        P##v2 = *reinterpret_cast<const vd2 *>(A.val + i1_);                                         \
+        P##v3 = *reinterpret_cast<const vd2 *>(A.val + i1_ + 2);                                     \
+        P##c1 = *reinterpret_cast<const vi4 *>(A.col + i1_);                                         \
+        const int rowc_ = min((M).r0 + tid, (M).r1 - 1);                                             \
+        P##b0 = A.rp[rowc_] - s2_;                                                                   \
+        P##o0 = own[rowc_];                                                                          \
+        P##o1 = P##o2 = P##o3 = 0.0;                                                                 \
+        if (FORM != kChebNormOnly) P##o1 = dinv[rowc_];                                              \
+        if (FORM == kChebIter) {                                                                     \
+            P##o2 = a.g[rowc_];                                                                      \
+            P##o3 = a.x[rowc_];                                                                      \
+        }                                                                                            \
+    }
+#define SCHWZ_CHEB_STEP(M, MN, P)                                                                    \
+    {                                                                                                \
+        const int b0 = P##b0;                                                                        \
+        const double o0 = P##o0, o1 = P##o1, o2 = P##o2, o3 = P##o3;                                 \
+        lds_barrier(); /* every lane is done with the previous tile's entries */                     \
+        rstart[tid] = b0;                                                                            \
+        *reinterpret_cast<vd2 *>(&vals[4 * tid]) = P##v0;                                            \
+        *reinterpret_cast<vd2 *>(&vals[4 * tid + 2]) = P##v1;                                        \
+        *reinterpret_cast<vi4 *>(&cols[4 * tid]) = P##c0;                                            \
+        *reinterpret_cast<vd2 *>(&vals[4 * (tid + kBlock)]) = P##v2;                                 \
+        *reinterpret_cast<vd2 *>(&vals[4 * (tid + kBlock) + 2]) = P##v3;                             \
+        *reinterpret_cast<vi4 *>(&cols[4 * (tid + kBlock)]) = P##c1;                                 \
+        lds_barrier();                                                                               \
+        const int b1 = (M).r0 + tid + 1 < (M).r1 ? rstart[tid + 1] : (M).e - ((M).s & ~3);          \
+        double sum = 0.0;                                                                            \
+        _Pragma("unroll") for (int j0 = 0; j0 < CAP; j0 += 8)                                        \
+        {                                                                                            \
+            double vv[8], xx[8];                                                                     \
+            int cc[8];                                                                               \
+            _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
+            {                                                                                        \
+                vv[j] = vals[b0 + j0 + j];                                                           \
+                cc[j] = cols[b0 + j0 + j];                                                           \
+            }                                                                                        \
+            _Pragma("unroll") for (int j = 0; j < 8; ++j) xx[j] = a.g[cc[j]];                        \
+            if (j0 == 0) {                                                                           \
+                __builtin_amdgcn_sched_barrier(0);                                                   \
+                SCHWZ_CHEB_ISSUE(MN, P)                                                              \
+                __builtin_amdgcn_sched_barrier(0);                                                   \
+            }                                                                                        \
+            _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
+            {                                                                                        \
+                const double pv = vv[j] * xx[j];                                                     \
+                sum += (b0 + j0 + j < b1) ? pv : 0.0;                                                \
+            }                                                                                        \
+        }                                                                                            \
+        const int rowc = min((M).r0 + tid, (M).r1 - 1);                                              \
+        const bool mine = (M).r0 + tid < (M).r1;                                                     \
+        const double rn = o0 - sum;                                                                  \
+        if (FORM != kChebNormOnly) {                                                                 \
+            const double z = a.dinv ? o1 * rn : rn;                                                  \
+            const double cz = a.c * z;                                                               \
+            const double dnew = FORM == kChebIter ? a.a * o2 + cz : cz;                              \
+            const double xn = o3 + o2;                                                               \
+            if (mine) {                                                                              \
+                a.r[rowc] = rn;                                                                      \
+                a.dn[rowc] = dnew;                                                                   \
+                if (FORM == kChebIter) a.x[rowc] = xn;                                               \
+            }                                                                                        \
+        }                                                                                            \
+        if (NORM) {                                                                                  \
+            const double t = rn * rn;                                                                \
+            acc += mine ? t : 0.0;                                                                   \
+        }                                                                                            \
+    }
+        vd2 Av0, Av1, Av2, Av3, Bv0, Bv1, Bv2, Bv3;
+        vi4 Ac0, Ac1, Bc0, Bc1;
+        int Ab0, Bb0;
+        double Ao0, Ao1, Ao2, Ao3, Bo0, Bo1, Bo2, Bo3;
+        Meta m0 = meta(0), m1 = meta(1);
+        SCHWZ_CHEB_ISSUE(m0, A)
+        SCHWZ_CHEB_ISSUE(m1, B)
+        Meta m2 = meta(2), m3 = meta(3);
+        int k = 0;
+        for (; k + 1 < ntw; k += 2) {
+            SCHWZ_CHEB_STEP(m0, m2, A)
+            SCHWZ_CHEB_STEP(m1, m3, B)
+            m0 = m2;
+            m1 = m3;
+            m2 = meta(k + 4);
+            m3 = meta(k + 5);
+        }
+        if (k < ntw) SCHWZ_CHEB_STEP(m0, m2, A)
+#undef SCHWZ_CHEB_STEP
+#undef SCHWZ_CHEB_ISSUE
+    }
+    if (NORM) {
+        const double s0 = block_sum(acc, red);
+        if (tid == 0) a.part[blockIdx.x] = s0;
+    }
+}
+
+// Every other matrix (a row longer than the largest CAP, a tile that does not fit the aligned window): one row per
+// lane, summed in CSR order, grid-stride, the same epilogues.  Built for correctness only.
+template <int FORM, bool NORM>
+__global__ __launch_bounds__(kBlock) void cheb_rows_kernel(CsrView A, ChebArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    if (FORM == kChebIter && cheb_leaves(a, red)) return;
+    if (FORM == kChebStart && a.st && blockIdx.x == 0 && threadIdx.x == 0) {
+        a.st->nu2 = 0.0;
+        a.st->rr = 0.0;
+        a.st->iters = 0;
+        a.st->stop_iter = INT_MAX;
+    }
+    const double *const own = FORM == kChebIter ? (const double *)a.r : a.b;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.nrows; i += stride) {
+        double sum = 0.0;
+        for (int j = A.rp[i]; j < A.rp[i + 1]; ++j) {
+            const double pv = A.val[j] * a.g[A.col[j]];
+            sum += pv;
+        }
+        const double rn = own[i] - sum;
+        if (FORM != kChebNormOnly) {
+            const double z = a.dinv ? a.dinv[i] * rn : rn;
+            const double cz = a.c * z;
+            if (FORM == kChebIter) {
+                const double di = a.g[i];
+                a.x[i] = a.x[i] + di;
+                a.dn[i] = a.a * di + cz;
+            } else {
+                a.dn[i] = cz;
+            }
+            a.r[i] = rn;
+        }
+        if (NORM) acc += rn * rn;
+    }
+    if (NORM) {
+        const double s0 = block_sum(acc, red);
+        if (threadIdx.x == 0) a.part[blockIdx.x] = s0;
+    }
+}
+
+// x += d: the last correction of a fixed-work solve
+__global__ __launch_bounds__(kBlock) void cheb_axpy_kernel(int64_t n, double *__restrict__ x, const double *__restrict__ d)
+{
+#pragma clang fp contract(off)
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) x[i] = x[i] + d[i];
+}
+
+// End of a solve with a tolerance (one workgroup): no stop so far, so iterate m stands; its norm from the partial sums
+__global__ __launch_bounds__(kBlock) void cheb_finish_kernel(ChebState *st, const double *part, int nparts, int m)
+{
+    __shared__ double red[4];
+    if (st->stop_iter != INT_MAX) return;
+    const double rr = fold_partials(part, nparts, red);
+    if (threadIdx.x == 0) {
+        st->rr = rr;
+        st->iters = m;
+        st->stop_iter = m;
+    }
+}
+
+// The lazy norm of a fixed-work solve (one workgroup): the partial sums of the NORM-only launch folded into the state
+__global__ __launch_bounds__(kBlock) void cheb_fold_kernel(ChebState *st, const double *part, int nparts)
+{
+    __shared__ double red[4];
+    const double rr = fold_partials(part, nparts, red);
+    if (threadIdx.x == 0) st->rr = rr;
+}
+
+// Gershgorin bound on M^-1 A: max_i |dinv_i| sum_j |a_ij|, the row sum in CSR order; the maximum over rows is
+// order-independent, hence deterministic (a NaN sticks).  With dinv != null: dinv_i = 1 / a_ii, and the smallest row
+// whose diagonal is missing, zero, negative or not finite in pbad (LLONG_MAX: none).  One slot per workgroup.
+__global__ __launch_bounds__(kBlock) void cheb_bound_kernel(CsrView A, double *__restrict__ dinv, double *__restrict__ pmax,
+                                                            long long *__restrict__ pbad)
+{
+#pragma clang fp contract(off)
+    __shared__ double smax[4];
+    __shared__ long long sbad[4];
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    double m = 0.0;
+    long long bad = LLONG_MAX;
+    auto take = [](double cur, double v) -> double { return (v > cur || v != v) ? v : cur; };
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.nrows; i += stride) {
+        double s = 0.0, dg = 0.0;
+        bool has = false;
+        for (int j = A.rp[i]; j < A.rp[i + 1]; ++j) {
+            const double v = A.val[j];
+            s += fabs(v);
+            if (A.col[j] == i) {
+                dg = v;
+                has = true;
+            }
+        }
+        double di = 1.0;
+        if (dinv) {
+            if (!has || !(dg > 0.0) || !isfinite(dg))
+                bad = min(bad, (long long)i);
+            else
+                di = 1.0 / dg;
+            dinv[i] = di;
+        }
+        m = take(m, fabs(di) * s);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        m = take(m, __shfl_down(m, off, 64));
+        bad = min(bad, (long long)__shfl_down(bad, off, 64));
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+        smax[w] = m;
+        sbad[w] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        pmax[blockIdx.x] = take(take(smax[0], smax[1]), take(smax[2], smax[3]));
+        pbad[blockIdx.x] = min(min(sbad[0], sbad[1]), min(sbad[2], sbad[3]));
+    }
+}
+
+}  // namespace schwz
+
+using namespace schwz;
+
+struct schwz_cheb {
+    const schwz_csr *A = nullptr;
+    int precond = 0;
+    int64_t n = 0;
+    double lmin = 0.0, lmax = 0.0;
+    double *r = nullptr, *d[2] = {nullptr, nullptr}, *dinv = nullptr;
+    double *part = nullptr;  // 2 banks of kMaxGrid partial sums: the NORM launches alternate
+    ChebState *state = nullptr;
+    ChebState *h_state = nullptr;  // pinned, 2 slots
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool stream_ok = false;  // the tile pipeline takes the matrix
+    int gs = 0, gv = 0;      // grids of the matrix launches and of the vector launch, both <= kMaxGrid
+    int seq = kChebSeq;
+    // the last solve
+    bool fixed = false;      // fixed work: iters and norm are the host's (last_iters, last_rr), not the state's
+    int last_iters = 0;
+    bool norm_pending = false;  // fixed work: ||r_m|| not computed yet
+    int norm_d = 0;             // ... from r and d[norm_d]
+    double last_rr = 0.0;       // ||r_m||^2 once computed (NaN: never computable, max_iters = 0 and nobody asked)
+};
+
+template <int FORM, bool NORM>
+static void cheb_launch_form(const schwz_cheb *s, const ChebArgs &a, hipStream_t st)
+{
+    const CsrView &A = s->A->v;
+    if (s->stream_ok) {
+        if (A.stream_cap <= 8)
+            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, 8>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
+        else if (A.stream_cap <= 16)
+            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, 16>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
+        else
+            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, 32>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
+    } else {
+        hipLaunchKernelGGL((cheb_rows_kernel<FORM, NORM>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
+    }
+}
+
+static void cheb_launch(const schwz_cheb *s, int form, bool norm, const ChebArgs &a, hipStream_t st)
+{
+    if (form == kChebStart) {
+        if (norm)
+            cheb_launch_form<kChebStart, true>(s, a, st);
+        else
+            cheb_launch_form<kChebStart, false>(s, a, st);
+    } else if (form == kChebIter) {
+        if (norm)
+            cheb_launch_form<kChebIter, true>(s, a, st);
+        else
+            cheb_launch_form<kChebIter, false>(s, a, st);
+    } else {
+        cheb_launch_form<kChebNormOnly, true>(s, a, st);
+    }
+}
+
+static int cheb_build(schwz_cheb *s)
+{
+    const CsrView &A = s->A->v;
+    const int64_t n = s->n;
+    const size_t nb = (size_t)(n ? n : 1) * sizeof(double);
+    // Every grid holds at most kMaxGrid workgroups, so that the workgroups of the next launch can fold its partial
+    // sums themselves.  Row-per-lane kernels (fallback, vector launch, bound): one row per lane up to
+    // kBlock * kMaxGrid = 524 288 rows, grid-stride beyond.  Tile pipeline: short-lived workgroups of kChebSeq
+    // consecutive tiles while such a grid fits (6144 tiles, about 1.5 M rows), longer runs of tiles beyond.
+    s->gv = grid_for(n);
+    s->stream_ok = A.stream_cap != 0 && A.tile_nz && !A.tile_order;
+    if (s->stream_ok) {
+        const int sh = A.xcd_shift;
+        const int nslots = A.stream_order ? A.stream_nper : ((A.ntiles + (kXcds << sh) - 1) >> (sh + 3)) << sh;
+        const int per_xcd = kMaxGrid / kXcds;
+        s->seq = std::max(kChebSeq, (nslots + per_xcd - 1) / per_xcd);
+        s->gs = kXcds * std::max(1, (nslots + s->seq - 1) / s->seq);
+    } else {
+        s->gs = grid_for(n);
+    }
+    for (double **v : {&s->r, &s->d[0], &s->d[1]}) {
+        SCHWZ_HIP_TRY(hipMalloc((void **)v, nb));
+        SCHWZ_HIP_TRY(hipMemset(*v, 0, nb));
+    }
+    SCHWZ_HIP_TRY(hipMalloc((void **)&s->part, (size_t)2 * kMaxGrid * sizeof(double)));
+    SCHWZ_HIP_TRY(hipMemset(s->part, 0, (size_t)2 * kMaxGrid * sizeof(double)));
+    SCHWZ_HIP_TRY(hipMalloc((void **)&s->state, sizeof(ChebState)));
+    SCHWZ_HIP_TRY(hipMemset(s->state, 0, sizeof(ChebState)));
+    SCHWZ_HIP_TRY(hipHostMalloc((void **)&s->h_state, 2 * sizeof(ChebState), hipHostMallocDefault));
+    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
+    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
+    if (s->precond == SCHWZ_PRECOND_JACOBI) {
+        SCHWZ_HIP_TRY(hipMalloc((void **)&s->dinv, nb));
+        SCHWZ_HIP_TRY(hipMemset(s->dinv, 0, nb));
+    }
+    if (n == 0) {
+        s->lmax = 1.0;
+        s->lmin = s->lmax / 30.0;
+        return SCHWZ_OK;
+    }
+    // the bound (and 1 / diag): one slot per workgroup, the maximum taken here
+    const int g = s->gv;
+    long long *d_bad = nullptr;
+    SCHWZ_HIP_TRY(hipMalloc((void **)&d_bad, (size_t)g * sizeof(long long)));
+    std::vector<double> h_max((size_t)g);
+    std::vector<long long> h_bad((size_t)g);
+    hipLaunchKernelGGL(cheb_bound_kernel, dim3(g), dim3(kBlock), 0, 0, A, s->dinv, s->part, d_bad);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpy(h_max.data(), s->part, (size_t)g * sizeof(double), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(h_bad.data(), d_bad, (size_t)g * sizeof(long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d_bad);
+    SCHWZ_HIP_TRY(err);
+    long long bad = LLONG_MAX;
+    double lmax = 0.0;
+    for (int i = 0; i < g; ++i) {
+        bad = std::min(bad, h_bad[(size_t)i]);
+        const double v = h_max[(size_t)i];
+        lmax = (v > lmax || v != v) ? v : lmax;
+    }
+    if (bad != LLONG_MAX) {
+        char msg[200];
+        std::snprintf(msg, sizeof(msg),
+                      "schwz_cheb_create: row %lld has no positive finite diagonal entry (Jacobi needs one)", bad);
+        set_error(msg);
+        return SCHWZ_ERR_NOT_SPD;
+    }
+    if (!(lmax > 0.0) || !std::isfinite(lmax)) {
+        set_error("schwz_cheb_create: the Gershgorin bound of the matrix is not a positive finite number");
+        return SCHWZ_ERR_NOT_SPD;
+    }
+    s->lmax = lmax;
+    s->lmin = lmax / 30.0;
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    return SCHWZ_OK;
+}
+
+// ||b - A g|| of a fixed-work solve, by one NORM-only launch on `st`; synchronises `st`
+static int cheb_norm_now(schwz_cheb *s, const double *own, const double *g, hipStream_t st)
+{
+    ChebArgs a;
+    a.g = g;
+    a.b = own;
+    a.part = s->part;
+    a.seq = s->seq;
+    cheb_launch(s, kChebNormOnly, true, a, st);
+    hipLaunchKernelGGL(cheb_fold_kernel, dim3(1), dim3(kBlock), 0, st, s->state, (const double *)s->part, s->gs);
+    SCHWZ_HIP_TRY(hipGetLastError());
+    SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(ChebState), hipMemcpyDeviceToHost, st));
+    SCHWZ_HIP_TRY(hipStreamSynchronize(st));
+    s->last_rr = s->h_state[0].rr;
+    s->norm_pending = false;
+    return SCHWZ_OK;
+}
+
+extern "C" {
+
+int schwz_cheb_create(const schwz_csr *A, int precond, schwz_cheb **out)
+{
+    // the argument checks come before the matrix is looked at (they need no device)
+    SCHWZ_REQUIRE(out, "schwz_cheb_create: null output");
+    *out = nullptr;
+    SCHWZ_REQUIRE(precond >= SCHWZ_PRECOND_NONE && precond <= SCHWZ_PRECOND_ISAI,
+                  "schwz_cheb_create: unknown preconditioner");
+    if (precond != SCHWZ_PRECOND_NONE && precond != SCHWZ_PRECOND_JACOBI) {
+        set_error("schwz_cheb_create: the Chebyshev local solve exists without a preconditioner and with scalar Jacobi only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    SCHWZ_REQUIRE(A, "schwz_cheb_create: null matrix");
+    SCHWZ_REQUIRE(A->v.nrows == A->v.ncols, "schwz_cheb_create: matrix not square");
+    schwz_cheb *s = new schwz_cheb();
+    s->A = A;
+    s->precond = precond;
+    s->n = A->v.nrows;
+    const int rc = cheb_build(s);
+    if (rc) {
+        schwz_cheb_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return SCHWZ_OK;
+}
+
+void schwz_cheb_destroy(schwz_cheb *s)
+{
+    if (!s) return;
+    for (void *ptr : {(void *)s->r, (void *)s->d[0], (void *)s->d[1], (void *)s->dinv, (void *)s->part, (void *)s->state})
+        (void)hipFree(ptr);
+    if (s->h_state) (void)hipHostFree(s->h_state);
+    if (s->ev[0]) (void)hipEventDestroy(s->ev[0]);
+    if (s->ev[1]) (void)hipEventDestroy(s->ev[1]);
+    delete s;
+}
+
+int schwz_cheb_bounds(const schwz_cheb *s, double *lmin, double *lmax)
+{
+    SCHWZ_REQUIRE(s && lmin && lmax, "schwz_cheb_bounds: null argument");
+    *lmin = s->lmin;
+    *lmax = s->lmax;
+    return SCHWZ_OK;
+}
+
+int schwz_cheb_set_bounds(schwz_cheb *s, double lmin, double lmax)
+{
+    // (the values are checked first: they need no solver)
+    SCHWZ_REQUIRE(std::isfinite(lmin) && std::isfinite(lmax) && lmin > 0.0 && lmin < lmax,
+                  "schwz_cheb_set_bounds: the bounds must be finite with 0 < lmin < lmax");
+    SCHWZ_REQUIRE(s, "schwz_cheb_set_bounds: null solver");
+    s->lmin = lmin;
+    s->lmax = lmax;
+    return SCHWZ_OK;
+}
+
+int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol, int max_iters, int *h_iters,
+                     double *h_resnorm, schwz_stream stream)
+{
+    SCHWZ_REQUIRE(s && d_b && d_x, "schwz_cheb_solve: null argument");
+    SCHWZ_REQUIRE(max_iters >= 0, "schwz_cheb_solve: negative max_iters");
+    hipStream_t st = (hipStream_t)stream;
+    const int m = max_iters;
+    s->fixed = true;
+    s->last_iters = 0;
+    s->norm_pending = false;
+    s->last_rr = 0.0;
+    if (s->n == 0) {
+        if (h_iters) *h_iters = 0;
+        if (h_resnorm) *h_resnorm = 0.0;
+        return SCHWZ_OK;
+    }
+    if (m == 0) {
+        // nothing is launched and x keeps its bits; the norm of b - A x only for a caller that asks now
+        s->last_rr = std::numeric_limits<double>::quiet_NaN();
+        if (h_resnorm) {
+            const int rc = cheb_norm_now(s, d_b, d_x, st);
+            if (rc) return rc;
+            *h_resnorm = std::sqrt(s->last_rr);
+        }
+        if (h_iters) *h_iters = 0;
+        return SCHWZ_OK;
+    }
+    // the scalars, in fp64 and in the order of the header
+    const double theta = (s->lmax + s->lmin) / 2.0;
+    const double delta = (s->lmax - s->lmin) / 2.0;
+    const double sigma = theta / delta;
+    double rho = 1.0 / sigma;
+    const bool tol = rtol > 0.0;
+    ChebArgs a;
+    a.dinv = s->dinv;
+    a.r = s->r;
+    a.x = d_x;
+    a.seq = s->seq;
+    a.rtol = rtol;
+    a.st = tol ? s->state : nullptr;
+    a.nchk = s->gs;
+    // START: r_0 = b - A x_0, d_0 = (1 / theta) M^-1 r_0
+    int cur = 0;
+    a.g = d_x;
+    a.b = d_b;
+    a.dn = s->d[0];
+    a.c = 1.0 / theta;
+    a.k = 0;
+    a.part = s->part;
+    cheb_launch(s, kChebStart, tol, a, st);
+    SCHWZ_HIP_TRY(hipGetLastError());
+    auto advance = [&]() {  // the scalars of the launch that produces d_{k+1} from d_k
+        const double rho_next = 1.0 / (2.0 * sigma - rho);
+        a.a = rho_next * rho;
+        a.c = 2.0 * rho_next / delta;
+        rho = rho_next;
+    };
+    if (!tol) {
+        for (int k = 1; k < m; ++k) {
+            advance();
+            a.g = s->d[cur];
+            a.dn = s->d[cur ^ 1];
+            a.k = k;
+            cheb_launch(s, kChebIter, false, a, st);
+            cur ^= 1;
+        }
+        hipLaunchKernelGGL(cheb_axpy_kernel, dim3(s->gv), dim3(kBlock), 0, st, s->n, d_x, (const double *)s->d[cur]);
+        SCHWZ_HIP_TRY(hipGetLastError());
+        s->last_iters = m;
+        s->norm_pending = true;
+        s->norm_d = cur;
+        if (h_resnorm) {
+            const int rc = cheb_norm_now(s, s->r, s->d[cur], st);  // on the asking call's stream
+            if (rc) return rc;
+            *h_resnorm = std::sqrt(s->last_rr);
+        }
+        if (h_iters) *h_iters = m;
+        return SCHWZ_OK;
+    }
+    // With a tolerance: launch k = 1 ... m produces iterate k; it checks iterate k - 1 where that one left its norm,
+    // and leaves its own where k = 0 (mod SCHWZ_CHEB_CHECK_EVERY) or k = m.  The host control flow is that of
+    // schwz_pcg_f32_solve: chunks of 16, 32, then 64 launches and a poll of the pinned state copy one chunk behind;
+    // launches past the stop return at once.
+    s->fixed = false;
+    int chunk = 16, k = 1, pending = -1, bank = 0, nb = 0;
+    bool prev_norm = true, stopped = false;
+    while (k <= m && !stopped) {
+        const int end = (k - 1 + chunk < m) ? k - 1 + chunk : m;
+        for (; k <= end; ++k) {
+            advance();
+            const bool norm = (k % SCHWZ_CHEB_CHECK_EVERY) == 0 || k == m;
+            a.g = s->d[cur];
+            a.dn = s->d[cur ^ 1];
+            a.k = k;
+            a.chk = prev_norm ? s->part + (size_t)nb * kMaxGrid : nullptr;
+            a.part = s->part + (size_t)(nb ^ 1) * kMaxGrid;
+            cheb_launch(s, kChebIter, norm, a, st);
+            if (norm) nb ^= 1;
+            prev_norm = norm;
+            cur ^= 1;
+        }
+        SCHWZ_HIP_TRY(hipGetLastError());
+        if (k <= m) {
+            if (pending >= 0) {
+                SCHWZ_HIP_TRY(hipEventSynchronize(s->ev[pending]));
+                if (s->h_state[pending].stop_iter != INT_MAX) stopped = true;
+            }
+            SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[bank], s->state, sizeof(ChebState), hipMemcpyDeviceToHost, st));
+            SCHWZ_HIP_TRY(hipEventRecord(s->ev[bank], st));
+            pending = bank;
+            bank ^= 1;
+            if (chunk < 64) chunk *= 2;
+        }
+    }
+    // (after a stop the host may have ended between two norm launches: the finish kernel then leaves at once)
+    hipLaunchKernelGGL(cheb_finish_kernel, dim3(1), dim3(kBlock), 0, st, s->state,
+                       (const double *)(s->part + (size_t)nb * kMaxGrid), s->gs, m);
+    SCHWZ_HIP_TRY(hipGetLastError());
+    if (h_iters || h_resnorm) {
+        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(ChebState), hipMemcpyDeviceToHost, st));
+        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
+        if (h_iters) *h_iters = s->h_state[0].iters;
+        if (h_resnorm) *h_resnorm = std::sqrt(s->h_state[0].rr);
+    }
+    return SCHWZ_OK;
+}
+
+int schwz_cheb_last_stats(schwz_cheb *s, int *h_iters, double *h_resnorm)
+{
+    SCHWZ_REQUIRE(s && h_iters && h_resnorm, "schwz_cheb_last_stats: null argument");
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    if (s->fixed) {
+        // the lazy norm runs behind the synchronisation above, on the null stream: never on a saved stream handle
+        if (s->norm_pending) {
+            const int rc = cheb_norm_now(s, s->r, s->d[s->norm_d], nullptr);
+            if (rc) return rc;
+        }
+        *h_iters = s->last_iters;
+        *h_resnorm = std::sqrt(s->last_rr);
+        return SCHWZ_OK;
+    }
+    SCHWZ_HIP_TRY(hipMemcpy(&s->h_state[0], s->state, sizeof(ChebState), hipMemcpyDeviceToHost));
+    *h_iters = s->h_state[0].iters;
+    *h_resnorm = std::sqrt(s->h_state[0].rr);
+    return SCHWZ_OK;
+}
+
+}  // extern "C"

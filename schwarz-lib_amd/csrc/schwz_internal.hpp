@@ -748,6 +748,7 @@ struct schwz_problem {
 };
 
 struct schwz_pcg_f32;  // cg_f32.hip
+struct schwz_cheb;     // chebyshev.hip
 
 struct schwz_subdomain {
     // ---- host index sets -------------------------------------------------
@@ -785,6 +786,10 @@ struct schwz_subdomain {
     // `precision` is SCHWZ_PRECISION_F32; `cg` stays what it is, so that F64 restores the fp64 path exactly
     schwz_pcg_f32 *cg32 = nullptr;
     int precision = 0;
+    // Chebyshev local solve (schwz_ras_set_sym_solver, csrc/chebyshev.hip): created at first use, used while
+    // `sym_solver` is SCHWZ_SYM_CHEBYSHEV; `cg` stays what it is, so that SCHWZ_SYM_CG restores the CG path exactly
+    schwz_cheb *cheb = nullptr;
+    int sym_solver = 0;
     schwz_trs *trs = nullptr;
     // interface rows: only overlap rows are non-empty; stored compactly
     schwz_idx *d_i_rp = nullptr, *d_i_col = nullptr;  // cols index x~ directly

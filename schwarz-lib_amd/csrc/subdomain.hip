@@ -54,6 +54,7 @@ static bool want_unified(schwz_subdomain *sd)
     const char *e = std::getenv("SCHWZ_RESTRICT_FUSE");
     if (e && e[0] == '0') return false;
     if (sd->precision == SCHWZ_PRECISION_F32) return false;  // the fp32 solver updates y in place
+    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return false;  // so does the Chebyshev solver
     return sd->cg && sd->overlap_size == 0 && sd->halo_size == 0 && sd->local_size > 0 && !sd->cg->prio_on &&
            pcg_defers_x(sd->cg);
 }
@@ -108,6 +109,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
     if (sd->on_device) {
         schwz_pcg_destroy(sd->cg);
         schwz_pcg_f32_destroy(sd->cg32);
+        schwz_cheb_destroy(sd->cheb);
         schwz_gmres_destroy(sd->gmres);
         schwz_bicgstab_destroy(sd->bicg);
         schwz_trs_destroy(sd->trs);
@@ -310,6 +312,7 @@ int schwz_ras_unpack_f32(schwz_subdomain *sd, const float *d_recv, schwz_stream 
 int schwz_ras_early_pack_ok(const schwz_subdomain *sd)
 {
     if (sd && sd->precision == SCHWZ_PRECISION_F32) return 0;  // the fp32 solver records no boundary event
+    if (sd && sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return 0;  // nor does the Chebyshev solver
     return sd && sd->on_device && sd->cg && sd->cg->prio_on && sd->cg->prio_event ? 1 : 0;
 }
 
@@ -513,6 +516,7 @@ int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resn
     *h_resnorm = 0.0;
     if (sd->local_size_x == 0) return SCHWZ_OK;
     if (sd->precision == SCHWZ_PRECISION_F32) return schwz_pcg_f32_last_stats(sd->cg32, h_iters, h_resnorm);
+    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return schwz_cheb_last_stats(sd->cheb, h_iters, h_resnorm);
     if (sd->cg) return pcg_last_stats(sd->cg, h_iters, h_resnorm);
     if (sd->gmres) return schwz_gmres_last_stats(sd->gmres, h_iters, h_resnorm);
     if (sd->bicg) return schwz_bicgstab_last_stats(sd->bicg, h_iters, h_resnorm);
@@ -564,6 +568,13 @@ int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream 
         return schwz_pcg_f32_solve(sd->cg32, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
                                    stream);
     }
+    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) {
+        // separate form (want_unified), y updated in place; the restriction is the copy launch
+        sd->cg->x2_out = nullptr;
+        sd->cg->x2_written = false;
+        sd->y_ahead = true;
+        return schwz_cheb_solve(sd->cheb, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr, stream);
+    }
     if (sd->unified) {
         // state A: out of place, d_x -> d_x_alt; state B: in place on d_x_alt
         sd->cg->x2_out = nullptr;
@@ -585,7 +596,7 @@ int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = sd->local_size_x;
     if (n == 0) return SCHWZ_OK;
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || sd->bicg || sd->precision == SCHWZ_PRECISION_F32 || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || sd->bicg || sd->precision == SCHWZ_PRECISION_F32 || sd->sym_solver == SCHWZ_SYM_CHEBYSHEV || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
         // no fused kernel for this configuration: the two steps back to back
         int rc = schwz_ras_local_residual_launch(sd, stream);
         if (rc) return rc;
@@ -683,7 +694,7 @@ int schwz_ras_y_form(const schwz_subdomain *sd) { return sd && sd->on_device && 
 
 int schwz_ras_cg_flavour(const schwz_subdomain *sd)
 {
-    if (sd && sd->precision == SCHWZ_PRECISION_F32) return 0;
+    if (sd && (sd->precision == SCHWZ_PRECISION_F32 || sd->sym_solver == SCHWZ_SYM_CHEBYSHEV)) return 0;
     return sd && sd->cg ? schwz_pcg_flavour(sd->cg) : 0;
 }
 
@@ -706,6 +717,10 @@ int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
                   "matrix (CG) without a preconditioner or with scalar Jacobi only");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
+    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) {
+        set_error("schwz_ras_set_local_precision: the Chebyshev local solve has no fp32 form");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
     if (!sd->cg32) {
         const int rc = schwz_pcg_f32_create(sd->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, &sd->cg32);
         if (rc) return rc;
@@ -718,6 +733,55 @@ int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
     if (rc) return rc;
     SCHWZ_HIP_TRY(hipDeviceSynchronize());
     return SCHWZ_OK;
+}
+
+int schwz_ras_sym_solver(const schwz_subdomain *sd) { return sd ? sd->sym_solver : SCHWZ_SYM_CG; }
+
+int schwz_ras_set_sym_solver(schwz_subdomain *sd, int which)
+{
+    SCHWZ_REQUIRE(sd, "schwz_ras_set_sym_solver: null subdomain");
+    SCHWZ_REQUIRE(which == SCHWZ_SYM_CG || which == SCHWZ_SYM_CHEBYSHEV, "schwz_ras_set_sym_solver: unknown solver");
+    REQUIRE_DEVICE(sd, "schwz_ras_set_sym_solver");
+    if (which == SCHWZ_SYM_CG) {
+        sd->sym_solver = which;  // (the next solve chooses its form again: choose_form)
+        return SCHWZ_OK;
+    }
+    const schwz_solver_options &o = sd->opt;
+    const bool jacobi = o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1);
+    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->cg ||
+        !(o.precond == SCHWZ_PRECOND_NONE || jacobi) || o.par_ilu_sweeps != 0 || o.trisolve_sweeps != 0) {
+        set_error("schwz_ras_set_sym_solver: the Chebyshev local solve exists for the iterative solver of a symmetric "
+                  "matrix without a preconditioner or with scalar Jacobi only (no ParILU options)");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (sd->precision == SCHWZ_PRECISION_F32) {
+        set_error("schwz_ras_set_sym_solver: the Chebyshev local solve has no fp32 form (SCHWZ_PRECISION_F32 is set)");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (!sd->cheb) {
+        const int rc = schwz_cheb_create(sd->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, &sd->cheb);
+        if (rc) return rc;
+    }
+    // a solve still in flight on a stream the null stream does not wait for must not race with the copy below
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    sd->sym_solver = which;
+    // y gets a vector of its own now (schwz_ras_y_form answers 0 from here on)
+    const int rc = choose_form(sd, nullptr);
+    if (rc) return rc;
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    return SCHWZ_OK;
+}
+
+int schwz_ras_cheb_bounds(const schwz_subdomain *sd, double *lmin, double *lmax)
+{
+    SCHWZ_REQUIRE(sd && sd->cheb, "schwz_ras_cheb_bounds: the subdomain has no Chebyshev solver (schwz_ras_set_sym_solver)");
+    return schwz_cheb_bounds(sd->cheb, lmin, lmax);
+}
+
+int schwz_ras_set_cheb_bounds(schwz_subdomain *sd, double lmin, double lmax)
+{
+    SCHWZ_REQUIRE(sd && sd->cheb, "schwz_ras_set_cheb_bounds: the subdomain has no Chebyshev solver (schwz_ras_set_sym_solver)");
+    return schwz_cheb_set_bounds(sd->cheb, lmin, lmax);
 }
 
 int schwz_ras_nonsym_solver(const schwz_subdomain *sd) { return sd && sd->bicg ? SCHWZ_NONSYM_BICGSTAB : SCHWZ_NONSYM_GMRES; }
@@ -776,6 +840,10 @@ int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which)
     // the fp32 iteration (cg_f32.hip): 8 B per nonzero, p gathered and q stored in fp32, then e, r read and written,
     // p, q, 1/diag read (update launch) and p read and written, r, 1/diag read (direction launch): 44 B per row
     if (which == 1 && sd->precision == SCHWZ_PRECISION_F32) return 8 * nnz + 4 * (n + 1) + 8 * n + 44 * n;
+    // the fused Chebyshev launch (chebyshev.hip): the CSR stream, then per row d read and d' written, r and x read and
+    // written, 1/diag read with Jacobi
+    if (which == 1 && sd->sym_solver == SCHWZ_SYM_CHEBYSHEV)
+        return 12 * nnz + 4 * (n + 1) + (sd->opt.precond == SCHWZ_PRECOND_NONE ? 48 : 56) * n;
     return which == 0 ? spmv : spmv + 136 * n;
 }
 

@@ -128,6 +128,16 @@ struct Metadata {
     // (GMRES(restart_iter), the reference's) or "bicgstab" (schwz_ras_set_nonsym_solver); without
     // non_symmetric_matrix or with a direct local solver it has no effect, like restart_iter
     std::string non_symmetric_solver = "gmres";
+    // extension: the method of the iterative local solve of a symmetric matrix: "cg" (the reference's) or "chebyshev"
+    // (schwz_ras_set_sym_solver: local_precond null or block-jacobi of block size 1, double precision); with
+    // non_symmetric_matrix or a direct local solver it has no effect, like restart_iter.  Bounds on the spectrum of
+    // M^-1 A: 0 means automatic (lambda_max: the Gershgorin bound of the local matrix, lambda_min: lambda_max /
+    // chebyshev_eig_ratio), explicit values override either end.  Beyond the defaults the bounds are the user's
+    // responsibility: a lambda_max below the true one makes the local iteration diverge.
+    std::string symmetric_solver = "cg";
+    double chebyshev_eig_ratio = 30.0;
+    double chebyshev_lambda_min = 0.0;
+    double chebyshev_lambda_max = 0.0;
     ValueType current_residual_norm = -1.0;
     ValueType min_residual_norm = -1.0;
 

@@ -269,6 +269,29 @@ void SchwarzBase<V, I, M>::initialize()
         throw ::BadDimension(__FILE__, __LINE__, "initialize", "non_symmetric_solver must be 'gmres' or 'bicgstab'");
     const bool bicgstab_local = m.non_symmetric_solver == "bicgstab" && s.non_symmetric_matrix &&
                                 opt.local_solver == SCHWZ_SOLVER_ITERATIVE;
+    // extension: Chebyshev as the iterative local solver of a symmetric matrix (schwz_ras_set_sym_solver)
+    if (m.symmetric_solver != "cg" && m.symmetric_solver != "chebyshev")
+        throw ::BadDimension(__FILE__, __LINE__, "initialize", "symmetric_solver must be 'cg' or 'chebyshev'");
+    const bool cheb_local = m.symmetric_solver == "chebyshev" && !s.non_symmetric_matrix &&
+                            opt.local_solver == SCHWZ_SOLVER_ITERATIVE;
+    if (cheb_local && opt.precond != SCHWZ_PRECOND_NONE && opt.precond != SCHWZ_PRECOND_JACOBI)
+        throw ::NotImplemented(__FILE__, __LINE__,
+                               "symmetric_solver 'chebyshev' with local_precond '" + m.local_precond +
+                                   "' (available: null, block-jacobi with precond_max_block_size 1)");
+    if (cheb_local && (m.par_ilu_sweeps != 0 || m.trisolve_sweeps != 0))
+        throw ::NotImplemented(__FILE__, __LINE__, "symmetric_solver 'chebyshev' with par_ilu_sweeps / trisolve_sweeps");
+    if (cheb_local && single_local)
+        throw ::NotImplemented(__FILE__, __LINE__, "symmetric_solver 'chebyshev' with local_solver_precision 'single'");
+    if (cheb_local) {
+        const double ratio = m.chebyshev_eig_ratio, lo = m.chebyshev_lambda_min, hi = m.chebyshev_lambda_max;
+        if (!(ratio > 1.0 && std::isfinite(ratio)))
+            throw ::BadDimension(__FILE__, __LINE__, "initialize", "chebyshev_eig_ratio must be a finite number > 1");
+        if (!(lo >= 0.0 && std::isfinite(lo) && hi >= 0.0 && std::isfinite(hi)))
+            throw ::BadDimension(__FILE__, __LINE__, "initialize",
+                                 "chebyshev_lambda_min / chebyshev_lambda_max must be finite and >= 0 (0: automatic)");
+        if (lo > 0.0 && hi > 0.0 && !(lo < hi))
+            throw ::BadDimension(__FILE__, __LINE__, "initialize", "chebyshev_lambda_min must be below chebyshev_lambda_max");
+    }
 
     // ---- Initialize::setup_global_matrix (initialization.cpp:197-272) ----------------------
     // extension: "--matrix_filename=poisson3d:NX[xNYxNZ]" or SCHWZ_LAPLACIAN_DIM=3 select the 3-D
@@ -422,6 +445,14 @@ void SchwarzBase<V, I, M>::initialize()
     SCHWZ_CALL(schwz_subdomain_to_device(im.sd, rhs.data(), &opt));
     if (single_local) SCHWZ_CALL(schwz_ras_set_local_precision(im.sd, SCHWZ_PRECISION_F32));
     if (bicgstab_local) SCHWZ_CALL(schwz_ras_set_nonsym_solver(im.sd, SCHWZ_NONSYM_BICGSTAB));
+    if (cheb_local) {
+        SCHWZ_CALL(schwz_ras_set_sym_solver(im.sd, SCHWZ_SYM_CHEBYSHEV));
+        double lo = 0.0, hi = 0.0;
+        SCHWZ_CALL(schwz_ras_cheb_bounds(im.sd, &lo, &hi));
+        if (m.chebyshev_lambda_max != 0.0) hi = m.chebyshev_lambda_max;
+        lo = m.chebyshev_lambda_min != 0.0 ? (double)m.chebyshev_lambda_min : hi / m.chebyshev_eig_ratio;
+        SCHWZ_CALL(schwz_ras_set_cheb_bounds(im.sd, lo, hi));
+    }
 
     im.f32_wire = s.use_mixed_precision && std::is_same<M, float>::value;
     const size_t nsend = (size_t)std::max<int64_t>(im.sizes[9], 1), nrecv = (size_t)std::max<int64_t>(im.sizes[8], 1);
@@ -544,6 +575,8 @@ void SchwarzBase<V, I, M>::initialize()
             const long long lmi = m.local_max_iters == -1 ? (long long)m.local_size_x : (long long)m.local_max_iters;
             if (bicgstab_local)
                 std::cout << " Local max iters " << lmi << " (BiCGSTAB)" << std::endl;
+            else if (cheb_local)
+                std::cout << " Local max iters " << lmi << " (Chebyshev)" << std::endl;
             else
                 std::cout << " Local max iters " << lmi << " with restart iter " << s.restart_iter << std::endl;
         } else {

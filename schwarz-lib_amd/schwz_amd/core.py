@@ -190,6 +190,50 @@ class Bicgstab:
         self.close()
 
 
+class Chebyshev:
+    """Device-resident Chebyshev iteration for SPD matrices, one reduction-free launch per iteration (schwz_cheb, an
+    extension: the reference's symmetric local solver is CG).  precond: PRECOND_NONE or PRECOND_JACOBI.  The bounds
+    on the spectrum of M^-1 A start as (Gershgorin bound / 30, Gershgorin bound); better ones are the caller's
+    (set_bounds), and an upper bound below the true one makes the iteration diverge.  solve() returns (corrections
+    applied, recurred residual norm); with rtol <= 0 the norm costs one more matrix pass and is computed only when
+    asked for."""
+
+    def __init__(self, csr, precond=capi.PRECOND_NONE):
+        self.csr = csr
+        h = C.c_void_p()
+        check(lib.schwz_cheb_create(csr.h, precond, C.byref(h)))
+        self.h = h
+
+    def bounds(self):
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        check(lib.schwz_cheb_bounds(self.h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def set_bounds(self, lmin, lmax):
+        check(lib.schwz_cheb_set_bounds(self.h, float(lmin), float(lmax)))
+
+    def solve(self, d_b, d_x, rtol, max_iters, stream=0, want_stats=True):
+        it = C.c_int(0)
+        rn = C.c_double(0.0)
+        check(lib.schwz_cheb_solve(self.h, ptr(d_b), ptr(d_x), rtol, max_iters,
+                                   C.byref(it) if want_stats else None,
+                                   C.byref(rn) if want_stats else None, _stream_arg(stream)))
+        return it.value, rn.value
+
+    def last_stats(self):
+        it, rn = C.c_int(0), C.c_double(0.0)
+        check(lib.schwz_cheb_last_stats(self.h, C.byref(it), C.byref(rn)))
+        return it.value, rn.value
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.schwz_cheb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class Gmres:
     """Device-resident restarted GMRES, right preconditioned (gko::solver::Gmres with
     krylov_dim = restart; solve.cpp:486-520)."""
@@ -716,6 +760,23 @@ class Subdomain:
 
     def nonsym_solver(self):
         return int(lib.schwz_ras_nonsym_solver(self.h))
+
+    def set_sym_solver(self, which):
+        """Method of the iterative local solve of a symmetric matrix from the next solve on
+        (schwz_ras_set_sym_solver): capi.SYM_CG (what to_device creates) or capi.SYM_CHEBYSHEV."""
+        check(lib.schwz_ras_set_sym_solver(self.h, int(which)))
+
+    def sym_solver(self):
+        return int(lib.schwz_ras_sym_solver(self.h))
+
+    def cheb_bounds(self):
+        """(lmin, lmax) of the subdomain's Chebyshev solver (after set_sym_solver(SYM_CHEBYSHEV))."""
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        check(lib.schwz_ras_cheb_bounds(self.h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def set_cheb_bounds(self, lmin, lmax):
+        check(lib.schwz_ras_set_cheb_bounds(self.h, float(lmin), float(lmax)))
 
     def local_solve(self, stream=0, want_iters=False):
         it = C.c_int(0)

@@ -133,6 +133,18 @@ class Metadata:
     # residual).  Without non_symmetric_matrix, or with a direct local solver, the field has no effect, like
     # restart_iter; any other name is refused.
     non_symmetric_solver: str = "gmres"
+    # extension (no field of the reference's Metadata): the method of the iterative local solve of a symmetric matrix:
+    # "cg" (the reference's) or "chebyshev" (schwz_cheb: a fixed polynomial in the Jacobi-preconditioned matrix, one
+    # reduction-free launch per inner iteration; local_precond 'null' or block-jacobi of block size 1, double precision).
+    # With non_symmetric_matrix or a direct local solver the field has no effect, like restart_iter; any other name is
+    # refused.  The bounds on the spectrum of M^-1 A: chebyshev_lambda_max = 0 takes the Gershgorin bound of every
+    # local matrix, chebyshev_lambda_min = 0 takes lambda_max / chebyshev_eig_ratio; explicit values override either
+    # end.  Beyond these defaults the bounds are the user's responsibility: a lambda_max below the true largest
+    # eigenvalue makes the local iteration diverge.
+    symmetric_solver: str = "cg"
+    chebyshev_eig_ratio: float = 30.0
+    chebyshev_lambda_min: float = 0.0
+    chebyshev_lambda_max: float = 0.0
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
@@ -281,6 +293,46 @@ def _nonsym_solver_code(settings, metadata):
             and _local_solver_code(settings) == capi.SOLVER_ITERATIVE:
         return capi.NONSYM_BICGSTAB
     return capi.NONSYM_GMRES
+
+
+def _sym_solver_code(settings, metadata):
+    """capi.SYM_* of metadata.symmetric_solver.  The name is checked whatever the other settings are; it selects
+    Chebyshev only for the iterative local solver of a symmetric matrix, where the combinations the solver does not
+    have are refused.  Runs before any device call."""
+    name = getattr(metadata, "symmetric_solver", "cg")
+    if name not in ("cg", "chebyshev"):
+        raise capi.SchwzError(capi.ERR_INVALID, "symmetric_solver must be 'cg' or 'chebyshev', not %r" % (name,))
+    if name == "cg" or settings.non_symmetric_matrix or _local_solver_code(settings) != capi.SOLVER_ITERATIVE:
+        return capi.SYM_CG
+    if _precond_name_code(metadata) not in (capi.PRECOND_NONE, capi.PRECOND_JACOBI):
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "symmetric_solver 'chebyshev' is implemented for local_precond 'null' and "
+                                       "'block-jacobi' with precond_max_block_size 1 only")
+    if any(_sweep_counts(metadata)):
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "symmetric_solver 'chebyshev' takes no par_ilu_sweeps / trisolve_sweeps")
+    if getattr(metadata, "local_solver_precision", "double") != "double":
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "symmetric_solver 'chebyshev' has no fp32 form (local_solver_precision 'single')")
+    ratio = float(getattr(metadata, "chebyshev_eig_ratio", 30.0))
+    lo = float(getattr(metadata, "chebyshev_lambda_min", 0.0))
+    hi = float(getattr(metadata, "chebyshev_lambda_max", 0.0))
+    if not (ratio > 1.0 and ratio < float("inf")):
+        raise capi.SchwzError(capi.ERR_INVALID, "chebyshev_eig_ratio must be a finite number > 1")
+    if not (0.0 <= lo < float("inf") and 0.0 <= hi < float("inf")):
+        raise capi.SchwzError(capi.ERR_INVALID,
+                              "chebyshev_lambda_min / chebyshev_lambda_max must be finite and >= 0 (0: automatic)")
+    if lo > 0.0 and hi > 0.0 and not lo < hi:
+        raise capi.SchwzError(capi.ERR_INVALID, "chebyshev_lambda_min must be below chebyshev_lambda_max")
+    return capi.SYM_CHEBYSHEV
+
+
+def _cheb_bounds(metadata, auto_lmax):
+    """(lmin, lmax) of a subdomain's Chebyshev solver: explicit values override either end, 0 means automatic
+    (lmax: the solver's Gershgorin bound, lmin: lmax / chebyshev_eig_ratio)."""
+    hi = float(metadata.chebyshev_lambda_max) or float(auto_lmax)
+    lo = float(metadata.chebyshev_lambda_min) or hi / float(metadata.chebyshev_eig_ratio)
+    return lo, hi
 
 
 def _precond_name_code(metadata):
@@ -479,6 +531,7 @@ class SolverRAS:
         precond_code = _precond_code(m)
         precision_code = _precision_code(s, m)
         nonsym_code = _nonsym_solver_code(s, m)
+        sym_code = _sym_solver_code(s, m)
         if self._distributed_ingest():
             prob = self._ingest_distributed()
         else:
@@ -506,6 +559,9 @@ class SolverRAS:
                 sd.set_local_precision(precision_code)
             if nonsym_code != capi.NONSYM_GMRES:  # (GMRES is what to_device creates: the setter is not called)
                 sd.set_nonsym_solver(nonsym_code)
+            if sym_code != capi.SYM_CG:  # (CG is what to_device creates: the setter is not called)
+                sd.set_sym_solver(sym_code)
+                sd.set_cheb_bounds(*_cheb_bounds(m, sd.cheb_bounds()[1]))
             # use_mixed_precision (MixedValueType = float): halos travel as fp32
             self.send_buf[me] = be.empty(sd.num_send, s.use_mixed_precision)
             self.recv_buf[me] = be.empty(sd.num_recv, s.use_mixed_precision)
@@ -542,6 +598,8 @@ class SolverRAS:
             lmi = m.local_size_x if m.local_max_iters == -1 else m.local_max_iters
             if nonsym_code == capi.NONSYM_BICGSTAB:
                 self._print(" Local max iters %d (BiCGSTAB)" % lmi)
+            elif sym_code == capi.SYM_CHEBYSHEV:
+                self._print(" Local max iters %d (Chebyshev)" % lmi)
             else:
                 self._print(" Local max iters %d with restart iter %d" % (lmi, s.restart_iter))
         else:
