@@ -443,6 +443,8 @@ int launch_gather_f32(int64_t n, const schwz_idx *idx, const double *from, float
 int launch_scatter_f32(int64_t n, const schwz_idx *idx, const float *from, double *into, hipStream_t s);
 
 int spmv_grid(const CsrView &A, int variant);
+// the SpMV variants whose kernels have the fused check + start residual mode (kSpmvResidDual)
+inline bool spmv_variant_has_dual(int variant) { return variant == 0 || variant == 4 || (variant >= 6 && variant <= 9); }
 int launch_spmv(const CsrView &A, int mode, const SpmvArgs &a, int variant, hipStream_t s);
 int launch_spmv_dict(const CsrView &A, int mode, const SpmvArgs &a, int grid, hipStream_t s);
 int launch_spmv_pattern(const CsrView &A, int mode, const SpmvArgs &a, int grid, hipStream_t s);
@@ -750,6 +752,12 @@ struct schwz_problem {
 struct schwz_pcg_f32;  // cg_f32.hip
 struct schwz_cheb;     // chebyshev.hip
 
+namespace schwz {
+// The solver the next local solve of a subdomain runs: local_kind (subdomain.hip) decides it, and everything that
+// depends on the solver switches over it.  A new solver adds one enumerator and one case per switch.
+enum class LocalKind { Direct, Gmres, Bicgstab, CgF32, Chebyshev, Cg };
+}  // namespace schwz
+
 struct schwz_subdomain {
     // ---- host index sets -------------------------------------------------
     int P = 0, me = 0, overlap = 0;
@@ -779,18 +787,20 @@ struct schwz_subdomain {
     bool on_device = false;
     schwz_solver_options opt{};
     schwz_csr *A = nullptr;  // local_matrix
-    schwz_pcg *cg = nullptr;
-    schwz_gmres *gmres = nullptr;  // non-symmetric local matrix
-    schwz_bicgstab *bicg = nullptr;  // ... once schwz_ras_set_nonsym_solver asked for BiCGSTAB (then gmres is null)
-    // mixed-precision local solve (schwz_ras_set_local_precision, csrc/cg_f32.hip): created at first use, used while
+    // The solver objects.  Which of them the next local solve runs is local_kind's answer (subdomain.hip); nothing
+    // else chooses a path by these pointers or by `precision` / `sym_solver`.
+    schwz_pcg *cg = nullptr;       // symmetric local matrix, iterative (LocalKind::Cg, and the two below beside it)
+    schwz_gmres *gmres = nullptr;  // non-symmetric local matrix (Gmres)
+    schwz_bicgstab *bicg = nullptr;  // ... once schwz_ras_set_nonsym_solver asked for BiCGSTAB (Bicgstab; gmres is null then)
+    // mixed-precision local solve (schwz_ras_set_local_precision, csrc/cg_f32.hip): created at first use, CgF32 while
     // `precision` is SCHWZ_PRECISION_F32; `cg` stays what it is, so that F64 restores the fp64 path exactly
     schwz_pcg_f32 *cg32 = nullptr;
     int precision = 0;
-    // Chebyshev local solve (schwz_ras_set_sym_solver, csrc/chebyshev.hip): created at first use, used while
+    // Chebyshev local solve (schwz_ras_set_sym_solver, csrc/chebyshev.hip): created at first use, Chebyshev while
     // `sym_solver` is SCHWZ_SYM_CHEBYSHEV; `cg` stays what it is, so that SCHWZ_SYM_CG restores the CG path exactly
     schwz_cheb *cheb = nullptr;
     int sym_solver = 0;
-    schwz_trs *trs = nullptr;
+    schwz_trs *trs = nullptr;  // the direct solvers' factors (Direct)
     // interface rows: only overlap rows are non-empty; stored compactly
     schwz_idx *d_i_rp = nullptr, *d_i_col = nullptr;  // cols index x~ directly
     double *d_i_val = nullptr;
@@ -801,7 +811,7 @@ struct schwz_subdomain {
     double *d_rhs = nullptr;     // b_loc
     double *d_btilde = nullptr;  // b~ = local_solution on entry of the solve
     double *d_y = nullptr;       // init_guess / solve result of the separate form (allocated at first need)
-    // Unified form (subdomain.hip, use_unified): no overlap, no halo, CG with x deferred -- y and x~ are the same n
+    // Unified form (subdomain.hip, want_unified): no overlap, no halo, CG with x deferred -- y and x~ are the same n
     // values, and y lives in one of the two x~ buffers.  State A: y IS x~ (d_x).  State B (y_in_alt): y is d_x_alt,
     // after a solve that has not been restricted.
     bool unified = false;

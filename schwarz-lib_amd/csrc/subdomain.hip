@@ -49,14 +49,42 @@ static int dev_zeros(int64_t n, double **d)
 // Everything else is the SEPARATE form: y = d_y, the restriction swaps (schwz_pcg::x2_out) or copies.  The form is
 // chosen per solve (the switches are read per solve); a change of form carries y over with one copy.  With
 // neighbours (overlap or halo entries, the priority-row split of the last x update) the form is always separate.
-static bool want_unified(schwz_subdomain *sd)
+//
+// ---- which solver the next local solve runs ------------------------------------------------------------------
+// The one place that reads opt.local_solver, gmres, bicg, precision and sym_solver to decide it.  It relies on:
+//   - precision == F32 and sym_solver == CHEBYSHEV exclude each other: each setter refuses while the other is set;
+//   - both need cg (the setters' eligibility test) and have created cg32 / cheb before they set the field;
+//   - gmres and bicg exclude each other and exclude cg: create_local_solver makes gmres or cg, and
+//     schwz_ras_set_nonsym_solver replaces one of gmres / bicg by the other.
+// (Cg is also the answer of an iterative subdomain whose solver could not be created: who takes that path checks cg.)
+// Only Cg has the unified form, the restriction by the solver, the fused check + start residual, the boundary
+// event of pack_early and a flavour; the other kinds update d_y in place (solve_in_place).
+static LocalKind local_kind(const schwz_subdomain *sd)
+{
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE) return LocalKind::Direct;
+    if (sd->gmres) return LocalKind::Gmres;
+    if (sd->bicg) return LocalKind::Bicgstab;
+    if (sd->precision == SCHWZ_PRECISION_F32) return LocalKind::CgF32;
+    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return LocalKind::Chebyshev;
+    return LocalKind::Cg;
+}
+
+static int local_maxit(const schwz_subdomain *sd)
+{
+    return sd->opt.local_max_iters == -1 ? (int)sd->local_size_x : sd->opt.local_max_iters;
+}
+
+// SCHWZ_RESTRICT_FUSE=0: y in a vector of its own and the restriction as a copy launch (read per solve: tests switch it)
+static bool restrict_fuse_on()
 {
     const char *e = std::getenv("SCHWZ_RESTRICT_FUSE");
-    if (e && e[0] == '0') return false;
-    if (sd->precision == SCHWZ_PRECISION_F32) return false;  // the fp32 solver updates y in place
-    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return false;  // so does the Chebyshev solver
-    return sd->cg && sd->overlap_size == 0 && sd->halo_size == 0 && sd->local_size > 0 && !sd->cg->prio_on &&
-           pcg_defers_x(sd->cg);
+    return !(e && e[0] == '0');
+}
+
+static bool want_unified(schwz_subdomain *sd)
+{
+    return local_kind(sd) == LocalKind::Cg && sd->cg && restrict_fuse_on() && sd->overlap_size == 0 &&
+           sd->halo_size == 0 && sd->local_size > 0 && !sd->cg->prio_on && pcg_defers_x(sd->cg);
 }
 
 // the second x~ buffer, allocated at first need (zeroed); false: no room
@@ -99,6 +127,131 @@ static int choose_form(schwz_subdomain *sd, hipStream_t st)
     }
     sd->unified = uni;
     return SCHWZ_OK;
+}
+
+// One fp64 CG solve in the form choose_form has just settled; solve(y) launches it.  Unified: state A out of place,
+// d_x -> d_x_alt, state B in place on d_x_alt.  Separate: in place on d_y, with step 4 inside step 3 -- the last x
+// update also writes the interior rows into the OTHER x~ buffer (schwz_pcg::x2_out) and copies the overlap / halo
+// entries of the current one behind them, and schwz_ras_restrict then only swaps the two buffers.  A solve that is
+// discarded (the verdict was "converged": no restriction) leaves the current buffer untouched, like the reference,
+// which breaks before the solve.  The second buffer is allocated on first use; SCHWZ_RESTRICT_FUSE=0 keeps the copy.
+template <typename Solve>
+static int cg_solve_in_form(schwz_subdomain *sd, Solve solve)
+{
+    schwz_pcg *cg = sd->cg;
+    cg->x2_out = nullptr;
+    if (sd->unified) {
+        cg->x_out = sd->y_in_alt ? nullptr : sd->d_x_alt;
+    } else {
+        sd->y_ahead = true;
+        if (restrict_fuse_on() && sd->local_size > 0 && ensure_x_alt(sd)) {
+            cg->x2_out = sd->d_x_alt;
+            cg->x2_rows = sd->local_size;
+            cg->x2_src = sd->d_x;
+            cg->x2_total = sd->local_size_x + sd->halo_size;
+        }
+    }
+    const int rc = solve(y_of(sd));
+    cg->x_out = nullptr;
+    if (sd->unified && !rc) sd->y_in_alt = true;
+    return rc;
+}
+
+// The kinds without a form of their own: y = d_y updated in place, the restriction is the copy launch.  (A BiCGSTAB
+// breakdown simply ends this local solve: the next outer iteration starts again from y with a fresh rhat.)
+static int solve_in_place(schwz_subdomain *sd, int *h_iters, schwz_stream stream)
+{
+    if (sd->cg) {
+        const int rc = choose_form(sd, (hipStream_t)stream);  // -> separate: want_unified is false for these kinds
+        if (rc) return rc;
+        sd->cg->x2_out = nullptr;
+        sd->cg->x2_written = false;  // (or schwz_ras_restrict would swap in a stale buffer)
+    }
+    sd->y_ahead = true;
+    const double tol = sd->opt.local_tol;
+    const int maxit = local_maxit(sd);
+    switch (local_kind(sd)) {
+    case LocalKind::Direct:
+        if (h_iters) *h_iters = 0;
+        return schwz_trs_solve(sd->trs, sd->d_btilde, sd->d_y, stream);
+    case LocalKind::Gmres: return schwz_gmres_solve(sd->gmres, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::Bicgstab: return schwz_bicgstab_solve(sd->bicg, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::CgF32: return schwz_pcg_f32_solve(sd->cg32, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::Chebyshev: return schwz_cheb_solve(sd->cheb, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::Cg: break;  // not in place: schwz_ras_local_solve takes it through cg_solve_in_form
+    }
+    return SCHWZ_ERR_INVALID;
+}
+
+// Rows the neighbours wait for (the put lists: interior rows next to the subdomain boundary) become final ahead of
+// the rest of the solution, so that the next halo exchange can start beside the tail of the solve
+// (schwz_ras_pack_early).  Two ranges [0, lo) and [hi, n) around the widest gap of the sorted put ids `ids`; false:
+// no put id, or one beyond the interior (no split at all).
+static bool priority_rows(const std::vector<schwz_idx> &ids, int64_t n, int64_t local_size, int64_t *lo_out, int64_t *hi_out)
+{
+    if (ids.empty() || ids.back() >= local_size) return false;
+    int64_t lo = 0, hi = n, gap = -1, prev = -1;
+    for (size_t k = 0; k <= ids.size(); ++k) {
+        const int64_t cur = k < ids.size() ? (int64_t)ids[k] : n;
+        if (cur - prev > gap) {
+            gap = cur - prev;
+            lo = prev + 1;
+            hi = cur;
+        }
+        prev = cur;
+    }
+    lo = (lo + 1) & ~int64_t(1);
+    hi = hi & ~int64_t(1);
+    if (hi < lo) hi = lo;
+    // (put lists spread over more than a quarter of the rows, an irregular partition: no split, the event follows
+    // the whole update and the exchange overlaps the restriction only)
+    const bool split = lo + (n - hi) <= n / 4;
+    *lo_out = split ? lo : (n & ~int64_t(1));
+    *hi_out = split ? hi : (n & ~int64_t(1));
+    return true;
+}
+
+// the solver object of sd->opt around sd->A: what local_kind then finds
+static int create_local_solver(schwz_subdomain *sd, std::vector<schwz_idx> put_idx)
+{
+    const schwz_solver_options &o = sd->opt;
+    const int64_t n = sd->local_size_x;
+    int rc;
+    if (o.local_solver == SCHWZ_SOLVER_ITERATIVE) {
+        const int bsz = o.precond_block_size < 1 ? 1 : o.precond_block_size;
+        // solve.cpp:486-520: GMRES(restart_iter); the preconditioner objects are the CG's
+        if (o.non_symmetric)
+            return schwz_gmres_create_ex(sd->A, o.precond, bsz, o.restart_iter < 1 ? 1 : o.restart_iter, o.par_ilu_sweeps,
+                                         o.trisolve_sweeps, &sd->gmres);
+        if ((rc = o.par_ilu_sweeps || o.trisolve_sweeps
+                      ? schwz_pcg_create_ilu(sd->A, o.precond, o.par_ilu_sweeps, o.trisolve_sweeps, &sd->cg)
+                      : schwz_pcg_create_ex(sd->A, o.precond, bsz, &sd->cg)))
+            return rc;
+        sd->cg->variant = o.spmv_variant;
+        std::sort(put_idx.begin(), put_idx.end());
+        if (priority_rows(put_idx, n, sd->local_size, &sd->cg->prio_lo, &sd->cg->prio_hi)) {
+            SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->cg->prio_event, hipEventDisableTiming));
+            sd->cg->prio_on = true;
+        }
+        return SCHWZ_OK;
+    }
+    // factorization == "umfpack": P A Q = L U on the host, the triangular solves with both permutations on the GPU
+    // (solve.cpp:144-173,253-267,321-390); else Solve::compute_local_factors + the Ginkgo TRS setup
+    // (solve.cpp:75-143,281-399), L L^T with one permutation
+    const bool lu = o.local_solver == SCHWZ_SOLVER_DIRECT_LU;
+    schwz_idx *l_rp = nullptr, *l_col = nullptr, *u_rp = nullptr, *u_col = nullptr, *perm = nullptr, *col_perm = nullptr;
+    double *l_val = nullptr, *u_val = nullptr;
+    if ((rc = lu ? schwz_lu(n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), o.natural_factor_ordering, &l_rp,
+                            &l_col, &l_val, &u_rp, &u_col, &u_val, &perm, &col_perm)
+                 : schwz_cholesky(n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), o.natural_factor_ordering,
+                                  &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val, &perm)))
+        return rc;
+    rc = lu ? schwz_trs_create_lu(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, col_perm, &sd->trs)
+            : schwz_trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, &sd->trs);
+    for (void *p : {(void *)l_rp, (void *)l_col, (void *)l_val, (void *)u_rp, (void *)u_col, (void *)u_val, (void *)perm,
+                    (void *)col_perm})
+        schwz_free(p);
+    return rc;
 }
 
 extern "C" {
@@ -187,82 +340,7 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
     SCHWZ_HIP_TRY(hipHostMalloc((void **)&sd->h_scalar, 4 * sizeof(double), hipHostMallocMapped));
     SCHWZ_HIP_TRY(hipHostGetDevicePointer((void **)&sd->d_h_scalar, sd->h_scalar, 0));
     SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->ev_scalar, hipEventDisableTiming));
-    if (opt->local_solver == SCHWZ_SOLVER_ITERATIVE) {
-        const int bsz = opt->precond_block_size < 1 ? 1 : opt->precond_block_size;
-        const bool sweeps = opt->par_ilu_sweeps || opt->trisolve_sweeps;
-        if (opt->non_symmetric) {
-            // solve.cpp:486-520: GMRES(restart_iter); the preconditioner objects are the CG's
-            if ((rc = schwz_gmres_create_ex(sd->A, opt->precond, bsz, opt->restart_iter < 1 ? 1 : opt->restart_iter,
-                                            opt->par_ilu_sweeps, opt->trisolve_sweeps, &sd->gmres)))
-                return rc;
-        } else {
-            if ((rc = sweeps ? schwz_pcg_create_ilu(sd->A, opt->precond, opt->par_ilu_sweeps, opt->trisolve_sweeps, &sd->cg)
-                             : schwz_pcg_create_ex(sd->A, opt->precond, bsz, &sd->cg)))
-                return rc;
-            sd->cg->variant = opt->spmv_variant;
-            // Rows the neighbours wait for (the put lists: interior rows next to the subdomain boundary) become
-            // final ahead of the rest of the solution, so that the next halo exchange can start beside the tail
-            // of the solve (schwz_ras_pack_early).  Two ranges [0, lo) and [hi, n) around the widest gap of the
-            // sorted put ids.
-            if (sd->num_send > 0) {
-                std::vector<schwz_idx> ids(put_idx);
-                std::sort(ids.begin(), ids.end());
-                int64_t lo = 0, hi = n, gap = -1;
-                int64_t prev = -1;
-                for (size_t k = 0; k <= ids.size(); ++k) {
-                    const int64_t cur = k < ids.size() ? (int64_t)ids[k] : n;
-                    if (cur - prev > gap) {
-                        gap = cur - prev;
-                        lo = prev + 1;
-                        hi = cur;
-                    }
-                    prev = cur;
-                }
-                lo = (lo + 1) & ~int64_t(1);
-                hi = hi & ~int64_t(1);
-                if (hi < lo) hi = lo;
-                if (ids.back() < sd->local_size) {
-                    // (put lists spread over more than a quarter of the rows, an irregular partition: no
-                    // split, the event follows the whole update and the exchange overlaps the restriction only)
-                    const bool split = lo + (n - hi) <= n / 4;
-                    sd->cg->prio_lo = split ? lo : (n & ~int64_t(1));
-                    sd->cg->prio_hi = split ? hi : (n & ~int64_t(1));
-                    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->cg->prio_event, hipEventDisableTiming));
-                    sd->cg->prio_on = true;
-                }
-            }
-        }
-    } else if (opt->local_solver == SCHWZ_SOLVER_DIRECT_LU) {
-        // factorization == "umfpack": P A Q = L U on the host, the triangular solves with both
-        // permutations on the GPU (solve.cpp:144-173,253-267,321-390)
-        schwz_idx *l_rp, *l_col, *u_rp, *u_col, *row_perm, *col_perm;
-        double *l_val, *u_val;
-        if ((rc = schwz_lu(n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), opt->natural_factor_ordering,
-                           &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val, &row_perm, &col_perm)))
-            return rc;
-        rc = schwz_trs_create_lu(n, l_rp, l_col, l_val, u_rp, u_col, u_val, row_perm, col_perm, &sd->trs);
-        for (void *p : {(void *)l_rp, (void *)l_col, (void *)l_val, (void *)u_rp, (void *)u_col, (void *)u_val,
-                        (void *)row_perm, (void *)col_perm})
-            schwz_free(p);
-        if (rc) return rc;
-    } else {
-        // Solve::compute_local_factors + the Ginkgo TRS setup (solve.cpp:75-143,281-399)
-        schwz_idx *l_rp, *l_col, *u_rp, *u_col, *perm;
-        double *l_val, *u_val;
-        if ((rc = schwz_cholesky(n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(),
-                                 opt->natural_factor_ordering, &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val,
-                                 &perm)))
-            return rc;
-        rc = schwz_trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, &sd->trs);
-        schwz_free(l_rp);
-        schwz_free(l_col);
-        schwz_free(l_val);
-        schwz_free(u_rp);
-        schwz_free(u_col);
-        schwz_free(u_val);
-        schwz_free(perm);
-        if (rc) return rc;
-    }
+    if ((rc = create_local_solver(sd, put_idx))) return rc;
     // y: inside the x~ buffers where the two coincide (state A), else a vector of its own
     sd->unified = want_unified(sd) && ensure_x_alt(sd);
     if (!sd->unified && (rc = dev_zeros(n, &sd->d_y))) return rc;
@@ -311,9 +389,7 @@ int schwz_ras_unpack_f32(schwz_subdomain *sd, const float *d_recv, schwz_stream 
 // schwz_ras_pack would read after schwz_ras_restrict.
 int schwz_ras_early_pack_ok(const schwz_subdomain *sd)
 {
-    if (sd && sd->precision == SCHWZ_PRECISION_F32) return 0;  // the fp32 solver records no boundary event
-    if (sd && sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return 0;  // nor does the Chebyshev solver
-    return sd && sd->on_device && sd->cg && sd->cg->prio_on && sd->cg->prio_event ? 1 : 0;
+    return sd && sd->on_device && local_kind(sd) == LocalKind::Cg && sd->cg && sd->cg->prio_on && sd->cg->prio_event ? 1 : 0;
 }
 
 int schwz_ras_pack_early(schwz_subdomain *sd, void *d_send, int single, schwz_stream stream)
@@ -515,79 +591,27 @@ int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resn
     *h_iters = 0;
     *h_resnorm = 0.0;
     if (sd->local_size_x == 0) return SCHWZ_OK;
-    if (sd->precision == SCHWZ_PRECISION_F32) return schwz_pcg_f32_last_stats(sd->cg32, h_iters, h_resnorm);
-    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return schwz_cheb_last_stats(sd->cheb, h_iters, h_resnorm);
-    if (sd->cg) return pcg_last_stats(sd->cg, h_iters, h_resnorm);
-    if (sd->gmres) return schwz_gmres_last_stats(sd->gmres, h_iters, h_resnorm);
-    if (sd->bicg) return schwz_bicgstab_last_stats(sd->bicg, h_iters, h_resnorm);
+    switch (local_kind(sd)) {
+    case LocalKind::Direct: return SCHWZ_OK;
+    case LocalKind::Gmres: return schwz_gmres_last_stats(sd->gmres, h_iters, h_resnorm);
+    case LocalKind::Bicgstab: return schwz_bicgstab_last_stats(sd->bicg, h_iters, h_resnorm);
+    case LocalKind::CgF32: return schwz_pcg_f32_last_stats(sd->cg32, h_iters, h_resnorm);
+    case LocalKind::Chebyshev: return schwz_cheb_last_stats(sd->cheb, h_iters, h_resnorm);
+    case LocalKind::Cg: return sd->cg ? pcg_last_stats(sd->cg, h_iters, h_resnorm) : SCHWZ_OK;
+    }
     return SCHWZ_OK;
-}
-
-// Step 4 inside step 3: the last x update of a CG solve also writes the interior rows into the OTHER x~ buffer
-// (schwz_pcg::x2_out) and copies the overlap / halo entries of the current one behind them, and schwz_ras_restrict
-// then only swaps the two buffers: the state after the restriction is the reference's.  A solve that is discarded (the verdict was "converged": no restriction) leaves
-// the current buffer untouched, like the reference, which breaks before the solve.  The second buffer is allocated
-// on first use; SCHWZ_RESTRICT_FUSE=0 keeps the copy launch.
-static void restrict_by_solver(schwz_subdomain *sd)
-{
-    const char *e = std::getenv("SCHWZ_RESTRICT_FUSE");  // read per solve: tests switch it
-    const bool on = !(e && e[0] == '0');
-    if (sd->cg) sd->cg->x2_out = nullptr;
-    if (!on || !sd->cg || sd->local_size == 0) return;
-    if (!ensure_x_alt(sd)) return;
-    sd->cg->x2_out = sd->d_x_alt;
-    sd->cg->x2_rows = sd->local_size;
-    sd->cg->x2_src = sd->d_x;
-    sd->cg->x2_total = sd->local_size_x + sd->halo_size;
 }
 
 int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_local_solve");
-    if (sd->opt.local_solver == SCHWZ_SOLVER_DIRECT || sd->opt.local_solver == SCHWZ_SOLVER_DIRECT_LU) {
-        if (h_inner_iters) *h_inner_iters = 0;
-        return schwz_trs_solve(sd->trs, sd->d_btilde, sd->d_y, stream);
-    }
-    const int64_t n = sd->local_size_x;
-    const int maxit = sd->opt.local_max_iters == -1 ? (int)n : sd->opt.local_max_iters;
-    if (sd->gmres)
-        return schwz_gmres_solve(sd->gmres, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
-                                 stream);
-    // (a breakdown simply ends this local solve: the next outer iteration starts again from y with a fresh rhat)
-    if (sd->bicg)
-        return schwz_bicgstab_solve(sd->bicg, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
-                                    stream);
+    if (local_kind(sd) != LocalKind::Cg) return solve_in_place(sd, h_inner_iters, stream);
     SCHWZ_REQUIRE(sd->cg, "schwz_ras_local_solve: the subdomain has no iterative solver");
-    int rc = choose_form(sd, (hipStream_t)stream);
+    const int rc = choose_form(sd, (hipStream_t)stream);
     if (rc) return rc;
-    if (sd->precision == SCHWZ_PRECISION_F32) {
-        // separate form (want_unified), y updated in place; the restriction is the copy launch
-        sd->cg->x2_out = nullptr;
-        sd->cg->x2_written = false;
-        sd->y_ahead = true;
-        return schwz_pcg_f32_solve(sd->cg32, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
-                                   stream);
-    }
-    if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) {
-        // separate form (want_unified), y updated in place; the restriction is the copy launch
-        sd->cg->x2_out = nullptr;
-        sd->cg->x2_written = false;
-        sd->y_ahead = true;
-        return schwz_cheb_solve(sd->cheb, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr, stream);
-    }
-    if (sd->unified) {
-        // state A: out of place, d_x -> d_x_alt; state B: in place on d_x_alt
-        sd->cg->x2_out = nullptr;
-        sd->cg->x_out = sd->y_in_alt ? nullptr : sd->d_x_alt;
-        rc = schwz_pcg_solve(sd->cg, sd->d_btilde, y_of(sd), sd->opt.local_tol, maxit, h_inner_iters, nullptr, stream);
-        sd->cg->x_out = nullptr;
-        if (!rc) sd->y_in_alt = true;
-        return rc;
-    }
-    restrict_by_solver(sd);
-    sd->y_ahead = true;
-    return schwz_pcg_solve(sd->cg, sd->d_btilde, sd->d_y, sd->opt.local_tol, maxit, h_inner_iters, nullptr,
-                           stream);
+    return cg_solve_in_form(sd, [&](double *y) {
+        return schwz_pcg_solve(sd->cg, sd->d_btilde, y, sd->opt.local_tol, local_maxit(sd), h_inner_iters, nullptr, stream);
+    });
 }
 
 int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
@@ -596,52 +620,40 @@ int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = sd->local_size_x;
     if (n == 0) return SCHWZ_OK;
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || sd->gmres || sd->bicg || sd->precision == SCHWZ_PRECISION_F32 || sd->sym_solver == SCHWZ_SYM_CHEBYSHEV || (sd->opt.spmv_variant != 0 && sd->opt.spmv_variant != 4 && sd->opt.spmv_variant != 6 && sd->opt.spmv_variant != 7 && sd->opt.spmv_variant != 8 && sd->opt.spmv_variant != 9)) {
-        // no fused kernel for this configuration: the two steps back to back
-        int rc = schwz_ras_local_residual_launch(sd, stream);
+    // the check residual shares the matrix pass of the CG start residual (kSpmvResidDual) ...
+    if (local_kind(sd) == LocalKind::Cg && sd->cg && spmv_variant_has_dual(sd->opt.spmv_variant)) {
+        int rc = choose_form(sd, st);
         if (rc) return rc;
-        return schwz_ras_local_solve(sd, nullptr, stream);
+        // x~ and y coincide on [interior|overlap] when there is no overlap at all
+        // (single subdomain): the check residual is then the CG start residual ...
+        const double *x2 = (sd->overlap_size == 0) ? nullptr : sd->d_x;
+        // ... unless a solve has run since the last restriction (a discarded solve, x~ kept): y has moved on and the
+        // check residual, which belongs to x~, gets its own launch
+        if (x2 || !(sd->unified ? sd->y_in_alt : sd->y_ahead))
+            return cg_solve_in_form(sd, [&](double *y) {
+                schwz_pcg *cg = sd->cg;
+                double *keep = cg->d_norm_sq;
+                cg->d_norm_sq = sd->d_h_scalar;  // mapped pinned host memory, written by the kernel
+                int rc = pcg_begin(cg, sd->d_btilde, y, sd->opt.local_tol, true, x2, n, st);
+                cg->d_norm_sq = keep;
+                if (!rc) {
+                    // the norm is final behind the start launch's fold: a kernel of pcg_begin, or the first launch of
+                    // pcg_iterate, which then records the event (nothing on the device waits for it earlier:
+                    // schwz_ras_norm_sq_to_device is enqueued after this function)
+                    if (cg->init.pending)
+                        cg->init_event = sd->ev_scalar;
+                    else if (hipEventRecord(sd->ev_scalar, st) != hipSuccess)
+                        rc = SCHWZ_ERR_HIP;
+                }
+                if (!rc) rc = pcg_iterate(cg, y, sd->opt.local_tol, local_maxit(sd), st);
+                cg->init_event = nullptr;
+                return rc;
+            });
     }
-    int rc = choose_form(sd, st);
+    // ... where a kernel for it exists; otherwise the two steps back to back
+    const int rc = schwz_ras_local_residual_launch(sd, stream);
     if (rc) return rc;
-    // x~ and y coincide on [interior|overlap] when there is no overlap at all
-    // (single subdomain): the check residual is then the CG start residual ...
-    const double *x2 = (sd->overlap_size == 0) ? nullptr : sd->d_x;
-    // ... unless a solve has run since the last restriction (a discarded solve, x~ kept): y has moved on and the
-    // check residual, which belongs to x~, gets its own launch
-    if (!x2 && (sd->unified ? sd->y_in_alt : sd->y_ahead)) {
-        if ((rc = schwz_ras_local_residual_launch(sd, stream))) return rc;
-        return schwz_ras_local_solve(sd, nullptr, stream);
-    }
-    const int maxit = sd->opt.local_max_iters == -1 ? (int)n : sd->opt.local_max_iters;
-    double *const y = y_of(sd);
-    if (sd->unified) {
-        sd->cg->x2_out = nullptr;
-        sd->cg->x_out = sd->d_x_alt;  // (state A: d_x is read, and stays x~)
-    } else {
-        restrict_by_solver(sd);
-        sd->y_ahead = true;
-    }
-    double *keep = sd->cg->d_norm_sq;
-    sd->cg->d_norm_sq = sd->d_h_scalar;  // mapped pinned host memory, written by the kernel
-    rc = pcg_begin(sd->cg, sd->d_btilde, y, sd->opt.local_tol, true, x2, n, st);
-    sd->cg->d_norm_sq = keep;
-    if (!rc) {
-        // the norm is final behind the start launch's fold: a kernel of pcg_begin, or the first launch of pcg_iterate,
-        // which then records the event (nothing on the device waits for it earlier: schwz_ras_norm_sq_to_device
-        // is enqueued after this function)
-        if (sd->cg->init.pending)
-            sd->cg->init_event = sd->ev_scalar;
-        else if (hipEventRecord(sd->ev_scalar, st) != hipSuccess)
-            rc = SCHWZ_ERR_HIP;
-    }
-    if (!rc) rc = pcg_iterate(sd->cg, y, sd->opt.local_tol, maxit, st);
-    sd->cg->init_event = nullptr;
-    if (sd->unified) {
-        sd->cg->x_out = nullptr;
-        if (!rc) sd->y_in_alt = true;
-    }
-    return rc;
+    return schwz_ras_local_solve(sd, nullptr, stream);
 }
 
 int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream)
@@ -694,11 +706,35 @@ int schwz_ras_y_form(const schwz_subdomain *sd) { return sd && sd->on_device && 
 
 int schwz_ras_cg_flavour(const schwz_subdomain *sd)
 {
-    if (sd && (sd->precision == SCHWZ_PRECISION_F32 || sd->sym_solver == SCHWZ_SYM_CHEBYSHEV)) return 0;
-    return sd && sd->cg ? schwz_pcg_flavour(sd->cg) : 0;
+    return sd && local_kind(sd) == LocalKind::Cg && sd->cg ? schwz_pcg_flavour(sd->cg) : 0;
 }
 
 int schwz_ras_local_precision(const schwz_subdomain *sd) { return sd ? sd->precision : SCHWZ_PRECISION_F64; }
+
+// The fp32 CG and the Chebyshev solver stand in for the CG of a symmetric matrix without a preconditioner or with
+// scalar Jacobi: SCHWZ_PRECOND_NONE or SCHWZ_PRECOND_JACOBI, whichever they are to be created with; -1: not such a
+// subdomain.
+static int plain_cg_precond(const schwz_subdomain *sd)
+{
+    const schwz_solver_options &o = sd->opt;
+    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->cg) return -1;
+    if (o.precond == SCHWZ_PRECOND_NONE) return SCHWZ_PRECOND_NONE;
+    if (o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1))
+        return SCHWZ_PRECOND_JACOBI;
+    return -1;
+}
+
+// behind a setter that changed local_kind: y moves to where the new kind keeps it (a vector of its own:
+// schwz_ras_y_form answers 0 from here on)
+static int settle_form(schwz_subdomain *sd)
+{
+    // a solve still in flight on a stream the null stream does not wait for must not race with the copy below
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    const int rc = choose_form(sd, nullptr);
+    if (rc) return rc;
+    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    return SCHWZ_OK;
+}
 
 int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
 {
@@ -709,10 +745,8 @@ int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
         sd->precision = precision;  // (the next solve chooses its form again: choose_form)
         return SCHWZ_OK;
     }
-    const schwz_solver_options &o = sd->opt;
-    const bool jacobi = o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1);
-    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->cg ||
-        !(o.precond == SCHWZ_PRECOND_NONE || jacobi)) {
+    const int precond = plain_cg_precond(sd);
+    if (precond < 0) {
         set_error("schwz_ras_set_local_precision: the fp32 local solve exists for the iterative solver of a symmetric "
                   "matrix (CG) without a preconditioner or with scalar Jacobi only");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
@@ -721,18 +755,10 @@ int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
         set_error("schwz_ras_set_local_precision: the Chebyshev local solve has no fp32 form");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
-    if (!sd->cg32) {
-        const int rc = schwz_pcg_f32_create(sd->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, &sd->cg32);
-        if (rc) return rc;
-    }
-    // a solve still in flight on a stream the null stream does not wait for must not race with the copy below
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    int rc;
+    if (!sd->cg32 && (rc = schwz_pcg_f32_create(sd->A, precond, &sd->cg32))) return rc;
     sd->precision = precision;
-    // y gets a vector of its own now (schwz_ras_y_form answers 0 from here on)
-    const int rc = choose_form(sd, nullptr);
-    if (rc) return rc;
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    return SCHWZ_OK;
+    return settle_form(sd);
 }
 
 int schwz_ras_sym_solver(const schwz_subdomain *sd) { return sd ? sd->sym_solver : SCHWZ_SYM_CG; }
@@ -746,10 +772,8 @@ int schwz_ras_set_sym_solver(schwz_subdomain *sd, int which)
         sd->sym_solver = which;  // (the next solve chooses its form again: choose_form)
         return SCHWZ_OK;
     }
-    const schwz_solver_options &o = sd->opt;
-    const bool jacobi = o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1);
-    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->cg ||
-        !(o.precond == SCHWZ_PRECOND_NONE || jacobi) || o.par_ilu_sweeps != 0 || o.trisolve_sweeps != 0) {
+    const int precond = plain_cg_precond(sd);
+    if (precond < 0 || sd->opt.par_ilu_sweeps != 0 || sd->opt.trisolve_sweeps != 0) {
         set_error("schwz_ras_set_sym_solver: the Chebyshev local solve exists for the iterative solver of a symmetric "
                   "matrix without a preconditioner or with scalar Jacobi only (no ParILU options)");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
@@ -758,18 +782,10 @@ int schwz_ras_set_sym_solver(schwz_subdomain *sd, int which)
         set_error("schwz_ras_set_sym_solver: the Chebyshev local solve has no fp32 form (SCHWZ_PRECISION_F32 is set)");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
-    if (!sd->cheb) {
-        const int rc = schwz_cheb_create(sd->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, &sd->cheb);
-        if (rc) return rc;
-    }
-    // a solve still in flight on a stream the null stream does not wait for must not race with the copy below
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
+    int rc;
+    if (!sd->cheb && (rc = schwz_cheb_create(sd->A, precond, &sd->cheb))) return rc;
     sd->sym_solver = which;
-    // y gets a vector of its own now (schwz_ras_y_form answers 0 from here on)
-    const int rc = choose_form(sd, nullptr);
-    if (rc) return rc;
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    return SCHWZ_OK;
+    return settle_form(sd);
 }
 
 int schwz_ras_cheb_bounds(const schwz_subdomain *sd, double *lmin, double *lmax)
@@ -792,7 +808,8 @@ int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which)
     SCHWZ_REQUIRE(which == SCHWZ_NONSYM_GMRES || which == SCHWZ_NONSYM_BICGSTAB,
                   "schwz_ras_set_nonsym_solver: unknown solver");
     REQUIRE_DEVICE(sd, "schwz_ras_set_nonsym_solver");
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !(sd->gmres || sd->bicg)) {
+    // (exactly one of gmres / bicg and no cg: what local_kind relies on)
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !sd->gmres == !sd->bicg || sd->cg) {
         set_error("schwz_ras_set_nonsym_solver: the choice exists for the iterative local solver of a non-symmetric "
                   "matrix only");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
@@ -837,14 +854,18 @@ int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which)
     if (!sd) return 0;
     const int64_t n = sd->local_size_x, nnz = (int64_t)sd->l_col.size();
     const int64_t spmv = 12 * nnz + 4 * (n + 1) + 16 * n;
-    // the fp32 iteration (cg_f32.hip): 8 B per nonzero, p gathered and q stored in fp32, then e, r read and written,
-    // p, q, 1/diag read (update launch) and p read and written, r, 1/diag read (direction launch): 44 B per row
-    if (which == 1 && sd->precision == SCHWZ_PRECISION_F32) return 8 * nnz + 4 * (n + 1) + 8 * n + 44 * n;
-    // the fused Chebyshev launch (chebyshev.hip): the CSR stream, then per row d read and d' written, r and x read and
-    // written, 1/diag read with Jacobi
-    if (which == 1 && sd->sym_solver == SCHWZ_SYM_CHEBYSHEV)
+    if (which == 0) return spmv;
+    switch (local_kind(sd)) {
+    case LocalKind::CgF32:
+        // cg_f32.hip: 8 B per nonzero, p gathered and q stored in fp32, then e, r read and written, p, q, 1/diag read
+        // (update launch) and p read and written, r, 1/diag read (direction launch): 44 B per row
+        return 8 * nnz + 4 * (n + 1) + 8 * n + 44 * n;
+    case LocalKind::Chebyshev:
+        // the fused launch of chebyshev.hip: the CSR stream, then per row d read and d' written, r and x read and
+        // written, 1/diag read with Jacobi
         return 12 * nnz + 4 * (n + 1) + (sd->opt.precond == SCHWZ_PRECOND_NONE ? 48 : 56) * n;
-    return which == 0 ? spmv : spmv + 136 * n;
+    default: return spmv + 136 * n;
+    }
 }
 
 }  // extern "C"

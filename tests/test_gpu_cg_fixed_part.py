@@ -56,6 +56,7 @@ class Rig:
                 self.idx.append(torch.arange(sd.local_size_x, dtype=torch.int32, device="cuda"))
         self.forms = []   # schwz_ras_y_form of every subdomain after every op
         self.flavours = []
+        self.flavours_after = []   # schwz_ras_cg_flavour of every subdomain after every op
 
     def get(self, me, which):
         sd, torch = self.sds[me], self.torch
@@ -110,6 +111,12 @@ class Rig:
                      np.zeros(sd.local_size_x))
         elif name == "put_b":
             self.put(me, 1, self.b[me] if arg else np.zeros(sd.local_size_x))
+        elif name in ("precision", "sym"):
+            if name == "precision":
+                sd.set_local_precision(getattr(self.schwz.capi, "PRECISION_" + arg))
+            else:
+                sd.set_sym_solver(getattr(self.schwz.capi, "SYM_" + arg))
+            return sd.local_precision(), sd.sym_solver(), sd.early_pack_ok()
         else:
             raise KeyError(name)
         return None
@@ -131,11 +138,14 @@ class Rig:
     def _record(self, rec, name, returned):
         self.torch.cuda.synchronize()
         self.forms.append([sd.y_form() for sd in self.sds])
+        self.flavours_after.append([sd.cg_flavour() for sd in self.sds])
         ys = [self.get(me, 2) for me in range(self.P)]
         xs = [self.get(me, 0) for me in range(self.P)]
         assert all(np.isfinite(v).all() for v in ys + xs), name
         rec.append(dict(op=name, ret=returned, y=[digest(v) for v in ys], x=[digest(v) for v in xs],
                         y_is_x=[np.array_equal(a, b) for a, b in zip(ys, xs)], y_any=[bool(v.any()) for v in ys],
+                        y_is_x_interior=[np.array_equal(a[:sd.local_size], b[:sd.local_size])
+                                         for sd, a, b in zip(self.sds, ys, xs)],
                         x_any=[bool(v.any()) for v in xs]))
 
 
@@ -294,6 +304,72 @@ def test_out_of_place_flush_on_odd_rows(schwz, torch_cuda, variant):
     assert a.forms[0] == [1] and a.forms[1] == [2] and a.forms[2] == [1]
     assert ra[1]["ret"][0] > ra[5]["ret"][0] > 0.0
     assert ra[13]["op"] == "stats" and ra[13]["ret"][0][0] == 40
+
+
+# ---- a switch of the local solver inside the state machine of the forms ----------------------------------------------
+
+SWITCH_SCRIPT = (
+    [S("put_y", 3), S("step"), S("step")]                                                  # CG, state A
+    + [S("sym", "CHEBYSHEV"), S("step"), S("stats"), S("solve"), S("solve"), S("restrict")]   # switched in state A
+    + [S("sym", "CG"), S("step"), S("stats")]
+    + [S("check_solve"), S("sym", "CHEBYSHEV"), S("check_solve"), S("stats"), S("restrict")]  # switched in state B
+    + [S("sym", "CG"), S("check_solve"), S("precision", "F32"), S("step"), S("stats"), S("solve")]   # state B again
+    + [S("precision", "F64"), S("check_solve"), S("check_solve"), S("restrict"), S("step"), S("stats")]
+)
+
+
+def switch_kinds(script):
+    """The solver selected after every recorded operation of `script` ("step" records two)."""
+    kinds, kind = [], "CG"
+    for name, arg, _ in script:
+        if name == "sym":
+            kind = arg
+        elif name == "precision":
+            kind = "F32" if arg == "F32" else "CG"
+        kinds += [kind] * (2 if name == "step" else 1)
+    return kinds
+
+
+@pytest.mark.parametrize("P", [1, 2])
+def test_switching_the_local_solver_in_either_form(schwz, torch_cuda, P):
+    """5 x 7 x 9 with SCHWZ_CG_DEFERX=2 (one subdomain: unified form), CG -> Chebyshev -> CG -> Chebyshev -> CG ->
+    fp32 -> CG with the switches in state A and in state B (behind a discarded solve), against
+    SCHWZ_RESTRICT_FUSE=0: no arithmetic depends on where y lives, so every returned value, y and x~ are equal bit for
+    bit.  While Chebyshev or the fp32 CG is selected y has a vector of its own and there is no flavour; a CG solve of
+    one subdomain leaves state B, its restriction state A; every solver reports its K iterations; with two subdomains
+    the restriction after an in-place solve copies y (a swap would bring in a buffer no solve has written)."""
+    env = {"SCHWZ_CG_DEFERX": "2"}
+    a = Rig(schwz, torch_cuda, SMALL, P, env)
+    b = Rig(schwz, torch_cuda, SMALL, P, dict(env, **FUSE0))
+    ra, rb = a.run(SWITCH_SCRIPT), b.run(SWITCH_SCRIPT)
+    same(ra, rb, "switches, P = %d" % P)
+    kinds = switch_kinds(SWITCH_SCRIPT)
+    assert len(kinds) == len(ra) and {"CG", "CHEBYSHEV", "F32"} == set(kinds)
+    cg_solve = False   # the last solve was a CG solve (and no switch since)
+    for i, (r, kind) in enumerate(zip(ra, kinds)):
+        where = (i, r["op"], kind)
+        if r["op"] in ("sym", "precision"):
+            want = (int(kind == "F32"), int(kind == "CHEBYSHEV"), kind == "CG" and P > 1)
+            assert r["ret"] == [want] * P and rb[i]["ret"] == [want] * P, where
+            cg_solve = False
+        if r["op"] in ("check_solve", "solve"):
+            cg_solve = kind == "CG"
+        if kind != "CG":
+            for rig in (a, b):
+                assert rig.forms[i] == [0] * P and rig.flavours_after[i] == [0] * P, where
+        elif P == 1 and r["op"] == "check_solve":
+            assert a.forms[i] == [2] and a.flavours_after[i][0] & 4, where
+        elif P == 1 and r["op"] == "restrict" and cg_solve:
+            assert a.forms[i] == [1], where
+        if r["op"] == "stats":
+            assert [it for it, _ in r["ret"]] == [K] * P, where
+        if r["op"] == "restrict":
+            assert r["y_is_x_interior"] == [True] * P and rb[i]["y_is_x_interior"] == [True] * P, where
+    assert all(f == [0] * P for f in b.forms)
+    assert sum(r["op"] == "restrict" and k != "CG" for r, k in zip(ra, kinds)) == 4
+    # (the steps do something, with every solver)
+    norms = [r["ret"][0] for r in ra if r["op"] == "check_solve"]
+    assert norms[0] > norms[2] > 0.0 and all(v > 0.0 for v in norms)
 
 
 # ---- with neighbours nothing changes -------------------------------------------------------------------------------
