@@ -42,6 +42,46 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// block_sum for N values at once behind ONE pair of barriers, and barriers that order LDS only: global loads and
+// stores in flight (the prefetched windows of a walk) stay in flight.  Each value takes block_sum's
+// own path -- wave_sum, one slot per wave, (red[0] + red[1]) + (red[2] + red[3]) -- so the bits are block_sum's.
+// `red` must hold 4 N doubles.
+template <int N>
+__device__ __forceinline__ void block_sum_lds(double (&v)[N], double *red)
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = wave_sum(v[k]);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    lds_barrier();  // protect `red` from a previous use
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[4 * k + w] = v[k];
+    }
+    lds_barrier();
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (red[4 * k] + red[4 * k + 1]) + (red[4 * k + 2] + red[4 * k + 3]);
+}
+
+// The lane's part of fold_partials for BANKS banks of `count` partial sums each (bank b at part + b * count): the same
+// strided sums in the same order, their loads requested eight per bank at a time instead of one after the other.
+template <int BANKS>
+__device__ __forceinline__ void fold_lane_sums(const double *part, int count, double (&s)[BANKS])
+{
+    constexpr int U = 8;
+    for (int i0 = threadIdx.x; i0 < count; i0 += U * kBlock) {
+        double v[BANKS][U];
+#pragma unroll
+        for (int b = 0; b < BANKS; ++b)
+#pragma unroll
+            for (int k = 0; k < U; ++k) v[b][k] = i0 + k * kBlock < count ? part[(size_t)b * count + i0 + k * kBlock] : 0.0;
+#pragma unroll
+        for (int b = 0; b < BANKS; ++b)
+#pragma unroll
+            for (int k = 0; k < U; ++k)
+                if (i0 + k * kBlock < count) s[b] += v[b][k];
+    }
+}
+
 // Every workgroup folds the per-workgroup partial sums of the previous launch
 // itself (fixed order): no extra launch and no atomics on the critical path.
 __device__ __forceinline__ double fold_partials(const double *part, int count, double *red)

@@ -424,6 +424,9 @@ struct SpmvArgs {
     int init_fold = 0;
     int norm_bank = 1;
     double *norm_sq_out = nullptr;
+    // launch timeline of the z-sweep walks (measurement builds of spmv_pair.hip only, -DSCHWZ_WITH_PROBES; the product
+    // never sets or reads it): kWalkStampWords 64-bit words per workgroup of this launch, tools/walk_timeline.py
+    unsigned long long *walk_probe = nullptr;
 };
 
 // launch grid of the streaming vector kernels: one lane per element up to kMaxGrid workgroups

@@ -608,6 +608,64 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_kernel(CsrView A, SpmvArgs a
 #define SCHWZ_INIT_PLAIN_STORE 1  // start walk: r0 leaves with a plain store -- its next two readers (first direction, first update) follow at once and find part of it on die: -0.5 ... -0.75 % per step at 256^3 / 512 x 512 x 64, neutral on 1 GB vectors (profiles/r03_cache_hints.txt)
 #endif
 
+// SCHWZ_WALK_PRO (build-time switch, tools/walk_ab.sh): what a walk workgroup does before its first step -- a constant
+// per launch that does not depend on the bytes (profiles/r16_walk_timeline.txt: 8.6 us of the update walk's life, 14 us
+// of the fused direction walk's, of which the tables and the fold took 4.9 and 6.9 us).
+// bit 0: the slot tables are staged and the lane's strided sums of the previous launch's partial sums are taken at
+//   kernel entry, while the scalar loads of the segment and its chain rows are on their way and BEFORE the windows
+//   are requested; only the cross-wave part of the fold follows the window requests, behind barriers that order LDS
+//   alone (block_sum_lds; the fused direction walk's two folds share them).  Before, tables and partial sums were
+//   requested behind the windows, came back behind them (vector loads return in order), and each fold's two
+//   __syncthreads() waited for every prefetched plane, not only for those of the first position.
+// bit 1: the partial sums are requested eight per bank at a time (fold_lane_sums) instead of one after the other.
+// Every sum keeps its order: the same bits.  0 restores the earlier prologue.
+#ifndef SCHWZ_WALK_PRO
+#define SCHWZ_WALK_PRO 3
+#endif
+
+// Launch timeline of the walk kernels (measurement build only: make variant DEFS=-DSCHWZ_WITH_PROBES, read by
+// tools/walk_timeline.py).  Lane 0 of a workgroup stores the 100 MHz wall clock at kWalkStamps points of its life into
+// SpmvArgs::walk_probe: [form | blockIdx << 8 | XCC id << 40, chain positions of the segment, stamps...].  In the
+// product SCHWZ_STAMP is empty.
+// SCHWZ_WALK_STAMP_WAIT=1: the "windows" stamp first waits for every load in flight, i.e. it says when the first
+// windows have landed, not when they were requested (this changes what is measured behind it).
+enum { kStampEntry, kStampSegment, kStampWindows, kStampTables, kStampFirstStep, kStampLastStep, kStampDone, kWalkStamps };
+enum { kFormUpdate = 1, kFormStart = 2, kFormDirdot = 3, kFormFirst = 4 };
+#ifdef SCHWZ_WITH_PROBES
+constexpr int kWalkStampWords = 2 + kWalkStamps;
+#ifndef SCHWZ_WALK_STAMP_WAIT
+#define SCHWZ_WALK_STAMP_WAIT 0
+#endif
+__device__ __forceinline__ void walk_stamp(const SpmvArgs &a, int form, int k)
+{
+    if (threadIdx.x == 0 && a.walk_probe) {
+        unsigned long long *rec = a.walk_probe + (size_t)blockIdx.x * kWalkStampWords;
+        if (k == kStampEntry) {
+            const unsigned long long xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & 0xfu;  // HW_REG_XCC_ID, bits 3:0
+            rec[0] = (unsigned long long)form | ((unsigned long long)blockIdx.x << 8) | (xcc << 40);
+        }
+        rec[2 + k] = wall_clock64();
+    }
+}
+__device__ __forceinline__ void walk_stamp_positions(const SpmvArgs &a, int npos)
+{
+    if (threadIdx.x == 0 && a.walk_probe) a.walk_probe[(size_t)blockIdx.x * kWalkStampWords + 1] = (unsigned long long)npos;
+}
+#define SCHWZ_STAMP(form, k) walk_stamp(a, form, k)
+// a scalar the stamp behind it has to wait for (the chain rows: scalar loads)
+#define SCHWZ_STAMP_AFTER(value) asm volatile("" ::"s"(value))
+#define SCHWZ_STAMP_POSITIONS(npos) walk_stamp_positions(a, npos)
+#define SCHWZ_STAMP_LANDED()                                           \
+    do {                                                               \
+        if (SCHWZ_WALK_STAMP_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    } while (0)
+#else
+#define SCHWZ_STAMP(form, k) ((void)0)
+#define SCHWZ_STAMP_AFTER(value) ((void)0)
+#define SCHWZ_STAMP_POSITIONS(npos) ((void)0)
+#define SCHWZ_STAMP_LANDED() ((void)0)
+#endif
+
 // ---------------------------------------------------------------------------------------------------
 // z-sweep ("brick") walk of the q-free CG update launch for matrices in the canonical 3-D stencil layout
 // {-PL, -NX, -1, 0, +1, +NX, +PL} (CsrView::sweep_*).  tools/probes/brick_probe.hip priced the memory
@@ -655,6 +713,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     __shared__ double red[4];
     double cg_alpha = 1.0;
     const int tid = threadIdx.x;
+    [[maybe_unused]] constexpr int kForm = INIT ? kFormStart : kFormUpdate;
+    SCHWZ_STAMP(kForm, kStampEntry);
     if (!INIT) {
         if (a.it >= a.cg_state->stop_iter) return;
     }
@@ -668,7 +728,11 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     // length alpha (every workgroup folds the partial sums of the previous launch itself) -- is fetched AFTER the
     // first windows have been requested (round 3): the two latencies overlap instead of adding up at the start of
     // every workgroup's life.
-    auto tables_and_alpha = [&]() {
+    // (SCHWZ_WALK_PRO bit 0: tables and the lane's strided sums of the partial sums at kernel entry -- `early` --, the
+    // cross-wave part of the fold behind the window requests -- `late`; without it both where `late` is called)
+    constexpr bool kEarly = (SCHWZ_WALK_PRO & 1) != 0;
+    double fold_lane = 0.0, rho_it = 0.0;
+    auto stage_tables = [&]() {
         for (int i = tid; i < A.canon_npat * 9; i += kBlock) {
             if (SCHWZ_WALK_ZEROCOEF) {
                 const int m = A.canon_mask[i / 9], k = i % 9;
@@ -678,8 +742,31 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
             }
         }
         if (tid < A.canon_npat) cmask[tid] = A.canon_mask[tid];
+    };
+    auto tables_and_alpha = [&](bool early) {
+        if (kEarly && early) {
+            if (!INIT) {
+                rho_it = a.cg_state->rho[a.it & 1];
+                if (SCHWZ_WALK_PRO & 2) {
+                    double s[1] = {0.0};
+                    fold_lane_sums(a.pq_partials, a.pq_nparts, s);
+                    fold_lane = s[0];
+                } else {
+                    for (int i = tid; i < a.pq_nparts; i += kBlock) fold_lane += a.pq_partials[i];  // fold_partials' sums
+                }
+            }
+            stage_tables();
+            return;
+        }
+        if (!kEarly) stage_tables();
         if (!INIT) {
-            cg_alpha = a.cg_state->rho[a.it & 1] / fold_partials(a.pq_partials, a.pq_nparts, red);
+            if (kEarly) {
+                double v[1] = {fold_lane};
+                block_sum_lds(v, red);
+                cg_alpha = rho_it / v[0];
+            } else {
+                cg_alpha = a.cg_state->rho[a.it & 1] / fold_partials(a.pq_partials, a.pq_nparts, red);
+            }
             if (blockIdx.x == 0 && tid == 0 && a.alpha_out) *a.alpha_out = cg_alpha;
         }
         lds_barrier();
@@ -699,6 +786,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
     typedef const unsigned __attribute__((address_space(4))) *const_words;
     typedef const int __attribute__((address_space(4))) *const_ints;
+    if (kEarly && (z0 < z1 || blockIdx.x == 0)) tables_and_alpha(true);
     if (z0 < z1) {
         // first row of the band at a chain position (scalar loads: the position is workgroup-uniform); a
         // position without a plane (the ends of a chain) reads plane 0 -- valid memory no mask lets through
@@ -770,6 +858,9 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         int brow[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) brow[k] = band_row(z0 - 1 + k);
+        SCHWZ_STAMP_AFTER(brow[0] + brow[1] + brow[2] + brow[3] + brow[4]);
+        SCHWZ_STAMP(kForm, kStampSegment);
+        SCHWZ_STAMP_POSITIONS(z1 - z0);
         {
             // everything the first two positions need is requested before anything is waited for
             pvd2 first[NH], second[NH];
@@ -783,7 +874,10 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
                 r_a[h] = fetch(brow[1], h);
                 r_b[h] = fetch(z0 + 1 < z1 ? brow[2] : brow[1], h);
             }
-            tables_and_alpha();
+            SCHWZ_STAMP_LANDED();
+            SCHWZ_STAMP(kForm, kStampWindows);
+            tables_and_alpha(false);
+            SCHWZ_STAMP(kForm, kStampTables);
             store_own(z0 - 1, first);
             store_own(z0, second);
         }
@@ -884,6 +978,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
 #pragma unroll
             for (int k = 0; k < 4; ++k) brow[k] = brow[k + 1];
             brow[4] = band_row(z + 4);
+            if (z == z0) SCHWZ_STAMP(kForm, kStampFirstStep);
         };
         int z = z0;
         for (; z + 1 < z1; z += 2) {
@@ -891,9 +986,12 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
             step(z + 1, own_a, r_b);
         }
         if (z < z1) step(z, own_b, r_a);
+        SCHWZ_STAMP(kForm, kStampLastStep);
     } else if (!INIT && blockIdx.x == 0) {
-        tables_and_alpha();  // (an empty first slot still reports alpha)
+        tables_and_alpha(false);  // (an empty first slot still reports alpha)
     }
+    // (one reduction of all the sums behind a single pair of LDS-only barriers was measured here: inside the noise,
+    // profiles/r16_walk_launch_constant.txt.  Not kept.)
     const double s0 = block_sum(acc0, red);
     const double s1 = block_sum(acc1, red);
     if (tid == 0) {
@@ -904,6 +1002,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         const double s2 = block_sum(acc2, red);
         if (tid == 0) a.partials[2 * a.part_stride + blockIdx.x] = s2;
     }
+    SCHWZ_STAMP(kForm, kStampDone);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -940,7 +1039,9 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     double *const halo_ring = own_ring + 4 * T;                       // p' of the NX rows above the band [kHaloSlots][NX]
     PairVal *const cpv = reinterpret_cast<PairVal *>(halo_ring + kHaloSlots * NX);
     int *const cmask = reinterpret_cast<int *>(cpv + A.canon_npat * 5);
-    __shared__ double red[4];
+    __shared__ double red[8];
+    [[maybe_unused]] constexpr int kForm = FIRST ? kFormFirst : kFormDirdot;
+    SCHWZ_STAMP(kForm, kStampEntry);
     // (FIRST reads nothing of CgState: with init_fold its own workgroup 0 is still to write it.  After a zero start
     // residual the launch is needless; the update launch behind it sees stop_iter == 0 and leaves.)
     if (!FIRST && a.it >= a.cg_state->stop_iter) return;
@@ -955,7 +1056,11 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     };
     // the slot tables and beta (folded from the previous launch's partial sums by every workgroup): fetched after
     // the first windows have been requested, like in the update walk above
-    auto tables_and_beta = [&]() {
+    // (SCHWZ_WALK_PRO bit 0, as in the update walk: `early` at kernel entry, `late` behind the window requests, where
+    // the two folds share one pair of LDS-only barriers)
+    constexpr bool kEarly = (SCHWZ_WALK_PRO & 1) != 0;
+    double fold_rho = 0.0, fold_rr = 0.0, rho_it = 0.0;
+    auto stage_tables = [&]() {
         for (int i = tid; i < A.canon_npat * 5; i += kBlock) {
             if (SCHWZ_WALK_ZEROCOEF) {
                 const int m = A.canon_sym_mask[i / 5], k = i % 5;
@@ -965,10 +1070,39 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             }
         }
         if (tid < A.canon_npat) cmask[tid] = A.canon_sym_mask[tid];
+    };
+    auto tables_and_beta = [&](bool early) {
+        if (kEarly && early) {
+            if (!FIRST) {
+                rho_it = a.cg_state->rho[a.it & 1];
+                if (SCHWZ_WALK_PRO & 2) {
+                    double s[2] = {0.0, 0.0};
+                    fold_lane_sums(a.pq_partials, a.pq_nparts, s);
+                    fold_rho = s[0];
+                    fold_rr = s[1];
+                } else {
+                    for (int i = tid; i < a.pq_nparts; i += kBlock) {  // fold_partials' sums of both banks
+                        fold_rho += a.pq_partials[i];
+                        fold_rr += a.pq_partials[a.pq_nparts + i];
+                    }
+                }
+            }
+            stage_tables();
+            return;
+        }
+        if (!kEarly) stage_tables();
         if (!FIRST) {
-            cg_rho_new = fold_partials(a.pq_partials, a.pq_nparts, red);
-            cg_rr = fold_partials(a.pq_partials + a.pq_nparts, a.pq_nparts, red);
-            cg_beta = cg_rho_new / a.cg_state->rho[a.it & 1];
+            if (kEarly) {
+                double v[2] = {fold_rho, fold_rr};
+                block_sum_lds(v, red);
+                cg_rho_new = v[0];
+                cg_rr = v[1];
+                cg_beta = cg_rho_new / rho_it;
+            } else {
+                cg_rho_new = fold_partials(a.pq_partials, a.pq_nparts, red);
+                cg_rr = fold_partials(a.pq_partials + a.pq_nparts, a.pq_nparts, red);
+                cg_beta = cg_rho_new / a.cg_state->rho[a.it & 1];
+            }
         }
         init_fold();
         lds_barrier();
@@ -986,6 +1120,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     double acc0 = 0.0;
     typedef const unsigned __attribute__((address_space(4))) *const_words;
     typedef const int __attribute__((address_space(4))) *const_ints;
+    if (kEarly && (z0 < z1 || (!FIRST && blockIdx.x == 0))) tables_and_beta(true);
     if (z0 < z1) {
         const const_ints chain = (const_ints)(uintptr_t)A.chain_plane;
         const const_ints chain_far = (const_ints)(uintptr_t)A.chain_far;
@@ -1085,6 +1220,9 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         int brow[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) brow[k] = band_row(z0 - 1 + k);
+        SCHWZ_STAMP_AFTER(brow[0] + brow[1] + brow[2] + brow[3] + brow[4]);
+        SCHWZ_STAMP(kForm, kStampSegment);
+        SCHWZ_STAMP_POSITIONS(z1 - z0);
         {
             // the previous position is read by rows whose far-after slot points backwards along the chain
             Own before, first;
@@ -1099,7 +1237,10 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
                 load_halo(brow[2], hreg);    // position z0 + 1
                 load_halo(brow[3], hreg_b);  // position z0 + 2
             }
-            tables_and_beta();
+            SCHWZ_STAMP_LANDED();
+            SCHWZ_STAMP(kForm, kStampWindows);
+            tables_and_beta(false);
+            SCHWZ_STAMP(kForm, kStampTables);
             if (SCHWZ_DD & 2) store_halo(0, h0);
             store_own(z0 - 1, brow[0], before, false);
             store_own(z0, brow[1], first, true);
@@ -1181,6 +1322,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             for (int k = 0; k < 4; ++k) brow[k] = brow[k + 1];
             brow[4] = band_row(z + 4);
             hs = hs_next;
+            if (z == z0) SCHWZ_STAMP(kForm, kStampFirstStep);
         };
         int z = z0;
         for (; z + 1 < z1; z += 2) {
@@ -1188,8 +1330,9 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             step(z + 1, own_a, rle_b, hreg_b);
         }
         if (z < z1) step(z, own_b, rle_a, hreg);
+        SCHWZ_STAMP(kForm, kStampLastStep);
     } else if (!FIRST && blockIdx.x == 0) {
-        tables_and_beta();  // (an empty first slot still advances the CG state below)
+        tables_and_beta(false);  // (an empty first slot still advances the CG state below)
     } else {
         init_fold();  // (... or initialises it)
     }
@@ -1198,6 +1341,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         a.partials[blockIdx.x] = s0;
         a.partials[a.part_stride + blockIdx.x] = 0.0;
     }
+    SCHWZ_STAMP(kForm, kStampDone);
     if (!FIRST && blockIdx.x == 0 && tid == 0) {
         // what cg_direction_kernel's workgroup 0 does (see the chunk-by-chunk kernel's epilogue)
         CgState *st = const_cast<CgState *>(a.cg_state);
@@ -1253,12 +1397,36 @@ bool pair_sweep_dual_ok(const CsrView &A, int grid)
 
 // One instantiation of a z-sweep walk kernel, one workgroup per segment slot: raises its dynamic-LDS limit once,
 // launches it.  false: the device does not grant 96 KiB of dynamic LDS to the kernel (nothing was launched).
+#ifdef SCHWZ_WITH_PROBES
+// the timeline buffer of the measurement build: kMaxGrid records of kWalkStampWords words for each of the next
+// `launches` walk launches, in launch order (tools/walk_timeline.py owns and zeroes the memory)
+static unsigned long long *g_walk_probe = nullptr;
+static int g_walk_probe_cap = 0, g_walk_probe_used = 0;
+extern "C" void schwz_walk_probe_set(unsigned long long *dev_buf, int launches)
+{
+    g_walk_probe = dev_buf;
+    g_walk_probe_cap = dev_buf ? launches : 0;
+    g_walk_probe_used = 0;
+}
+extern "C" int schwz_walk_probe_used() { return g_walk_probe_used; }
+extern "C" int schwz_walk_probe_record_words() { return kWalkStampWords; }
+extern "C" int schwz_walk_probe_launch_records() { return kMaxGrid; }
+#endif
+
 template <void (*KERNEL)(CsrView, SpmvArgs)>
 static bool launch_walk_kernel(int nslots, const CsrView &A, const SpmvArgs &b, size_t lds, hipStream_t s)
 {
     static const hipError_t e = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                     kSweepLdsLimit);
     if (e != hipSuccess || lds > kSweepLdsLimit) return false;
+#ifdef SCHWZ_WITH_PROBES
+    if (g_walk_probe_used < g_walk_probe_cap && nslots <= kMaxGrid) {
+        SpmvArgs c = b;
+        c.walk_probe = g_walk_probe + (size_t)g_walk_probe_used++ * kMaxGrid * kWalkStampWords;
+        hipLaunchKernelGGL(KERNEL, dim3(nslots), dim3(kBlock), lds, s, A, c);
+        return true;
+    }
+#endif
     hipLaunchKernelGGL(KERNEL, dim3(nslots), dim3(kBlock), lds, s, A, b);
     return true;
 }
