@@ -34,6 +34,19 @@ CodingOptions coding_options_from_env()
     o.sweep_Tdir = number("SCHWZ_SWEEP_TDIR");
     o.sweep_Ldir = number("SCHWZ_SWEEP_LDIR");
     o.sweep_first_per_cu = number("SCHWZ_SWEEP_FIRSTPERCU").value_or(6);
+    // "u,d,f" per mille (update and start / fused direction / first direction table); one number: all three
+    if (const char *e = std::getenv("SCHWZ_SWEEP_TRIM")) {
+        int t[3] = {0, 0, 0}, n = 0;
+        for (const char *c = e; n < 3; ++c) {
+            t[n++] = std::atoi(c);
+            if (!(c = std::strchr(c, ','))) break;
+        }
+        for (int k = n; k < 3; ++k) t[k] = n == 1 ? t[0] : 0;
+        o.sweep_trim = t[0];
+        o.sweep_trim_dir = t[1];
+        o.sweep_trim_first = t[2];
+    }
+    o.sweep_cus = number("SCHWZ_SWEEP_CUS");
     const char *why = std::getenv("SCHWZ_SWEEP_WHY");
     o.sweep_why = why && why[0] == '1';
     return o;
@@ -613,7 +626,7 @@ void plan_pair_records(const CodingOptions &opt, const HostCsr &M, int deal_shif
 
 namespace {
 
-struct Run { int p0, p1; };  // chain positions [p0, p1) of consecutive walkable planes
+using Run = WalkRun;  // chain positions [p0, p1) of consecutive walkable planes
 
 // segments a launch needs when its runs are cut into pieces of at most `len` chain positions, per band
 int64_t segment_count(const std::vector<Run> &runs, int bands, int len)
@@ -635,20 +648,66 @@ int segment_length(const std::vector<Run> &runs, int64_t PL, int T, std::optiona
     return L < 2 ? 16 : L;
 }
 
-// Workgroup slots {band, p0, p1, rows of the band} for bands of T rows: segments of about L chain positions, L
-// raised by `step` until segments + kXcds fit `room` slots; dealt to the XCDs, entry [q * kXcds + x] the q-th
-// segment of XCD x ({0, 0, 0, 0}: none).
-std::vector<int4> segment_table(const std::vector<Run> &runs, int64_t PL, int T, int L, int step, int room)
+}  // namespace
+
+// (coding_plan.hpp)
+std::vector<int4> walk_segment_table(const std::vector<WalkRun> &runs, int64_t PL, int T, int L, int cus, int trim,
+                                     int floor, int step, int room)
 {
     const int bands = (int)((PL + T - 1) / T);  // (gen mode: the last band of a plane is partial)
     while (segment_count(runs, bands, L) + kXcds > room && L < (1 << 20)) L += step;
+    trim = std::min(std::max(trim, 0), kWalkTrimMax);
+    // equal pieces of `len` positions are ceil(R / len) pieces: nseg of them, or one less where the remainder is nothing
+    auto pieces = [&](const Run &r, int &len) {
+        const int R = r.p1 - r.p0, nseg = (R + L - 1) / L;
+        len = (R + nseg - 1) / nseg;
+        return (R + len - 1) / len;
+    };
+    int64_t filled = 0, late_left = 0;
+    for (const Run &r : runs) {
+        int len;
+        filled += (int64_t)pieces(r, len) * bands;
+    }
+    // Pieces from the end of the table that are late: piece j from the end holds the sorted entries
+    // [filled - (j + 1) bands, filled - j bands), of which min(bands, cus - j bands) are among the last `cus`.
+    if (trim > 0 && filled > cus)
+        for (int64_t j = 0; 2 * std::min<int64_t>(bands, (int64_t)cus - j * bands) > bands; ++j) late_left = j + 1;
     struct Seg { int band, p0, p1; };
     std::vector<Seg> segs;
-    for (const Run &r : runs) {
-        const int nseg = (r.p1 - r.p0 + L - 1) / L, len = (r.p1 - r.p0 + nseg - 1) / nseg;
-        for (int b = 0; b < bands; ++b)
-            for (int p = r.p0; p < r.p1; p += len) segs.push_back({b, p, std::min(p + len, r.p1)});
+    std::vector<std::vector<int>> cuts(runs.size());  // per run: the first position of every piece, and p1
+    for (size_t i = runs.size(); i-- > 0;) {
+        const Run &r = runs[i];
+        int len;
+        const int R = r.p1 - r.p0, npieces = pieces(r, len);
+        std::vector<int> &c = cuts[i];
+        const int late = (int)std::min<int64_t>(late_left, npieces), early = npieces - late;
+        late_left -= late;
+        if (late == 0 || early == 0 || len < kWalkTrimMinLen) {
+            // equal pieces, the last one the remainder: what every table was before there was a trim
+            for (int p = r.p0; p < r.p1; p += len) c.push_back(p);
+        } else {
+            // early e, late (1 - t) e, early e + late (1 - t) e = R; whole positions: the late pieces' share rounded to
+            // the nearest, lowered until no late piece is longer than an early one, never below the floor
+            const double keep = 1.0 - trim / 1000.0;
+            int late_sum = (int)(late * keep * R / (early + late * keep) + 0.5);
+            while (late_sum > late && (late_sum + late - 1) / late > (R - late_sum) / early) --late_sum;
+            late_sum = std::max(late_sum, late * std::min(floor, len));
+            const int early_sum = R - late_sum;
+            int p = r.p0;
+            for (int k = 0; k < early; ++k) {
+                c.push_back(p);
+                p += early_sum / early + (k < early_sum % early ? 1 : 0);
+            }
+            for (int k = 0; k < late; ++k) {
+                c.push_back(p);
+                p += late_sum / late + (k < late_sum % late ? 1 : 0);
+            }
+        }
+        c.push_back(r.p1);
     }
+    for (size_t i = 0; i < runs.size(); ++i)
+        for (int b = 0; b < bands; ++b)
+            for (size_t k = 0; k + 1 < cuts[i].size(); ++k) segs.push_back({b, cuts[i][k], cuts[i][k + 1]});
     // deal: XCD x takes the bands [x * bands / 8, (x + 1) * bands / 8) (a band's window shares its NX-row
     // halos with the neighbouring bands: the same L2), segment by segment along the chain
     std::stable_sort(segs.begin(), segs.end(), [](const Seg &x, const Seg &y) { return x.p0 != y.p0 ? x.p0 < y.p0 : x.band < y.band; });
@@ -682,8 +741,6 @@ std::vector<int4> segment_table(const std::vector<Run> &runs, int64_t PL, int T,
     return out;
 }
 
-}  // namespace
-
 // The z-sweep walk (spmv_pair_sweep_kernel, spmv_pair_dirdot_sweep_kernel): host side.
 //
 // Geometry.  The matrix is cut into PLANES of PL consecutive rows (PL = the dominant far offset of the
@@ -704,6 +761,7 @@ WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, i
 {
     WalkPlan W;
     if (!P.single) return W;
+    if (opt.sweep_cus && *opt.sweep_cus > 0) cus = *opt.sweep_cus;  // SCHWZ_SWEEP_CUS: planned for another CU count
     auto no_walk = [&](const char *why) {
         W = WalkPlan();
         W.why = why;
@@ -964,7 +1022,7 @@ WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, i
     // as the partial-sum slots next to the segments allow (up to one per chunk)
     const int seg_slots = (int)((segment_count(runs, bands, L) + kXcds - 1) / kXcds * kXcds) + kXcds;
     const int gen_blocks = (int)std::min<int64_t>((int64_t)gen.size(), std::max(256, std::min(1024, grid - seg_slots)));
-    W.seg = segment_table(runs, PL, T, L, 4, grid - gen_blocks);
+    W.seg = walk_segment_table(runs, PL, T, L, cus, opt.sweep_trim, 8, 4, grid - gen_blocks);
     // The fused direction launch may take taller bands than the update launch (SCHWZ_SWEEP_TDIR=512|1024|2048):
     // its window carries an NX-row halo of r AND p per band, so a band of twice the rows halves that share,
     // while the update launch keeps four halo lines per window and prefers the shorter band.  A table of its
@@ -981,7 +1039,7 @@ WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, i
         T_dir = T;
     if (T_dir != T) {
         const int Ld = segment_length(runs, PL, T_dir, opt.sweep_Ldir, T_dir >= 2048 ? 1 : (T_dir == 1024 ? 2 : 3), cus, 8);
-        W.seg_dir = segment_table(runs, PL, T_dir, Ld, 4, grid - gen_blocks);
+        W.seg_dir = walk_segment_table(runs, PL, T_dir, Ld, cus, opt.sweep_trim_dir, 8, 4, grid - gen_blocks);
         if ((int64_t)W.seg_dir.size() + gen_blocks > grid) W.seg_dir.clear();
     }
     if (W.seg_dir.empty()) T_dir = T;
@@ -1000,7 +1058,7 @@ WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, i
     W.T_first = T_dir;
     if (opt.sweep_first_per_cu > 0 && T <= T_dir) {
         const int Lf = segment_length(runs, PL, T, std::nullopt, opt.sweep_first_per_cu, cus, 6);
-        W.seg_first = segment_table(runs, PL, T, Lf, 2, grid - gen_blocks);
+        W.seg_first = walk_segment_table(runs, PL, T, Lf, cus, opt.sweep_trim_first, 6, 2, grid - gen_blocks);
         if ((int64_t)W.seg_first.size() + gen_blocks > grid) W.seg_first.clear();
         else W.T_first = T;
     }

@@ -59,6 +59,20 @@ struct CodingOptions {
     std::optional<int> sweep_T, sweep_L, sweep_Tdir, sweep_Ldir;  // SCHWZ_SWEEP_T / L / TDIR / LDIR
     int sweep_first_per_cu = 6;           // SCHWZ_SWEEP_FIRSTPERCU
     bool sweep_why = false;               // SCHWZ_SWEEP_WHY
+    // SCHWZ_SWEEP_TRIM="u,d,f" (one number: all three; 0: equal pieces): per mille by which the pieces of a run whose
+    // workgroups are the last dispatched to their CU are shorter than the others (walk_segment_table), for the table of
+    // the update and start walks, of the fused direction walk and of the first-direction walk.
+    // Defaults (profiles/r17_walk_trim.txt, MI355X, 256^3): the condition prologue + positions x step equal for late and
+    // early workgroups on the timeline of the equal pieces gives 124 (update) and 75 (fused direction); in alternating
+    // runs 90 and 120 measured the same on the update table (150 slower) and 60 and 90 the same on the fused direction
+    // table (30 less, 120 no more): 90 and 60, together -1.3 % per step on the cube and -1.1 % on the 512 x 512 x 64
+    // slab against the parent library, each a gain by the rule of r16_walk_launch_constant.txt.  The first-direction
+    // walk ends with a workgroup of its FIRST round, which a trim only lengthens: 260 measured nothing and the table
+    // keeps equal pieces.
+    int sweep_trim = 90, sweep_trim_dir = 60, sweep_trim_first = 0;
+    // SCHWZ_SWEEP_CUS: the number of CUs the walk's tables are planned for instead of the device's (a table of at most
+    // that many segments is one dispatch round and is never trimmed: this is how a small matrix gets a late round)
+    std::optional<int> sweep_cus;
 };
 CodingOptions coding_options_from_env();
 
@@ -139,6 +153,27 @@ struct WalkPlan {
     int nslots_dir() const { return seg_dir.empty() ? nslots() : (int)seg_dir.size(); }
     int nslots_first() const { return seg_first.empty() ? nslots_dir() : (int)seg_first.size(); }
 };
+// The segment table of one walk launch, from geometry alone.  runs: chain positions [p0, p1) of consecutive walkable
+// planes of PL rows, cut into bands of T rows; L: the segment length aimed at, raised by `step` until segments + kXcds
+// fit `room` slots.  A run of R positions becomes nseg = ceil(R / L) pieces per band, and nseg does not depend on the
+// trim: only where the cuts fall does.
+//   trim = 0: equal pieces of ceil(R / nseg) positions, the last one the remainder.
+//   trim > 0 (per mille, at most kWalkTrimMax): the workgroups dispatched LAST to their CU run every step slower than the
+//     others (profiles/r16_walk_timeline.txt), so their pieces are made shorter, len_late ~ (1 - trim / 1000) len_early,
+//     and the other pieces of the run share the rest evenly.  Block b reads entry b and the hardware deals the blocks
+//     round robin over the XCDs, so those workgroups hold the last `cus` filled entries; in table order (first
+//     position, then band) that is a whole number of pieces or nearly so: a piece is late when more than half of its
+//     segments are among them.  Untouched: a table of at most `cus` segments (one round), a run whose equal pieces have
+//     fewer than kWalkTrimMinLen positions (one position is more than 6 % there), a run without late or without early
+//     pieces.  No late piece goes below `floor` positions (the planner's floor of the table) unless the equal piece did.
+// Entries {band, p0, p1, rows of the band}, dealt to the XCDs: entry [q * kXcds + x] is the q-th segment of XCD x
+// ({0, 0, 0, 0}: none).  Every band of a run has the same cuts, and an entry holds the same band whatever the trim.
+struct WalkRun { int p0, p1; };
+constexpr int kWalkTrimMinLen = 16;
+constexpr int kWalkTrimMax = 500;
+std::vector<int4> walk_segment_table(const std::vector<WalkRun> &runs, int64_t PL, int T, int L, int cus, int trim,
+                                     int floor, int step, int room);
+
 // grid: workgroups of an SpMV launch on this matrix (their partial-sum slots bound segments + companion workgroups)
 inline int walk_grid(int64_t ntiles) { return (int)((std::min<int64_t>(ntiles, kMaxGrid) + kXcds - 1) / kXcds) * kXcds; }
 WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, int64_t ncols, int grid, int cus,

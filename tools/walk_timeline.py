@@ -13,6 +13,7 @@ iterations per solve) and prints, for each of the four walk forms, the medians o
   steady step      (end of last step - end of first step) / (positions - 1)
   drain            end of last step -> partial sums written
   exit spread      last exit - median exit, and how much of a workgroup's lateness repeats from launch to launch
+  dispatch rounds  per round of workgroups on a CU (block index // CUs): median prologue, steady step, positions and exit
   gap              last exit of the launch before -> first entry of this one (kernel end + dispatch of the next)
 
   python3 tools/walk_timeline.py [--solves 3] [--size 256] [--trace DIR]
@@ -77,6 +78,7 @@ def main():
     import bench
     lib = S.capi.lib
     n = a.size
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     solver, _ = bench.make_solver(S, S.InProcessComm(1), (n, n, n), 10, 1e-30, 200, 0.0, 0)
     solver.begin_run()
     for _ in range(4):
@@ -130,7 +132,7 @@ def main():
                  span=done.max() - entry.min(), gap=(entry.min() - prev_exit) if prev_exit is not None else np.nan,
                  late=dict(zip(blk.tolist(), (done - np.median(done)).tolist())),
                  wg=dict(zip(blk[walked].tolist(), zip(npos.tolist(), ((w[:, 5] - w[:, 4]) / np.maximum(npos - 1, 1)).tolist(),
-                                                       (w[:, 4] - w[:, 0]).tolist()))),
+                                                       (w[:, 4] - w[:, 0]).tolist(), (w[:, 6] - entry.min()).tolist()))),
                  late_xcc=[float(np.mean((done - np.median(done))[xcc == x])) if (xcc == x).any() else np.nan for x in range(8)])
         per_form[form].append(m)
         prev_exit = done.max()
@@ -172,6 +174,20 @@ def main():
             print("  the latest twentieth of the workgroups (indices %d ... %d, median %d) / all: positions %.1f / %.1f, steady step %.2f / %.2f us, prologue %.2f / %.2f us"
                   % (min(late_keys), max(late_keys), int(np.median(late_keys)), mean_of(late_keys, 0), mean_of(keys, 0),
                      mean_of(late_keys, 1), mean_of(keys, 1), mean_of(late_keys, 2), mean_of(keys, 2)))
+        # by dispatch round: block b reads table entry b and is the (b // 8)-th workgroup of its XCD, so with `cus` CUs the
+        # blocks [r cus, (r + 1) cus) are the r-th workgroup to arrive on their CU -- what the plan's trim acts on
+        # (SCHWZ_SWEEP_TRIM, walk_segment_table): equal lives need prologue_r + positions_r x step_r equal over r
+        all_keys = sorted(set().union(*[set(m["wg"]) for m in ms]))
+        for rnd in range((max(all_keys) // cus + 1) if all_keys else 0):
+            ks = [k for k in all_keys if k // cus == rnd]
+            if not ks:
+                continue
+
+            def median_of(j):
+                return float(np.median([m["wg"][k][j] for m in ms for k in ks if k in m["wg"]]))
+            print("  dispatch round %d (indices %d ... %d): prologue %.2f us, steady step %.3f us, positions %.0f, exit %.2f us after the first entry (latest %.2f)"
+                  % (rnd, min(ks), max(ks), median_of(2), median_of(1), median_of(0), median_of(3),
+                     float(np.median([max(m["wg"][k][3] for k in ks if k in m["wg"]) for m in ms]))))
         print("  mean exit - median exit by XCC id: %s" % " ".join("%.1f" % float(np.nanmean([m["late_xcc"][x] for m in ms])) for x in range(8)))
     return 0
 
