@@ -27,6 +27,7 @@
 
 #include "schwz_internal.hpp"
 #include "device_utils.hpp"
+#include "stream_pipeline.hpp"
 
 namespace schwz {
 
@@ -41,9 +42,6 @@ struct CgStateF32 {
     int iters;
     int stop_iter;
 };
-
-typedef float vf4 __attribute__((ext_vector_type(4)));
-typedef int vi4 __attribute__((ext_vector_type(4)));
 
 // ---- fp32 copy of the matrix values ---------------------------------------------------------------------------
 
@@ -74,135 +72,29 @@ __global__ __launch_bounds__(kBlock) void f32_dinv_kernel(CsrView A, float *__re
 
 // ---- q = A32 p with the partial sums of p.q ---------------------------------------------------------------------
 
-// The straight-line tile pipeline of spmv_stream_kernel (spmv_stream.hip) on fp32 values: the same tiles, tile
-// tables and XCD deal, one 16-byte load of 4 values and one of 4 columns per lane and half tile, products staged in
-// LDS (16 KiB per tile), CAP masked adds per row in CSR order, no branch in the tile loop, q stored non-temporally.
-// seq > 0: short-lived workgroups of `seq` consecutive tiles of their XCD's sequence, the grid covers the matrix once;
-// seq == 0: persistent workgroups striding through the sequence (pcg_f32_build chooses).  Row sums are fp32;
-// p_i q_i is added up in fp64, one partial sum per workgroup in part[blockIdx.x].
+// The tile pipeline of stream_pipeline.hpp on fp32 values: one 16-byte load of 4 values and one of 4 columns per lane
+// and half tile, 16 KiB of LDS per tile, q stored non-temporally.  seq > 0: short-lived workgroups, seq == 0:
+// persistent ones (pcg_f32_build chooses).  Row sums are fp32; p_i q_i is added up in fp64, one partial sum per
+// workgroup in part[blockIdx.x].
 template <int CAP>
 __global__ __launch_bounds__(kBlock) void f32_spmv_stream_kernel(CsrView A, const float *__restrict__ val32,
                                                                  const float *__restrict__ p, float *__restrict__ q,
                                                                  const CgStateF32 *st, int it, double *part, int seq)
 {
 #pragma clang fp contract(off)
-    __shared__ __attribute__((aligned(16))) float vals[kTileNnz + 4 + CAP];
-    __shared__ __attribute__((aligned(16))) int cols[kTileNnz + 4 + CAP];
-    __shared__ int rstart[kBlock + 1];
     __shared__ double red[4];
     if (it >= st->stop_iter) return;
     const int tid = threadIdx.x;
-    const int xcd = blockIdx.x % kXcds;
-    const int slot = blockIdx.x / kXcds;
-    const int per_xcd = gridDim.x / kXcds;
-    typedef const int __attribute__((address_space(4))) *const_ints;
-    const const_ints sorder = (const_ints)(uintptr_t)A.stream_order;
-    const int nslots = sorder ? A.stream_nper : xcd_slots(A);
-    const int sh = A.xcd_shift;
-    auto tile_at = [&](int j) -> int {
-        if (sorder) {
-            const int t = sorder[(int64_t)xcd * A.stream_nper + j];
-            return t < 0 ? A.ntiles : t;
-        }
-        return ((j >> sh) << (sh + 3)) + (xcd << sh) + (j & (A.xcd_block - 1));
-    };
-    auto slot_at = [&](int k) -> int { return seq ? slot * seq + k : slot + k * per_xcd; };
-    int ntw = seq ? max(0, min(seq, nslots - slot * seq)) : (slot < nslots ? (nslots - slot + per_xcd - 1) / per_xcd : 0);
-    while (ntw > 0 && tile_at(slot_at(ntw - 1)) >= A.ntiles) --ntw;
-    // the masked reads of a tile's last rows may run up to CAP entries past the window: finite values, columns
-    // inside p (never summed, but gathered)
-    if (tid < 4 + CAP) {
-        vals[kTileNnz + tid] = 0.0f;
-        cols[kTileNnz + tid] = 0;
-    }
     double acc = 0.0;
-    if (ntw > 0) {
-        const const_ints trow = (const_ints)(uintptr_t)A.tile_row;
-        const const_ints tnz = (const_ints)(uintptr_t)A.tile_nz;
-        struct Meta {
-            int r0, r1, s, e;
-        };
-        auto meta = [&](int k) -> Meta {
-            // beyond the workgroup's last tile: loaded (no branch in the loop), never computed
-            const int t = tile_at(slot_at(min(k, ntw - 1)));
-            const bool past = k >= ntw;
-            const int r0 = trow[t], s0 = tnz[t];
-            return Meta{r0, past ? r0 + 1 : trow[t + 1], s0, past ? s0 : tnz[t + 1]};
-        };
-#define SCHWZ_F32_ISSUE(M, P)                                                                        \
-    {                                                                                                \
-        const int s2_ = (M).s & ~3;                                                                  \
-        const int last_ = max(((M).e - 1) & ~3, s2_);                                                \
-        const int i0_ = min(s2_ + 4 * tid, last_), i1_ = min(s2_ + 4 * (tid + kBlock), last_);       \
-        P##v0 = *reinterpret_cast<const vf4 *>(val32 + i0_);                                         \
-        P##c0 = *reinterpret_cast<const vi4 *>(A.col + i0_);                                         \
-        P##v1 = *reinterpret_cast<const vf4 *>(val32 + i1_);                                         \
-        P##c1 = *reinterpret_cast<const vi4 *>(A.col + i1_);                                         \
-        const int rowc_ = min((M).r0 + tid, (M).r1 - 1);                                             \
-        P##b0 = A.rp[rowc_] - s2_;                                                                   \
-        P##o0 = p[rowc_];                                                                            \
-    }
-#define SCHWZ_F32_STEP(M, MN, P)                                                                     \
-    {                                                                                                \
-        const int b0 = P##b0;                                                                        \
-        const float o0 = P##o0;                                                                      \
-        lds_barrier(); /* every lane is done with the previous tile's entries */                     \
-        rstart[tid] = b0;                                                                            \
-        *reinterpret_cast<vf4 *>(&vals[4 * tid]) = P##v0;                                            \
-        *reinterpret_cast<vi4 *>(&cols[4 * tid]) = P##c0;                                            \
-        *reinterpret_cast<vf4 *>(&vals[4 * (tid + kBlock)]) = P##v1;                                 \
-        *reinterpret_cast<vi4 *>(&cols[4 * (tid + kBlock)]) = P##c1;                                 \
-        lds_barrier();                                                                               \
-        const int b1 = (M).r0 + tid + 1 < (M).r1 ? rstart[tid + 1] : (M).e - ((M).s & ~3);          \
-        float sum = 0.0f;                                                                            \
-        _Pragma("unroll") for (int j0 = 0; j0 < CAP; j0 += 8)                                        \
-        {                                                                                            \
-            float vv[8], xx[8];                                                                      \
-            int cc[8];                                                                               \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
-            {                                                                                        \
-                vv[j] = vals[b0 + j0 + j];                                                           \
-                cc[j] = cols[b0 + j0 + j];                                                           \
-            }                                                                                        \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) xx[j] = p[cc[j]];                          \
-            if (j0 == 0) {                                                                           \
-                __builtin_amdgcn_sched_barrier(0);                                                   \
-                SCHWZ_F32_ISSUE(MN, P)                                                               \
-                __builtin_amdgcn_sched_barrier(0);                                                   \
-            }                                                                                        \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
-            {                                                                                        \
-                const float pv = vv[j] * xx[j];                                                      \
-                sum += (b0 + j0 + j < b1) ? pv : 0.0f;                                               \
-            }                                                                                        \
-        }                                                                                            \
-        const int rowc = min((M).r0 + tid, (M).r1 - 1);                                              \
-        const bool mine = (M).r0 + tid < (M).r1;                                                     \
-        __builtin_nontemporal_store(sum, q + rowc);                                                  \
-        const double t = (double)o0 * (double)sum;                                                   \
-        acc += mine ? t : 0.0;                                                                       \
-    }
-        vf4 Av0, Av1, Bv0, Bv1;
-        vi4 Ac0, Ac1, Bc0, Bc1;
-        int Ab0, Bb0;
-        float Ao0, Bo0;
-        Meta m0 = meta(0), m1 = meta(1);
-        SCHWZ_F32_ISSUE(m0, A)
-        SCHWZ_F32_ISSUE(m1, B)
-        Meta m2 = meta(2), m3 = meta(3);
-        int k = 0;
-        for (; k + 1 < ntw; k += 2) {
-            SCHWZ_F32_STEP(m0, m2, A)
-            SCHWZ_F32_STEP(m1, m3, B)
-            m0 = m2;
-            m1 = m3;
-            m2 = meta(k + 4);
-            m3 = meta(k + 5);
-        }
-        if (k < ntw) SCHWZ_F32_STEP(m0, m2, A)
-#undef SCHWZ_F32_STEP
-#undef SCHWZ_F32_ISSUE
-    }
+    // the own-row operand: p at the lane's row (p captured by value: read through a reference the load is no longer
+    // known not to alias the q stores, which costs two registers and, at CAP = 8, a wave per SIMD)
+    auto load = [p](int rowc) -> float { return p[rowc]; };
+    auto row = [&](float sum, float pi, int rowc, bool mine) {
+        __builtin_nontemporal_store(sum, q + rowc);
+        const double t = (double)pi * (double)sum;
+        acc += mine ? t : 0.0;
+    };
+    SCHWZ_STREAM_PIPELINE(A, CAP, float, val32, p, seq, true, float, load, row)
     const double s0 = block_sum(acc, red);
     if (tid == 0) part[blockIdx.x] = s0;
 }
@@ -465,10 +357,8 @@ static int pcg_f32_build(schwz_pcg_f32 *s)
     // beyond.  Stream kernel: short-lived workgroups of kSeq32 consecutive tiles while such a grid fits (up to
     // 6144 tiles, about 1.5 M rows), persistent workgroups striding through their XCD's sequence beyond.
     s->gv = grid_for((n + 3) / 4);
-    if (A.stream_cap != 0 && A.tile_nz && !A.tile_order) {
-        const int sh = A.xcd_shift;
-        const int nslots = A.stream_order ? A.stream_nper : ((A.ntiles + (kXcds << sh) - 1) >> (sh + 3)) << sh;
-        const int g = kXcds * ((nslots + kSeq32 - 1) / kSeq32);
+    if (stream_takes(A)) {
+        const int g = kXcds * ((stream_slots(A) + kSeq32 - 1) / kSeq32);
         s->seq = g <= kMaxGrid ? kSeq32 : 0;
         s->gs = s->seq ? g : kMaxGrid;
     } else {
@@ -531,17 +421,11 @@ static int pcg_f32_build(schwz_pcg_f32 *s)
 static int launch_spmv_f32(schwz_pcg_f32 *s, const float *p, float *q, int it, hipStream_t st)
 {
     const CsrView &A = s->A->v;
-    if (A.stream_cap != 0 && A.tile_nz && !A.tile_order) {
-#define SCHWZ_F32_CASE(C)                                                                                      \
-    hipLaunchKernelGGL((f32_spmv_stream_kernel<C>), dim3(s->gs), dim3(kBlock), 0, st, A, (const float *)s->val32, \
-                       p, q, (const CgStateF32 *)s->state, it, s->part_pq(), s->seq)
-        if (A.stream_cap <= 8)
-            SCHWZ_F32_CASE(8);
-        else if (A.stream_cap <= 16)
-            SCHWZ_F32_CASE(16);
-        else
-            SCHWZ_F32_CASE(32);
-#undef SCHWZ_F32_CASE
+    if (stream_takes(A)) {
+        stream_cap_dispatch(A, [&](auto cap) {
+            hipLaunchKernelGGL((f32_spmv_stream_kernel<decltype(cap)::value>), dim3(s->gs), dim3(kBlock), 0, st, A,
+                               (const float *)s->val32, p, q, (const CgStateF32 *)s->state, it, s->part_pq(), s->seq);
+        });
     } else {
         hipLaunchKernelGGL(f32_spmv_rows_kernel, dim3(s->gs), dim3(kBlock), 0, st, A, (const float *)s->val32, p, q,
                            (const CgStateF32 *)s->state, it, s->part_pq());

@@ -41,6 +41,7 @@
 
 #include "schwz_internal.hpp"
 #include "device_utils.hpp"
+#include "stream_pipeline.hpp"
 
 namespace schwz {
 
@@ -100,18 +101,14 @@ __device__ __forceinline__ bool cheb_leaves(const ChebArgs &a, double *red)
     return stop;
 }
 
-// The straight-line tile pipeline of spmv_stream_kernel (spmv_stream.hip): the same tiles, tile tables and XCD deal,
-// short-lived workgroups of `seq` consecutive tiles of their XCD's sequence, products staged in LDS, CAP masked adds
-// per row in CSR order, no branch in the tile loop but the one around the stores: a lane past the tile's last row
-// repeats that row's loads and arithmetic and stores nothing, because r and x are updated in place (a second store
-// of the same value would be harmless, a second load after another wave's store would not).
+// The tile pipeline of stream_pipeline.hpp, short-lived workgroups of `seq` consecutive tiles, with the iteration's
+// row update as its epilogue.  The one branch in the tile loop is the one around the stores: a lane past the tile's
+// last row repeats that row's loads and arithmetic and stores nothing, because r and x are updated in place (a second
+// store of the same value would be harmless, a second load after another wave's store would not).
 template <int FORM, bool NORM, int CAP>
 __global__ __launch_bounds__(kBlock) void cheb_stream_kernel(CsrView A, ChebArgs a)
 {
 #pragma clang fp contract(off)
-    __shared__ __attribute__((aligned(16))) double vals[kTileNnz + 4 + CAP];
-    __shared__ __attribute__((aligned(16))) int cols[kTileNnz + 4 + CAP];
-    __shared__ int rstart[kBlock + 1];
     __shared__ double red[4];
     if (FORM == kChebIter && cheb_leaves(a, red)) return;
     const int tid = threadIdx.x;
@@ -121,143 +118,40 @@ __global__ __launch_bounds__(kBlock) void cheb_stream_kernel(CsrView A, ChebArgs
         a.st->iters = 0;
         a.st->stop_iter = INT_MAX;
     }
-    const int xcd = blockIdx.x % kXcds;
-    const int slot = blockIdx.x / kXcds;
-    typedef const int __attribute__((address_space(4))) *const_ints;
-    const const_ints sorder = (const_ints)(uintptr_t)A.stream_order;
-    const int nslots = sorder ? A.stream_nper : xcd_slots(A);
-    const int sh = A.xcd_shift;
-    auto tile_at = [&](int j) -> int {
-        if (sorder) {
-            const int t = sorder[(int64_t)xcd * A.stream_nper + j];
-            return t < 0 ? A.ntiles : t;
-        }
-        return ((j >> sh) << (sh + 3)) + (xcd << sh) + (j & (A.xcd_block - 1));
-    };
-    const int seq = a.seq;
-    auto slot_at = [&](int k) -> int { return slot * seq + k; };
-    int ntw = max(0, min(seq, nslots - slot * seq));
-    while (ntw > 0 && tile_at(slot_at(ntw - 1)) >= A.ntiles) --ntw;
-    // the masked reads of a tile's last rows may run up to CAP entries past the window: finite values, columns
-    // inside the gathered vector (never summed, but gathered)
-    if (tid < 4 + CAP) {
-        vals[kTileNnz + tid] = 0.0;
-        cols[kTileNnz + tid] = 0;
-    }
     double acc = 0.0;
-    if (ntw > 0) {
-        const const_ints trow = (const_ints)(uintptr_t)A.tile_row;
-        const const_ints tnz = (const_ints)(uintptr_t)A.tile_nz;
-        struct Meta {
-            int r0, r1, s, e;
-        };
-        auto meta = [&](int k) -> Meta {
-            // beyond the workgroup's last tile: loaded (no branch in the loop), never computed
-            const int t = tile_at(slot_at(min(k, ntw - 1)));
-            const bool past = k >= ntw;
-            const int r0 = trow[t], s0 = tnz[t];
-            return Meta{r0, past ? r0 + 1 : trow[t + 1], s0, past ? s0 : tnz[t + 1]};
-        };
-        typedef int vi4 __attribute__((ext_vector_type(4)));
-        const double *const own = FORM == kChebIter ? (const double *)a.r : a.b;  // what A g is subtracted from
-        const double *const dinv = a.dinv ? a.dinv : own;  // a valid address either way (the value is selected away)
-#define SCHWZ_CHEB_ISSUE(M, P)                                                                       \
-    {                                                                                                \
-        const int s2_ = (M).s & ~3;                                                                  \
-        const int last_ = max(((M).e - 1) & ~3, s2_);                                                \
-        const int i0_ = min(s2_ + 4 * tid, last_), i1_ = min(s2_ + 4 * (tid + kBlock), last_);       \
-        P##v0 = *reinterpret_cast<const vd2 *>(A.val + i0_);                                         \
-        P##v1 = *reinterpret_cast<const vd2 *>(A.val + i0_ + 2);                                     \
-        P##c0 = *reinterpret_cast<const vi4 *>(A.col + i0_);                                         \
-        P##v2 = *reinterpret_cast<const vd2 *>(A.val + i1_);                                         \
-        P##v3 = *reinterpret_cast<const vd2 *>(A.val + i1_ + 2);                                     \
-        P##c1 = *reinterpret_cast<const vi4 *>(A.col + i1_);                                         \
-        const int rowc_ = min((M).r0 + tid, (M).r1 - 1);                                             \
-        P##b0 = A.rp[rowc_] - s2_;                                                                   \
-        P##o0 = own[rowc_];                                                                          \
-        P##o1 = P##o2 = P##o3 = 0.0;                                                                 \
-        if (FORM != kChebNormOnly) P##o1 = dinv[rowc_];                                              \
-        if (FORM == kChebIter) {                                                                     \
-            P##o2 = a.g[rowc_];                                                                      \
-            P##o3 = a.x[rowc_];                                                                      \
-        }                                                                                            \
-    }
-#define SCHWZ_CHEB_STEP(M, MN, P)                                                                    \
-    {                                                                                                \
-        const int b0 = P##b0;                                                                        \
-        const double o0 = P##o0, o1 = P##o1, o2 = P##o2, o3 = P##o3;                                 \
-        lds_barrier(); /* every lane is done with the previous tile's entries */                     \
-        rstart[tid] = b0;                                                                            \
-        *reinterpret_cast<vd2 *>(&vals[4 * tid]) = P##v0;                                            \
-        *reinterpret_cast<vd2 *>(&vals[4 * tid + 2]) = P##v1;                                        \
-        *reinterpret_cast<vi4 *>(&cols[4 * tid]) = P##c0;                                            \
-        *reinterpret_cast<vd2 *>(&vals[4 * (tid + kBlock)]) = P##v2;                                 \
-        *reinterpret_cast<vd2 *>(&vals[4 * (tid + kBlock) + 2]) = P##v3;                             \
-        *reinterpret_cast<vi4 *>(&cols[4 * (tid + kBlock)]) = P##c1;                                 \
-        lds_barrier();                                                                               \
-        const int b1 = (M).r0 + tid + 1 < (M).r1 ? rstart[tid + 1] : (M).e - ((M).s & ~3);          \
-        double sum = 0.0;                                                                            \
-        _Pragma("unroll") for (int j0 = 0; j0 < CAP; j0 += 8)                                        \
-        {                                                                                            \
-            double vv[8], xx[8];                                                                     \
-            int cc[8];                                                                               \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
-            {                                                                                        \
-                vv[j] = vals[b0 + j0 + j];                                                           \
-                cc[j] = cols[b0 + j0 + j];                                                           \
-            }                                                                                        \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j) xx[j] = a.g[cc[j]];                        \
-            if (j0 == 0) {                                                                           \
-                __builtin_amdgcn_sched_barrier(0);                                                   \
-                SCHWZ_CHEB_ISSUE(MN, P)                                                              \
-                __builtin_amdgcn_sched_barrier(0);                                                   \
-            }                                                                                        \
-            _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
-            {                                                                                        \
-                const double pv = vv[j] * xx[j];                                                     \
-                sum += (b0 + j0 + j < b1) ? pv : 0.0;                                                \
-            }                                                                                        \
-        }                                                                                            \
-        const int rowc = min((M).r0 + tid, (M).r1 - 1);                                              \
-        const bool mine = (M).r0 + tid < (M).r1;                                                     \
-        const double rn = o0 - sum;                                                                  \
-        if (FORM != kChebNormOnly) {                                                                 \
-            const double z = a.dinv ? o1 * rn : rn;                                                  \
-            const double cz = a.c * z;                                                               \
-            const double dnew = FORM == kChebIter ? a.a * o2 + cz : cz;                              \
-            const double xn = o3 + o2;                                                               \
-            if (mine) {                                                                              \
-                a.r[rowc] = rn;                                                                      \
-                a.dn[rowc] = dnew;                                                                   \
-                if (FORM == kChebIter) a.x[rowc] = xn;                                               \
-            }                                                                                        \
-        }                                                                                            \
-        if (NORM) {                                                                                  \
-            const double t = rn * rn;                                                                \
-            acc += mine ? t : 0.0;                                                                   \
-        }                                                                                            \
-    }
-        vd2 Av0, Av1, Av2, Av3, Bv0, Bv1, Bv2, Bv3;
-        vi4 Ac0, Ac1, Bc0, Bc1;
-        int Ab0, Bb0;
-        double Ao0, Ao1, Ao2, Ao3, Bo0, Bo1, Bo2, Bo3;
-        Meta m0 = meta(0), m1 = meta(1);
-        SCHWZ_CHEB_ISSUE(m0, A)
-        SCHWZ_CHEB_ISSUE(m1, B)
-        Meta m2 = meta(2), m3 = meta(3);
-        int k = 0;
-        for (; k + 1 < ntw; k += 2) {
-            SCHWZ_CHEB_STEP(m0, m2, A)
-            SCHWZ_CHEB_STEP(m1, m3, B)
-            m0 = m2;
-            m1 = m3;
-            m2 = meta(k + 4);
-            m3 = meta(k + 5);
+    const double *const own = FORM == kChebIter ? (const double *)a.r : a.b;  // what A g is subtracted from
+    const double *const dinv = a.dinv ? a.dinv : own;  // a valid address either way (the value is selected away)
+    struct Ops {
+        double o0, o1, o2, o3;  // own, dinv, d, x at the lane's row
+    };
+    auto load = [&](int rowc) -> Ops {
+        Ops o{own[rowc], 0.0, 0.0, 0.0};
+        if (FORM != kChebNormOnly) o.o1 = dinv[rowc];
+        if (FORM == kChebIter) {
+            o.o2 = a.g[rowc];
+            o.o3 = a.x[rowc];
         }
-        if (k < ntw) SCHWZ_CHEB_STEP(m0, m2, A)
-#undef SCHWZ_CHEB_STEP
-#undef SCHWZ_CHEB_ISSUE
-    }
+        return o;
+    };
+    auto row = [&](double sum, const Ops &o, int rowc, bool mine) {
+        const double rn = o.o0 - sum;
+        if (FORM != kChebNormOnly) {
+            const double z = a.dinv ? o.o1 * rn : rn;
+            const double cz = a.c * z;
+            const double dnew = FORM == kChebIter ? a.a * o.o2 + cz : cz;
+            const double xn = o.o3 + o.o2;
+            if (mine) {
+                a.r[rowc] = rn;
+                a.dn[rowc] = dnew;
+                if (FORM == kChebIter) a.x[rowc] = xn;
+            }
+        }
+        if (NORM) {
+            const double t = rn * rn;
+            acc += mine ? t : 0.0;
+        }
+    };
+    SCHWZ_STREAM_PIPELINE(A, CAP, double, A.val, a.g, a.seq, false, Ops, load, row)
     if (NORM) {
         const double s0 = block_sum(acc, red);
         if (tid == 0) a.part[blockIdx.x] = s0;
@@ -418,12 +312,9 @@ static void cheb_launch_form(const schwz_cheb *s, const ChebArgs &a, hipStream_t
 {
     const CsrView &A = s->A->v;
     if (s->stream_ok) {
-        if (A.stream_cap <= 8)
-            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, 8>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
-        else if (A.stream_cap <= 16)
-            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, 16>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
-        else
-            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, 32>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
+        stream_cap_dispatch(A, [&](auto cap) {
+            hipLaunchKernelGGL((cheb_stream_kernel<FORM, NORM, decltype(cap)::value>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
+        });
     } else {
         hipLaunchKernelGGL((cheb_rows_kernel<FORM, NORM>), dim3(s->gs), dim3(kBlock), 0, st, A, a);
     }
@@ -456,10 +347,9 @@ static int cheb_build(schwz_cheb *s)
     // kBlock * kMaxGrid = 524 288 rows, grid-stride beyond.  Tile pipeline: short-lived workgroups of kChebSeq
     // consecutive tiles while such a grid fits (6144 tiles, about 1.5 M rows), longer runs of tiles beyond.
     s->gv = grid_for(n);
-    s->stream_ok = A.stream_cap != 0 && A.tile_nz && !A.tile_order;
+    s->stream_ok = stream_takes(A);
     if (s->stream_ok) {
-        const int sh = A.xcd_shift;
-        const int nslots = A.stream_order ? A.stream_nper : ((A.ntiles + (kXcds << sh) - 1) >> (sh + 3)) << sh;
+        const int nslots = stream_slots(A);
         const int per_xcd = kMaxGrid / kXcds;
         s->seq = std::max(kChebSeq, (nslots + per_xcd - 1) / per_xcd);
         s->gs = kXcds * std::max(1, (nslots + s->seq - 1) / s->seq);

@@ -170,12 +170,4 @@ __device__ __forceinline__ int xcd_tile(const CsrView &A, int xcd, int j)
     return tile < A.ntiles ? tile : -1;
 }
 
-// number of sequence slots per XCD
-__device__ __forceinline__ int xcd_slots(const CsrView &A)
-{
-    const int sh = A.xcd_shift;
-    return ((A.ntiles + (kXcds << sh) - 1) >> (sh + 3)) << sh;
-}
-
-
 }  // namespace schwz

@@ -17,6 +17,7 @@
 #include <string>
 #include <sys/mman.h>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -345,6 +346,31 @@ struct CsrView {
     int dual_nchunks = 0, dual_blocks = 0;
 };
 
+// sequence slots per XCD of the block-cyclic deal of the tiles (runs of xcd_block tiles, whole runs per XCD)
+__host__ __device__ inline int xcd_slots(const CsrView &A)
+{
+    const int sh = A.xcd_shift;
+    return ((A.ntiles + (kXcds << sh) - 1) >> (sh + 3)) << sh;
+}
+
+// The tile pipeline over plain CSR (stream_pipeline.hpp): whether it takes the matrix, the slots of an XCD's sequence
+// (the explicit one of wide planes, or the block-cyclic deal), and the instantiation for the matrix's longest row.
+inline bool stream_takes(const CsrView &A) { return A.stream_cap != 0 && A.tile_nz && !A.tile_order; }
+
+__host__ __device__ inline int stream_slots(const CsrView &A) { return A.stream_order ? A.stream_nper : xcd_slots(A); }
+
+// f(std::integral_constant<int, CAP>) with CAP = 8 / 16 / 32, the smallest that holds A.stream_cap
+template <typename F>
+inline void stream_cap_dispatch(const CsrView &A, F &&f)
+{
+    if (A.stream_cap <= 8)
+        f(std::integral_constant<int, 8>());
+    else if (A.stream_cap <= 16)
+        f(std::integral_constant<int, 16>());
+    else
+        f(std::integral_constant<int, 32>());
+}
+
 // epilogues of the tiled SpMV kernel
 enum SpmvMode {
     kSpmvPlain = 0,      // y = alpha*A*x + beta*y
@@ -453,7 +479,6 @@ int launch_spmv_dict(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
 int launch_spmv_pattern(const CsrView &A, int mode, const SpmvArgs &a, int grid, hipStream_t s);
 int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hipStream_t s);
 int launch_spmv_stream(const CsrView &A, int mode, const SpmvArgs &a, int grid, hipStream_t s, bool *done);
-int launch_spmv_stream_ablate(const CsrView &A, const SpmvArgs &a, int abl, hipStream_t s);  // measurement build only
 // the measurement variants of schwz_csr_spmv (tools/probes/spmv_variants.hip): null in the product library
 typedef int (*SpmvProbeHook)(const CsrView &A, int mode, const SpmvArgs &a, int variant, int grid, hipStream_t s);
 extern SpmvProbeHook g_spmv_probe_hook;
