@@ -14,6 +14,23 @@
  *   - `d_` pointers are device (HBM) pointers, `h_` pointers are host pointers.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).
  *     All device entry points are asynchronous on `stream` unless noted.
+ *     Any stream will do, blocking or not: every launch, copy and event of a
+ *     call goes to the stream it was handed (graphs are captured on a private
+ *     stream and replayed on the caller's), and nothing is left to the default
+ *     stream.  Calls that hand a value back to the host (h_iters / h_resnorm,
+ *     the *_wait, *_last_stats, get_interior and true_residual_sq calls) wait
+ *     for it; a solve with rtol > 0 polls its state, and GMRES / BiCGSTAB look
+ *     at theirs once per cycle / per SCHWZ_BICGSTAB_POLL_BATCH iterations.
+ *   - creation calls (schwz_*_create*, schwz_subdomain_to_device,
+ *     schwz_window_alloc) take no stream and are complete on return: the
+ *     object may be used on any stream at once.
+ *   - one object (solver, triangular solve, subdomain) is used on one stream at
+ *     a time; the caller orders a change of stream with an event.  Exceptions
+ *     are the calls documented to run beside a solve on a second stream
+ *     (schwz_ras_pack_early, schwz_ras_norm_sq_to_device).
+ *   - a matrix (schwz_csr) is read-only once created: any number of solvers and
+ *     subdomains created on one matrix may run at the same time on different
+ *     streams.  Destroy a matrix after the objects created on it.
  *   - values are fp64 (bench_ras.cpp:204 fixes BenchRas<double,int>), local
  *     indices int32, global row ids int64 (1024^3 rows fit int32, global nnz
  *     does not -- SURVEY F7).

@@ -539,6 +539,7 @@ int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, doub
     a.y = s->r;
     a.p = s->p;  // the kernel also writes p := r, which the first direction launch repeats (with rhat and phat)
     a.partials = s->pre->partials;
+    a.stream_part = s->pre->stream_part;
     if ((rc = launch_spmv(A, kSpmvResidInit, a, s->variant, st))) return rc;
     int pending = -1, slot = 0;
     for (int k = 0;; ++k) {
@@ -560,6 +561,7 @@ int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, doub
         q.x = phat;
         q.y = s->v;
         q.partials = s->pre->partials;  // phat . v, unused
+        q.stream_part = s->pre->stream_part;
         q.stop_iter = &s->state->stop_it;
         q.it = k;
         if ((rc = launch_spmv(A, kSpmvDot, q, s->variant, st))) return rc;

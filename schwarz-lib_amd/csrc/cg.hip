@@ -754,6 +754,7 @@ static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->p, nb));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->q, nb));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->partials, sizeof(double) * 8 * kMaxGrid));
+    s->stream_part = stream_part_alloc(A->v);
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->d_norm_sq, sizeof(double) * 2));
     SCHWZ_HIP_TRY(hipMalloc((void **)&s->state, sizeof(CgState)));
     SCHWZ_HIP_TRY(hipHostMalloc((void **)&s->h_state, 2 * sizeof(CgState), hipHostMallocDefault));
@@ -897,6 +898,7 @@ void schwz_pcg_destroy(schwz_pcg *s)
     (void)hipFree(s->d_dcode);
     (void)hipFree(s->d_ddict);
     (void)hipFree(s->partials);
+    (void)hipFree(s->stream_part);
     (void)hipFree(s->d_norm_sq);
     (void)hipFree(s->state);
     (void)hipHostFree(s->h_state);
@@ -1130,6 +1132,7 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
     a.p = s->p;
     a.dinv = s->dinv;
     a.partials = s->partials;
+    a.stream_part = s->stream_part;
     a.row_limit = row_limit;
     // x2 == x over all rows: the check residual IS the start residual (rr bank)
     const bool same = fused && d_x2 == nullptr && row_limit >= s->n;
@@ -1321,6 +1324,7 @@ struct CgSolve {
         a.x = pl.deferx ? slot(it) : s->p;
         a.y = s->q;
         a.partials = part_spmv;
+        a.stream_part = s->stream_part;
         a.stop_iter = &s->state->stop_iter;
         a.it = it;
         return profiled(live, 0, q, [&] { return launch_spmv(A, pl.dot_mode, a, s->variant, q); });

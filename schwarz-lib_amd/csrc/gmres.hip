@@ -324,6 +324,7 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
         a.y = s->V;
         a.p = s->w;  // the kernel also writes p := r; w is scratch here
         a.partials = s->pre->partials;
+        a.stream_part = s->pre->stream_part;
         int rc = launch_spmv(A, kSpmvResidInit, a, s->variant, st);
         if (rc) return rc;
         hipLaunchKernelGGL(gmres_start_kernel, dim3(1), dim3(kBlock), 0, st, s->state, s->pre->partials + gs, gs, rtol,
@@ -338,6 +339,7 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
             q.x = s->z;
             q.y = s->w;
             q.partials = s->pre->partials;  // z . w, unused
+            q.stream_part = s->pre->stream_part;
             q.stop_iter = &s->state->stop_it;
             q.it = it;
             if ((rc = launch_spmv(A, kSpmvDot, q, s->variant, st))) return rc;

@@ -588,14 +588,9 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
         }
     }
     if (stream_cap && (int)tiles.size() - 1 > kMaxGrid) {
-        // scratch for the per-workgroup partial sums of the short-lived workgroups of spmv_stream.hip
-        const int cap = (int)tiles.size() + 8 * kXcds;
-        if (hipMalloc(&A->d_stream_part, (size_t)2 * cap * sizeof(double)) == hipSuccess) {
-            A->v.stream_part = (double *)A->d_stream_part;
-            A->v.stream_part_cap = cap;
-        } else {
-            (void)hipGetLastError();
-        }
+        // slots of the scratch for the per-workgroup partial sums of the short-lived workgroups of spmv_stream.hip
+        // (allocated by the solvers and subdomains that launch on this matrix: stream_part_alloc)
+        A->v.stream_part_cap = (int)tiles.size() + 8 * kXcds;
     }
     A->v.tile_order = order.empty() ? nullptr : (const schwz_idx *)A->d_order;
     {
@@ -645,7 +640,6 @@ void schwz_csr_destroy(schwz_csr *A)
     (void)hipFree(A->d_val);
     (void)hipFree(A->d_tile);
     (void)hipFree(A->d_tile_nz);
-    (void)hipFree(A->d_stream_part);
     (void)hipFree(A->d_stream_order);
     (void)hipFree(A->d_wtile);
     (void)hipFree(A->d_order);

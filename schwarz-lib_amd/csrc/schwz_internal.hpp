@@ -252,9 +252,8 @@ struct CsrView {
     // of its row sums (8 / 16 / 32 >= the longest row; 0: the matrix keeps spmv_tiled2_kernel)
     const schwz_idx *tile_nz = nullptr;
     int stream_cap = 0;
-    // spmv_stream.hip: per-workgroup partial sums of a launch whose grid exceeds the kMaxGrid slots the consumers
-    // fold (2 banks of stream_part_cap doubles; one launch at a time per matrix)
-    double *stream_part = nullptr;
+    // spmv_stream.hip: slots per bank of the scratch (SpmvArgs::stream_part) a launch needs whose grid exceeds the
+    // kMaxGrid slots the consumers fold; 0: no launch on this matrix does.  The scratch belongs to whoever launches
     int stream_part_cap = 0;
     // spmv_stream.hip on wide planes: the tile sequence of every XCD, laid out explicitly (entry [xcd * stream_nper + j],
     // -1 past the end) so that a tile's +-plane neighbours are close in the sequence; null: the block-cyclic deal
@@ -431,6 +430,10 @@ struct SpmvArgs {
     // spmv_stream.hip: consecutive tiles per workgroup of a grid that covers the matrix once (0: persistent
     // workgroups striding through their XCD's sequence, the form of round 2)
     int seq = 0;
+    // spmv_stream.hip: scratch for the per-workgroup partial sums of such a launch, 2 banks of CsrView::stream_part_cap
+    // doubles (stream_part_alloc).  It belongs to the object that launches -- a solver, a subdomain -- not to the
+    // matrix, so that objects sharing a matrix can run on different streams; nullptr: the persistent form
+    double *stream_part = nullptr;
     // q-free CG on the walks, a solve that started in the walk (round 3, "virtual first direction"): p0 = D^-1 r0 is
     // never stored -- the first update walk builds its windows from r0 (a.x = r0, windows x ring_scale) and writes
     // r1 to cg_r_out, so r0 stays intact for the first fused direction launch (a.x = r0, p read as p_scale x a.x)
@@ -454,6 +457,19 @@ struct SpmvArgs {
     // never sets or reads it): kWalkStampWords 64-bit words per workgroup of this launch, tools/walk_timeline.py
     unsigned long long *walk_probe = nullptr;
 };
+
+// SpmvArgs::stream_part for launches on A: nullptr where A needs none, or where the allocation fails (those launches
+// keep the persistent form); hipFree releases it
+inline double *stream_part_alloc(const CsrView &A)
+{
+    void *p = nullptr;
+    if (A.stream_part_cap <= 0) return nullptr;
+    if (hipMalloc(&p, (size_t)2 * A.stream_part_cap * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return (double *)p;
+}
 
 // launch grid of the streaming vector kernels: one lane per element up to kMaxGrid workgroups
 inline int grid_for(int64_t n)
@@ -585,7 +601,6 @@ struct schwz_csr {
     schwz::CsrView v;
     void *d_rp = nullptr, *d_col = nullptr, *d_val = nullptr, *d_tile = nullptr, *d_wtile = nullptr, *d_order = nullptr;
     void *d_tile_nz = nullptr;
-    void *d_stream_part = nullptr;
     void *d_stream_order = nullptr;
     // device arrays of the codings, one struct per plan of coding_plan.hpp (uploaded and bound to `v` by
     // spmv_dict.hip / spmv_pair.hip)
@@ -629,6 +644,7 @@ struct schwz_pcg {
     schwz::DiagView diag;
     void *d_dcode = nullptr, *d_ddict = nullptr;
     double *partials = nullptr;  // 3 * kMaxGrid (SpMV banks) + 2 * kMaxGrid (vector banks) + 3 * kMaxGrid (start banks, InitFold)
+    double *stream_part = nullptr;  // SpmvArgs::stream_part of this solver's launches (and of the GMRES / BiCGSTAB around it)
     double *d_norm_sq = nullptr; // kSpmvResidDual result
     schwz::CgState *state = nullptr;
     schwz::CgState *h_state = nullptr;  // pinned
@@ -847,6 +863,7 @@ struct schwz_subdomain {
     // separate form: a solve has run since the last restriction (y is ahead of x~)
     bool y_ahead = false;
     double *d_partials = nullptr;
+    double *d_stream_part = nullptr;  // SpmvArgs::stream_part of the subdomain's own norm launches
     double *h_scalar = nullptr;  // pinned, mapped
     double *d_h_scalar = nullptr;  // device alias of h_scalar
     hipEvent_t ev_scalar = nullptr;

@@ -181,12 +181,12 @@ int launch_spmv_stream(const CsrView &A, int mode, const SpmvArgs &a, int grid, 
     const int seq = stream_seq_max();
     if (seq && A.ntiles >= 4 * kMaxGrid) {
         const int g = kXcds * ((stream_slots(A) + seq - 1) / seq);
-        if (mode == kSpmvPlain || (A.stream_part && g <= A.stream_part_cap)) {
+        if (mode == kSpmvPlain || (a.stream_part && g <= A.stream_part_cap)) {
             b.seq = seq;
             launch_grid = g;
             if (mode != kSpmvPlain) {
                 fold = true;
-                b.partials = A.stream_part;
+                b.partials = a.stream_part;
                 b.part_stride = g;
             }
         }

@@ -268,7 +268,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
         schwz_trs_destroy(sd->trs);
         schwz_csr_destroy(sd->A);
         void *ptrs[] = {sd->d_i_rp, sd->d_i_col, sd->d_i_val, sd->d_put_idx, sd->d_get_idx, sd->d_x, sd->d_x_alt,
-                        sd->d_rhs, sd->d_btilde, sd->d_y, sd->d_partials};
+                        sd->d_rhs, sd->d_btilde, sd->d_y, sd->d_partials, sd->d_stream_part};
         for (void *p : ptrs) (void)hipFree(p);
         if (sd->h_scalar) (void)hipHostFree(sd->h_scalar);
         if (sd->ev_scalar) (void)hipEventDestroy(sd->ev_scalar);
@@ -337,6 +337,7 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
     std::vector<double> rhs(h_local_rhs, h_local_rhs + n);
     if ((rc = dev_upload(rhs, &sd->d_rhs)) || (rc = dev_upload(rhs, &sd->d_btilde))) return rc;
     SCHWZ_HIP_TRY(hipMalloc((void **)&sd->d_partials, sizeof(double) * (2 * kMaxGrid + 2)));
+    sd->d_stream_part = stream_part_alloc(sd->A->v);
     SCHWZ_HIP_TRY(hipHostMalloc((void **)&sd->h_scalar, 4 * sizeof(double), hipHostMallocMapped));
     SCHWZ_HIP_TRY(hipHostGetDevicePointer((void **)&sd->d_h_scalar, sd->h_scalar, 0));
     SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->ev_scalar, hipEventDisableTiming));
@@ -495,6 +496,7 @@ static int residual_norm_sq_launch(schwz_subdomain *sd, const double *b, int64_t
     a.x = sd->d_x;
     a.b = b;
     a.partials = sd->d_partials;
+    a.stream_part = sd->d_stream_part;
     a.row_limit = row_limit;
     int rc = launch_spmv(sd->A->v, kSpmvResidNorm, a, sd->opt.spmv_variant, st);
     if (rc) return rc;

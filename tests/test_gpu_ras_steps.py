@@ -41,6 +41,10 @@ def global_case(name):
     rng = np.random.default_rng(sum(name.encode()) + 2000)
     if name.startswith("band_p"):
         return hp.sym_band_matrix(1500, 6, 40, rng) + (int(name[6:]), None, None)
+    if name == "nonsym_band_p3":            # the SPD band with its upper triangle halved: still diagonally dominant
+        rp, col, val = hp.sym_band_matrix(1500, 6, 40, rng)
+        val = np.where(col > np.repeat(np.arange(1500), np.diff(rp)), 0.5 * val, val)
+        return rp, col, val, 3, None, None
     if name == "scaled_band_p3":
         rp, col, val = hp.sym_band_matrix(1500, 6, 40, rng, spd=False)
         val, s, _ = hp.rescale_rows_cols(rp, col, val, rng)
@@ -69,7 +73,8 @@ def global_case(name):
 class StepRig:
     """The subdomains `which` of one partition on the device, x~ (interior, overlap and halo) and the rhs random."""
 
-    def __init__(self, schwz, torch, name, env, variant=0, which=None, maxit=0, connect=True):
+    def __init__(self, schwz, torch, name, env, variant=0, which=None, maxit=0, connect=True, device_kw=None):
+        """device_kw: further options of Subdomain.to_device (the local solver of test_gpu_streams.py)."""
         self.schwz, self.torch = schwz, torch
         rp, col, val, P, fr, s = global_case(name)
         self.P = P
@@ -96,7 +101,7 @@ class StepRig:
                 self.l2g[me] = sd.local_to_global
                 self.rhs[me] = self.rhs_global[self.l2g[me][:sd.local_size_x]].copy()
                 sd.to_device(self.rhs[me], precond=schwz.capi.PRECOND_JACOBI, local_tol=0.0, local_max_iters=maxit,
-                             spmv_variant=variant)
+                             spmv_variant=variant, **(device_kw or {}))
                 nx = sd.local_size_x + sd.halo_size
                 self.idx[me] = torch.arange(max(nx, 1), dtype=torch.int32, device="cuda")
                 self.x[me] = np.random.default_rng(4000 + me).standard_normal(nx)
