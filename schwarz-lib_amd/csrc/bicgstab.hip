@@ -30,16 +30,15 @@
 // A solve ends with one more direction launch of a single workgroup, which only folds ||r|| and decides.
 //
 // Who writes what in BicgState, so that no launch reads a value another workgroup of the same launch writes:
-//   direction (it = k)  reads rho[(k-1)&1], alpha, omega, r0;  workgroup 0 writes rho[k&1], resn, (r0), stop_it
-//   s                   reads rho[k&1];                        workgroup 0 writes alpha, or stop_it = k
-//   update              reads alpha, r0;                       workgroup 0 writes omega, iters, or stop_it = k + 1
-// Every workgroup takes every decision itself from the folds; a workgroup that sees an early stop_it = k at its
+//   direction (it = k)  reads rho[(k-1)&1], alpha, omega, r0;  workgroup 0 writes rho[k&1], resn, (r0), stop_iter
+//   s                   reads rho[k&1];                        workgroup 0 writes alpha, or stop_iter = k
+//   update              reads alpha, r0;                       workgroup 0 writes omega, iters, or stop_iter = k + 1
+// Every workgroup takes every decision itself from the folds; a workgroup that sees an early stop_iter = k at its
 // entry test leaves like the others would.  The update launch of a half step still has work to do when the stop
-// is decided: its stop_it is k + 1, which the workgroups of launch k read as "not yet".
+// is decided: its stop_iter is k + 1, which the workgroups of launch k read as "not yet".
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstring>
 
 #include "device_utils.hpp"
 #include "schwz_hip.h"
@@ -55,7 +54,7 @@ struct BicgState {
     double rho[2];  // rho_k in slot k & 1
     double alpha, omega;
     int iters;
-    int stop_it;    // iteration index from which on launches return at once (INT_MAX: not decided)
+    int stop_iter;  // iteration index from which on launches return at once (INT_MAX: not decided)
     int breakdown;  // 0..3
     int pad;
 };
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void bicg_direction_kernel(int64_t n, doubl
 {
     __shared__ double red[4];
     __shared__ double ddict[256];
-    if (!first && it >= st->stop_it) return;
+    if (!first && it >= st->stop_iter) return;
     const double rr = fold_partials(rr_partials, nparts, red);
     const double rho = first ? rr : fold_partials(rho_partials, nparts, red);
     const double resn = sqrt(rr);
@@ -104,9 +103,9 @@ __global__ __launch_bounds__(kBlock) void bicg_direction_kernel(int64_t n, doubl
         st->rho[it & 1] = rho;
         if (bd1) st->breakdown = 1;
         if (stop || bd1)
-            st->stop_it = it;
+            st->stop_iter = it;
         else if (first)
-            st->stop_it = INT_MAX;
+            st->stop_iter = INT_MAX;
     }
     if (stop || bd1) return;
     if (dg.mode == 2) {
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void bicg_dot_kernel(int64_t n, const doubl
                                                           const BicgState *st, int it)
 {
     __shared__ double red[4];
-    if (it >= st->stop_it) return;
+    if (it >= st->stop_iter) return;
     double aa = 0.0, ab = 0.0;
     const int64_t n2 = n >> 1;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
@@ -225,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void bicg_s_kernel(int64_t n, const double 
 {
     __shared__ double red[4];
     __shared__ double ddict[256];
-    if (it >= st->stop_it) return;
+    if (it >= st->stop_iter) return;
     const double sigma = fold_partials(sigma_partials, nparts, red);
     const double alpha = st->rho[it & 1] / sigma;
     // (a quotient that overflows counts as a breakdown too: x never receives a non-finite alpha)
@@ -233,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void bicg_s_kernel(int64_t n, const double 
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (bd2) {
             st->breakdown = 2;
-            st->stop_it = it;
+            st->stop_iter = it;
         } else {
             st->alpha = alpha;
         }
@@ -298,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void bicg_update_kernel(int64_t n, double *
                                                              int it, double rtol, double *partials_out)
 {
     __shared__ double red[4];
-    if (it >= st->stop_it) return;
+    if (it >= st->stop_iter) return;
     const double sn = sqrt(fold_partials(ss_partials, nparts, red));
     const double tau = fold_partials(tt_partials, nparts, red);
     const double theta = fold_partials(tt_partials + nparts, nparts, red);
@@ -313,7 +312,7 @@ __global__ __launch_bounds__(kBlock) void bicg_update_kernel(int64_t n, double *
         if (ends) {
             st->resn = sn;
             if (bd3) st->breakdown = 3;
-            st->stop_it = it + 1;  // this launch carries `it`: its other workgroups read "not yet"
+            st->stop_iter = it + 1;  // this launch carries `it`: its other workgroups read "not yet"
         } else {
             st->omega = omega;
         }
@@ -390,15 +389,14 @@ using namespace schwz;
 
 struct schwz_bicgstab {
     const schwz_csr *A = nullptr;
-    schwz_pcg *pre = nullptr;  // owns the preconditioner (and the SpMV partial-sum banks)
+    schwz_pcg *pre = nullptr;  // owns the preconditioner (and the SpMV partial-sum banks): adopted, destroyed by hand
     int64_t n = 0;
     bool diag = false;     // Jacobi: phat / shat stored by the direction and s launches
     bool general = false;  // block-Jacobi / ILU / ISAI: precond_apply between the launches
-    double *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *s = nullptr, *t = nullptr;
-    double *phat = nullptr, *shat = nullptr;  // p and s themselves without a preconditioner
-    double *part = nullptr;                   // 6 banks of kMaxGrid: sigma, ||s||^2, tau, theta, rhat.r, r.r
-    BicgState *state = nullptr, *h_state = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Dev<double> r, rhat, p, v, s, t;
+    Dev<double> phat, shat;  // (unallocated: p and s themselves, without a preconditioner)
+    Dev<double> part;        // 6 banks of kMaxGrid: sigma, ||s||^2, tau, theta, rhat.r, r.r
+    StateMirror<BicgState> state;
     int variant = 0;
 };
 
@@ -415,29 +413,17 @@ int bicgstab_create_adopt(const schwz_csr *A, schwz_pcg *pre, schwz_bicgstab **o
     s->diag = pre->precond == SCHWZ_PRECOND_JACOBI && pre->diag.mode != 0;
     s->general = pre->precond != SCHWZ_PRECOND_NONE && !s->diag;
     const size_t ld = (size_t)((s->n + 1) & ~int64_t(1));  // whole 16-byte elements
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16);
-    };
-    for (double **vec : {&s->r, &s->rhat, &s->p, &s->v, &s->s, &s->t}) alloc((void **)vec, sizeof(double) * ld);
-    if (s->diag || s->general) {
-        alloc((void **)&s->phat, sizeof(double) * ld);
-        alloc((void **)&s->shat, sizeof(double) * ld);
-    }
-    alloc((void **)&s->part, sizeof(double) * 6 * kMaxGrid);
-    alloc((void **)&s->state, sizeof(BicgState));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_state, 2 * sizeof(BicgState), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemset(s->state, 0, sizeof(BicgState));
-    if (e != hipSuccess) {
-        set_error(std::string("schwz_bicgstab_create: ") + hipGetErrorString(e));
+    int rc = SCHWZ_OK;
+    for (Dev<double> *vec : {&s->r, &s->rhat, &s->p, &s->v, &s->s, &s->t})
+        if (!rc) rc = vec->alloc(ld);
+    if (!rc && (s->diag || s->general) && !(rc = s->phat.alloc(ld))) rc = s->shat.alloc(ld);
+    if (!rc && !(rc = s->part.alloc(6 * kMaxGrid))) rc = s->state.create();
+    if (rc) {
         (void)hipGetLastError();
         s->pre = nullptr;
         schwz_bicgstab_destroy(s);
-        return SCHWZ_ERR_HIP;
+        return rc;
     }
-    std::memset(s->h_state, 0, 2 * sizeof(BicgState));
     *out = s;
     return SCHWZ_OK;
 }
@@ -473,11 +459,6 @@ int schwz_bicgstab_create(const schwz_csr *A, int precond, int block_size, int p
 void schwz_bicgstab_destroy(schwz_bicgstab *s)
 {
     if (!s) return;
-    void *ptrs[] = {s->r, s->rhat, s->p, s->v, s->s, s->t, s->phat, s->shat, s->part, s->state};
-    for (void *p : ptrs) (void)hipFree(p);
-    if (s->h_state) (void)hipHostFree(s->h_state);
-    for (hipEvent_t ev : s->ev)
-        if (ev) (void)hipEventDestroy(ev);
     schwz_pcg_destroy(s->pre);
     delete s;
 }
@@ -485,22 +466,20 @@ void schwz_bicgstab_destroy(schwz_bicgstab *s)
 int schwz_bicgstab_last_stats(schwz_bicgstab *s, int *h_iters, double *h_resnorm)
 {
     SCHWZ_REQUIRE(s && h_iters && h_resnorm, "schwz_bicgstab_last_stats: null argument");
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    SCHWZ_HIP_TRY(hipMemcpy(&s->h_state[0], s->state, sizeof(BicgState), hipMemcpyDeviceToHost));
-    *h_iters = s->h_state[0].iters;
-    *h_resnorm = s->h_state[0].resn;
+    if (const int rc = s->state.read_blocking()) return rc;
+    *h_iters = s->state.host(0).iters;
+    *h_resnorm = s->state.host(0).resn;
     return SCHWZ_OK;
 }
 
 int schwz_bicgstab_breakdown(schwz_bicgstab *s)
 {
     if (!s) return 0;
-    if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(&s->h_state[0], s->state, sizeof(BicgState), hipMemcpyDeviceToHost) != hipSuccess) {
+    if (s->state.read_blocking()) {
         set_error("schwz_bicgstab_breakdown: the state could not be read");
         return -1;
     }
-    return s->h_state[0].breakdown;
+    return s->state.host(0).breakdown;
 }
 
 #define BICG_LAUNCH(kernel_u1, kernel_u2, grid, ...)                                           \
@@ -541,8 +520,9 @@ int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, doub
     a.partials = s->pre->partials;
     a.stream_part = s->pre->stream_part;
     if ((rc = launch_spmv(A, kSpmvResidInit, a, s->variant, st))) return rc;
-    int pending = -1, slot = 0;
-    for (int k = 0;; ++k) {
+    bool stopped = false;
+    s->state.begin();
+    for (int k = 0; !stopped; ++k) {
         const int first = k == 0 ? 1 : 0;
         const bool closing = k >= max_iters;  // folds ||r|| and decides: one workgroup, which stores no vector
         const double *rho_in = first ? s->pre->partials + gs : rho;
@@ -550,10 +530,10 @@ int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, doub
         const int nparts = first ? gs : gv;
         if (s->diag)
             BICG_LAUNCH((bicg_direction_kernel<1, true>), (bicg_direction_kernel<2, true>), closing ? 1 : gv, n, s->p,
-                        s->r, s->v, s->phat, s->rhat, dg, rho_in, rr_in, nparts, s->state, k, rtol, max_iters, first);
+                        s->r, s->v, s->phat, s->rhat, dg, rho_in, rr_in, nparts, s->state.dev(), k, rtol, max_iters, first);
         else
             BICG_LAUNCH((bicg_direction_kernel<1, false>), (bicg_direction_kernel<2, false>), closing ? 1 : gv, n, s->p,
-                        s->r, s->v, (double *)nullptr, s->rhat, dg, rho_in, rr_in, nparts, s->state, k, rtol, max_iters,
+                        s->r, s->v, (double *)nullptr, s->rhat, dg, rho_in, rr_in, nparts, s->state.dev(), k, rtol, max_iters,
                         first);
         if (closing) break;
         if (s->general && (rc = precond_apply(s->pre, s->p, s->phat, st))) return rc;
@@ -562,42 +542,34 @@ int schwz_bicgstab_solve(schwz_bicgstab *s, const double *d_b, double *d_x, doub
         q.y = s->v;
         q.partials = s->pre->partials;  // phat . v, unused
         q.stream_part = s->pre->stream_part;
-        q.stop_iter = &s->state->stop_it;
+        q.stop_iter = &s->state.dev()->stop_iter;
         q.it = k;
         if ((rc = launch_spmv(A, kSpmvDot, q, s->variant, st))) return rc;
-        BICG_LAUNCH((bicg_dot_kernel<1, false>), (bicg_dot_kernel<2, false>), gv, n, s->rhat, s->v, sig, s->state, k);
+        BICG_LAUNCH((bicg_dot_kernel<1, false>), (bicg_dot_kernel<2, false>), gv, n, s->rhat, s->v, sig, s->state.dev(), k);
         if (s->diag)
             BICG_LAUNCH((bicg_s_kernel<1, true>), (bicg_s_kernel<2, true>), gv, n, s->r, s->v, s->s, s->shat, dg, sig, gv,
-                        s->state, k, ssq);
+                        s->state.dev(), k, ssq);
         else
             BICG_LAUNCH((bicg_s_kernel<1, false>), (bicg_s_kernel<2, false>), gv, n, s->r, s->v, s->s,
-                        (double *)nullptr, dg, sig, gv, s->state, k, ssq);
+                        (double *)nullptr, dg, sig, gv, s->state.dev(), k, ssq);
         // (speculative when the half step ends the solve: nothing reads shat and t then)
         if (s->general && (rc = precond_apply(s->pre, s->s, s->shat, st))) return rc;
         q.x = shat;
         q.y = s->t;
         if ((rc = launch_spmv(A, kSpmvDot, q, s->variant, st))) return rc;
-        BICG_LAUNCH((bicg_dot_kernel<1, true>), (bicg_dot_kernel<2, true>), gv, n, s->t, s->s, tt, s->state, k);
+        BICG_LAUNCH((bicg_dot_kernel<1, true>), (bicg_dot_kernel<2, true>), gv, n, s->t, s->s, tt, s->state.dev(), k);
         BICG_LAUNCH((bicg_update_kernel<1>), (bicg_update_kernel<2>), gv, n, d_x, s->r, s->s, s->t, phat, shat, s->rhat,
-                    ssq, tt, gv, s->state, k, rtol, rho);
+                    ssq, tt, gv, s->state.dev(), k, rtol, rho);
         SCHWZ_HIP_TRY(hipGetLastError());
         if ((k + 1) % kBicgBatch != 0 || k + 1 >= max_iters) continue;
         // the host reads the state one batch behind the launches
-        if (pending >= 0) {
-            SCHWZ_HIP_TRY(hipEventSynchronize(s->ev[pending]));
-            if (s->h_state[pending].stop_it != INT_MAX) break;
-        }
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[slot], s->state, sizeof(BicgState), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipEventRecord(s->ev[slot], st));
-        pending = slot;
-        slot ^= 1;
+        if ((rc = s->state.poll(st, &stopped))) return rc;
     }
     SCHWZ_HIP_TRY(hipGetLastError());
     if (h_iters || h_resnorm) {
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(BicgState), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-        if (h_iters) *h_iters = s->h_state[0].iters;
-        if (h_resnorm) *h_resnorm = s->h_state[0].resn;
+        if ((rc = s->state.read(st))) return rc;
+        if (h_iters) *h_iters = s->state.host(0).iters;
+        if (h_resnorm) *h_resnorm = s->state.host(0).resn;
     }
     return SCHWZ_OK;
 }

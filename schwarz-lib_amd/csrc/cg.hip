@@ -577,7 +577,7 @@ static int pcg_setup_general(schwz_pcg *s)
         if (!val.empty())
             SCHWZ_HIP_TRY(hipMemcpy(val.data(), A.val, val.size() * sizeof(double), hipMemcpyDeviceToHost));
     }
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->z, (size_t)(n ? n : 1) * sizeof(double)));
+    if (const int rc_z = s->z.alloc((size_t)n)) return rc_z;
     if (s->precond == SCHWZ_PRECOND_ILU || s->precond == SCHWZ_PRECOND_ISAI) {
         schwz_idx *l_rp, *l_col, *u_rp, *u_col;
         double *l_val, *u_val;
@@ -600,10 +600,7 @@ static int pcg_setup_general(schwz_pcg *s)
             if (!rc) rc = schwz_isai(n, u_rp, u_col, u_val, 0, &wu);
             if (!rc) rc = schwz_csr_create(n, n, l_rp, l_col, wl, &s->isai_l);
             if (!rc) rc = schwz_csr_create(n, n, u_rp, u_col, wu, &s->isai_u);
-            if (!rc && hipMalloc((void **)&s->isai_tmp, (size_t)(n ? n : 1) * sizeof(double)) != hipSuccess) {
-                set_error("schwz_pcg_create: out of device memory (ISAI work vector)");
-                rc = SCHWZ_ERR_HIP;
-            }
+            if (!rc) rc = s->isai_tmp.alloc((size_t)n);
             schwz_free(wl);
             schwz_free(wu);
         } else if (s->trisolve_sweeps > 0) {
@@ -732,36 +729,23 @@ static int pcg_setup_general(schwz_pcg *s)
         id[(size_t)b] = found;
     }
     int rc;
-    void *d;
-    if ((rc = upload(id.data(), id.size(), &d))) return rc;
-    s->d_blk_id = (schwz_idx *)d;
-    if ((rc = upload(uniq.data(), uniq.size(), &d))) return rc;
-    s->d_blk_inv = (double *)d;
-    if (!uniform) {
-        if ((rc = upload(row_blk.data(), row_blk.size(), &d))) return rc;
-        s->d_row_blk = (schwz_idx *)d;
-        if ((rc = upload(bptr.data(), bptr.size(), &d))) return rc;
-        s->d_blk_ptr = (schwz_idx *)d;
-    }
+    if ((rc = s->d_blk_id.put(id)) || (rc = s->d_blk_inv.put(uniq))) return rc;
+    if (!uniform && ((rc = s->d_row_blk.put(row_blk)) || (rc = s->d_blk_ptr.put(bptr)))) return rc;
     return SCHWZ_OK;
 }
 
 // everything of schwz_pcg_create_ex that can fail half way: the caller destroys `s` on error
 static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
 {
-    const size_t nb = (size_t)(s->n ? s->n : 1) * sizeof(double);
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->r, nb));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->p, nb));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->q, nb));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->partials, sizeof(double) * 8 * kMaxGrid));
-    s->stream_part = stream_part_alloc(A->v);
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->d_norm_sq, sizeof(double) * 2));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->state, sizeof(CgState)));
-    SCHWZ_HIP_TRY(hipHostMalloc((void **)&s->h_state, 2 * sizeof(CgState), hipHostMallocDefault));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
+    const size_t n = (size_t)s->n;
+    int rc;
+    if ((rc = s->r.alloc(n)) || (rc = s->p.alloc(n)) || (rc = s->q.alloc(n)) || (rc = s->partials.alloc(8 * kMaxGrid)))
+        return rc;
+    s->stream_part.p = stream_part_alloc(A->v);
+    if ((rc = s->norm_sq_own.alloc(2)) || (rc = s->state.create())) return rc;
+    s->d_norm_sq = s->norm_sq_own;
     if (precond == SCHWZ_PRECOND_JACOBI) {
-        SCHWZ_HIP_TRY(hipMalloc((void **)&s->dinv, nb));
+        if ((rc = s->dinv.alloc(n))) return rc;
         if (s->n) {
             hipLaunchKernelGGL(extract_dinv_kernel, dim3(grid_for(s->n)), dim3(kBlock), 0, 0, A->v, s->dinv);
             SCHWZ_HIP_TRY(hipGetLastError());
@@ -799,20 +783,16 @@ static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
             } else if (ok && dict.size() <= 16 && !A->v.pair_id) {  // linear search above stays cheap
                 // (row-pair coded matrices keep the full vector: their q-free iteration reads it as
                 // such and beats the stored-q iteration the codes would select)
-                int rc;
-                if ((rc = upload(code.data(), code.size(), &s->d_dcode)) ||
-                    (rc = upload(dict.data(), dict.size(), &s->d_ddict)))
-                    return rc;
+                if ((rc = s->d_dcode.put(code)) || (rc = s->d_ddict.put(dict))) return rc;
                 s->diag.mode = 2;
-                s->diag.code = (const uint8_t *)s->d_dcode;
-                s->diag.dict = (const double *)s->d_ddict;
+                s->diag.code = s->d_dcode.as<uint8_t>();
+                s->diag.dict = s->d_ddict.as<double>();
                 s->diag.ndict = (int)dict.size();
             }
         }
     }
     if (precond == SCHWZ_PRECOND_BLOCK_JACOBI || precond == SCHWZ_PRECOND_ILU || precond == SCHWZ_PRECOND_ISAI) {
-        int rc = pcg_setup_general(s);
-        if (rc) return rc;
+        if ((rc = pcg_setup_general(s))) return rc;
     }
     return SCHWZ_OK;
 }
@@ -873,37 +853,13 @@ int schwz::pcg_create_impl(const schwz_csr *A, int precond, int block_size, int 
 
 extern "C" {
 
+// the adopted objects, then the solver: its buffers, events, streams and recorded graphs release themselves
 void schwz_pcg_destroy(schwz_pcg *s)
 {
     if (!s) return;
-    if (s->prio_event) (void)hipEventDestroy(s->prio_event);
-    (void)hipFree(s->r);
-    (void)hipFree(s->r_alt);
-    (void)hipFree(s->p);
-    (void)hipFree(s->q);
-    (void)hipFree(s->p_ring);
-    (void)hipFree(s->alpha_hist);
-    (void)hipFree(s->dinv);
-    (void)hipFree(s->z);
-    (void)hipFree(s->d_blk_id);
-    (void)hipFree(s->d_blk_inv);
-    (void)hipFree(s->d_row_blk);
-    (void)hipFree(s->d_blk_ptr);
-    for (auto &g : s->graphs) (void)hipGraphExecDestroy(g.exec);
-    if (s->capture_stream) (void)hipStreamDestroy(s->capture_stream);
     schwz_trs_destroy(s->ilu);
     schwz_csr_destroy(s->isai_l);
     schwz_csr_destroy(s->isai_u);
-    (void)hipFree(s->isai_tmp);
-    (void)hipFree(s->d_dcode);
-    (void)hipFree(s->d_ddict);
-    (void)hipFree(s->partials);
-    (void)hipFree(s->stream_part);
-    (void)hipFree(s->d_norm_sq);
-    (void)hipFree(s->state);
-    (void)hipHostFree(s->h_state);
-    if (s->ev[0]) (void)hipEventDestroy(s->ev[0]);
-    if (s->ev[1]) (void)hipEventDestroy(s->ev[1]);
     delete s;
 }
 
@@ -966,10 +922,9 @@ int pcg_last_stats(schwz_pcg *s, int *h_iters, double *h_resnorm)
 {
     const int rc_lazy = pcg_finish_lazy(s);
     if (rc_lazy) return rc_lazy;
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    SCHWZ_HIP_TRY(hipMemcpy(&s->h_state[0], s->state, sizeof(CgState), hipMemcpyDeviceToHost));
-    *h_iters = s->h_state[0].iters;
-    *h_resnorm = sqrt(s->h_state[0].rr);
+    if (const int rc = s->state.read_blocking()) return rc;
+    *h_iters = s->state.host(0).iters;
+    *h_resnorm = sqrt(s->state.host(0).rr);
     if (*h_resnorm != *h_resnorm) return pcg_take_trs_error(s);
     return SCHWZ_OK;
 }
@@ -1092,21 +1047,18 @@ static int pcg_plan_flavour(const CgPlan &pl, int diag_mode)
 // residual -- the stored first direction.
 static bool pcg_acquire_buffers(schwz_pcg *s, CgPlan &pl)
 {
-    const size_t nb = (size_t)((s->n + 1) & ~int64_t(1)) * sizeof(double);
+    const size_t n_pad = (size_t)((s->n + 1) & ~int64_t(1));
     if (pl.deferx && !s->p_ring) {
         s->ring_has_q = pl.qfree;
-        if (hipMalloc((void **)&s->p_ring, nb * (kDeferDepth - (pl.qfree ? 2 : 1))) != hipSuccess ||
-            hipMalloc((void **)&s->alpha_hist, kDeferDepth * sizeof(double)) != hipSuccess) {
+        if (s->p_ring.alloc(n_pad * (kDeferDepth - (pl.qfree ? 2 : 1))) || s->alpha_hist.alloc(kDeferDepth)) {
             (void)hipGetLastError();
-            (void)hipFree(s->p_ring);
-            s->p_ring = nullptr;
+            s->p_ring = Dev<double>();
             s->ring_failed = true;
             return false;
         }
     }
-    if (pl.p0_virtual && !s->r_alt && hipMalloc((void **)&s->r_alt, nb) != hipSuccess) {
+    if (pl.p0_virtual && !s->r_alt && s->r_alt.alloc(n_pad)) {
         (void)hipGetLastError();
-        s->r_alt = nullptr;
         pl.p0_virtual = false;
     }
     return true;
@@ -1174,13 +1126,13 @@ int pcg_begin(schwz_pcg *s, const double *d_b, double *d_x, double rtol, bool fu
         const int gv = grid_for(s->n);
         double *part_vec = s->partials + 3 * kMaxGrid;
         hipLaunchKernelGGL(dot_rz_kernel, dim3(gv), dim3(kBlock), 0, st, s->n, s->r, s->z, s->p, nullptr, 0, part_vec);
-        hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state, part_vec, gv, rtol, nullptr,
+        hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(), part_vec, gv, rtol, nullptr,
                            1);
         SCHWZ_HIP_TRY(hipGetLastError());
         return SCHWZ_OK;
     }
     if (s->init.pending) return SCHWZ_OK;  // pcg_iterate: the first-direction launch (or, without one, this kernel there)
-    hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state, s->partials, gs, rtol,
+    hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(), s->partials, gs, rtol,
                        fused ? s->d_norm_sq : nullptr, same ? 1 : 2);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
@@ -1252,7 +1204,7 @@ struct CgSolve {
         fx.n = n;
         fx.x = s->x_out ? s->x_out : d_x;
         fx.alpha_hist = s->alpha_hist;
-        fx.st = s->state;
+        fx.st = s->state.dev();
         fx.fused = pl.qfree ? 0 : 1;  // how the in-launch update of this iteration forms x + alpha p
         fx.pq_partials = part_spmv;   // p.(A p) of the last iteration: SpMV bank 0, gs slots
         fx.pq_nparts = gs;
@@ -1325,7 +1277,7 @@ struct CgSolve {
         a.y = s->q;
         a.partials = part_spmv;
         a.stream_part = s->stream_part;
-        a.stop_iter = &s->state->stop_iter;
+        a.stop_iter = &s->state.dev()->stop_iter;
         a.it = it;
         return profiled(live, 0, q, [&] { return launch_spmv(A, pl.dot_mode, a, s->variant, q); });
     }
@@ -1339,7 +1291,7 @@ struct CgSolve {
         u.cg_x = pl.deferx ? nullptr : d_x;
         u.alpha_out = pl.deferx ? s->alpha_hist + it % kDeferDepth : nullptr;
         u.cg_r = s->r;
-        u.cg_state = s->state;
+        u.cg_state = s->state.dev();
         u.pq_partials = part_spmv;
         u.pq_nparts = gs;
         u.diag_mode = s->diag.mode;
@@ -1363,7 +1315,7 @@ struct CgSolve {
         f.x = pl.deferx ? slot(it) : pbuf[it & 1];
         f.y = pl.deferx ? slot(it + 1) : pbuf[(it + 1) & 1];
         f.cg_r = s->r;
-        f.cg_state = s->state;
+        f.cg_state = s->state.dev();
         f.pq_partials = part_vec;
         f.pq_nparts = gs;
         f.diag_mode = s->diag.mode;
@@ -1389,7 +1341,7 @@ struct CgSolve {
     void launch_update_deferred(int it, hipStream_t q) const
     {
         hipLaunchKernelGGL((cg_update_kernel<1, false, true>), dim3(gv), dim3(kBlock), 0, q, n, (double *)nullptr, s->r,
-                           (const double *)nullptr, s->q, s->diag, part_spmv, gs, s->state, it, part_vec,
+                           (const double *)nullptr, s->q, s->diag, part_spmv, gs, s->state.dev(), it, part_vec,
                            s->alpha_hist + it % kDeferDepth);
     }
 
@@ -1406,14 +1358,14 @@ struct CgSolve {
                 if (pl.vlast)
                     hipLaunchKernelGGL(cg_rebuild_direction_kernel, dim3(gv), dim3(kBlock), 0, qq, n,
                                        (const double *)slot(it > 0 ? it - 1 : 0), it == 1 ? fx.p0_scale : 1.0,
-                                       (const double *)s->r, s->diag.mode, s->diag.uniform, (const CgState *)s->state, it,
+                                       (const double *)s->r, s->diag.mode, s->diag.uniform, (const CgState *)s->state.dev(), it,
                                        slot(it));
                 const int rc = launch_spmv(A, kSpmvCgUpdate, qfree_update_args(it, false), s->variant, qq);
                 if (rc) return rc;
             } else {
                 launch_update_deferred(it, qq);
             }
-            hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, qq, part_vec, update_parts(), s->state, it,
+            hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, qq, part_vec, update_parts(), s->state.dev(), it,
                                rtol);
             SCHWZ_HIP_TRY(hipGetLastError());
             return SCHWZ_OK;
@@ -1431,11 +1383,11 @@ struct CgSolve {
         if (lazy_now)
             postpone_last(it, q);
         else if (last)
-            hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, q, part_vec, update_parts(), s->state, it,
+            hipLaunchKernelGGL(cg_state_advance_kernel, dim3(1), dim3(kBlock), 0, q, part_vec, update_parts(), s->state.dev(), it,
                                rtol);
         else
             hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, slot(it), s->r, s->diag,
-                               part_vec, update_parts(), s->state, it, rtol, slot(it + 1));
+                               part_vec, update_parts(), s->state.dev(), it, rtol, slot(it + 1));
     }
 
     // q-free iteration (row-pair coded matrices): the update launch, then the fused direction + p.(A p) launch
@@ -1458,7 +1410,7 @@ struct CgSolve {
             close_deferred(it, q, lazy_now, last);
         else
             hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, pbuf[it & 1], s->r,
-                               s->diag, part_vec, gs, s->state, it, rtol);
+                               s->diag, part_vec, gs, s->state.dev(), it, rtol);
         return SCHWZ_OK;
     }
 
@@ -1479,16 +1431,16 @@ struct CgSolve {
         const DiagView none;
         const DiagView &dg = pl.general ? none : s->diag;
         hipLaunchKernelGGL((cg_update_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, d_x, s->r, s->p, s->q, dg,
-                           part_spmv, gs, s->state, it, part_vec);
+                           part_spmv, gs, s->state.dev(), it, part_vec);
         const int gz = pl.general ? grid_for(n) : gv;
         if (pl.general) {
             const int rc = pcg_apply_general(s, q);
             if (rc) return rc;
-            hipLaunchKernelGGL(dot_rz_kernel, dim3(gz), dim3(kBlock), 0, q, n, s->r, s->z, (double *)nullptr, s->state, it,
+            hipLaunchKernelGGL(dot_rz_kernel, dim3(gz), dim3(kBlock), 0, q, n, s->r, s->z, (double *)nullptr, s->state.dev(), it,
                                part_vec);
         }
         hipLaunchKernelGGL((cg_direction_kernel<1, false>), dim3(gv), dim3(kBlock), 0, q, n, s->p, pl.general ? s->z : s->r,
-                           dg, part_vec, gz, s->state, it, rtol);
+                           dg, part_vec, gz, s->state.dev(), it, rtol);
         return SCHWZ_OK;
     }
 
@@ -1510,7 +1462,8 @@ struct CgSolve {
         for (const auto &g : s->graphs)
             if (g.x == d_x && g.rtol == rtol && g.variant == s->variant && g.flavour == pl.flavour) *out = g.exec;
         if (*out || s->graphs.size() >= 4) return SCHWZ_OK;
-        if (!s->capture_stream) SCHWZ_HIP_TRY(hipStreamCreateWithFlags(&s->capture_stream, hipStreamNonBlocking));
+        int rc_cs;
+        if (!s->capture_stream && (rc_cs = s->capture_stream.create())) return rc_cs;
         if (hipStreamBeginCapture(s->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             int rc = SCHWZ_OK;
             for (int k = 0; k < kGraphIters && !rc; ++k) rc = iterate(k, s->capture_stream, false);
@@ -1521,7 +1474,7 @@ struct CgSolve {
                 return rc;
             }
             if (e1 == hipSuccess && hipGraphInstantiate(out, graph, nullptr, nullptr, 0) == hipSuccess)
-                s->graphs.push_back({d_x, rtol, s->variant, pl.flavour, *out});
+                s->graphs.push_back({d_x, rtol, s->variant, pl.flavour, GraphExec(*out)});
             else
                 *out = nullptr;
             if (graph) (void)hipGraphDestroy(graph);
@@ -1538,13 +1491,13 @@ struct CgSolve {
         a.it = 0;
         if (!pl.walk_started) {
             a.x = s->p;
-            a.stop_iter = &s->state->stop_iter;
+            a.stop_iter = &s->state.dev()->stop_iter;
             return launch_spmv(A, kSpmvDotSym, a, s->variant, st);
         }
         // z-sweep start: p0 = D^-1 r0 is built here, from the r the launch reads anyway
         a.y = pl.p0_virtual ? nullptr : slot(0);
         a.cg_r = s->r;
-        a.cg_state = s->state;
+        a.cg_state = s->state.dev();
         a.diag_mode = s->diag.mode;
         a.diag_uniform = s->diag.uniform;
         a.sweep_first = 1;
@@ -1590,7 +1543,7 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
     if (pl.fusedir && max_iters > 0 && (rc = cg.first_dot())) return rc;
     if (s->init.pending && !(pl.fusedir && max_iters > 0 && pl.walk_started)) {
         // no first-direction launch took the fold of the start launch's partial sums along: the kernel of its own
-        hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state, s->init.partials, s->init.nparts,
+        hipLaunchKernelGGL(cg_init_finalize_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(), s->init.partials, s->init.nparts,
                            s->init.rtol, s->init.norm_sq_out, s->init.norm_bank);
         SCHWZ_HIP_TRY(hipGetLastError());
     }
@@ -1601,11 +1554,12 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
         s->init_event = nullptr;
     }
     s->p_pending = false;
-    int chunk = 16;
-    int it = 0, pending = -1, bank = 0;
+    ChunkSchedule chunks;
+    int it = 0;
     bool stopped = false;
+    s->state.begin();
     while (it < max_iters && !stopped) {
-        const int end = (poll && it + chunk < max_iters) ? it + chunk : max_iters;
+        const int end = chunks.end(it, max_iters, poll);
         while (it < end) {
             if (replay && it % kGraphIters == 0 && end - it >= kGraphIters) {
                 SCHWZ_HIP_TRY(hipGraphLaunch(replay, st));
@@ -1617,15 +1571,8 @@ int pcg_iterate(schwz_pcg *s, double *d_x, double rtol, int max_iters, hipStream
         }
         SCHWZ_HIP_TRY(hipGetLastError());
         if (poll && it < max_iters) {
-            if (pending >= 0) {
-                SCHWZ_HIP_TRY(hipEventSynchronize(s->ev[pending]));
-                if (s->h_state[pending].stop_iter != INT_MAX) stopped = true;
-            }
-            SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[bank], s->state, sizeof(CgState), hipMemcpyDeviceToHost, st));
-            SCHWZ_HIP_TRY(hipEventRecord(s->ev[bank], st));
-            pending = bank;
-            bank ^= 1;
-            if (chunk < 64) chunk *= 2;
+            if ((rc = s->state.poll(st, &stopped))) return rc;
+            chunks.grow();
         }
     }
     // the increments of the last, partly filled ring (iterations past a tolerance stop are not
@@ -1668,11 +1615,11 @@ int schwz_pcg_solve(schwz_pcg *s, const double *d_b, double *d_x, double rtol, i
     if ((rc = pcg_iterate(s, d_x, rtol, max_iters, st))) return rc;
     if (h_iters || h_resnorm) {
         if ((rc = pcg_finish_lazy(s))) return rc;
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(CgState), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-        if (h_iters) *h_iters = s->h_state[0].iters;
-        if (h_resnorm) *h_resnorm = sqrt(s->h_state[0].rr);
-        if (s->h_state[0].rr != s->h_state[0].rr) return pcg_take_trs_error(s);
+        if ((rc = s->state.read(st))) return rc;
+        const CgState &h = s->state.host(0);
+        if (h_iters) *h_iters = h.iters;
+        if (h_resnorm) *h_resnorm = sqrt(h.rr);
+        if (h.rr != h.rr) return pcg_take_trs_error(s);
     }
     return SCHWZ_OK;
 }

@@ -333,13 +333,11 @@ struct schwz_pcg_f32 {
     const schwz_csr *A = nullptr;
     int precond = 0;
     int64_t n = 0;
-    float *val32 = nullptr;  // nnz + 4 (the 16-byte loads of a tile's last quad may touch the padding)
-    float *r = nullptr, *p = nullptr, *q = nullptr, *e = nullptr, *dinv = nullptr;
-    double *y = nullptr;     // A x of the start residual
-    double *part = nullptr;  // 4 banks of kMaxGrid partial sums: ||b - A x||^2, p.q, and r.z with r.r
-    CgStateF32 *state = nullptr;
-    CgStateF32 *h_state = nullptr;  // pinned, 2 slots
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Dev<float> val32;  // nnz + 4 (the 16-byte loads of a tile's last quad may touch the padding)
+    Dev<float> r, p, q, e, dinv;
+    Dev<double> y;     // A x of the start residual
+    Dev<double> part;  // 4 banks of kMaxGrid partial sums: ||b - A x||^2, p.q, and r.z with r.r
+    StateMirror<CgStateF32> state;
     int gs = 0, gv = 0;  // grids of the SpMV launch and of the vector launches, both <= kMaxGrid
     int seq = 0;         // tiles per short-lived workgroup of the stream kernel; 0: persistent workgroups
     double *part_norm() const { return part; }
@@ -351,7 +349,7 @@ static int pcg_f32_build(schwz_pcg_f32 *s)
 {
     const CsrView &A = s->A->v;
     const int64_t n = s->n, nnz = A.nnz;
-    const size_t nb = (size_t)(n ? n + 4 : 4) * sizeof(float);
+    const size_t nv = (size_t)n + 4;  // entries of a vector
     // Every grid holds at most kMaxGrid workgroups, so that the workgroups of the next launch can fold its partial
     // sums themselves.  Vector launches: one quad per lane up to 4 * kBlock * kMaxGrid = 2 M entries, grid-stride
     // beyond.  Stream kernel: short-lived workgroups of kSeq32 consecutive tiles while such a grid fits (up to
@@ -364,31 +362,21 @@ static int pcg_f32_build(schwz_pcg_f32 *s)
     } else {
         s->gs = grid_for(n);
     }
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->val32, (size_t)(nnz + 4) * sizeof(float)));
-    SCHWZ_HIP_TRY(hipMemset(s->val32, 0, (size_t)(nnz + 4) * sizeof(float)));
-    for (float **v : {&s->r, &s->p, &s->q, &s->e}) {
-        SCHWZ_HIP_TRY(hipMalloc((void **)v, nb));
-        SCHWZ_HIP_TRY(hipMemset(*v, 0, nb));
-    }
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->y, (size_t)(n ? n : 1) * sizeof(double)));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->part, (size_t)4 * kMaxGrid * sizeof(double)));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->state, sizeof(CgStateF32)));
-    SCHWZ_HIP_TRY(hipMemset(s->state, 0, sizeof(CgStateF32)));
-    SCHWZ_HIP_TRY(hipHostMalloc((void **)&s->h_state, 2 * sizeof(CgStateF32), hipHostMallocDefault));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
+    int rc;
+    if ((rc = s->val32.alloc((size_t)nnz + 4, true))) return rc;
+    for (Dev<float> *v : {&s->r, &s->p, &s->q, &s->e})
+        if ((rc = v->alloc(nv, true))) return rc;
+    if ((rc = s->y.alloc((size_t)n)) || (rc = s->part.alloc((size_t)4 * kMaxGrid)) || (rc = s->state.create())) return rc;
     // the fp32 values, and whether every finite one stayed finite (read once, here)
-    unsigned long long *d_bad = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc((void **)&d_bad, sizeof(unsigned long long)));
+    Dev<unsigned long long> d_bad;
+    if ((rc = d_bad.alloc(1))) return rc;
     unsigned long long bad = ~0ull;
-    hipError_t err = hipMemcpy(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice);
-    if (err == hipSuccess && nnz > 0) {
+    SCHWZ_HIP_TRY(hipMemcpy(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice));
+    if (nnz > 0) {
         hipLaunchKernelGGL(f32_convert_kernel, dim3(grid_for(nnz)), dim3(kBlock), 0, 0, nnz, A.val, s->val32, d_bad);
-        err = hipGetLastError();
+        SCHWZ_HIP_TRY(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    SCHWZ_HIP_TRY(err);
+    SCHWZ_HIP_TRY(hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
     if (bad != ~0ull) {
         // name the entry: its row from the row pointers (error path only)
         std::vector<schwz_idx> rp((size_t)n + 1);
@@ -406,8 +394,7 @@ static int pcg_f32_build(schwz_pcg_f32 *s)
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
     if (s->precond == SCHWZ_PRECOND_JACOBI) {
-        SCHWZ_HIP_TRY(hipMalloc((void **)&s->dinv, nb));
-        SCHWZ_HIP_TRY(hipMemset(s->dinv, 0, nb));
+        if ((rc = s->dinv.alloc(nv, true))) return rc;
         if (n) {
             hipLaunchKernelGGL(f32_dinv_kernel, dim3(grid_for(n)), dim3(kBlock), 0, 0, A, s->dinv);
             SCHWZ_HIP_TRY(hipGetLastError());
@@ -424,11 +411,11 @@ static int launch_spmv_f32(schwz_pcg_f32 *s, const float *p, float *q, int it, h
     if (stream_takes(A)) {
         stream_cap_dispatch(A, [&](auto cap) {
             hipLaunchKernelGGL((f32_spmv_stream_kernel<decltype(cap)::value>), dim3(s->gs), dim3(kBlock), 0, st, A,
-                               (const float *)s->val32, p, q, (const CgStateF32 *)s->state, it, s->part_pq(), s->seq);
+                               (const float *)s->val32, p, q, (const CgStateF32 *)s->state.dev(), it, s->part_pq(), s->seq);
         });
     } else {
         hipLaunchKernelGGL(f32_spmv_rows_kernel, dim3(s->gs), dim3(kBlock), 0, st, A, (const float *)s->val32, p, q,
-                           (const CgStateF32 *)s->state, it, s->part_pq());
+                           (const CgStateF32 *)s->state.dev(), it, s->part_pq());
     }
     return SCHWZ_OK;
 }
@@ -461,17 +448,7 @@ int schwz_pcg_f32_create(const schwz_csr *A, int precond, schwz_pcg_f32 **out)
     return SCHWZ_OK;
 }
 
-void schwz_pcg_f32_destroy(schwz_pcg_f32 *s)
-{
-    if (!s) return;
-    for (void *ptr : {(void *)s->val32, (void *)s->r, (void *)s->p, (void *)s->q, (void *)s->e, (void *)s->dinv,
-                      (void *)s->y, (void *)s->part, (void *)s->state})
-        (void)hipFree(ptr);
-    if (s->h_state) (void)hipHostFree(s->h_state);
-    if (s->ev[0]) (void)hipEventDestroy(s->ev[0]);
-    if (s->ev[1]) (void)hipEventDestroy(s->ev[1]);
-    delete s;
-}
+void schwz_pcg_f32_destroy(schwz_pcg_f32 *s) { delete s; }
 
 int schwz_pcg_f32_solve(schwz_pcg_f32 *s, const double *d_b, double *d_x, double rtol, int max_iters, int *h_iters,
                         double *h_resnorm, schwz_stream stream)
@@ -496,50 +473,45 @@ int schwz_pcg_f32_solve(schwz_pcg_f32 *s, const double *d_b, double *d_x, double
     hipLaunchKernelGGL(f32_norm_kernel, gv, blk, 0, st, n, d_b, (const double *)s->y, s->part_norm());
     hipLaunchKernelGGL(f32_entry_kernel, gv, blk, 0, st, n, d_b, (const double *)s->y, (const float *)s->dinv, s->r,
                        s->p, s->e, (const double *)s->part_norm(), s->gv, s->part_vec());
-    hipLaunchKernelGGL(f32_init_state_kernel, dim3(1), blk, 0, st, s->state, (const double *)s->part_norm(), s->gv,
+    hipLaunchKernelGGL(f32_init_state_kernel, dim3(1), blk, 0, st, s->state.dev(), (const double *)s->part_norm(), s->gv,
                        (const double *)s->part_vec(), s->gv, rtol);
     SCHWZ_HIP_TRY(hipGetLastError());
-    // the control flow of pcg_iterate: with a tolerance, chunks of 16, 32, then 64 iterations and a poll of the
-    // pinned state copy one chunk behind; launches past the stop iteration return at once
+    // the control flow of pcg_iterate: with a tolerance, growing chunks of iterations (ChunkSchedule) and a poll of
+    // the pinned state copy one chunk behind; launches past the stop iteration return at once
     const bool poll = rtol > 0.0;
-    int chunk = 16, it = 0, pending = -1, bank = 0;
+    ChunkSchedule chunks;
+    int it = 0;
     bool stopped = false;
+    s->state.begin();
     while (it < max_iters && !stopped) {
-        const int end = (poll && it + chunk < max_iters) ? it + chunk : max_iters;
+        const int end = chunks.end(it, max_iters, poll);
         for (; it < end; ++it) {
             if ((rc = launch_spmv_f32(s, s->p, s->q, it, st))) return rc;
             hipLaunchKernelGGL(f32_update_kernel, gv, blk, 0, st, n, s->e, s->r, (const float *)s->p,
-                               (const float *)s->q, (const float *)s->dinv, (const CgStateF32 *)s->state, it,
+                               (const float *)s->q, (const float *)s->dinv, (const CgStateF32 *)s->state.dev(), it,
                                (const double *)s->part_pq(), s->gs, s->part_vec());
             if (it + 1 < max_iters)
                 hipLaunchKernelGGL(f32_direction_kernel<true>, gv, blk, 0, st, n, s->p, (const float *)s->r,
-                                   (const float *)s->dinv, s->state, it, rtol, (const double *)s->part_vec(), s->gv);
+                                   (const float *)s->dinv, s->state.dev(), it, rtol, (const double *)s->part_vec(), s->gv);
             else  // (the last iteration's direction is read by nobody: the state advance alone)
                 hipLaunchKernelGGL(f32_direction_kernel<false>, dim3(1), blk, 0, st, n, s->p, (const float *)s->r,
-                                   (const float *)s->dinv, s->state, it, rtol, (const double *)s->part_vec(), s->gv);
+                                   (const float *)s->dinv, s->state.dev(), it, rtol, (const double *)s->part_vec(), s->gv);
         }
         SCHWZ_HIP_TRY(hipGetLastError());
         if (poll && it < max_iters) {
-            if (pending >= 0) {
-                SCHWZ_HIP_TRY(hipEventSynchronize(s->ev[pending]));
-                if (s->h_state[pending].stop_iter != INT_MAX) stopped = true;
-            }
-            SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[bank], s->state, sizeof(CgStateF32), hipMemcpyDeviceToHost, st));
-            SCHWZ_HIP_TRY(hipEventRecord(s->ev[bank], st));
-            pending = bank;
-            bank ^= 1;
-            if (chunk < 64) chunk *= 2;
+            if ((rc = s->state.poll(st, &stopped))) return rc;
+            chunks.grow();
         }
     }
     if (max_iters > 0) {
-        hipLaunchKernelGGL(f32_exit_kernel, gv, blk, 0, st, n, d_x, (const float *)s->e, (const CgStateF32 *)s->state);
+        hipLaunchKernelGGL(f32_exit_kernel, gv, blk, 0, st, n, d_x, (const float *)s->e, (const CgStateF32 *)s->state.dev());
         SCHWZ_HIP_TRY(hipGetLastError());
     }
     if (h_iters || h_resnorm) {
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(CgStateF32), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-        if (h_iters) *h_iters = s->h_state[0].iters;
-        if (h_resnorm) *h_resnorm = s->h_state[0].nu * std::sqrt(s->h_state[0].rr);
+        if ((rc = s->state.read(st))) return rc;
+        const CgStateF32 &h = s->state.host(0);
+        if (h_iters) *h_iters = h.iters;
+        if (h_resnorm) *h_resnorm = h.nu * std::sqrt(h.rr);
     }
     return SCHWZ_OK;
 }
@@ -553,16 +525,15 @@ int schwz_pcg_f32_spmv(schwz_pcg_f32 *s, const float *d_p, float *d_q, double *h
         return SCHWZ_OK;
     }
     // a state no launch leaves early on
-    CgStateF32 &h = s->h_state[0];
+    CgStateF32 &h = s->state.host(0);
     h = CgStateF32();
     h.stop_iter = INT_MAX;
-    SCHWZ_HIP_TRY(hipMemcpyAsync(s->state, &h, sizeof(CgStateF32), hipMemcpyHostToDevice, st));
-    const int rc = launch_spmv_f32(s, d_p, d_q, 0, st);
+    SCHWZ_HIP_TRY(hipMemcpyAsync(s->state.dev(), &h, sizeof(CgStateF32), hipMemcpyHostToDevice, st));
+    int rc = launch_spmv_f32(s, d_p, d_q, 0, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(f32_fold_pq_kernel, dim3(1), dim3(kBlock), 0, st, s->state, (const double *)s->part_pq(), s->gs);
+    hipLaunchKernelGGL(f32_fold_pq_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(), (const double *)s->part_pq(), s->gs);
     SCHWZ_HIP_TRY(hipGetLastError());
-    SCHWZ_HIP_TRY(hipMemcpyAsync(&h, s->state, sizeof(CgStateF32), hipMemcpyDeviceToHost, st));
-    SCHWZ_HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = s->state.read(st))) return rc;
     if (h_pq) *h_pq = h.pq;
     return SCHWZ_OK;
 }
@@ -570,10 +541,9 @@ int schwz_pcg_f32_spmv(schwz_pcg_f32 *s, const float *d_p, float *d_q, double *h
 int schwz_pcg_f32_last_stats(schwz_pcg_f32 *s, int *h_iters, double *h_resnorm)
 {
     SCHWZ_REQUIRE(s && h_iters && h_resnorm, "schwz_pcg_f32_last_stats: null argument");
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    SCHWZ_HIP_TRY(hipMemcpy(&s->h_state[0], s->state, sizeof(CgStateF32), hipMemcpyDeviceToHost));
-    *h_iters = s->h_state[0].iters;
-    *h_resnorm = s->h_state[0].nu * std::sqrt(s->h_state[0].rr);
+    if (const int rc = s->state.read_blocking()) return rc;
+    *h_iters = s->state.host(0).iters;
+    *h_resnorm = s->state.host(0).nu * std::sqrt(s->state.host(0).rr);
     return SCHWZ_OK;
 }
 

@@ -291,11 +291,9 @@ struct schwz_cheb {
     int precond = 0;
     int64_t n = 0;
     double lmin = 0.0, lmax = 0.0;
-    double *r = nullptr, *d[2] = {nullptr, nullptr}, *dinv = nullptr;
-    double *part = nullptr;  // 2 banks of kMaxGrid partial sums: the NORM launches alternate
-    ChebState *state = nullptr;
-    ChebState *h_state = nullptr;  // pinned, 2 slots
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Dev<double> r, d[2], dinv;
+    Dev<double> part;  // 2 banks of kMaxGrid partial sums: the NORM launches alternate
+    StateMirror<ChebState> state;
     bool stream_ok = false;  // the tile pipeline takes the matrix
     int gs = 0, gv = 0;      // grids of the matrix launches and of the vector launch, both <= kMaxGrid
     int seq = kChebSeq;
@@ -341,7 +339,6 @@ static int cheb_build(schwz_cheb *s)
 {
     const CsrView &A = s->A->v;
     const int64_t n = s->n;
-    const size_t nb = (size_t)(n ? n : 1) * sizeof(double);
     // Every grid holds at most kMaxGrid workgroups, so that the workgroups of the next launch can fold its partial
     // sums themselves.  Row-per-lane kernels (fallback, vector launch, bound): one row per lane up to
     // kBlock * kMaxGrid = 524 288 rows, grid-stride beyond.  Tile pipeline: short-lived workgroups of kChebSeq
@@ -356,21 +353,11 @@ static int cheb_build(schwz_cheb *s)
     } else {
         s->gs = grid_for(n);
     }
-    for (double **v : {&s->r, &s->d[0], &s->d[1]}) {
-        SCHWZ_HIP_TRY(hipMalloc((void **)v, nb));
-        SCHWZ_HIP_TRY(hipMemset(*v, 0, nb));
-    }
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->part, (size_t)2 * kMaxGrid * sizeof(double)));
-    SCHWZ_HIP_TRY(hipMemset(s->part, 0, (size_t)2 * kMaxGrid * sizeof(double)));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&s->state, sizeof(ChebState)));
-    SCHWZ_HIP_TRY(hipMemset(s->state, 0, sizeof(ChebState)));
-    SCHWZ_HIP_TRY(hipHostMalloc((void **)&s->h_state, 2 * sizeof(ChebState), hipHostMallocDefault));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
-    if (s->precond == SCHWZ_PRECOND_JACOBI) {
-        SCHWZ_HIP_TRY(hipMalloc((void **)&s->dinv, nb));
-        SCHWZ_HIP_TRY(hipMemset(s->dinv, 0, nb));
-    }
+    int rc;
+    for (Dev<double> *v : {&s->r, &s->d[0], &s->d[1]})
+        if ((rc = v->alloc((size_t)n, true))) return rc;
+    if ((rc = s->part.alloc((size_t)2 * kMaxGrid, true)) || (rc = s->state.create())) return rc;
+    if (s->precond == SCHWZ_PRECOND_JACOBI && (rc = s->dinv.alloc((size_t)n, true))) return rc;
     if (n == 0) {
         s->lmax = 1.0;
         s->lmin = s->lmax / 30.0;
@@ -378,16 +365,14 @@ static int cheb_build(schwz_cheb *s)
     }
     // the bound (and 1 / diag): one slot per workgroup, the maximum taken here
     const int g = s->gv;
-    long long *d_bad = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc((void **)&d_bad, (size_t)g * sizeof(long long)));
+    Dev<long long> d_bad;
+    if ((rc = d_bad.alloc((size_t)g))) return rc;
     std::vector<double> h_max((size_t)g);
     std::vector<long long> h_bad((size_t)g);
     hipLaunchKernelGGL(cheb_bound_kernel, dim3(g), dim3(kBlock), 0, 0, A, s->dinv, s->part, d_bad);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpy(h_max.data(), s->part, (size_t)g * sizeof(double), hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(h_bad.data(), d_bad, (size_t)g * sizeof(long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    SCHWZ_HIP_TRY(err);
+    SCHWZ_HIP_TRY(hipGetLastError());
+    SCHWZ_HIP_TRY(hipMemcpy(h_max.data(), s->part, (size_t)g * sizeof(double), hipMemcpyDeviceToHost));
+    SCHWZ_HIP_TRY(hipMemcpy(h_bad.data(), d_bad, (size_t)g * sizeof(long long), hipMemcpyDeviceToHost));
     long long bad = LLONG_MAX;
     double lmax = 0.0;
     for (int i = 0; i < g; ++i) {
@@ -421,11 +406,10 @@ static int cheb_norm_now(schwz_cheb *s, const double *own, const double *g, hipS
     a.part = s->part;
     a.seq = s->seq;
     cheb_launch(s, kChebNormOnly, true, a, st);
-    hipLaunchKernelGGL(cheb_fold_kernel, dim3(1), dim3(kBlock), 0, st, s->state, (const double *)s->part, s->gs);
+    hipLaunchKernelGGL(cheb_fold_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(), (const double *)s->part, s->gs);
     SCHWZ_HIP_TRY(hipGetLastError());
-    SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(ChebState), hipMemcpyDeviceToHost, st));
-    SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-    s->last_rr = s->h_state[0].rr;
+    if (const int rc = s->state.read(st)) return rc;
+    s->last_rr = s->state.host(0).rr;
     s->norm_pending = false;
     return SCHWZ_OK;
 }
@@ -458,16 +442,7 @@ int schwz_cheb_create(const schwz_csr *A, int precond, schwz_cheb **out)
     return SCHWZ_OK;
 }
 
-void schwz_cheb_destroy(schwz_cheb *s)
-{
-    if (!s) return;
-    for (void *ptr : {(void *)s->r, (void *)s->d[0], (void *)s->d[1], (void *)s->dinv, (void *)s->part, (void *)s->state})
-        (void)hipFree(ptr);
-    if (s->h_state) (void)hipHostFree(s->h_state);
-    if (s->ev[0]) (void)hipEventDestroy(s->ev[0]);
-    if (s->ev[1]) (void)hipEventDestroy(s->ev[1]);
-    delete s;
-}
+void schwz_cheb_destroy(schwz_cheb *s) { delete s; }
 
 int schwz_cheb_bounds(const schwz_cheb *s, double *lmin, double *lmax)
 {
@@ -527,7 +502,7 @@ int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol,
     a.x = d_x;
     a.seq = s->seq;
     a.rtol = rtol;
-    a.st = tol ? s->state : nullptr;
+    a.st = tol ? s->state.dev() : nullptr;
     a.nchk = s->gs;
     // START: r_0 = b - A x_0, d_0 = (1 / theta) M^-1 r_0
     int cur = 0;
@@ -569,13 +544,15 @@ int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol,
     }
     // With a tolerance: launch k = 1 ... m produces iterate k; it checks iterate k - 1 where that one left its norm,
     // and leaves its own where k = 0 (mod SCHWZ_CHEB_CHECK_EVERY) or k = m.  The host control flow is that of
-    // schwz_pcg_f32_solve: chunks of 16, 32, then 64 launches and a poll of the pinned state copy one chunk behind;
-    // launches past the stop return at once.
+    // schwz_pcg_f32_solve: growing chunks of launches (ChunkSchedule) and a poll of the pinned state copy one chunk
+    // behind; launches past the stop return at once.
     s->fixed = false;
-    int chunk = 16, k = 1, pending = -1, bank = 0, nb = 0;
+    ChunkSchedule chunks;
+    int k = 1, nb = 0, rc;
     bool prev_norm = true, stopped = false;
+    s->state.begin();
     while (k <= m && !stopped) {
-        const int end = (k - 1 + chunk < m) ? k - 1 + chunk : m;
+        const int end = chunks.end(k - 1, m, true);
         for (; k <= end; ++k) {
             advance();
             const bool norm = (k % SCHWZ_CHEB_CHECK_EVERY) == 0 || k == m;
@@ -591,26 +568,18 @@ int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol,
         }
         SCHWZ_HIP_TRY(hipGetLastError());
         if (k <= m) {
-            if (pending >= 0) {
-                SCHWZ_HIP_TRY(hipEventSynchronize(s->ev[pending]));
-                if (s->h_state[pending].stop_iter != INT_MAX) stopped = true;
-            }
-            SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[bank], s->state, sizeof(ChebState), hipMemcpyDeviceToHost, st));
-            SCHWZ_HIP_TRY(hipEventRecord(s->ev[bank], st));
-            pending = bank;
-            bank ^= 1;
-            if (chunk < 64) chunk *= 2;
+            if ((rc = s->state.poll(st, &stopped))) return rc;
+            chunks.grow();
         }
     }
     // (after a stop the host may have ended between two norm launches: the finish kernel then leaves at once)
-    hipLaunchKernelGGL(cheb_finish_kernel, dim3(1), dim3(kBlock), 0, st, s->state,
+    hipLaunchKernelGGL(cheb_finish_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(),
                        (const double *)(s->part + (size_t)nb * kMaxGrid), s->gs, m);
     SCHWZ_HIP_TRY(hipGetLastError());
     if (h_iters || h_resnorm) {
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(ChebState), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-        if (h_iters) *h_iters = s->h_state[0].iters;
-        if (h_resnorm) *h_resnorm = std::sqrt(s->h_state[0].rr);
+        if ((rc = s->state.read(st))) return rc;
+        if (h_iters) *h_iters = s->state.host(0).iters;
+        if (h_resnorm) *h_resnorm = std::sqrt(s->state.host(0).rr);
     }
     return SCHWZ_OK;
 }
@@ -618,9 +587,9 @@ int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol,
 int schwz_cheb_last_stats(schwz_cheb *s, int *h_iters, double *h_resnorm)
 {
     SCHWZ_REQUIRE(s && h_iters && h_resnorm, "schwz_cheb_last_stats: null argument");
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
     if (s->fixed) {
-        // the lazy norm runs behind the synchronisation above, on the null stream: never on a saved stream handle
+        // the lazy norm runs behind a device synchronisation, on the null stream: never on a saved stream handle
+        SCHWZ_HIP_TRY(hipDeviceSynchronize());
         if (s->norm_pending) {
             const int rc = cheb_norm_now(s, s->r, s->d[s->norm_d], nullptr);
             if (rc) return rc;
@@ -629,9 +598,9 @@ int schwz_cheb_last_stats(schwz_cheb *s, int *h_iters, double *h_resnorm)
         *h_resnorm = std::sqrt(s->last_rr);
         return SCHWZ_OK;
     }
-    SCHWZ_HIP_TRY(hipMemcpy(&s->h_state[0], s->state, sizeof(ChebState), hipMemcpyDeviceToHost));
-    *h_iters = s->h_state[0].iters;
-    *h_resnorm = std::sqrt(s->h_state[0].rr);
+    if (const int rc = s->state.read_blocking()) return rc;
+    *h_iters = s->state.host(0).iters;
+    *h_resnorm = std::sqrt(s->state.host(0).rr);
     return SCHWZ_OK;
 }
 

@@ -31,7 +31,7 @@ namespace schwz {
 struct GmresState {
     double r0;      // ||b - A x_start||, the reference of the reduction test
     double resn;    // current residual norm (true at a cycle start, rotated rhs inside a cycle)
-    int stop_it;    // Krylov vectors after which the solve stops (INT_MAX: not decided)
+    int stop_iter;  // Krylov vectors after which the solve stops (INT_MAX: not decided)
     int iters;      // Krylov vectors built so far
 };
 
@@ -47,16 +47,16 @@ __global__ void gmres_start_kernel(GmresState *st, const double *rr_partials, in
                                    int first, int max_iters, double *g, int m)
 {
     __shared__ double red[4];
-    if (!first && it_base >= st->stop_it) return;
+    if (!first && it_base >= st->stop_iter) return;
     const double beta = sqrt(fold_partials(rr_partials, nparts, red));
     if (threadIdx.x == 0) {
         if (first) {
             st->r0 = beta;
             st->iters = 0;
-            st->stop_it = INT_MAX;
+            st->stop_iter = INT_MAX;
         }
         st->resn = beta;
-        if (it_base >= max_iters || beta <= rtol * st->r0 || beta == 0.0) st->stop_it = it_base;
+        if (it_base >= max_iters || beta <= rtol * st->r0 || beta == 0.0) st->stop_iter = it_base;
         g[0] = beta;
         for (int i = 1; i <= m; ++i) g[i] = 0.0;
     }
@@ -66,7 +66,7 @@ __global__ void gmres_start_kernel(GmresState *st, const double *rr_partials, in
 __global__ __launch_bounds__(kBlock) void gmres_scale_kernel(int64_t n, double *__restrict__ v, const GmresState *st,
                                                              int it_base)
 {
-    if (it_base >= st->stop_it) return;
+    if (it_base >= st->stop_iter) return;
     const double beta = st->resn;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) v[i] /= beta;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void gmres_project_kernel(int64_t n, double
                                                                const GmresState *st, int it)
 {
     __shared__ double red[4];
-    if (it >= st->stop_it) return;
+    if (it >= st->stop_iter) return;
     double h = 0.0;
     if (vprev) {
         h = fold_partials(partials_in, nparts, red);
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void gmres_finish_kernel(int64_t n, const d
                                                               int m, int j, GmresState *st, int it, double rtol)
 {
     __shared__ double red[4];
-    if (it >= st->stop_it) return;
+    if (it >= st->stop_iter) return;
     const double hn = sqrt(fold_partials(ww_partials, nparts, red));
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
@@ -139,13 +139,13 @@ __global__ __launch_bounds__(kBlock) void gmres_finish_kernel(int64_t n, const d
         const double resn = fabs(g[j + 1]);
         st->resn = resn;
         st->iters = it + 1;
-        // other workgroups of this launch compare `it` with stop_it concurrently: it only ever
+        // other workgroups of this launch compare `it` with stop_iter concurrently: it only ever
         // drops to it + 1, which they read as "not yet"
-        if (resn <= rtol * st->r0) st->stop_it = it + 1;
+        if (resn <= rtol * st->r0) st->stop_iter = it + 1;
     }
 }
 
-// End of a cycle that built k = min(launched, stop_it - it_base) vectors: H y = g by back
+// End of a cycle that built k = min(launched, stop_iter - it_base) vectors: H y = g by back
 // substitution (every workgroup, redundantly: k is small), t = sum_i y_i v_i.
 __global__ __launch_bounds__(kBlock) void gmres_combine_kernel(int64_t n, const double *__restrict__ V, int64_t ldv,
                                                                double *__restrict__ t, const double *H,
@@ -153,8 +153,8 @@ __global__ __launch_bounds__(kBlock) void gmres_combine_kernel(int64_t n, const 
                                                                const GmresState *st, int it_base)
 {
     extern __shared__ double y[];  // m
-    if (it_base >= st->stop_it) return;
-    const int k = min(launched, st->stop_it - it_base);
+    if (it_base >= st->stop_iter) return;
+    const int k = min(launched, st->stop_iter - it_base);
     if (threadIdx.x == 0) {
         for (int i = k - 1; i >= 0; --i) {
             double s = g[i];
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void gmres_axpy_kernel(int64_t n, double *_
                                                             const double *__restrict__ z, const GmresState *st,
                                                             int it_base)
 {
-    if (it_base >= st->stop_it) return;
+    if (it_base >= st->stop_iter) return;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) x[i] += z[i];
 }
@@ -187,15 +187,14 @@ using namespace schwz;
 
 struct schwz_gmres {
     const schwz_csr *A = nullptr;
-    schwz_pcg *pre = nullptr;  // owns the preconditioner (and the SpMV partial-sum banks)
+    schwz_pcg *pre = nullptr;  // owns the preconditioner (and the SpMV partial-sum banks): adopted, destroyed by hand
     int64_t n = 0, ldv = 0;
     int m = 1;
-    double *V = nullptr;  // (m + 1) vectors of ldv
-    double *w = nullptr, *z = nullptr;
-    double *H = nullptr, *cs = nullptr, *sn = nullptr, *g = nullptr;
-    double *part = nullptr;  // 2 banks of kMaxGrid
-    GmresState *state = nullptr, *h_state = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Dev<double> V;  // (m + 1) vectors of ldv
+    Dev<double> w, z;
+    Dev<double> H, cs, sn, g;
+    Dev<double> part;  // 2 banks of kMaxGrid
+    StateMirror<GmresState> state;
     int variant = 0;
 };
 
@@ -212,28 +211,13 @@ int gmres_create_adopt(const schwz_csr *A, int restart, schwz_pcg *pre, schwz_gm
     s->ldv = (s->n + 1) & ~int64_t(1);  // 16-byte aligned columns
     s->pre = pre;
     const size_t ld = (size_t)(s->ldv ? s->ldv : 2), m = (size_t)restart;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 8);
-    };
-    alloc((void **)&s->V, sizeof(double) * ld * (m + 1));
-    alloc((void **)&s->w, sizeof(double) * ld);
-    alloc((void **)&s->z, sizeof(double) * ld);
-    alloc((void **)&s->H, sizeof(double) * (m + 1) * m);
-    alloc((void **)&s->cs, sizeof(double) * m);
-    alloc((void **)&s->sn, sizeof(double) * m);
-    alloc((void **)&s->g, sizeof(double) * (m + 1));
-    alloc((void **)&s->part, sizeof(double) * 2 * kMaxGrid);
-    alloc((void **)&s->state, sizeof(GmresState));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_state, 2 * sizeof(GmresState), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemset(s->H, 0, sizeof(double) * (m + 1) * m);
-    if (e != hipSuccess) {
-        set_error(std::string("schwz_gmres_create: ") + hipGetErrorString(e));
+    int rc;
+    if ((rc = s->V.alloc(ld * (m + 1))) || (rc = s->w.alloc(ld)) || (rc = s->z.alloc(ld)) ||
+        (rc = s->H.alloc((m + 1) * m, true)) || (rc = s->cs.alloc(m)) || (rc = s->sn.alloc(m)) ||
+        (rc = s->g.alloc(m + 1)) || (rc = s->part.alloc(2 * kMaxGrid)) || (rc = s->state.create())) {
         s->pre = nullptr;
         schwz_gmres_destroy(s);
-        return SCHWZ_ERR_HIP;
+        return rc;
     }
     *out = s;
     return SCHWZ_OK;
@@ -278,11 +262,6 @@ int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int r
 void schwz_gmres_destroy(schwz_gmres *s)
 {
     if (!s) return;
-    void *ptrs[] = {s->V, s->w, s->z, s->H, s->cs, s->sn, s->g, s->part, s->state};
-    for (void *p : ptrs) (void)hipFree(p);
-    if (s->h_state) (void)hipHostFree(s->h_state);
-    for (hipEvent_t ev : s->ev)
-        if (ev) (void)hipEventDestroy(ev);
     schwz_pcg_destroy(s->pre);
     delete s;
 }
@@ -290,10 +269,9 @@ void schwz_gmres_destroy(schwz_gmres *s)
 int schwz_gmres_last_stats(schwz_gmres *s, int *h_iters, double *h_resnorm)
 {
     SCHWZ_REQUIRE(s && h_iters && h_resnorm, "schwz_gmres_last_stats: null argument");
-    SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    SCHWZ_HIP_TRY(hipMemcpy(&s->h_state[0], s->state, sizeof(GmresState), hipMemcpyDeviceToHost));
-    *h_iters = s->h_state[0].iters;
-    *h_resnorm = s->h_state[0].resn;
+    if (const int rc = s->state.read_blocking()) return rc;
+    *h_iters = s->state.host(0).iters;
+    *h_resnorm = s->state.host(0).resn;
     return SCHWZ_OK;
 }
 
@@ -313,8 +291,8 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
     const int m = s->m;
     const int gs = spmv_grid(A, s->variant), gv = gm_grid(n);
     double *bank[2] = {s->part, s->part + kMaxGrid};
-    int pending = -1, slot = 0;
     bool stopped = false;
+    s->state.begin();
     for (int c = 0; !stopped; ++c) {
         const int it_base = c * m;
         // ---- r = b - A x -> v_0, beta, loop-top tests ----
@@ -327,9 +305,9 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
         a.stream_part = s->pre->stream_part;
         int rc = launch_spmv(A, kSpmvResidInit, a, s->variant, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(gmres_start_kernel, dim3(1), dim3(kBlock), 0, st, s->state, s->pre->partials + gs, gs, rtol,
+        hipLaunchKernelGGL(gmres_start_kernel, dim3(1), dim3(kBlock), 0, st, s->state.dev(), s->pre->partials + gs, gs, rtol,
                            it_base, c == 0 ? 1 : 0, max_iters, s->g, m);
-        hipLaunchKernelGGL(gmres_scale_kernel, dim3(gv), dim3(kBlock), 0, st, n, s->V, s->state, it_base);
+        hipLaunchKernelGGL(gmres_scale_kernel, dim3(gv), dim3(kBlock), 0, st, n, s->V, s->state.dev(), it_base);
         const int launched = std::min(m, max_iters - it_base);
         for (int j = 0; j < launched; ++j) {
             const int it = it_base + j;
@@ -340,7 +318,7 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
             q.y = s->w;
             q.partials = s->pre->partials;  // z . w, unused
             q.stream_part = s->pre->stream_part;
-            q.stop_iter = &s->state->stop_it;
+            q.stop_iter = &s->state.dev()->stop_iter;
             q.it = it;
             if ((rc = launch_spmv(A, kSpmvDot, q, s->variant, st))) return rc;
             double *hcol = s->H + (size_t)j * (size_t)(m + 1);
@@ -349,34 +327,26 @@ int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rto
                 const double *vprev = i > 0 ? s->V + (size_t)(i - 1) * (size_t)s->ldv : nullptr;
                 const double *vnext = i <= j ? s->V + (size_t)i * (size_t)s->ldv : nullptr;
                 hipLaunchKernelGGL(gmres_project_kernel, dim3(gv), dim3(kBlock), 0, st, n, s->w, vprev, vnext,
-                                   bank[(i + 1) & 1], gv, bank[i & 1], i > 0 ? hcol + (i - 1) : nullptr, s->state, it);
+                                   bank[(i + 1) & 1], gv, bank[i & 1], i > 0 ? hcol + (i - 1) : nullptr, s->state.dev(), it);
             }
             hipLaunchKernelGGL(gmres_finish_kernel, dim3(gv), dim3(kBlock), 0, st, n, s->w,
                                s->V + (size_t)(j + 1) * (size_t)s->ldv, bank[(j + 1) & 1], gv, s->H, s->cs, s->sn, s->g,
-                               m, j, s->state, it, rtol);
+                               m, j, s->state.dev(), it, rtol);
         }
         // ---- x += M^-1 (V y) ----
         hipLaunchKernelGGL(gmres_combine_kernel, dim3(gv), dim3(kBlock), sizeof(double) * (size_t)m, st, n, s->V,
-                           s->ldv, s->w, s->H, s->g, m, launched, s->state, it_base);
+                           s->ldv, s->w, s->H, s->g, m, launched, s->state.dev(), it_base);
         if ((rc = precond_apply(s->pre, s->w, s->z, st))) return rc;
-        hipLaunchKernelGGL(gmres_axpy_kernel, dim3(gv), dim3(kBlock), 0, st, n, d_x, s->z, s->state, it_base);
+        hipLaunchKernelGGL(gmres_axpy_kernel, dim3(gv), dim3(kBlock), 0, st, n, d_x, s->z, s->state.dev(), it_base);
         SCHWZ_HIP_TRY(hipGetLastError());
         if (it_base + launched >= max_iters) break;
         // the host reads the state one cycle behind the launches
-        if (pending >= 0) {
-            SCHWZ_HIP_TRY(hipEventSynchronize(s->ev[pending]));
-            if (s->h_state[pending].stop_it != INT_MAX) stopped = true;
-        }
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[slot], s->state, sizeof(GmresState), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipEventRecord(s->ev[slot], st));
-        pending = slot;
-        slot ^= 1;
+        if ((rc = s->state.poll(st, &stopped))) return rc;
     }
     if (h_iters || h_resnorm) {
-        SCHWZ_HIP_TRY(hipMemcpyAsync(&s->h_state[0], s->state, sizeof(GmresState), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-        if (h_iters) *h_iters = s->h_state[0].iters;
-        if (h_resnorm) *h_resnorm = s->h_state[0].resn;
+        if (const int rc = s->state.read(st)) return rc;
+        if (h_iters) *h_iters = s->state.host(0).iters;
+        if (h_resnorm) *h_resnorm = s->state.host(0).resn;
     }
     return SCHWZ_OK;
 }

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <new>
@@ -209,6 +210,7 @@ struct DevBuf {
     void *p = nullptr;
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
     DevBuf &operator=(DevBuf &&o) noexcept
     {
         std::swap(p, o.p);
@@ -217,6 +219,15 @@ struct DevBuf {
     ~DevBuf()
     {
         if (p) (void)hipFree(p);
+    }
+    // replaces the allocation by `bytes` fresh ones (at least 16), zeroed on request
+    int alloc(size_t bytes, bool zero = false)
+    {
+        *this = DevBuf();
+        bytes = bytes ? bytes : 16;
+        SCHWZ_HIP_TRY(hipMalloc(&p, bytes));
+        if (zero) SCHWZ_HIP_TRY(hipMemset(p, 0, bytes));
+        return SCHWZ_OK;
     }
     // replaces the allocation by a copy of h (plus `pad` zeroed elements)
     template <typename T>
@@ -228,6 +239,72 @@ struct DevBuf {
     template <typename T>
     const T *as() const { return static_cast<const T *>(p); }
 };
+
+// ... of `count` T, handed to launches as the T * it converts to.  The vectors and scalars of the solver objects
+// are these: destroying a solver is `delete`, and a create that fails half way leaves nothing behind.
+template <typename T>
+struct Dev : DevBuf {
+    int alloc(size_t count, bool zero = false) { return DevBuf::alloc(count * sizeof(T), zero); }
+    operator T *() const { return static_cast<T *>(p); }
+};
+
+// pinned host memory that frees itself
+template <typename T>
+struct Pinned {
+    T *p = nullptr;
+    Pinned() = default;
+    Pinned(const Pinned &) = delete;
+    ~Pinned()
+    {
+        if (p) (void)hipHostFree(p);
+    }
+    int alloc(size_t count)  // zeroed
+    {
+        SCHWZ_HIP_TRY(hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault));
+        std::memset(p, 0, count * sizeof(T));
+        return SCHWZ_OK;
+    }
+};
+
+// a HIP handle that destroys itself and converts to the raw handle the runtime calls take
+template <typename H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    explicit Handle(H h_) : h(h_) {}
+    Handle(Handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle &operator=(Handle &&o) noexcept
+    {
+        std::swap(h, o.h);
+        return *this;
+    }
+    ~Handle()
+    {
+        if (h) (void)Destroy(h);
+    }
+    operator H() const { return h; }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    int create()  // (no timing: an ordering point only)
+    {
+        SCHWZ_HIP_TRY(hipEventCreateWithFlags(&h, hipEventDisableTiming));
+        return SCHWZ_OK;
+    }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    int create()  // non-blocking
+    {
+        SCHWZ_HIP_TRY(hipStreamCreateWithFlags(&h, hipStreamNonBlocking));
+        return SCHWZ_OK;
+    }
+};
+using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
+
+}  // namespace schwz
+
+#include "solver_state.hpp"
+
+namespace schwz {
 
 // ---- SpMV tiling constants (see DESIGN.md "CSR SpMV") ------------------------
 constexpr int kBlock = 256;      // threads per workgroup = 4 waves of 64
@@ -459,7 +536,7 @@ struct SpmvArgs {
 };
 
 // SpmvArgs::stream_part for launches on A: nullptr where A needs none, or where the allocation fails (those launches
-// keep the persistent form); hipFree releases it
+// keep the persistent form); hipFree releases it (a solver adopts it into a Dev<double>)
 inline double *stream_part_alloc(const CsrView &A)
 {
     void *p = nullptr;
@@ -628,27 +705,28 @@ struct schwz_pcg {
     const schwz_csr *A = nullptr;
     int precond = 0;
     int64_t n = 0;
-    double *r = nullptr, *p = nullptr, *q = nullptr, *dinv = nullptr;
-    double *r_alt = nullptr;  // second residual buffer of the virtual first direction (cg.hip: r1 goes there, r0 stays)
+    // (every device buffer, event and stream below frees itself: schwz_pcg_destroy lists none of them)
+    schwz::Dev<double> r, p, q, dinv;
+    schwz::Dev<double> r_alt;  // second residual buffer of the virtual first direction (cg.hip: r1 goes there, r0 stays)
     // general preconditioners (block-Jacobi, ILU(0)): z = M^-1 r is a vector of its own
-    double *z = nullptr;
+    schwz::Dev<double> z;
     int block_size = 1;
-    schwz_idx *d_blk_id = nullptr;  // block-Jacobi: index of each block's inverse
-    double *d_blk_inv = nullptr;    // unique inverse blocks, [nunique][bs][bs] (a k x k inverse in the top left corner)
-    schwz_idx *d_row_blk = nullptr, *d_blk_ptr = nullptr;  // detected blocks of different sizes: block of a row, boundaries
+    schwz::Dev<schwz_idx> d_blk_id;  // block-Jacobi: index of each block's inverse
+    schwz::Dev<double> d_blk_inv;    // unique inverse blocks, [nunique][bs][bs] (a k x k inverse in the top left corner)
+    schwz::Dev<schwz_idx> d_row_blk, d_blk_ptr;  // detected blocks of different sizes: block of a row, boundaries
+    // (the three adopted objects: schwz_pcg_destroy destroys them)
     schwz_trs *ilu = nullptr;       // ILU(0): level-scheduled L and U sweeps
     int par_ilu_sweeps = 0;         // ILU / ISAI factors from this many ParILU sweeps (0: exact host ILU(0))
     int trisolve_sweeps = 0;        // ILU applied by this many Jacobi passes per factor (0: exact solves)
     schwz_csr *isai_l = nullptr, *isai_u = nullptr;  // ISAI: approximate inverses of L and U
-    double *isai_tmp = nullptr;
+    schwz::Dev<double> isai_tmp;
     schwz::DiagView diag;
-    void *d_dcode = nullptr, *d_ddict = nullptr;
-    double *partials = nullptr;  // 3 * kMaxGrid (SpMV banks) + 2 * kMaxGrid (vector banks) + 3 * kMaxGrid (start banks, InitFold)
-    double *stream_part = nullptr;  // SpmvArgs::stream_part of this solver's launches (and of the GMRES / BiCGSTAB around it)
-    double *d_norm_sq = nullptr; // kSpmvResidDual result
-    schwz::CgState *state = nullptr;
-    schwz::CgState *h_state = nullptr;  // pinned
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    schwz::DevBuf d_dcode, d_ddict;
+    schwz::Dev<double> partials;  // 3 * kMaxGrid (SpMV banks) + 2 * kMaxGrid (vector banks) + 3 * kMaxGrid (start banks, InitFold)
+    schwz::Dev<double> stream_part;  // SpmvArgs::stream_part of this solver's launches (and of the GMRES / BiCGSTAB around it)
+    schwz::Dev<double> norm_sq_own;
+    double *d_norm_sq = nullptr;  // kSpmvResidDual result: norm_sq_own, or for one start launch the caller's (subdomain.hip)
+    schwz::StateMirror<schwz::CgState> state;  // device state, pinned mirror, poll (solver_state.hpp)
     int variant = 0;
     // recorded runs of kGraphIters iterations (launch-bound small systems), see pcg_iterate
     struct Captured {
@@ -656,13 +734,13 @@ struct schwz_pcg {
         double rtol;
         int variant;
         int flavour;  // CgPlan::flavour of the solve that recorded it (which launches the graph holds)
-        hipGraphExec_t exec;
+        schwz::GraphExec exec;
     };
     std::vector<Captured> graphs;
-    hipStream_t capture_stream = nullptr;
+    schwz::Stream capture_stream;
     // deferred x update of large systems (pcg_iterate): ring of search directions and their alphas
-    double *p_ring = nullptr;      // kDeferDepth - 2 vectors; slots 0 and 1 of the ring are p and q
-    double *alpha_hist = nullptr;  // kDeferDepth
+    schwz::Dev<double> p_ring;      // kDeferDepth - 2 vectors; slots 0 and 1 of the ring are p and q
+    schwz::Dev<double> alpha_hist;  // kDeferDepth
     bool ring_failed = false;
     bool ring_has_q = true;  // slot 1 of the ring is s->q (q-free iteration); false: the stored-q iteration's ring
     // the start launch of the running solve left p to the first fused direction launch (z-sweep start)
@@ -697,7 +775,7 @@ struct schwz_pcg {
         double *norm_sq_out = nullptr;
         int norm_bank = 1;
     } init;
-    hipEvent_t init_event = nullptr;
+    hipEvent_t init_event = nullptr;  // borrowed
     // A solve of exactly max_iters iterations (rtol == 0) whose last iteration was cut down to what its result
     // needs: alpha of that iteration is formed inside the x update, and the residual update + state advance --
     // whose results nothing reads unless the caller asks for the iteration count / residual norm -- wait in
@@ -705,11 +783,11 @@ struct schwz_pcg {
     // drops them.
     struct LazyLast {
         bool pending = false;
-        hipStream_t stream = nullptr;
+        hipStream_t stream = nullptr;  // borrowed
     } lazy;
     std::function<int(hipStream_t)> lazy_run;
     int64_t prio_lo = 0, prio_hi = 0;  // even
-    hipEvent_t prio_event = nullptr;
+    schwz::Event prio_event;
     // how the last solve iterated: bits 0-1: 0 stored q, 1 q-free (three launches), 2 q-free with the fused
     // direction + p.(A p) launch; 4: deferred x update; 8: z-sweep walk of the update launch; 16: of the fused launch;
     // 32: of the start launch and the first direction as well; 64 / 128: first / last direction never stored

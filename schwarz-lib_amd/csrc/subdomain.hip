@@ -230,7 +230,7 @@ static int create_local_solver(schwz_subdomain *sd, std::vector<schwz_idx> put_i
         sd->cg->variant = o.spmv_variant;
         std::sort(put_idx.begin(), put_idx.end());
         if (priority_rows(put_idx, n, sd->local_size, &sd->cg->prio_lo, &sd->cg->prio_hi)) {
-            SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->cg->prio_event, hipEventDisableTiming));
+            if ((rc = sd->cg->prio_event.create())) return rc;
             sd->cg->prio_on = true;
         }
         return SCHWZ_OK;
