@@ -706,8 +706,54 @@ int schwz_ras_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stre
 int schwz_ras_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 
 /* HBM bytes one launch of the dominant kernels moves algorithmically
- * (SURVEY 8d): which: 0 = local SpMV, 1 = one PCG iteration, used by bench.py */
+ * (SURVEY 8d): which: 0 = local SpMV, 1 = one PCG iteration, used by bench.py;
+ * 2 = the coarse step of this subdomain (below; 0 without aggregates): 20 B per entry of W and 16 B per own aggregate
+ * (residual), the subdomain's m rows of the inverse, 8 m nc, plus 16 nc for s and c (GEMV), and the apply pass,
+ * 16 slots + 2 slots, plus 16 local_size_x where y is a buffer of its own */
 int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which);
+
+/* ---- Two-level RAS: aggregation coarse correction (an extension: the reference has one level only, so no line of
+ * it is replaced).  Z is the N x nc 0/1 matrix of a partition of the rows into aggregates, every aggregate inside the
+ * interior of one subdomain, the aggregates of subdomain p numbered [first_agg_p, first_agg_p + m_p), nc <= 4096.  At
+ * the start of an outer step, after schwz_ras_unpack and before schwz_ras_update_boundary, the host layer applies
+ *     x <- x + Z A0^-1 Z^T (b - A x),   A0 = Z^T A Z
+ * in this order: schwz_ras_coarse_residual for every subdomain, (several processes: all-gather of the segments of
+ * s), schwz_coarse_solve once per process, schwz_ras_coarse_apply for every subdomain.  After the exchange x~ holds
+ * current global values in all its slots, so the residual needs no SpMV -- (Z^T (b - A x))_a = beta_a - sum_j W_aj
+ * x~_j with beta_a = sum_{i in a} b_i and W_aj = sum_{i in a} A_ij over the interior rows, exact zeros dropped (on a
+ * stencil only slots at aggregate faces remain; on a general matrix up to the nonzeros of the interior rows) -- and
+ * the correction needs no second exchange: every slot, halo included, knows its row's aggregate and adds c[agg].
+ *
+ * schwz_ras_coarse_set_aggregates (after schwz_subdomain_to_device; host work + uploads, synchronous): h_slot_agg
+ * holds the global aggregate id of each of the local_size_x + halo slots of x~; plans beta, W, the piece table of
+ * the residual launch and the subdomain's m rows of A0.  SCHWZ_ERR_INVALID for nc outside [1, 4096], ids outside
+ * [0, nc) or an interior row outside [first_agg, first_agg + m); SCHWZ_ERR_NOT_IMPLEMENTED for overlap < 2 on more
+ * than one subdomain (such local matrices drop the couplings across the cut).  m = 0 (an empty subdomain) is fine.
+ * schwz_ras_coarse_rows: those m x nc values, row-major, for the host to assemble A0.
+ * schwz_dense_inverse (host only): h_inv = h_a^-1, n x n row-major, LU with partial pivoting; SCHWZ_ERR_INVALID for
+ * a zero, negligible or non-finite pivot -- a singular global matrix (pure Neumann) or an aggregate without rows.
+ * schwz_coarse_create: the per-process / per-device object holding the explicit inverse (nc^2 doubles, at most
+ * 128 MB), s and c (zeroed); schwz_coarse_vector: device pointers of s (which = 0) and c (1), nc long, fixed for the
+ * object's life.
+ * schwz_ras_coarse_residual writes s[first_agg .. first_agg + m): one workgroup per piece of at most 2048 entries
+ * of W sums in a fixed tree order, a second launch folds every aggregate's pieces in table order -- no atomics,
+ * the same bits from run to run.  schwz_coarse_solve: c = A0^-1 s, one launch, one wave per row.
+ * schwz_ras_coarse_apply: x~[j] += c[agg(j)] on every slot and y[j] += c[agg(j)] on the local_size_x entries of the
+ * warm start of the next local solve, one launch; where y is the x~ buffer itself (schwz_ras_y_form 1) the values
+ * are added once.  Correct for every local solver (the direct ones ignore y) and at any point between a
+ * restriction and the next solve.  All three obey `stream`.  The pointer rule of schwz_ras_vector holds: ask for ids
+ * 0 and 2 again after a solve or a restriction, not after these calls (they move nothing). */
+typedef struct schwz_coarse schwz_coarse;
+int schwz_ras_coarse_set_aggregates(schwz_subdomain *sd, const int32_t *h_slot_agg, int32_t first_agg, int32_t m,
+                                    int32_t nc);
+int schwz_ras_coarse_rows(const schwz_subdomain *sd, double *h_rows);
+int schwz_dense_inverse(int32_t n, const double *h_a, double *h_inv);
+int schwz_coarse_create(int32_t nc, const double *h_inv, schwz_coarse **out);
+void schwz_coarse_destroy(schwz_coarse *c);
+int schwz_coarse_vector(schwz_coarse *c, int which, double **d_ptr, int32_t *len);
+int schwz_ras_coarse_residual(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream);
+int schwz_coarse_solve(schwz_coarse *c, schwz_stream stream);
+int schwz_ras_coarse_apply(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream);
 
 #ifdef __cplusplus
 }

@@ -874,6 +874,29 @@ struct schwz_problem {
 struct schwz_pcg_f32;  // cg_f32.hip
 struct schwz_cheb;     // chebyshev.hip
 
+// ---- aggregation coarse correction (coarse.hip; the plan is coarse_plan.hpp's) ----
+// one per process / device: the explicit inverse of A0 = Z^T A Z, the coarse residual s and the correction c
+struct schwz_coarse {
+    int32_t nc = 0;
+    schwz::Dev<double> inv, s, c;
+};
+
+// a subdomain's part, uploaded by schwz_ras_coarse_set_aggregates
+struct schwz_coarse_part {
+    int32_t first_agg = 0, m = 0, nc = 0, npieces = 0;
+    int64_t nslots = 0, nw = 0;
+    schwz::Dev<double> beta, w_val, partial;
+    schwz::Dev<int32_t> w_slot, piece, piece_ptr;  // piece: {aggregate, begin, end} per piece
+    schwz::Dev<uint16_t> id16;
+    std::vector<double> rows;  // m x nc: the subdomain's rows of A0 (schwz_ras_coarse_rows)
+};
+
+namespace schwz {
+// x[j] += c[id16[j]] over nx slots and, where y is a buffer of its own (not null), y[j] += c[id16[j]] over ny <= nx
+int launch_coarse_apply(const schwz_coarse_part *part, const schwz_coarse *c, double *x, int64_t nx, double *y, int64_t ny,
+                        hipStream_t st);
+}  // namespace schwz
+
 namespace schwz {
 // The solver the next local solve of a subdomain runs: local_kind (subdomain.hip) decides it, and everything that
 // depends on the solver switches over it.  A new solver adds one enumerator and one case per switch.
@@ -945,6 +968,8 @@ struct schwz_subdomain {
     double *h_scalar = nullptr;  // pinned, mapped
     double *d_h_scalar = nullptr;  // device alias of h_scalar
     hipEvent_t ev_scalar = nullptr;
+    // aggregation coarse correction (schwz_ras_coarse_set_aggregates); null: one-level RAS, nothing of it runs
+    schwz_coarse_part *coarse = nullptr;
 };
 
 namespace schwz {

@@ -272,6 +272,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
         for (void *p : ptrs) (void)hipFree(p);
         if (sd->h_scalar) (void)hipHostFree(sd->h_scalar);
         if (sd->ev_scalar) (void)hipEventDestroy(sd->ev_scalar);
+        delete sd->coarse;
     }
     delete sd;
 }
@@ -679,6 +680,23 @@ int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream)
     return launch_copy(sd->local_size, sd->d_y, sd->d_x, (hipStream_t)stream);
 }
 
+// The coarse correction c (schwz_coarse_solve) added to every copy of every row this subdomain holds: all slots of
+// x~, and the warm start y of the next local solve on its local_size_x entries -- a short inner solve would otherwise
+// undo the correction.  Where y lives is y_of's answer at this moment: a buffer of its own (d_y; or, unified state B,
+// the other x~ buffer) takes the same launch, and where y IS x~ (unified state A) the one pass adds once.  Nothing
+// here changes the form: the next solve's choose_form copies a corrected y, its x2_out pass copies the corrected
+// overlap / halo entries of d_x, and the postponed residual update of a lazy last iteration reads neither vector.
+int schwz_ras_coarse_apply(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream)
+{
+    REQUIRE_DEVICE(sd, "schwz_ras_coarse_apply");
+    SCHWZ_REQUIRE(sd->coarse, "schwz_ras_coarse_apply: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
+    SCHWZ_REQUIRE(c, "schwz_ras_coarse_apply: null coarse object");
+    double *y = y_of(sd);
+    if (y == sd->d_x) y = nullptr;
+    return launch_coarse_apply(sd->coarse, c, sd->d_x, sd->local_size_x + sd->halo_size, y, y ? sd->local_size_x : 0,
+                               (hipStream_t)stream);
+}
+
 int schwz_ras_vector(schwz_subdomain *sd, int which, double **d_ptr, int64_t *len)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_vector");
@@ -857,6 +875,17 @@ int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which)
     const int64_t n = sd->local_size_x, nnz = (int64_t)sd->l_col.size();
     const int64_t spmv = 12 * nnz + 4 * (n + 1) + 16 * n;
     if (which == 0) return spmv;
+    if (which == 2) {
+        // the coarse step of this subdomain (coarse.hip): W (value, slot, gathered x~) and the aggregates' beta and s;
+        // its m rows of the GEMV over the explicit inverse with s read and c written; the apply pass -- x~ read and
+        // written and two bytes of id per slot, and y read and written where it is a buffer of its own
+        const schwz_coarse_part *p = sd->coarse;
+        if (!p) return 0;
+        const int64_t slots = p->nslots;
+        const bool own_y = !(sd->unified && !sd->y_in_alt);
+        return 20 * p->nw + 16 * (int64_t)p->m + 8 * (int64_t)p->m * p->nc + 16 * (int64_t)p->nc + 16 * slots + 2 * slots +
+               (own_y ? 16 * n : 0);
+    }
     switch (local_kind(sd)) {
     case LocalKind::CgF32:
         // cg_f32.hip: 8 B per nonzero, p gathered and q stored in fp32, then e, r read and written, p, q, 1/diag read

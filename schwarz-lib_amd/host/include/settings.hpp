@@ -138,6 +138,15 @@ struct Metadata {
     double chebyshev_eig_ratio = 30.0;
     double chebyshev_lambda_min = 0.0;
     double chebyshev_lambda_max = 0.0;
+    // extensions (the reference has one level only): the coarse space of a two-level RAS.  "none", or "aggregates":
+    // at the start of every outer step, after the halo exchange, x <- x + Z A0^-1 Z^T (b - A x), A0 = Z^T A Z, Z the
+    // 0/1 matrix of a partition of the rows into at most 4096 aggregates, each inside one subdomain's interior.
+    // coarse_aggregate_vector: one id >= 0 per global row in the caller's row ids (rows of one id in different
+    // subdomains become different aggregates); empty: coarse_aggregates > 0 parts of every subdomain's interior
+    // graph.  Synchronous two-sided loop only, overlap >= 2 on more than one subdomain.
+    std::string coarse_space = "none";
+    int coarse_aggregates = 0;
+    std::vector<long long> coarse_aggregate_vector;
     ValueType current_residual_norm = -1.0;
     ValueType min_residual_norm = -1.0;
 

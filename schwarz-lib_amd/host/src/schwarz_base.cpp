@@ -123,9 +123,17 @@ struct SchwarzBase<ValueType, IndexType, MixedValueType>::Impl {
     std::vector<double *> win_res;    // per rank: resid[P]
     std::vector<int32_t> flags_sent;
     bool counted = false;
+    // two-level RAS (Metadata::coarse_space): the per-process coarse object, every rank's first aggregate id, and
+    // pinned host copies of this rank's segment of s and of the whole of it (MPI_Allgatherv between them)
+    schwz_coarse *coarse = nullptr;
+    std::vector<int> coarse_first, coarse_count;
+    double *h_coarse_seg = nullptr, *h_coarse_all = nullptr;
 
     ~Impl()
     {
+        schwz_coarse_destroy(coarse);
+        if (h_coarse_seg) (void)hipHostFree(h_coarse_seg);
+        if (h_coarse_all) (void)hipHostFree(h_coarse_all);
         for (void *w : peer_recv) (void)schwz_window_close(w);
         for (void *w : peer_send) (void)schwz_window_close(w);
         if (host_win != MPI_WIN_NULL) MPI_Win_free(&host_win);
@@ -292,6 +300,23 @@ void SchwarzBase<V, I, M>::initialize()
         if (lo > 0.0 && hi > 0.0 && !(lo < hi))
             throw ::BadDimension(__FILE__, __LINE__, "initialize", "chebyshev_lambda_min must be below chebyshev_lambda_max");
     }
+    // extension: the aggregation coarse correction of a two-level RAS (schwz_ras_coarse_*, schwz_coarse_*)
+    if (m.coarse_space != "none" && m.coarse_space != "aggregates")
+        throw ::BadDimension(__FILE__, __LINE__, "initialize", "coarse_space must be 'none' or 'aggregates'");
+    const bool coarse_on = m.coarse_space == "aggregates";
+    if (coarse_on) {
+        if (m.coarse_aggregate_vector.empty() && m.coarse_aggregates <= 0)
+            throw ::BadDimension(__FILE__, __LINE__, "initialize",
+                                 "coarse_space 'aggregates' needs coarse_aggregates > 0 or a coarse_aggregate_vector");
+        for (long long a : m.coarse_aggregate_vector)
+            if (a < 0) throw ::BadDimension(__FILE__, __LINE__, "initialize", "coarse_aggregate_vector holds a negative id");
+        if (s.comm_settings.enable_onesided)
+            throw ::NotImplemented(__FILE__, __LINE__, "coarse_space 'aggregates' in the one-sided loops (enable_onesided)");
+        if (P > 1 && s.overlap < 2)
+            throw ::NotImplemented(__FILE__, __LINE__, "coarse_space 'aggregates' with overlap < 2 on more than one subdomain");
+        if (m.coarse_aggregate_vector.empty() && (long long)m.coarse_aggregates * P > 4096)
+            throw ::NotImplemented(__FILE__, __LINE__, "a coarse space of more than 4096 aggregates");
+    }
 
     // ---- Initialize::setup_global_matrix (initialization.cpp:197-272) ----------------------
     // extension: "--matrix_filename=poisson3d:NX[xNYxNZ]" or SCHWZ_LAPLACIAN_DIM=3 select the 3-D
@@ -452,6 +477,96 @@ void SchwarzBase<V, I, M>::initialize()
         if (m.chebyshev_lambda_max != 0.0) hi = m.chebyshev_lambda_max;
         lo = m.chebyshev_lambda_min != 0.0 ? (double)m.chebyshev_lambda_min : hi / m.chebyshev_eig_ratio;
         SCHWZ_CALL(schwz_ras_set_cheb_bounds(im.sd, lo, hi));
+    }
+
+    if (coarse_on) {
+        // Aggregate id of every global row, on every rank (host data through MPI): from the caller's vector, split by
+        // owner and compacted, or from coarse_aggregates parts of every rank's interior graph (empty parts renumbered
+        // away).  The ids of rank p are the range [first[p], first[p] + count[p]).
+        std::vector<int32_t> agg_of((size_t)N, 0);
+        im.coarse_first.assign((size_t)P, 0);
+        im.coarse_count.assign((size_t)P, 0);
+        const int64_t n_int = im.sizes[0];
+        if (!m.coarse_aggregate_vector.empty()) {
+            if ((int64_t)m.coarse_aggregate_vector.size() != N)
+                throw ::BadDimension(__FILE__, __LINE__, "initialize", "coarse_aggregate_vector must hold one id per global row");
+            int next = 0;
+            for (int p = 0; p < P; ++p) {
+                std::vector<long long> ids;
+                for (int64_t g = first_row[(size_t)p]; g < first_row[(size_t)p + 1]; ++g)
+                    ids.push_back(m.coarse_aggregate_vector[(size_t)(m.permutation.empty() ? g : (int64_t)m.permutation[(size_t)g])]);
+                std::vector<long long> uniq(ids);
+                std::sort(uniq.begin(), uniq.end());
+                uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+                for (int64_t g = first_row[(size_t)p]; g < first_row[(size_t)p + 1]; ++g)
+                    agg_of[(size_t)g] = next + (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), ids[(size_t)(g - first_row[(size_t)p])]) - uniq.begin());
+                im.coarse_first[(size_t)p] = next;
+                im.coarse_count[(size_t)p] = (int)uniq.size();
+                next += (int)uniq.size();
+                if (next > 4096) throw ::NotImplemented(__FILE__, __LINE__, "a coarse space of more than 4096 aggregates");
+            }
+        } else {
+            std::vector<int32_t> mine((size_t)n_int, 0);
+            int count = n_int > 0 ? 1 : 0;
+            const int k = (int)std::min<int64_t>(m.coarse_aggregates, n_int);
+            if (k > 1) {
+                std::vector<schwz_idx> lrp((size_t)im.sizes[1] + 1), lcol((size_t)std::max<int64_t>(im.sizes[4], 1));
+                std::vector<double> lval((size_t)std::max<int64_t>(im.sizes[4], 1));
+                SCHWZ_CALL(schwz_subdomain_local_matrix(im.sd, lrp.data(), lcol.data(), lval.data()));
+                std::vector<int64_t> brp((size_t)n_int + 1, 0);
+                std::vector<schwz_idx> bcol;
+                std::vector<double> bval;
+                for (int64_t i = 0; i < n_int; ++i) {  // the interior block: rows and columns of the owned rows
+                    for (schwz_idx q = lrp[(size_t)i]; q < lrp[(size_t)i + 1]; ++q)
+                        if (lcol[(size_t)q] < n_int) bcol.push_back(lcol[(size_t)q]), bval.push_back(lval[(size_t)q]);
+                    brp[(size_t)i + 1] = (int64_t)bcol.size();
+                }
+                schwz_problem *block = nullptr;
+                SCHWZ_CALL(schwz_problem_from_csr(n_int, brp.data(), bcol.data(), bval.data(), &block));
+                std::vector<uint32_t> part((size_t)n_int);
+                const int rc_part = schwz_partition_graph(block, k, part.data());
+                schwz_problem_destroy(block);
+                SCHWZ_CALL(rc_part);
+                std::vector<uint32_t> uniq(part);
+                std::sort(uniq.begin(), uniq.end());
+                uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+                for (int64_t i = 0; i < n_int; ++i)
+                    mine[(size_t)i] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), part[(size_t)i]) - uniq.begin());
+                count = (int)uniq.size();
+            }
+            MPI_Allgather(&count, 1, MPI_INT, im.coarse_count.data(), 1, MPI_INT, MPI_COMM_WORLD);
+            std::vector<int> rows_of((size_t)P), row_at((size_t)P);
+            int next = 0;
+            for (int p = 0; p < P; ++p) {
+                im.coarse_first[(size_t)p] = next;
+                next += im.coarse_count[(size_t)p];
+                rows_of[(size_t)p] = (int)(first_row[(size_t)p + 1] - first_row[(size_t)p]);
+                row_at[(size_t)p] = (int)first_row[(size_t)p];
+            }
+            if (next > 4096) throw ::NotImplemented(__FILE__, __LINE__, "a coarse space of more than 4096 aggregates");
+            for (auto &a : mine) a += im.coarse_first[(size_t)me];
+            MPI_Allgatherv(mine.data(), (int)n_int, MPI_INT32_T, agg_of.data(), rows_of.data(), row_at.data(), MPI_INT32_T,
+                           MPI_COMM_WORLD);
+        }
+        const int nc = im.coarse_first[(size_t)P - 1] + im.coarse_count[(size_t)P - 1];
+        if (nc < 1) throw ::BadDimension(__FILE__, __LINE__, "initialize", "the coarse space has no aggregate");
+        std::vector<int64_t> l2g((size_t)(im.sizes[1] + im.sizes[3]));
+        SCHWZ_CALL(schwz_subdomain_local_to_global(im.sd, l2g.data()));
+        std::vector<int32_t> slot(l2g.size());
+        for (size_t j = 0; j < l2g.size(); ++j) slot[j] = agg_of[(size_t)l2g[j]];
+        const int mloc = im.coarse_count[(size_t)me];
+        SCHWZ_CALL(schwz_ras_coarse_set_aggregates(im.sd, slot.data(), im.coarse_first[(size_t)me], mloc, nc));
+        // the rows of A0 from every rank, inverted once per process
+        std::vector<double> rows((size_t)std::max(mloc, 1) * (size_t)nc), a0((size_t)nc * nc), inv((size_t)nc * nc);
+        SCHWZ_CALL(schwz_ras_coarse_rows(im.sd, rows.data()));
+        std::vector<int> cnt((size_t)P), dsp((size_t)P);
+        for (int p = 0; p < P; ++p) cnt[(size_t)p] = im.coarse_count[(size_t)p] * nc, dsp[(size_t)p] = im.coarse_first[(size_t)p] * nc;
+        MPI_Allgatherv(rows.data(), mloc * nc, MPI_DOUBLE, a0.data(), cnt.data(), dsp.data(), MPI_DOUBLE, MPI_COMM_WORLD);
+        SCHWZ_CALL(schwz_dense_inverse(nc, a0.data(), inv.data()));
+        SCHWZ_CALL(schwz_coarse_create(nc, inv.data(), &im.coarse));
+        HIP_CALL(hipHostMalloc((void **)&im.h_coarse_seg, (size_t)std::max(mloc, 1) * sizeof(double), hipHostMallocDefault));
+        HIP_CALL(hipHostMalloc((void **)&im.h_coarse_all, (size_t)nc * sizeof(double), hipHostMallocDefault));
+        if (me == 0) std::cout << " Two-level RAS: " << nc << " aggregates" << std::endl;
     }
 
     im.f32_wire = s.use_mixed_precision && std::is_same<M, float>::value;
@@ -833,6 +948,28 @@ void SchwarzBase<V, I, M>::run(std::shared_ptr<gko::matrix::Dense<V>> &solution)
         SCHWZ_CALL(im.unpack(im.stream));
     };
 
+    // two-level RAS: x <- x + Z A0^-1 Z^T (b - A x) between the unpack and the boundary update -- this rank's segment
+    // of the coarse residual, the segments of all ranks through MPI_Allgatherv on host copies, the dense solve, the
+    // correction of x~ and of the warm start y
+    auto coarse_step = [&]() {
+        SCHWZ_CALL(schwz_ras_coarse_residual(im.sd, im.coarse, im.stream));
+        if (P > 1) {
+            double *d_s = nullptr;
+            int32_t nc = 0;
+            SCHWZ_CALL(schwz_coarse_vector(im.coarse, 0, &d_s, &nc));
+            const int mloc = im.coarse_count[(size_t)me];
+            if (mloc > 0)
+                HIP_CALL(hipMemcpyAsync(im.h_coarse_seg, d_s + im.coarse_first[(size_t)me], (size_t)mloc * sizeof(double),
+                                        hipMemcpyDeviceToHost, im.stream));
+            HIP_CALL(hipStreamSynchronize(im.stream));
+            MPI_Allgatherv(im.h_coarse_seg, mloc, MPI_DOUBLE, im.h_coarse_all, im.coarse_count.data(), im.coarse_first.data(),
+                           MPI_DOUBLE, MPI_COMM_WORLD);
+            HIP_CALL(hipMemcpyAsync(d_s, im.h_coarse_all, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, im.stream));
+        }
+        SCHWZ_CALL(schwz_coarse_solve(im.coarse, im.stream));
+        SCHWZ_CALL(schwz_ras_coarse_apply(im.sd, im.coarse, im.stream));
+    };
+
     std::vector<std::vector<V>> timings(5);
     auto &ppd = m.post_process_data;
     ppd.global_residual_vector_out.assign((size_t)P, {});
@@ -1121,6 +1258,7 @@ void SchwarzBase<V, I, M>::run(std::shared_ptr<gko::matrix::Dense<V>> &solution)
             two_stage_on = true;
         }
         if (!(cs.enable_onesided && it == 0)) exchange();  // restricted_schwarz.cpp:725
+        if (im.coarse) coarse_step();
         const double t1 = now();
         SCHWZ_CALL(schwz_ras_update_boundary(im.sd, im.stream));
         const double t2 = now();

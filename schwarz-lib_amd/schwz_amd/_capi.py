@@ -71,7 +71,11 @@ SYMBOLS = [
     "schwz_ras_norm_sq_to_device",
     "schwz_ras_restrict", "schwz_ras_vector", "schwz_ras_local_csr", "schwz_ras_jacobi_form", "schwz_ras_cg_flavour", "schwz_ras_y_form", "schwz_ras_get_interior",
     "schwz_ras_true_residual_sq", "schwz_ras_algorithmic_bytes",
+    "schwz_ras_coarse_set_aggregates", "schwz_ras_coarse_rows", "schwz_dense_inverse", "schwz_coarse_create",
+    "schwz_coarse_destroy", "schwz_coarse_vector", "schwz_ras_coarse_residual", "schwz_coarse_solve",
+    "schwz_ras_coarse_apply",
 ]
+COARSE_MAX_DOFS = 4096    # aggregates of a coarse space: two bytes per x~ slot, the explicit inverse at most 128 MB
 
 
 class SchwzError(RuntimeError):
@@ -251,6 +255,15 @@ _sig("schwz_ras_y_form", i32, [vp])
 _sig("schwz_ras_get_interior", i32, [vp, vp, vp])
 _sig("schwz_ras_true_residual_sq", i32, [vp, C.POINTER(dbl), vp])
 _sig("schwz_ras_algorithmic_bytes", i64, [vp, i32])
+_sig("schwz_ras_coarse_set_aggregates", i32, [vp, vp, i32, i32, i32])
+_sig("schwz_ras_coarse_rows", i32, [vp, vp])
+_sig("schwz_dense_inverse", i32, [i32, vp, vp])
+_sig("schwz_coarse_create", i32, [i32, vp, pvp])
+_sig("schwz_coarse_destroy", None, [vp])
+_sig("schwz_coarse_vector", i32, [vp, i32, pvp, C.POINTER(C.c_int32)])
+_sig("schwz_ras_coarse_residual", i32, [vp, vp, vp])
+_sig("schwz_coarse_solve", i32, [vp, vp])
+_sig("schwz_ras_coarse_apply", i32, [vp, vp, vp])
 
 
 def check(rc):

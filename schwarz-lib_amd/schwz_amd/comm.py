@@ -79,6 +79,10 @@ class InProcessComm:
         """values: {me: float} for the local subdomains -> list of P floats."""
         return [float(values[p]) for p in range(self.size)]
 
+    def allgather_segments(self, mine, out):
+        """The segments of the coarse residual of a two-level step: all subdomains of this process write into the
+        one vector s, so there is nothing to gather (SolverRAS never calls this here)."""
+
     def gather_vectors(self, pieces):
         """pieces: {me: np.ndarray} -> concatenation in rank order on root."""
         return np.concatenate([pieces[p] for p in range(self.size)])
@@ -278,6 +282,20 @@ class TorchDistComm:
     def finish_allgather_norm_sq(self, handle):
         handle["event"].synchronize()
         return [float(v) for v in handle["host"]]
+
+    def allgather_segments(self, mine, out):
+        """Every rank's 1-D device tensor `mine` (the same length on every rank: segments are padded to the largest)
+        into `out`, rank after rank -- the segments of the coarse residual of a two-level step.  nccl: one collective
+        on the current stream, no host synchronisation; gloo: through pinned host memory, like stage_through_host
+        does for the halos."""
+        dist = self._dist
+        if self.backend == "gloo" and mine.device.type != "cpu":
+            h_mine, h_out = self._host_copy(("cs", 0), mine), self._host_copy(("cr", 0), out)
+            h_mine.copy_(mine)  # synchronous device->host copy on the current stream
+            dist.all_gather(list(h_out.chunk(self.size)), h_mine, group=self.group)
+            out.copy_(h_out, non_blocking=True)
+        else:
+            dist.all_gather_into_tensor(out, mine, group=self.group)
 
     def gather_vectors(self, pieces):
         dist = self._dist

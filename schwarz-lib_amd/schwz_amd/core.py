@@ -815,9 +815,72 @@ class Subdomain:
     def algorithmic_bytes(self, which=0):
         return int(lib.schwz_ras_algorithmic_bytes(self.h, which))
 
+    # ---- aggregation coarse correction (schwz_ras_coarse_*) ----------------------
+
+    def coarse_set_aggregates(self, slot_agg, first_agg, m, nc):
+        """Plans and uploads this subdomain's part of the coarse correction: `slot_agg` holds the global aggregate
+        id of every x~ slot (local_size_x + halo), the subdomain owns the ids [first_agg, first_agg + m)."""
+        slot_agg = np.ascontiguousarray(slot_agg, dtype=np.int32)
+        assert len(slot_agg) == self.local_size_x + self.halo_size
+        check(lib.schwz_ras_coarse_set_aggregates(self.h, ptr(slot_agg), int(first_agg), int(m), int(nc)))
+        self._coarse_shape = (int(m), int(nc))
+
+    def coarse_rows(self):
+        """The subdomain's m rows of A0 = Z^T A Z as an (m, nc) array."""
+        m, nc = self._coarse_shape
+        out = np.zeros(max(m * nc, 1), dtype=np.float64)
+        check(lib.schwz_ras_coarse_rows(self.h, ptr(out)))
+        return out[:m * nc].reshape(m, nc)
+
+    def coarse_residual(self, coarse, stream=0):
+        check(lib.schwz_ras_coarse_residual(self.h, coarse.h, _stream_arg(stream)))
+
+    def coarse_apply(self, coarse, stream=0):
+        check(lib.schwz_ras_coarse_apply(self.h, coarse.h, _stream_arg(stream)))
+
     def close(self):
         if getattr(self, "h", None) and lib is not None:
             lib.schwz_subdomain_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def dense_inverse(a):
+    """Inverse of a dense square matrix on the host (schwz_dense_inverse: LU with partial pivoting); a singular
+    matrix raises ERR_INVALID."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    assert a.ndim == 2 and a.shape[0] == a.shape[1]
+    inv = np.zeros_like(a)
+    check(lib.schwz_dense_inverse(a.shape[0], ptr(a), ptr(inv)))
+    return inv
+
+
+class Coarse:
+    """The per-process part of the coarse correction on the device (schwz_coarse_create): the explicit inverse of
+    A0, the coarse residual s and the correction c."""
+
+    def __init__(self, inv):
+        inv = np.ascontiguousarray(inv, dtype=np.float64)
+        assert inv.ndim == 2 and inv.shape[0] == inv.shape[1]
+        self.nc = int(inv.shape[0])
+        h = C.c_void_p()
+        check(lib.schwz_coarse_create(self.nc, ptr(inv), C.byref(h)))
+        self.h = h
+
+    def vector(self, which):
+        """(device pointer, length) of s (which = 0) or c (1)."""
+        p, n = C.c_void_p(), C.c_int32(0)
+        check(lib.schwz_coarse_vector(self.h, int(which), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def solve(self, stream=0):
+        check(lib.schwz_coarse_solve(self.h, _stream_arg(stream)))
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.schwz_coarse_destroy(self.h)
             self.h = None
 
     def __del__(self):

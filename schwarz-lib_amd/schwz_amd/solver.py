@@ -145,6 +145,17 @@ class Metadata:
     chebyshev_eig_ratio: float = 30.0
     chebyshev_lambda_min: float = 0.0
     chebyshev_lambda_max: float = 0.0
+    # extensions (no field of the reference's Metadata, which has one level only): the coarse space of a two-level
+    # RAS.  coarse_space "none" (one-level RAS, launch for launch what it was) or "aggregates": at the start of every
+    # outer step, after the halo exchange, x <- x + Z A0^-1 Z^T (b - A x) with A0 = Z^T A Z and Z the 0/1 matrix of a
+    # partition of the rows into at most 4096 aggregates, each inside the interior of one subdomain; any other name is
+    # refused.  coarse_aggregate_vector: one aggregate id >= 0 per global row in the caller's row ids (like
+    # partition_vector); rows of one id that lie in different subdomains become different aggregates.  Without a
+    # vector, coarse_aggregates > 0 parts are cut out of every subdomain's interior graph by the graph partitioner.
+    # Synchronous two-sided loop only (enable_onesided is refused), overlap >= 2 on more than one subdomain.
+    coarse_space: str = "none"
+    coarse_aggregates: int = 0
+    coarse_aggregate_vector: object = None
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
@@ -333,6 +344,68 @@ def _cheb_bounds(metadata, auto_lmax):
     hi = float(metadata.chebyshev_lambda_max) or float(auto_lmax)
     lo = float(metadata.chebyshev_lambda_min) or hi / float(metadata.chebyshev_eig_ratio)
     return lo, hi
+
+
+def _coarse_enabled(settings, metadata):
+    """Whether metadata.coarse_space asks for the aggregation coarse correction; what can be checked without the
+    matrix is checked here.  Runs before any device call."""
+    name = getattr(metadata, "coarse_space", "none")
+    if not isinstance(name, str) or name not in ("none", "aggregates"):
+        raise capi.SchwzError(capi.ERR_INVALID, "coarse_space must be 'none' or 'aggregates', not %r" % (name,))
+    if name == "none":
+        return False
+    vec = getattr(metadata, "coarse_aggregate_vector", None)
+    P = max(int(metadata.num_subdomains), 1)
+    if vec is None:
+        try:
+            count = int(getattr(metadata, "coarse_aggregates", 0))
+        except (TypeError, ValueError):
+            count = 0
+        if count <= 0:
+            raise capi.SchwzError(capi.ERR_INVALID, "coarse_space 'aggregates' needs coarse_aggregates > 0 (aggregates "
+                                                    "per subdomain) or a coarse_aggregate_vector")
+    else:
+        v = np.asarray(vec)
+        if v.ndim != 1 or v.dtype.kind not in "iu" or (v.size and int(v.min()) < 0):
+            raise capi.SchwzError(capi.ERR_INVALID, "coarse_aggregate_vector must hold one integer aggregate id >= 0 "
+                                                    "per global row")
+    if settings.comm_settings.enable_onesided:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "coarse_space 'aggregates' exists for the synchronous two-sided loop only: the "
+                                       "one-sided loops (enable_onesided) have no global point for a coarse solve")
+    if P > 1 and int(settings.overlap) < 2:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
+                                       "coarse_space 'aggregates' needs settings.overlap >= 2 on more than one subdomain")
+    if vec is None and count * P > capi.COARSE_MAX_DOFS:
+        raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED, _too_many_aggregates(count * P))
+    return True
+
+
+def _too_many_aggregates(nc):
+    return "the coarse space has %d aggregates; at most %d are implemented" % (nc, capi.COARSE_MAX_DOFS)
+
+
+def _coarse_vector(metadata, N):
+    """metadata.coarse_aggregate_vector as an int64 array of the global size N (ERR_INVALID otherwise)."""
+    v = np.asarray(metadata.coarse_aggregate_vector)
+    if v.shape != (int(N),):
+        raise capi.SchwzError(capi.ERR_INVALID, "coarse_aggregate_vector must hold one aggregate id per global row "
+                                                "(%d rows), not %s" % (N, "x".join(str(d) for d in v.shape) or "a scalar"))
+    return v.astype(np.int64)
+
+
+def _split_aggregates(agg, first_row):
+    """Aggregate ids per (permuted) row, split by owner and compacted: rows of one id in different subdomains become
+    different aggregates, the ids of subdomain p become the range [first[p], first[p + 1]).  Returns (ids, first)."""
+    first_row = np.asarray(first_row, dtype=np.int64)
+    P = len(first_row) - 1
+    owner = np.searchsorted(first_row, np.arange(len(agg), dtype=np.int64), side="right") - 1
+    # (first_row may repeat an entry, empty subdomains: the owner is the last subdomain starting at or before the row)
+    key = owner * (int(agg.max()) + 1 if len(agg) else 1) + agg
+    uniq, ids = np.unique(key, return_inverse=True)
+    owner_of = uniq // (int(agg.max()) + 1 if len(agg) else 1)
+    first = np.searchsorted(owner_of, np.arange(P + 1), side="left")
+    return ids.astype(np.int64), first.astype(np.int64)
 
 
 def _precond_name_code(metadata):
@@ -532,6 +605,8 @@ class SolverRAS:
         precision_code = _precision_code(s, m)
         nonsym_code = _nonsym_solver_code(s, m)
         sym_code = _sym_solver_code(s, m)
+        coarse_on = _coarse_enabled(s, m)
+        self._coarse = None
         if self._distributed_ingest():
             prob = self._ingest_distributed()
         else:
@@ -539,8 +614,18 @@ class SolverRAS:
             prob = self._partition(prob)
         self.problem = prob
         P = m.num_subdomains
+        user_aggregates = None
+        if coarse_on and m.coarse_aggregate_vector is not None:
+            # the caller's ids by (permuted) row, split by owner: the count is known -- and refused -- before any upload
+            vec = _coarse_vector(m, prob.N)
+            if m.permutation is not None:
+                vec = vec[np.asarray(m.permutation, dtype=np.int64)]
+            user_aggregates = _split_aggregates(vec, m.first_row)
+            if int(user_aggregates[1][-1]) > capi.COARSE_MAX_DOFS:
+                raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED, _too_many_aggregates(int(user_aggregates[1][-1])))
         for me in comm.local_ranks:
             self.subdomains[me] = be.subdomain(prob, P, me, s.overlap, m.first_row)
+        coarse_plan = self._coarse_aggregates(user_aggregates) if coarse_on else None
         puts = comm.handshake({me: sd.get_lists() for me, sd in self.subdomains.items()})
         for me, sd in self.subdomains.items():
             for q, ids in puts[me]:
@@ -587,6 +672,8 @@ class SolverRAS:
             (me, [(q, len(ids)) for q, ids in sd.put_lists()],
              [(p, len(ids)) for p, ids in sd.get_lists()], sd.num_send, sd.num_recv)
             for me, sd in self.subdomains.items()]
+        if coarse_on:
+            self._setup_coarse(*coarse_plan)
         self.close()  # windows of an earlier initialize()
         self._win = None
         if s.comm_settings.enable_onesided and getattr(comm, "node_windows", False) \
@@ -604,6 +691,121 @@ class SolverRAS:
                 self._print(" Local max iters %d with restart iter %d" % (lmi, s.restart_iter))
         else:
             self._print(" Local direct solve with HIP TRS")
+
+    # ---------------------------------------------------------- coarse space
+    def _coarse_aggregates(self, user_aggregates):
+        """The aggregates of the local subdomains' interior rows, before any upload: ({me: global aggregate id of
+        every interior row}, first) with the ids of subdomain p the range [first[p], first[p + 1]).  From the caller's
+        vector, or coarse_aggregates parts of every interior graph cut by the graph partitioner (empty parts are
+        renumbered away)."""
+        m, comm = self.metadata, self.comm
+        P = m.num_subdomains
+        if user_aggregates is not None:
+            ids, first = user_aggregates
+            fr = np.asarray(m.first_row, dtype=np.int64)
+            return {me: ids[fr[me]:fr[me + 1]] for me in self.subdomains}, first
+        local, counts = {}, {}
+        for me, sd in self.subdomains.items():
+            n = sd.local_size
+            k = min(int(m.coarse_aggregates), n)
+            if k <= 1:
+                part = np.zeros(n, dtype=np.int64)
+            else:
+                rp, col, val = sd.local_matrix()
+                end = int(rp[n])
+                keep = col[:end] < n  # the interior block: rows and columns of the owned rows
+                rows = np.repeat(np.arange(n), np.diff(rp[:n + 1]))[keep]
+                brp = np.zeros(n + 1, dtype=np.int64)
+                np.cumsum(np.bincount(rows, minlength=n), out=brp[1:])
+                block = self.backend.problem_from_csr(brp, col[:end][keep], val[:end][keep])
+                part = np.unique(np.asarray(block.partition_graph(k), dtype=np.int64), return_inverse=True)[1]
+                block.close()
+            local[me] = part
+            counts[me] = int(part.max()) + 1 if n else 0
+        allcounts = [int(c) for c in comm.allgather_scalars(counts)]
+        first = np.concatenate([[0], np.cumsum(allcounts)]).astype(np.int64)
+        if int(first[-1]) > capi.COARSE_MAX_DOFS:
+            raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED, _too_many_aggregates(int(first[-1])))
+        return {me: local[me] + first[me] for me in local}, first
+
+    def _setup_coarse(self, interior_ids, first):
+        """After the upload: every subdomain learns the aggregate ids of its overlap and halo slots by one pass of
+        the ids, written as doubles into x~, through the halo exchange (ids up to 4096 are exact in the fp32 wire
+        format too), plans and uploads its part, the rows of A0 are gathered and inverted once per process."""
+        be, comm, torch = self.backend, self.comm, self.backend._torch
+        t_begin = time.perf_counter()
+        stream = be.stream()
+        nc = int(first[-1])
+        if nc < 1:
+            raise capi.SchwzError(capi.ERR_INVALID, "the coarse space has no aggregate (a matrix without rows)")
+        idx, vals = {}, {}
+        for me, sd in self.subdomains.items():
+            p, n = sd.vector(0)
+            idx[me] = torch.arange(max(n, 1), dtype=torch.int32, device=be.device)
+            v = np.full(max(n, 1), -1.0)
+            v[:sd.local_size] = interior_ids[me]
+            vals[me] = torch.from_numpy(v).to(be.device)
+            if n:
+                core.scatter(n, idx[me].data_ptr(), vals[me].data_ptr(), p, stream=stream)
+        for me, sd in self.subdomains.items():
+            self._pack(me, sd, stream)
+        comm.exchange(self._sends, self._recvs)
+        for me, sd in self.subdomains.items():
+            self._unpack(me, sd, stream)
+        rows = {}
+        for me, sd in self.subdomains.items():
+            p, n = sd.vector(0)
+            if n:
+                core.gather(n, idx[me].data_ptr(), p, vals[me].data_ptr(), stream=stream)
+                be.synchronize()
+            slot = np.rint(vals[me].cpu().numpy()[:n]).astype(np.int64)
+            if n:
+                vals[me].zero_()  # x~ starts the iteration as zeros again
+                core.scatter(n, idx[me].data_ptr(), vals[me].data_ptr(), p, stream=stream)
+                be.synchronize()
+            if (slot < 0).any() or (slot >= nc).any():
+                raise capi.SchwzError(capi.ERR_INVALID, "subdomain %d: a slot of x~ received no aggregate id from "
+                                                        "the halo exchange" % me)
+            mloc = int(first[me + 1] - first[me])
+            sd.coarse_set_aggregates(slot, int(first[me]), mloc, nc)
+            rows[me] = sd.coarse_rows().reshape(-1)
+        a0 = comm.gather_vectors(rows)
+        if hasattr(comm, "broadcast_object") and len(comm.local_ranks) < comm.size:
+            a0 = comm.broadcast_object(a0)
+        inv = core.dense_inverse(np.asarray(a0, dtype=np.float64).reshape(nc, nc))
+        obj = core.Coarse(inv)
+        gather = None
+        if len(comm.local_ranks) < comm.size:
+            # several rank processes: every rank's segment of s to everybody, padded to the largest segment
+            me = comm.local_ranks[0]
+            mmax = max(int((first[1:] - first[:-1]).max()), 1)
+            mloc = int(first[me + 1] - first[me])
+            where = np.concatenate([p * mmax + np.arange(first[p + 1] - first[p]) for p in range(comm.size)])
+            gather = dict(mine=torch.zeros(mmax, dtype=torch.float64, device=be.device),
+                          all=torch.zeros(comm.size * mmax, dtype=torch.float64, device=be.device),
+                          take=torch.arange(int(first[me]), int(first[me]) + max(mloc, 1), dtype=torch.int32,
+                                            device=be.device),
+                          where=torch.from_numpy(where.astype(np.int32)).to(be.device), mloc=mloc)
+        self._coarse = dict(obj=obj, gather=gather, nc=nc, first=first, interior=interior_ids,
+                            setup_seconds=time.perf_counter() - t_begin)
+
+    def _coarse_step(self, locals_, stream):
+        """x <- x + Z A0^-1 Z^T (b - A x) on the compute stream, between the unpack of the halo exchange and the
+        boundary update: the coarse residual of every local subdomain, (several processes) the all-gather of the
+        segments of s, the dense solve once per process, the correction of every local subdomain's x~ and y."""
+        co = self._coarse
+        obj, g = co["obj"], co["gather"]
+        for _, sd in locals_:
+            sd.coarse_residual(obj, stream)
+        if g is not None:
+            s_ptr, _ = obj.vector(0)
+            if g["mloc"]:
+                core.gather(g["mloc"], g["take"].data_ptr(), s_ptr, g["mine"].data_ptr(), stream=stream)
+            self.comm.allgather_segments(g["mine"], g["all"])
+            core.gather(co["nc"], g["where"].data_ptr(), g["all"].data_ptr(), s_ptr, stream=stream)
+        obj.solve(stream)
+        for _, sd in locals_:
+            sd.coarse_apply(obj, stream)
 
     def _debug_dumps(self, solver_code):
         """The reference's debug output for executors other than "cuda" (schwarz_base.cpp:252-257, solve.cpp:401-450,
@@ -1112,6 +1314,8 @@ class SolverRAS:
         # 0 boundary exchange (one-sided mode skips iteration 0, restricted_schwarz.cpp:725)
         if not (cs.enable_onesided and it == 0):
             self._exchange()
+        if getattr(self, "_coarse", None) is not None:
+            self._coarse_step(locals_, stream)
         t1 = time.perf_counter()
         # 1 boundary update
         for _, sd in locals_:
