@@ -1062,6 +1062,36 @@ WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, i
         if ((int64_t)W.seg_first.size() + gen_blocks > grid) W.seg_first.clear();
         else W.T_first = T;
     }
+    // ---- what the kernels read at entry: a record per slot, the tables ready to stage (coding_plan.hpp) ----
+    auto records = [&](const std::vector<int4> &seg) {
+        std::vector<WalkRecord> out(seg.size());
+        for (size_t i = 0; i < seg.size(); ++i) {
+            WalkRecord &r = out[i];
+            r.band = seg[i].x;
+            r.z0 = seg[i].y;
+            r.z1 = seg[i].z;
+            r.rows = seg[i].w;
+            for (int k = 0; k < 5; ++k) {
+                const int64_t p = (int64_t)r.z0 - 1 + k;
+                r.plane[k] = p >= 0 && p < (int64_t)chain_plane.size() ? chain_plane[(size_t)p] : -1;
+            }
+            r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        }
+        return out;
+    };
+    W.rec = records(W.seg);
+    W.rec_dir = records(W.seg_dir);
+    W.rec_first = records(W.seg_first);
+    auto ready = [](const std::vector<double> &val, const std::vector<int> &mask, int slots) {
+        std::vector<double> out(val.size(), 0.0);
+        for (size_t q = 0; q < mask.size(); ++q)
+            for (int k = 0; k < slots; ++k)
+                for (int b = 0; b < 2; ++b)
+                    if ((mask[q] >> (16 * b + k)) & 1) out[(q * slots + k) * 2 + b] = val[(q * slots + k) * 2 + b];
+        return out;
+    };
+    W.canon_ready = ready(cval, cmsk, 9);
+    W.canon_sym_ready = ready(sval, smsk, 5);
     W.gen_mode = gen_mode ? 1 : 0;
     W.T = T;
     W.T_dir = T_dir;

@@ -148,6 +148,14 @@ struct WalkPlan {
     std::vector<schwz_idx> gen;
     std::vector<double> canon_val, canon_sym_val;  // canon_sym_*: empty without upper-triangle twins
     std::vector<int> canon_mask, canon_sym_mask, chain_plane, chain_far;
+    // What the kernels read at entry.  rec / rec_dir / rec_first: one WalkRecord per slot of seg / seg_dir / seg_first
+    // (empty like them) -- the entry itself and chain_plane[z0 - 1 + k], k = 0 .. 4, copied as they are (-1: no plane;
+    // positions before the table's first: -1 too), so the first windows wait for one load, not for two in a row.
+    // canon_ready / canon_sym_ready: canon_val / canon_sym_val with +0.0 (all 64 bits clear) wherever the mask has no
+    // bit, the form the walks stage into LDS when they sum every slot -- a function of the matrix, made once here
+    // instead of by every workgroup of every launch.
+    std::vector<WalkRecord> rec, rec_dir, rec_first;
+    std::vector<double> canon_ready, canon_sym_ready;
     bool built() const { return !seg.empty(); }
     int nslots() const { return (int)seg.size(); }
     int nslots_dir() const { return seg_dir.empty() ? nslots() : (int)seg_dir.size(); }

@@ -312,7 +312,19 @@ constexpr int kTileNnz = 2048;   // products staged in LDS per tile (16 KiB fp64
 constexpr int kTileRows = 256;   // one lane per row in the reduction phase
 constexpr int kMaxGrid = 2048;   // 256 CUs x 8 workgroups, grid-stride beyond
 constexpr int kXcds = 8;
-constexpr int kGraphIters = 16;          // CG iterations per recorded hipGraph (even: rho slots repeat)
+
+// What a z-sweep walk workgroup needs to know before it can request its first windows, in one record per workgroup
+// slot (plan_walk, coding_plan.cpp): the slot's entry of the segment table {band, z0, z1, rows of the band} and the
+// plane indices of the chain positions z0 - 1 .. z0 + 3 (-1: no plane there), which the kernels would otherwise look
+// up in chain_plane behind the segment.  48 bytes: two scalar loads.
+struct alignas(16) WalkRecord {
+    int band, z0, z1, rows;
+    int plane[5];
+    int pad[3];
+};
+static_assert(sizeof(WalkRecord) == 48, "a walk record is three 16-byte pieces");
+
+constexpr int kGraphIters = 16;         // CG iterations per recorded hipGraph (even: rho slots repeat)
 constexpr int64_t kGraphRows = 1 << 21;  // systems up to this many rows replay their CG loop as graphs
 constexpr int kDeferDepth = 16;          // search directions kept before x += sum alpha_k p_k is applied
 constexpr int kWaveTileNnz = 512;  // products staged per wave (4 KiB fp64)
@@ -400,6 +412,9 @@ struct CsrView {
     // ... and the first-direction launch of a solve (one vector read, bound by latency: more, shorter workgroups)
     int sweep_T_first = 0, sweep_nslots_first = 0;
     const int4 *sweep_seg_first = nullptr;
+    // the three tables once more as records that also carry the first five chain rows of the segment (WalkRecord):
+    // what the kernels read; the int4 tables stay for whoever reads segments alone
+    const WalkRecord *sweep_rec = nullptr, *sweep_rec_dir = nullptr, *sweep_rec_first = nullptr;
     const schwz_idx *sweep_gen = nullptr;
     // per pattern of table 0: its entries in the nine slots [far before 0, far before 1, -NX, -1, 0, +1, +NX,
     // far after 0, far after 1] (9 PairVal) and the presence mask (bit k: row r has slot k, bit 16 + k: row r + 1)
@@ -410,6 +425,10 @@ struct CsrView {
     // far after 1], 5 PairVal
     const double *canon_sym_val = nullptr;
     const int *canon_sym_mask = nullptr;
+    // both tables in the form the walks keep in LDS when they sum every slot (SCHWZ_WALK_ZEROCOEF, spmv_pair.hip):
+    // canon_npat x 9 and canon_npat x 5 pairs, +0.0 where the mask has no bit -- one 16-byte load per staged entry
+    const double *canon_ready = nullptr;
+    const double *canon_sym_ready = nullptr;
     // chains of planes (see plan_walk, coding_plan.cpp): plane index per chain position (-1: none) and, per position, which
     // window each far slot reads (2 bits per slot B0, B1, A0, A1: 0 none, 1 previous position, 2 next)
     const int *chain_plane = nullptr;
@@ -687,7 +706,7 @@ struct schwz_csr {
         struct { schwz::DevBuf pair_id, rle, chunk_ptable, ptbl_desc, ptbl_len, ptbl_val, ptbl_meta; } pair;
         struct {
             schwz::DevBuf seg, seg_dir, seg_first, gen, canon_val, canon_mask, canon_sym_val, canon_sym_mask, chain_plane,
-                chain_far;
+                chain_far, rec, rec_dir, rec_first, canon_ready, canon_sym_ready;
         } walk;
         struct { schwz::DevBuf chunk_dual, chain_dual, dual_chunks; } dual;
     } coding;

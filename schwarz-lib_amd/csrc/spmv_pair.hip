@@ -618,10 +618,25 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_kernel(CsrView A, SpmvArgs a
 //   requested behind the windows, came back behind them (vector loads return in order), and each fold's two
 //   __syncthreads() waited for every prefetched plane, not only for those of the first position.
 // bit 1: the partial sums are requested eight per bank at a time (fold_lane_sums) instead of one after the other.
-// Every sum keeps its order: the same bits.  0 restores the earlier prologue.
+// bit 2 (needs bits 0 and 1): everything that depends on nothing but the kernel arguments and blockIdx.x is requested
+//   at kernel entry before anything is waited for -- stop_iter, the slot's WalkRecord (segment AND its first five
+//   chain rows, read through the constant address space: scalar loads that do not queue behind the vector loads), rho,
+//   the table entries in their staged form (CsrView::canon_ready: one unconditional 16-byte load per entry, kept in
+//   registers) and the lane sums -- and the early return and the empty-slot branch follow that one wait.  Then the
+//   windows are requested; the LDS stores of the tables join the cross-wave part of the fold behind them.  Before,
+//   stop_iter, the segment (a vector load), the sums, the mask, the values behind branches on the mask bits, the mask
+//   again and the chain rows were each waited for in turn.  The loads in front of the return have no side effect and
+//   valid addresses whether or not the launch is live.  With SCHWZ_WALK_ZEROCOEF=0 the tables are staged from
+//   canon_val / canon_mask as under bit 0.
+// Every sum keeps its order: the same bits.  3 restores the prologue of round 16, 0 the one before it.
 #ifndef SCHWZ_WALK_PRO
-#define SCHWZ_WALK_PRO 3
+#define SCHWZ_WALK_PRO 7
 #endif
+static_assert((SCHWZ_WALK_PRO & 4) == 0 || (SCHWZ_WALK_PRO & 3) == 3, "SCHWZ_WALK_PRO bit 2 builds on bits 0 and 1");
+// table entries a lane keeps in registers between kernel entry and the LDS stores (bit 2): kPairPats patterns of nine
+// slots at the most, of five in the fused direction walk
+constexpr int kWalkTabPerLane = (kPairPats * 9 + kBlock - 1) / kBlock;
+constexpr int kWalkSymTabPerLane = (kPairPats * 5 + kBlock - 1) / kBlock;
 
 // Launch timeline of the walk kernels (measurement build only: make variant DEFS=-DSCHWZ_WITH_PROBES, read by
 // tools/walk_timeline.py).  Lane 0 of a workgroup stores the 100 MHz wall clock at kWalkStamps points of its life into
@@ -715,7 +730,9 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     const int tid = threadIdx.x;
     [[maybe_unused]] constexpr int kForm = INIT ? kFormStart : kFormUpdate;
     SCHWZ_STAMP(kForm, kStampEntry);
-    if (!INIT) {
+    constexpr bool kPro2 = (SCHWZ_WALK_PRO & 4) != 0;            // one wait for everything but the windows (see SCHWZ_WALK_PRO)
+    constexpr bool kReady = kPro2 && SCHWZ_WALK_ZEROCOEF != 0;  // ... the tables among it, from their staged form
+    if (!kPro2 && !INIT) {
         if (a.it >= a.cg_state->stop_iter) return;
     }
     // INIT reads the right-hand side where the update launch reads r (the caller's b need only be 8-byte
@@ -732,6 +749,22 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     // cross-wave part of the fold behind the window requests -- `late`; without it both where `late` is called)
     constexpr bool kEarly = (SCHWZ_WALK_PRO & 1) != 0;
     double fold_lane = 0.0, rho_it = 0.0;
+    // (kReady) the lane's table entries between their request and their LDS stores: rounds of kBlock entries, a round
+    // that exists is loaded by every lane (the lanes past the table's end repeat its last entry and store nothing)
+    pvd2 tab[kWalkTabPerLane];
+    const int ntab = A.canon_npat * 9;
+    auto request_tables = [&]() {
+#pragma unroll
+        for (int k = 0; k < kWalkTabPerLane; ++k) {
+            tab[k] = pvd2{0.0, 0.0};
+            if (k * kBlock < ntab) tab[k] = *reinterpret_cast<const pvd2 *>(A.canon_ready + 2 * min(tid + k * kBlock, ntab - 1));
+        }
+    };
+    auto store_tables = [&]() {
+#pragma unroll
+        for (int k = 0; k < kWalkTabPerLane; ++k)
+            if (tid + k * kBlock < ntab) cpv[tid + k * kBlock] = PairVal{tab[k].x, tab[k].y};
+    };
     auto stage_tables = [&]() {
         for (int i = tid; i < A.canon_npat * 9; i += kBlock) {
             if (SCHWZ_WALK_ZEROCOEF) {
@@ -743,10 +776,28 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         }
         if (tid < A.canon_npat) cmask[tid] = A.canon_mask[tid];
     };
+    // (kPro2) the slot's record, through the constant address space: scalar loads
+    typedef const WalkRecord __attribute__((address_space(4))) *const_record;
+    int4 sg;
+    int rec_plane[5] = {0, 0, 0, 0, 0};
+    auto request_record = [&]() {
+        const const_record rec = (const_record)(uintptr_t)A.sweep_rec + blockIdx.x;
+        sg.x = rec->band, sg.y = rec->z0, sg.z = rec->z1, sg.w = rec->rows;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) rec_plane[k] = rec->plane[k];
+    };
     auto tables_and_alpha = [&](bool early) {
         if (kEarly && early) {
+            if (!INIT) rho_it = a.cg_state->rho[a.it & 1];
+            if (kPro2) {
+                request_record();
+                // (no instruction: keeps the compiler from moving the scalar requests above behind the vector requests
+                // below, where they landed behind a second wait for kernel arguments -- the arguments those need are
+                // operands here, so they arrive with the first batch)
+                asm volatile("" ::"s"(a.pq_partials), "s"(a.pq_nparts), "s"(A.canon_ready), "s"(ntab) : "memory");
+            }
+            if (kReady) request_tables();  // (before the sums: the first wait for a vector load is inside fold_lane_sums)
             if (!INIT) {
-                rho_it = a.cg_state->rho[a.it & 1];
                 if (SCHWZ_WALK_PRO & 2) {
                     double s[1] = {0.0};
                     fold_lane_sums(a.pq_partials, a.pq_nparts, s);
@@ -755,10 +806,11 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
                     for (int i = tid; i < a.pq_nparts; i += kBlock) fold_lane += a.pq_partials[i];  // fold_partials' sums
                 }
             }
-            stage_tables();
+            if (!kReady) stage_tables();
             return;
         }
         if (!kEarly) stage_tables();
+        if (kReady) store_tables();
         if (!INIT) {
             if (kEarly) {
                 double v[1] = {fold_lane};
@@ -771,13 +823,20 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         }
         lds_barrier();
     };
+    if (kPro2) {
+        // requests only, in front of the first wait: stop_iter, rho and the record (scalar), the tables, the lane sums
+        int stop_iter = 0;
+        if (!INIT) stop_iter = a.cg_state->stop_iter;
+        tables_and_alpha(true);
+        if (!INIT && a.it >= stop_iter) return;
+    }
     // partial-sum slots no workgroup of this launch or of its companion writes
     if (blockIdx.x == 0)
         for (int i = (int)gridDim.x + a.part_offset + tid; i < a.part_stride; i += kBlock) {
             a.partials[i] = a.partials[a.part_stride + i] = 0.0;
             if (DUAL) a.partials[2 * a.part_stride + i] = 0.0;
         }
-    const int4 sg = A.sweep_seg[blockIdx.x];
+    if (!kPro2) sg = A.sweep_seg[blockIdx.x];
     const int64_t PL = A.sweep_pl;
     const int band = sg.x, z0 = sg.y, z1 = sg.z;  // chain positions z0 <= z < z1
     constexpr bool GEN = RUNS == 0;
@@ -786,7 +845,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
     typedef const unsigned __attribute__((address_space(4))) *const_words;
     typedef const int __attribute__((address_space(4))) *const_ints;
-    if (kEarly && (z0 < z1 || blockIdx.x == 0)) tables_and_alpha(true);
+    if (!kPro2 && kEarly && (z0 < z1 || blockIdx.x == 0)) tables_and_alpha(true);
     if (z0 < z1) {
         // first row of the band at a chain position (scalar loads: the position is workgroup-uniform); a
         // position without a plane (the ends of a chain) reads plane 0 -- valid memory no mask lets through
@@ -857,7 +916,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         Ahead r_a[NH], r_b[NH];
         int brow[5];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) brow[k] = band_row(z0 - 1 + k);
+        for (int k = 0; k < 5; ++k)
+            brow[k] = kPro2 ? (rec_plane[k] < 0 ? 0 : rec_plane[k]) * (int)PL + band * T : band_row(z0 - 1 + k);
         SCHWZ_STAMP_AFTER(brow[0] + brow[1] + brow[2] + brow[3] + brow[4]);
         SCHWZ_STAMP(kForm, kStampSegment);
         SCHWZ_STAMP_POSITIONS(z1 - z0);
@@ -1042,9 +1102,11 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     __shared__ double red[8];
     [[maybe_unused]] constexpr int kForm = FIRST ? kFormFirst : kFormDirdot;
     SCHWZ_STAMP(kForm, kStampEntry);
+    constexpr bool kPro2 = (SCHWZ_WALK_PRO & 4) != 0;            // as in the update walk
+    constexpr bool kReady = kPro2 && SCHWZ_WALK_ZEROCOEF != 0;
     // (FIRST reads nothing of CgState: with init_fold its own workgroup 0 is still to write it.  After a zero start
     // residual the launch is needless; the update launch behind it sees stop_iter == 0 and leaves.)
-    if (!FIRST && a.it >= a.cg_state->stop_iter) return;
+    if (!kPro2 && !FIRST && a.it >= a.cg_state->stop_iter) return;
     double cg_rho_new = 0.0, cg_rr = 0.0, cg_beta = 0.0;
     const int tid = threadIdx.x;
     // FIRST, workgroup 0: CgState and the check norm from the start walk's partial sums, which the kernel boundary
@@ -1060,6 +1122,22 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     // the two folds share one pair of LDS-only barriers)
     constexpr bool kEarly = (SCHWZ_WALK_PRO & 1) != 0;
     double fold_rho = 0.0, fold_rr = 0.0, rho_it = 0.0;
+    // (kReady) the lane's table entries between their request and their LDS stores: rounds of kBlock entries, a round
+    // that exists is loaded by every lane (the lanes past the table's end repeat its last entry and store nothing)
+    pvd2 tab[kWalkSymTabPerLane];
+    const int ntab = A.canon_npat * 5;
+    auto request_tables = [&]() {
+#pragma unroll
+        for (int k = 0; k < kWalkSymTabPerLane; ++k) {
+            tab[k] = pvd2{0.0, 0.0};
+            if (k * kBlock < ntab) tab[k] = *reinterpret_cast<const pvd2 *>(A.canon_sym_ready + 2 * min(tid + k * kBlock, ntab - 1));
+        }
+    };
+    auto store_tables = [&]() {
+#pragma unroll
+        for (int k = 0; k < kWalkSymTabPerLane; ++k)
+            if (tid + k * kBlock < ntab) cpv[tid + k * kBlock] = PairVal{tab[k].x, tab[k].y};
+    };
     auto stage_tables = [&]() {
         for (int i = tid; i < A.canon_npat * 5; i += kBlock) {
             if (SCHWZ_WALK_ZEROCOEF) {
@@ -1071,10 +1149,25 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         }
         if (tid < A.canon_npat) cmask[tid] = A.canon_sym_mask[tid];
     };
+    // (kPro2) the slot's record, through the constant address space: scalar loads
+    typedef const WalkRecord __attribute__((address_space(4))) *const_record;
+    int4 sg;
+    int rec_plane[5] = {0, 0, 0, 0, 0};
+    auto request_record = [&]() {
+        const const_record rec = (const_record)(uintptr_t)A.sweep_rec_dir + blockIdx.x;
+        sg.x = rec->band, sg.y = rec->z0, sg.z = rec->z1, sg.w = rec->rows;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) rec_plane[k] = rec->plane[k];
+    };
     auto tables_and_beta = [&](bool early) {
         if (kEarly && early) {
+            if (!FIRST) rho_it = a.cg_state->rho[a.it & 1];
+            if (kPro2) {
+                request_record();
+                asm volatile("" ::"s"(a.pq_partials), "s"(a.pq_nparts), "s"(A.canon_sym_ready), "s"(ntab) : "memory");  // (as in the update walk)
+            }
+            if (kReady) request_tables();  // (before the sums, as in the update walk)
             if (!FIRST) {
-                rho_it = a.cg_state->rho[a.it & 1];
                 if (SCHWZ_WALK_PRO & 2) {
                     double s[2] = {0.0, 0.0};
                     fold_lane_sums(a.pq_partials, a.pq_nparts, s);
@@ -1087,10 +1180,11 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
                     }
                 }
             }
-            stage_tables();
+            if (!kReady) stage_tables();
             return;
         }
         if (!kEarly) stage_tables();
+        if (kReady) store_tables();
         if (!FIRST) {
             if (kEarly) {
                 double v[2] = {fold_rho, fold_rr};
@@ -1107,10 +1201,17 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         init_fold();
         lds_barrier();
     };
+    if (kPro2) {
+        // requests only, in front of the first wait (as in the update walk)
+        int stop_iter = 0;
+        if (!FIRST) stop_iter = a.cg_state->stop_iter;
+        tables_and_beta(true);
+        if (!FIRST && a.it >= stop_iter) return;
+    }
     if (blockIdx.x == 0)
         for (int i = (int)gridDim.x + a.part_offset + tid; i < a.part_stride; i += kBlock)
             a.partials[i] = a.partials[a.part_stride + i] = 0.0;
-    const int4 sg = A.sweep_seg_dir[blockIdx.x];  // (its own table: the band height may differ from the update launch's)
+    if (!kPro2) sg = A.sweep_seg_dir[blockIdx.x];  // (its own table: the band height may differ from the update launch's)
     const int64_t PL = A.sweep_pl;
     const int band = sg.x, z0 = sg.y, z1 = sg.z;
     constexpr bool GEN = RUNS == 0;          // planes that are not whole chunks: byte ids, partial last band (see above)
@@ -1120,7 +1221,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     double acc0 = 0.0;
     typedef const unsigned __attribute__((address_space(4))) *const_words;
     typedef const int __attribute__((address_space(4))) *const_ints;
-    if (kEarly && (z0 < z1 || (!FIRST && blockIdx.x == 0))) tables_and_beta(true);
+    if (!kPro2 && kEarly && (z0 < z1 || (!FIRST && blockIdx.x == 0))) tables_and_beta(true);
     if (z0 < z1) {
         const const_ints chain = (const_ints)(uintptr_t)A.chain_plane;
         const const_ints chain_far = (const_ints)(uintptr_t)A.chain_far;
@@ -1219,7 +1320,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         Rle rle_a[NH], rle_b[NH];
         int brow[5];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) brow[k] = band_row(z0 - 1 + k);
+        for (int k = 0; k < 5; ++k)
+            brow[k] = kPro2 ? (rec_plane[k] < 0 ? 0 : rec_plane[k]) * (int)PL + band * T : band_row(z0 - 1 + k);
         SCHWZ_STAMP_AFTER(brow[0] + brow[1] + brow[2] + brow[3] + brow[4]);
         SCHWZ_STAMP(kForm, kStampSegment);
         SCHWZ_STAMP_POSITIONS(z1 - z0);
@@ -1365,7 +1467,7 @@ bool pair_sweep_update_ok(const CsrView &A, int grid, int diag_mode)
 {
     const int nh = A.sweep_T / kPairRows, nhl = (A.sweep_nx + kBlock - 1) / kBlock;
     return A.pair_single && A.sweep_nslots > 0 && A.ncols < (int64_t(1) << 28) && diag_mode != 2 &&
-           A.sweep_nslots + A.sweep_gen_blocks <= grid && (nh == 1 || nh == 2) && nhl <= 4 &&
+           A.sweep_nslots + A.sweep_gen_blocks <= grid && (nh == 1 || nh == 2) && nhl <= 4 && A.canon_npat <= kPairPats &&
            sweep_update_lds(A.sweep_T, A.sweep_nx, A.canon_npat) <= kSweepLdsLimit;
 }
 
@@ -1538,6 +1640,7 @@ int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
         if (A.sweep_seg_first && A.sweep_nslots_first <= grid) {
             Af.sweep_T_dir = A.sweep_T_first;
             Af.sweep_seg_dir = A.sweep_seg_first;
+            Af.sweep_rec_dir = A.sweep_rec_first;
             Af.sweep_nslots_dir = A.sweep_nslots_first;
         }
         SpmvArgs b = a;
@@ -1678,6 +1781,11 @@ static void bind_walk(schwz_csr *A, const WalkPlan &W)
     v.canon_sym_mask = b.canon_sym_mask.as<int>();
     v.chain_plane = b.chain_plane.as<int>();
     v.chain_far = b.chain_far.as<int>();
+    v.sweep_rec = b.rec.as<WalkRecord>();
+    v.sweep_rec_dir = b.rec_dir.p ? b.rec_dir.as<WalkRecord>() : v.sweep_rec;
+    v.sweep_rec_first = b.rec_first.p ? b.rec_first.as<WalkRecord>() : v.sweep_rec_dir;
+    v.canon_ready = b.canon_ready.as<double>();
+    v.canon_sym_ready = b.canon_sym_ready.as<double>();
     A->h_chain_plane = W.chain_plane;
 }
 
@@ -1702,6 +1810,11 @@ static int upload_walk(schwz_csr *A, const WalkPlan &W)
         (rc = b.canon_mask.put(W.canon_mask)) || (rc = b.chain_plane.put(W.chain_plane)) ||
         (rc = b.chain_far.put(W.chain_far)) ||
         (!W.canon_sym_val.empty() && ((rc = b.canon_sym_val.put(W.canon_sym_val)) || (rc = b.canon_sym_mask.put(W.canon_sym_mask)))))
+        return rc;
+    // the records and ready tables the kernels read at entry (every build uploads them; SCHWZ_WALK_PRO bit 2 reads them)
+    if ((!W.rec_dir.empty() && (rc = b.rec_dir.put(W.rec_dir))) || (!W.rec_first.empty() && (rc = b.rec_first.put(W.rec_first))) ||
+        (rc = b.rec.put(W.rec)) || (rc = b.canon_ready.put(W.canon_ready)) ||
+        (!W.canon_sym_ready.empty() && (rc = b.canon_sym_ready.put(W.canon_sym_ready))))
         return rc;
     return SCHWZ_OK;
 }
