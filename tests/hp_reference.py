@@ -1044,3 +1044,187 @@ def window2049_square(rng, n=1100):
     on = pat.indices == rowid
     val[on] = rng.choice([-1.0, 1.0], n) * rng.uniform(1.0, 2.0, n)
     return pat.indptr.astype(np.int32), pat.indices.astype(np.int32), val
+
+
+# ---- the coarse correction (csrc/coarse.hip): residual of the aggregates, dense GEMV, apply --------------------------------
+
+COARSE_PIECE_CAP = 2048   # kCoarsePieceCap: W entries one workgroup reduces
+
+
+def pow2_operands(rng, n, lo=0, hi=0, exps=None):
+    """+-u 2^e with u uniform in [0.5, 2) and e drawn from [lo, hi] (or given): no operand is small against its
+    neighbours of the same exponent, which standard normal operands cannot promise over millions of products."""
+    e = rng.integers(lo, hi + 1, n) if exps is None else np.asarray(exps)
+    return np.ldexp(rng.choice([-1.0, 1.0], n) * rng.uniform(0.5, 2.0, n), e)
+
+
+def coarse_residual(rp, col, val, x, b, agg, m, dtype=LD):
+    """s_a = sum_{i in a} (b_i - sum_j A_ij x~_j), a = agg[i] in [0, m), over the rows of (rp, col, val) -- the
+    interior rows of a subdomain, columns index x~ -- from the definition: every row's residual in CSR order, the
+    rows of an aggregate added in ascending order, in `dtype`.  No W is formed."""
+    r = residual(rp, col, val, x, b, dtype)
+    s = np.zeros(m, dtype=dtype)
+    np.add.at(s, np.asarray(agg, dtype=np.int64), r)
+    return s
+
+
+def coarse_residual_bound(rp, col, val, x, b, agg, m):
+    """e_a with |s^_a - s_a| <= e_a for a float64 evaluation of the coarse residual as beta_a - sum_j W_aj x~_j,
+    W_aj = sum_{i in a} A_ij and beta_a = sum_{i in a} b_i formed first, against coarse_residual(...) in longdouble:
+
+        e_a = (gamma(K_a + 1) + (K_a + 2) 2^-64) (sum_{i in a} |b_i| + sum_{i in a} sum_j |A_ij| |x~_j|),
+
+    K_a = the rows of a plus their stored entries.  Derivation (Higham 3.1, as above): a value A_ij reaches s^_a
+    through the additions inside W_aj (c_j - 1 of them, c_j the entries of a in column j), one product, the additions
+    that join the n_W products of the aggregate into one number -- any tree over n_W leaves has n_W - 1 of them; an
+    addition to an exact zero (a lane without an entry, the fold's start) rounds nothing -- and the subtraction from
+    beta_a: c_j + n_W <= entries + 1 <= K_a rounded operations, since the n_W slots are distinct and slot j holds
+    c_j - 1 entries more than one.  A b_i passes rows - 1 additions and the subtraction: rows <= K_a.  So every term
+    carries at most gamma(K_a), and gamma(K_a + 1) bounds any order of these sums: the host plan's, the strided lanes
+    and the tree of block_sum, the fold in table order.  A W_aj that sums to an exact zero and is dropped is the same
+    statement with that sum.  The reference passes every term through at most k_i + 1 + rows <= K_a + 1 longdouble
+    roundings: the second term.  Nothing is measured on a kernel."""
+    rp = np.asarray(rp, dtype=np.int64)
+    agg = np.asarray(agg, dtype=np.int64)
+    K = np.zeros(m, dtype=np.int64)
+    np.add.at(K, agg, 1 + np.diff(rp))
+    mag = np.zeros(m, dtype=LD)
+    np.add.at(mag, agg, np.abs(np.asarray(b, dtype=LD)) + abs_row_sums(rp, col, val, x))
+    return (gamma(K + 1) + (K + 2) * LD(U_LD)) * mag
+
+
+def coarse_w(rp, col, val, b, agg, m):
+    """The host plan of the coarse residual restated (plan_coarse of coarse_plan.cpp) in float64: per aggregate the
+    slots in ascending order with W_aj summed row after row, exact zeros dropped, and beta_a summed over the rows in
+    ascending order.  Returns (w_ptr, w_slot, w_val, beta)."""
+    rp = np.asarray(rp, dtype=np.int64)
+    n = len(rp) - 1
+    agg = np.asarray(agg, dtype=np.int64)
+    col = np.asarray(col, dtype=np.int64)[:rp[n]]
+    val = np.asarray(val, dtype=np.float64)[:rp[n]]
+    a_of = np.repeat(agg, np.diff(rp))
+    ncols = int(col.max()) + 1 if len(col) else 1
+    key = a_of * ncols + col
+    order = np.argsort(key, kind="stable")          # rows of a slot stay in ascending order
+    key, v = key[order], val[order]
+    start = np.nonzero(np.concatenate([[True], key[1:] != key[:-1]]))[0] if len(key) else np.zeros(0, dtype=np.int64)
+    gp = np.concatenate([start, [len(key)]]).astype(np.int64)
+    w = spmv(gp, np.zeros(len(key), dtype=np.int64), v, np.ones(1), np.float64) if len(key) else np.zeros(0)
+    keep = w != 0.0
+    gkey = key[start][keep]
+    w_val, w_slot, w_agg = w[keep], gkey % ncols, gkey // ncols
+    w_ptr = np.zeros(m + 1, dtype=np.int64)
+    np.add.at(w_ptr, w_agg + 1, 1)
+    w_ptr = np.cumsum(w_ptr)
+    row_order = np.argsort(agg, kind="stable")
+    bp = np.zeros(m + 1, dtype=np.int64)
+    np.add.at(bp, agg + 1, 1)
+    beta = spmv(np.cumsum(bp), np.zeros(n, dtype=np.int64), np.asarray(b, dtype=np.float64)[row_order], np.ones(1),
+                np.float64)
+    return w_ptr, w_slot, w_val, beta
+
+
+def coarse_pieces(w_ptr, cap=COARSE_PIECE_CAP):
+    """[(aggregate, begin, end)] in table order and piece_ptr: an aggregate's W entries cut every `cap` entries."""
+    pieces, piece_ptr = [], [0]
+    for a in range(len(w_ptr) - 1):
+        for b0 in range(int(w_ptr[a]), int(w_ptr[a + 1]), cap):
+            pieces.append((a, b0, min(b0 + cap, int(w_ptr[a + 1]))))
+        piece_ptr.append(len(pieces))
+    return pieces, np.asarray(piece_ptr, dtype=np.int64)
+
+
+def block_tree_sum64(t):
+    """A workgroup's reduction of the float64 terms t restated: 256 lanes each add their share k, k + 256, ..., the
+    64 lanes of a wave fold by halves (offsets 32 .. 1), the four waves as (w0 + w1) + (w2 + w3)."""
+    lanes = np.zeros(256)
+    t = np.asarray(t, dtype=np.float64)
+    for k0 in range(0, len(t), 256):
+        part = t[k0:k0 + 256]
+        lanes[:len(part)] += part
+    w = lanes.reshape(4, 64).copy()
+    off = 32
+    while off:
+        w[:, :off] += w[:, off:2 * off]
+        off >>= 1
+    return (w[0, 0] + w[1, 0]) + (w[2, 0] + w[3, 0])
+
+
+def coarse_residual64(w_ptr, w_slot, w_val, beta, x, pieces=None, piece_ptr=None, piece_sum=block_tree_sum64):
+    """The device's evaluation restated in float64: one partial sum per piece (piece_sum), the pieces of an aggregate
+    folded in table order, s_a = beta_a - t.  `pieces`, `piece_ptr`: another table (the seeded defects)."""
+    if pieces is None:
+        pieces, piece_ptr = coarse_pieces(w_ptr)
+    t = np.asarray(w_val, dtype=np.float64) * np.asarray(x, dtype=np.float64)[w_slot]
+    partial = np.array([piece_sum(t[b0:b1]) for _, b0, b1 in pieces] + [0.0])
+    s = np.zeros(len(beta))
+    for a in range(len(beta)):
+        f = 0.0
+        for p in range(int(piece_ptr[a]), int(piece_ptr[a + 1])):
+            f += partial[p]
+        s[a] = beta[a] - f
+    return s
+
+
+def aggregates_by_w_count(rp, col, targets):
+    """One aggregate id per row: aggregate k < len(targets) is a contiguous row range whose rows hold exactly
+    targets[k] distinct columns, the ranges in ascending row order; every other row belongs to the last aggregate,
+    len(targets).  Found row by row: a range grows until it holds targets[k] columns; one more row adds about one
+    column, but also none or two, and where the count steps over the target the range starts one row later (the row
+    left out joins the last aggregate).  Asserts that every target is met exactly and that rows are left over."""
+    rp = np.asarray(rp, dtype=np.int64)
+    col = np.asarray(col, dtype=np.int64)
+    n = len(rp) - 1
+
+    def end_of(r0, t):
+        seen, cnt = np.zeros(int(col.max()) + 1, dtype=bool), 0
+        for r in range(r0, n):
+            c = col[rp[r]:rp[r + 1]]
+            cnt += int((~seen[c]).sum())
+            seen[c] = True
+            if cnt >= t:
+                return r + 1 if cnt == t else None
+        return None
+
+    agg = np.full(n, len(targets), dtype=np.int64)
+    r0 = 0
+    for k, t in enumerate(targets):
+        r1 = None
+        while r1 is None:
+            assert r0 < n, ("no contiguous row range with exactly %d columns" % t)
+            r1 = end_of(r0, t)
+            r0 += r1 is None
+        agg[r0:r1] = k
+        r0 = r1
+    assert (agg == len(targets)).any()
+    return agg
+
+
+def coarse_gemv(M, s, dtype=LD, block=256):
+    """(c, mag) with c = M s and mag_i = sum_j |M_ij| |s_j|, in `dtype`, in blocks of rows (nc = 4096 stays cheap)."""
+    _guard(dtype)
+    M = np.asarray(M)
+    n = M.shape[0]
+    sv = np.asarray(s, dtype=dtype)
+    c, mag = np.zeros(n, dtype=dtype), np.zeros(n, dtype=dtype)
+    for i0 in range(0, n, block):
+        p = M[i0:i0 + block].astype(dtype) * sv
+        c[i0:i0 + block] = p.sum(axis=1)
+        mag[i0:i0 + block] = np.abs(p).sum(axis=1)
+    return c, mag
+
+
+def coarse_gemv_bound(mag, nc):
+    """Row bound of a float64 evaluation of c_i = sum_j M_ij s_j against coarse_gemv(...) in longdouble, mag_i =
+    sum_j |M_ij| |s_j|:  (gamma(nc) + (nc + 2) 2^-64) mag_i -- nc products, each rounded once and passing at most
+    nc - 1 rounded additions in ANY order (64 strided lanes folded by halves, 16-byte pairs, pairwise), with or
+    without FMA; the reference's own sum adds the second term."""
+    return (gamma(nc) + (nc + 2) * LD(U_LD)) * np.asarray(mag, dtype=LD)
+
+
+def coarse_apply(x, y, c, slot_agg):
+    """The apply is one rounded addition per entry, so its reference is exact: (x~ + c[agg], y + c[agg[:len(y)]]) in
+    float64, to be compared bit for bit."""
+    slot_agg = np.asarray(slot_agg, dtype=np.int64)
+    c = np.asarray(c, dtype=np.float64)
+    return np.asarray(x, dtype=np.float64) + c[slot_agg], np.asarray(y, dtype=np.float64) + c[slot_agg[:len(y)]]

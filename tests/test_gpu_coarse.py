@@ -218,12 +218,14 @@ def watch_orthogonality(solver, torch, schwz, steps=3):
     return seen
 
 
-def test_coarse_residual_vanishes_after_the_correction_laplacian(schwz, torch_cuda):
+@pytest.mark.parametrize("box,nc", [((4, 4, 2), 54), ((4, 4, 4), 27)])
+def test_coarse_residual_vanishes_after_the_correction_laplacian(schwz, torch_cuda, box, nc):
+    """(4, 4, 4): 27 aggregates, 9 per slab -- the whole chain (residual, dense_inverse, GEMV, apply) with an odd nc."""
     shape, P = (12, 12, 12), 3
-    agg = boxes(shape, (4, 4, 2))
+    agg = boxes(shape, box)
     solver, m = make_solver(schwz, P, dict(laplacian_dim=3, laplacian_shape=shape, local_solver="direct-ginkgo"),
                             dict(tolerance=1e-8, max_iters=200, coarse_space="aggregates", coarse_aggregate_vector=agg))
-    assert solver._coarse["nc"] == 54
+    assert solver._coarse["nc"] == nc
     seen = watch_orthogonality(solver, torch_cuda, schwz)
     out = solver.run()
     print("worst |s_a| / scale in the first steps:", seen)

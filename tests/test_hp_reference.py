@@ -494,3 +494,166 @@ def test_residual_bound_rejects_a_skipped_first_entry_of_an_interface_row():
         v[first[k]] = 0.0
         got = hp.residual(irp, icol, v, x, b, np.float64)
         assert abs(got[rows[k]] - r[rows[k]]) > e[rows[k]]
+
+
+# ---- the coarse correction: residual of the aggregates, dense GEMV, apply ------------------------------------------------
+
+PIECE_TARGETS = (2047, 2048, 2049, 4096, 4097)
+
+
+@pytest.fixture(scope="module")
+def coarse_case():
+    """hp.sym_band_matrix(16384, 6, 40, default_rng(7)), x~ = +-u, contiguous aggregates of one row, then exactly
+    2047, 2048, 2049, 4096, 4097 W entries, then the rest: aggregates of 1, 2 and 3 pieces."""
+    hp.require_extended_precision()
+    rng = np.random.default_rng(7)
+    rp, col, val = hp.sym_band_matrix(16384, 6, 40, rng)
+    n = len(rp) - 1
+    x = hp.pow2_operands(rng, n)
+    b = hp.pow2_operands(rng, n)
+    agg = hp.aggregates_by_w_count(rp, col, (int(rp[1]),) + PIECE_TARGETS)
+    m = int(agg.max()) + 1
+    w_ptr, w_slot, w_val, beta = hp.coarse_w(rp, col, val, b, agg, m)
+    assert tuple(np.diff(w_ptr)[:6]) == (int(rp[1]),) + PIECE_TARGETS and m == 7
+    pieces, piece_ptr = hp.coarse_pieces(w_ptr)
+    assert set(np.diff(piece_ptr)) == {1, 2, 3}
+    return dict(rp=rp, col=col, val=val, x=x, b=b, agg=agg, m=m, w=(w_ptr, w_slot, w_val, beta), pieces=pieces,
+                piece_ptr=piece_ptr, s=hp.coarse_residual(rp, col, val, x, b, agg, m),
+                e=hp.coarse_residual_bound(rp, col, val, x, b, agg, m))
+
+
+def test_coarse_residual_bound_holds_for_float64_restatements_in_any_order(coarse_case):
+    """The plan's order -- W summed first, pieces of at most 2048 entries, a tree inside a piece, the fold in table
+    order -- and three random orders of the W entries, summed one after the other."""
+    c = coarse_case
+    w_ptr, w_slot, w_val, beta = c["w"]
+    got = hp.coarse_residual64(w_ptr, w_slot, w_val, beta, c["x"])
+    q = np.abs(got - c["s"]) / c["e"]
+    print("\ncoarse residual, plan order: error / bound per aggregate", np.asarray(q, dtype=np.float64))
+    assert (q <= 1.0).all()
+    for seed in (1, 2, 3):
+        rng = np.random.default_rng(seed)
+        s = np.zeros(c["m"])
+        for a in range(c["m"]):
+            k = w_ptr[a] + rng.permutation(w_ptr[a + 1] - w_ptr[a])
+            t = 0.0
+            for v in w_val[k] * c["x"][w_slot[k]]:
+                t += v
+            s[a] = beta[a] - t
+        assert (np.abs(s - c["s"]) <= c["e"]).all(), seed
+    # the definition itself in float64: rows in CSR order, no W at all
+    s64 = hp.coarse_residual(c["rp"], c["col"], c["val"], c["x"], c["b"], c["agg"], c["m"], np.float64)
+    assert (np.abs(s64 - c["s"]) <= c["e"]).all()
+
+
+def test_coarse_residual_bound_rejects_the_seeded_piece_defects(coarse_case):
+    """The last entry of a piece dropped; one piece left out of the fold; the fold adding the first piece of the next
+    aggregate.  What each defect removes or adds is asserted to be more than 4 e_a first: on the input."""
+    c = coarse_case
+    w_ptr, w_slot, w_val, beta = c["w"]
+    pieces, piece_ptr, e = c["pieces"], c["piece_ptr"], c["e"]
+    term = np.abs(w_val * c["x"][w_slot]).astype(LD)
+    for a in range(1, c["m"]):
+        assert term[w_ptr[a]:w_ptr[a + 1]].min() > 4 * e[a], a          # no entry of these aggregates is negligible
+    partial = np.array([hp.block_tree_sum64((w_val * c["x"][w_slot])[b0:b1]) for _, b0, b1 in pieces])
+    for p, (a, b0, b1) in enumerate(pieces):
+        if a == 0:
+            continue
+        # the last entry of piece p dropped
+        short = list(pieces)
+        short[p] = (a, b0, b1 - 1)
+        got = hp.coarse_residual64(w_ptr, w_slot, w_val, beta, c["x"], short, piece_ptr)
+        assert abs(got[a] - c["s"][a]) > e[a], ("dropped entry", p)
+        assert (np.abs(np.delete(got, a) - np.delete(c["s"], a)) <= np.delete(e, a)).all()
+    for a in range(1, c["m"]):
+        # the fold stops one piece early
+        assert abs(partial[piece_ptr[a + 1] - 1]) > 4 * e[a], a
+        early = piece_ptr.copy()
+        table = [q for k, q in enumerate(pieces) if k != piece_ptr[a + 1] - 1]
+        early[a + 1:] -= 1
+        got = hp.coarse_residual64(w_ptr, w_slot, w_val, beta, c["x"], table, early)
+        assert abs(got[a] - c["s"][a]) > e[a], ("piece left out", a)
+        # the fold runs one piece too far: the next aggregate's first piece
+        if a + 1 < c["m"]:
+            assert abs(partial[piece_ptr[a + 1]]) > 4 * e[a], a
+            got = _fold_one_too_far(c, a)
+            assert abs(got - c["s"][a]) > e[a], ("neighbour's piece", a)
+
+
+def _fold_one_too_far(c, a):
+    w_ptr, w_slot, w_val, beta = c["w"]
+    t = w_val * c["x"][w_slot]
+    f = 0.0
+    for p in range(int(c["piece_ptr"][a]), int(c["piece_ptr"][a + 1]) + 1):
+        f += hp.block_tree_sum64(t[c["pieces"][p][1]:c["pieces"][p][2]])
+    return beta[a] - f
+
+
+def _gemv_operands(nc, seed):
+    """M_ij = +-u 2^(e_i + f_j), s_j = +-u 2^-f_j, e and f in [-20, 20]: badly scaled operands, comparable terms."""
+    rng = np.random.default_rng(seed)
+    e, f = rng.integers(-20, 21, nc), rng.integers(-20, 21, nc)
+    M = hp.pow2_operands(rng, nc * nc, exps=(e[:, None] + f[None, :]).reshape(-1)).reshape(nc, nc)
+    return M, hp.pow2_operands(rng, nc, exps=-f)
+
+
+def _gemv_lanes64(M, s, skip=()):
+    """One wave per row: lane l adds its columns l, l + 64, ..., the lanes fold by halves."""
+    nc = M.shape[0]
+    lanes = np.zeros((nc, 64))
+    for k0 in range(0, nc, 64):
+        p = M[:, k0:k0 + 64] * s[k0:k0 + 64]
+        for j in skip:
+            if k0 <= j < k0 + 64:
+                p[:, j - k0] = 0.0
+        lanes[:, :p.shape[1]] += p
+    off = 32
+    while off:
+        lanes[:, :off] += lanes[:, off:2 * off]
+        off >>= 1
+    return lanes[:, 0].copy()
+
+
+def _pairwise64(p):
+    while p.shape[1] > 1:
+        if p.shape[1] & 1:
+            p = np.concatenate([p, np.zeros((p.shape[0], 1))], axis=1)
+        p = p[:, 0::2] + p[:, 1::2]
+    return p[:, 0]
+
+
+@pytest.mark.parametrize("nc", [1, 3, 65, 129, 130, 513])
+def test_coarse_gemv_bound_holds_and_rejects_a_skipped_column(nc):
+    hp.require_extended_precision()
+    M, s = _gemv_operands(nc, 100 + nc)
+    ref, mag = hp.coarse_gemv(M, s, block=100)
+    bound = hp.coarse_gemv_bound(mag, nc)
+    for got in (_gemv_lanes64(M, s), _pairwise64(M * s), M @ s):
+        assert (np.abs(got - ref) <= bound).all(), nc
+    skips = ([64] if nc > 64 else []) + ([nc - 1] if nc & 1 and nc > 1 else [])
+    for j in skips:
+        assert (np.abs(M[:, j] * s[j]) > 4 * bound).all(), (nc, j)          # on the input: every row shows it
+        assert (np.abs(_gemv_lanes64(M, s, skip=(j,)) - ref) > bound).all(), (nc, j)
+
+
+def test_coarse_apply_reference_is_exact_and_the_seeded_defects_differ_in_bits():
+    """x~ + c[agg] is one rounded addition: the reference is the same float64 expression.  Slot nx - 1 skipped, c
+    added twice, ids read shifted by one: each differs in bits, asserted on the operands first."""
+    rng = np.random.default_rng(5)
+    nx, ny, nc = 1001, 777, 37
+    x, y, c = (hp.pow2_operands(rng, k, -20, 20) for k in (nx, ny, nc))
+    ids = rng.integers(0, nc, nx)
+    want_x, want_y = hp.coarse_apply(x, y, c, ids)
+    exact = x.astype(LD) + c[ids].astype(LD)
+    assert np.array_equal(want_x, exact.astype(np.float64))                  # one rounding of the exact sum
+    # operands spread over 2^42 at most: no c is absorbed by its x~, once or twice
+    assert (want_x != x).all() and (want_y != y).all() and (want_x + c[ids] != want_x).all()
+    skipped = want_x.copy()
+    skipped[nx - 1] = x[nx - 1]
+    assert not np.array_equal(skipped.view(np.int64), want_x.view(np.int64))
+    twice = want_y + c[ids[:ny]]
+    assert (twice.view(np.int64) != want_y.view(np.int64)).all()
+    shifted = x[:-1] + c[ids[1:]]
+    differ = ids[1:] != ids[:-1]
+    assert differ.any() and (c[ids[1:]][differ] != c[ids[:-1]][differ]).all()
+    assert (shifted[differ].view(np.int64) != want_x[:-1][differ].view(np.int64)).any()
