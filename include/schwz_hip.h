@@ -232,6 +232,23 @@ int schwz_gmres_create(const schwz_csr *A, int precond, int block_size, int rest
 /* the same with the ParILU options of schwz_pcg_create_ilu (both 0: schwz_gmres_create) */
 int schwz_gmres_create_ex(const schwz_csr *A, int precond, int block_size, int restart, int par_ilu_sweeps,
                           int trisolve_sweeps, schwz_gmres **out);
+/* The same with the type the Krylov basis is stored in (an extension: compressed-basis GMRES).
+ * SCHWZ_GMRES_BASIS_F64 is schwz_gmres_create_ex, launch for launch.  SCHWZ_GMRES_BASIS_F32 stores every basis
+ * vector rounded to fp32 (4 (restart + 1) n bytes instead of 8) and orthogonalises by blocked classical
+ * Gram-Schmidt applied twice, in three passes over the basis and a constant number of launches per Krylov vector;
+ * all arithmetic, the matrix, the preconditioner, the Hessenberg matrix and x stay fp64, and the rounded vector is
+ * the one the next matrix-vector product sees, so the Arnoldi relation holds for the stored basis.  Caveat: the
+ * stop test inside a cycle is on the RECURRED norm (the rotated right-hand side).  The start residual of a cycle
+ * is itself only represented to fp32 accuracy (r = beta fl32(r / beta) + O(2^-24 beta)), so within ONE cycle the
+ * true residual follows the recurred one only down to about 2^-24 of that cycle's start residual; every restart
+ * recomputes the residual in fp64.  Restarted runs need the iterations of the fp64 basis; a reduction far beyond
+ * 2^-24 inside a single long cycle takes more iterations (or another cycle), never a wrong answer.  restart up to
+ * 2048 as for fp64.  SCHWZ_ERR_INVALID for an unknown basis code. */
+enum schwz_gmres_basis { SCHWZ_GMRES_BASIS_F64 = 0, SCHWZ_GMRES_BASIS_F32 = 1 };
+int schwz_gmres_create_basis(const schwz_csr *A, int precond, int block_size, int restart, int par_ilu_sweeps,
+                             int trisolve_sweeps, int basis, schwz_gmres **out);
+/* the basis type of a solver (SCHWZ_GMRES_BASIS_F64 for NULL) */
+int schwz_gmres_basis(const schwz_gmres *s);
 void schwz_gmres_destroy(schwz_gmres *s);
 int schwz_gmres_solve(schwz_gmres *s, const double *d_b, double *d_x, double rtol, int max_iters,
                       int *h_iters, double *h_resnorm, schwz_stream stream);
@@ -638,6 +655,16 @@ int schwz_ras_local_precision(const schwz_subdomain *sd);
 enum schwz_nonsym_solver { SCHWZ_NONSYM_GMRES = 0, SCHWZ_NONSYM_BICGSTAB = 1 };
 int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which);
 int schwz_ras_nonsym_solver(const schwz_subdomain *sd);
+
+/* The type the local GMRES stores its Krylov basis in (an extension; see schwz_gmres_create_basis for the method
+ * and for the caveat on the recurred norm inside one cycle).  Call after schwz_subdomain_to_device;
+ * SCHWZ_GMRES_BASIS_F64 is what the upload creates.  The setter replaces the GMRES object by one of the other
+ * basis type around the same preconditioner (device synchronisation; on failure the subdomain keeps what it has).
+ * While BiCGSTAB is set the choice is only remembered: a return to GMRES creates that type.  SCHWZ_ERR_INVALID for
+ * a null subdomain or an unknown code, SCHWZ_ERR_NOT_IMPLEMENTED unless the subdomain runs the iterative local
+ * solver with non_symmetric set.  The getter answers SCHWZ_GMRES_BASIS_F64 for a null subdomain. */
+int schwz_ras_set_gmres_basis(schwz_subdomain *sd, int which);
+int schwz_ras_gmres_basis(const schwz_subdomain *sd);
 
 /* Which method solves a symmetric local system iteratively (an extension; schwz_solver_options keeps its layout, so
  * the choice travels through a setter, after schwz_subdomain_to_device; it takes effect from the next local solve).

@@ -682,7 +682,7 @@ int pcg_create_impl(const schwz_csr *A, int precond, int block_size, int par_ilu
 // The two Krylov solvers of the non-symmetric branch (gmres.hip, bicgstab.hip) around a preconditioner object they
 // take over (on failure it stays the caller's), the object a solver holds, and giving it up before the solver is
 // destroyed: schwz_ras_set_nonsym_solver hands the preconditioner from one solver to the other.
-int gmres_create_adopt(const schwz_csr *A, int restart, schwz_pcg *pre, schwz_gmres **out);
+int gmres_create_adopt(const schwz_csr *A, int restart, int basis, schwz_pcg *pre, schwz_gmres **out);
 schwz_pcg *gmres_precond(schwz_gmres *s);
 schwz_pcg *gmres_release_precond(schwz_gmres *s);
 int bicgstab_create_adopt(const schwz_csr *A, schwz_pcg *pre, schwz_bicgstab **out);
@@ -956,6 +956,7 @@ struct schwz_subdomain {
     schwz_pcg *cg = nullptr;       // symmetric local matrix, iterative (LocalKind::Cg, and the two below beside it)
     schwz_gmres *gmres = nullptr;  // non-symmetric local matrix (Gmres)
     schwz_bicgstab *bicg = nullptr;  // ... once schwz_ras_set_nonsym_solver asked for BiCGSTAB (Bicgstab; gmres is null then)
+    int gmres_basis = 0;             // SCHWZ_GMRES_BASIS_*: the basis type of gmres, and of the one a return from bicg creates
     // mixed-precision local solve (schwz_ras_set_local_precision, csrc/cg_f32.hip): created at first use, CgF32 while
     // `precision` is SCHWZ_PRECISION_F32; `cg` stays what it is, so that F64 restores the fp64 path exactly
     schwz_pcg_f32 *cg32 = nullptr;

@@ -848,12 +848,42 @@ int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which)
         sd->gmres = nullptr;
         return SCHWZ_OK;
     }
-    if ((rc = gmres_create_adopt(sd->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, bicgstab_precond(sd->bicg),
-                                 &sd->gmres)))
+    if ((rc = gmres_create_adopt(sd->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, sd->gmres_basis,
+                                 bicgstab_precond(sd->bicg), &sd->gmres)))
         return rc;
     (void)bicgstab_release_precond(sd->bicg);
     schwz_bicgstab_destroy(sd->bicg);
     sd->bicg = nullptr;
+    return SCHWZ_OK;
+}
+
+int schwz_ras_gmres_basis(const schwz_subdomain *sd) { return sd ? sd->gmres_basis : SCHWZ_GMRES_BASIS_F64; }
+
+int schwz_ras_set_gmres_basis(schwz_subdomain *sd, int which)
+{
+    SCHWZ_REQUIRE(sd, "schwz_ras_set_gmres_basis: null subdomain");
+    SCHWZ_REQUIRE(which == SCHWZ_GMRES_BASIS_F64 || which == SCHWZ_GMRES_BASIS_F32,
+                  "schwz_ras_set_gmres_basis: unknown basis type");
+    REQUIRE_DEVICE(sd, "schwz_ras_set_gmres_basis");
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !sd->gmres == !sd->bicg || sd->cg) {
+        set_error("schwz_ras_set_gmres_basis: the choice exists for the iterative local solver of a non-symmetric "
+                  "matrix only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (which == sd->gmres_basis) return SCHWZ_OK;
+    if (sd->gmres) {
+        // as in schwz_ras_set_nonsym_solver: the new solver is created around the preconditioner while the old one
+        // still owns it, so a failure leaves the subdomain as it was
+        SCHWZ_HIP_TRY(hipDeviceSynchronize());
+        schwz_gmres *fresh = nullptr;
+        const int rc = gmres_create_adopt(sd->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, which,
+                                          gmres_precond(sd->gmres), &fresh);
+        if (rc) return rc;
+        (void)gmres_release_precond(sd->gmres);
+        schwz_gmres_destroy(sd->gmres);
+        sd->gmres = fresh;
+    }
+    sd->gmres_basis = which;  // (while BiCGSTAB is set: what a return to GMRES creates)
     return SCHWZ_OK;
 }
 

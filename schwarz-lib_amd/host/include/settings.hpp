@@ -128,6 +128,12 @@ struct Metadata {
     // (GMRES(restart_iter), the reference's) or "bicgstab" (schwz_ras_set_nonsym_solver); without
     // non_symmetric_matrix or with a direct local solver it has no effect, like restart_iter
     std::string non_symmetric_solver = "gmres";
+    // extension: the type GMRES stores its Krylov basis in: "double", or "single" for compressed-basis GMRES
+    // (schwz_ras_set_gmres_basis: fp32 basis vectors, fp64 arithmetic, blocked CGS2; inside one cycle the true
+    // residual follows the recurred norm the stop test sees only to about 2^-24 of the cycle's start residual).
+    // Without non_symmetric_matrix, with a direct local solver or with non_symmetric_solver "bicgstab" it has no
+    // effect, like restart_iter
+    std::string gmres_basis = "double";
     // extension: the method of the iterative local solve of a symmetric matrix: "cg" (the reference's) or "chebyshev"
     // (schwz_ras_set_sym_solver: local_precond null or block-jacobi of block size 1, double precision); with
     // non_symmetric_matrix or a direct local solver it has no effect, like restart_iter.  Bounds on the spectrum of

@@ -277,6 +277,11 @@ void SchwarzBase<V, I, M>::initialize()
         throw ::BadDimension(__FILE__, __LINE__, "initialize", "non_symmetric_solver must be 'gmres' or 'bicgstab'");
     const bool bicgstab_local = m.non_symmetric_solver == "bicgstab" && s.non_symmetric_matrix &&
                                 opt.local_solver == SCHWZ_SOLVER_ITERATIVE;
+    // extension: the fp32 Krylov basis of the local GMRES (schwz_ras_set_gmres_basis)
+    if (m.gmres_basis != "double" && m.gmres_basis != "single")
+        throw ::BadDimension(__FILE__, __LINE__, "initialize", "gmres_basis must be 'double' or 'single'");
+    const bool f32_basis = m.gmres_basis == "single" && s.non_symmetric_matrix &&
+                           opt.local_solver == SCHWZ_SOLVER_ITERATIVE && !bicgstab_local;
     // extension: Chebyshev as the iterative local solver of a symmetric matrix (schwz_ras_set_sym_solver)
     if (m.symmetric_solver != "cg" && m.symmetric_solver != "chebyshev")
         throw ::BadDimension(__FILE__, __LINE__, "initialize", "symmetric_solver must be 'cg' or 'chebyshev'");
@@ -470,6 +475,7 @@ void SchwarzBase<V, I, M>::initialize()
     SCHWZ_CALL(schwz_subdomain_to_device(im.sd, rhs.data(), &opt));
     if (single_local) SCHWZ_CALL(schwz_ras_set_local_precision(im.sd, SCHWZ_PRECISION_F32));
     if (bicgstab_local) SCHWZ_CALL(schwz_ras_set_nonsym_solver(im.sd, SCHWZ_NONSYM_BICGSTAB));
+    if (f32_basis) SCHWZ_CALL(schwz_ras_set_gmres_basis(im.sd, SCHWZ_GMRES_BASIS_F32));
     if (cheb_local) {
         SCHWZ_CALL(schwz_ras_set_sym_solver(im.sd, SCHWZ_SYM_CHEBYSHEV));
         double lo = 0.0, hi = 0.0;
@@ -693,7 +699,8 @@ void SchwarzBase<V, I, M>::initialize()
             else if (cheb_local)
                 std::cout << " Local max iters " << lmi << " (Chebyshev)" << std::endl;
             else
-                std::cout << " Local max iters " << lmi << " with restart iter " << s.restart_iter << std::endl;
+                std::cout << " Local max iters " << lmi << " with restart iter " << s.restart_iter
+                          << (f32_basis ? " (fp32 basis)" : "") << std::endl;
         } else {
             std::cout << " Local direct solve with HIP TRS" << std::endl;
         }

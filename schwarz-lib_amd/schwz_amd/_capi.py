@@ -25,6 +25,7 @@ SOLVER_ITERATIVE, SOLVER_DIRECT, SOLVER_DIRECT_LU = 0, 1, 2
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_BLOCK_JACOBI, PRECOND_ILU, PRECOND_ISAI = 0, 1, 2, 3, 4
 PRECISION_F64, PRECISION_F32 = 0, 1
 NONSYM_GMRES, NONSYM_BICGSTAB = 0, 1
+GMRES_BASIS_F64, GMRES_BASIS_F32 = 0, 1
 SYM_CG, SYM_CHEBYSHEV = 0, 1
 CHEB_CHECK_EVERY = 8      # SCHWZ_CHEB_CHECK_EVERY: a Chebyshev solve with a tolerance looks at every 8th residual norm
 BICGSTAB_POLL_BATCH = 8   # SCHWZ_BICGSTAB_POLL_BATCH: iterations between two looks of the host at the device state
@@ -44,6 +45,7 @@ SYMBOLS = [
     "schwz_ras_set_local_precision", "schwz_ras_local_precision",
     "schwz_bicgstab_create", "schwz_bicgstab_destroy", "schwz_bicgstab_solve", "schwz_bicgstab_last_stats",
     "schwz_bicgstab_breakdown", "schwz_ras_set_nonsym_solver", "schwz_ras_nonsym_solver",
+    "schwz_gmres_create_basis", "schwz_gmres_basis", "schwz_ras_set_gmres_basis", "schwz_ras_gmres_basis",
     "schwz_cheb_create", "schwz_cheb_destroy", "schwz_cheb_bounds", "schwz_cheb_set_bounds", "schwz_cheb_solve",
     "schwz_cheb_last_stats", "schwz_ras_set_sym_solver", "schwz_ras_sym_solver", "schwz_ras_cheb_bounds",
     "schwz_ras_set_cheb_bounds",
@@ -179,6 +181,10 @@ _sig("schwz_bicgstab_last_stats", i32, [vp, C.POINTER(C.c_int), C.POINTER(dbl)])
 _sig("schwz_bicgstab_breakdown", i32, [vp])
 _sig("schwz_ras_set_nonsym_solver", i32, [vp, i32])
 _sig("schwz_ras_nonsym_solver", i32, [vp])
+_sig("schwz_gmres_create_basis", i32, [vp, i32, i32, i32, i32, i32, i32, pvp])
+_sig("schwz_gmres_basis", i32, [vp])
+_sig("schwz_ras_set_gmres_basis", i32, [vp, i32])
+_sig("schwz_ras_gmres_basis", i32, [vp])
 _sig("schwz_cheb_create", i32, [vp, i32, pvp])
 _sig("schwz_cheb_destroy", None, [vp])
 _sig("schwz_cheb_bounds", i32, [vp, C.POINTER(dbl), C.POINTER(dbl)])

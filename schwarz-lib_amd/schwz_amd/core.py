@@ -239,10 +239,15 @@ class Gmres:
     krylov_dim = restart; solve.cpp:486-520)."""
 
     def __init__(self, csr, precond=capi.PRECOND_NONE, block_size=1, restart=1, par_ilu_sweeps=0,
-                 trisolve_sweeps=0):
+                 trisolve_sweeps=0, basis=capi.GMRES_BASIS_F64):
+        """basis: capi.GMRES_BASIS_F64, or capi.GMRES_BASIS_F32 for the compressed basis (fp32 Krylov vectors, fp64
+        arithmetic, blocked CGS2: schwz_gmres_create_basis)."""
         self.csr = csr
         h = C.c_void_p()
-        if par_ilu_sweeps or trisolve_sweeps:
+        if basis != capi.GMRES_BASIS_F64:
+            check(lib.schwz_gmres_create_basis(csr.h, precond, block_size, restart, int(par_ilu_sweeps),
+                                               int(trisolve_sweeps), int(basis), C.byref(h)))
+        elif par_ilu_sweeps or trisolve_sweeps:
             check(lib.schwz_gmres_create_ex(csr.h, precond, block_size, restart, int(par_ilu_sweeps),
                                             int(trisolve_sweeps), C.byref(h)))
         else:
@@ -760,6 +765,14 @@ class Subdomain:
 
     def nonsym_solver(self):
         return int(lib.schwz_ras_nonsym_solver(self.h))
+
+    def set_gmres_basis(self, which):
+        """The type the local GMRES of a non-symmetric matrix stores its Krylov basis in
+        (schwz_ras_set_gmres_basis): capi.GMRES_BASIS_F64 (what to_device creates) or capi.GMRES_BASIS_F32."""
+        check(lib.schwz_ras_set_gmres_basis(self.h, int(which)))
+
+    def gmres_basis(self):
+        return int(lib.schwz_ras_gmres_basis(self.h))
 
     def set_sym_solver(self, which):
         """Method of the iterative local solve of a symmetric matrix from the next solve on

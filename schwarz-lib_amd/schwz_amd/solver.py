@@ -133,6 +133,14 @@ class Metadata:
     # residual).  Without non_symmetric_matrix, or with a direct local solver, the field has no effect, like
     # restart_iter; any other name is refused.
     non_symmetric_solver: str = "gmres"
+    # extension (no field of the reference's Metadata): the type GMRES stores its Krylov basis in: "double" (the
+    # fp64 path as it always was) or "single" (compressed-basis GMRES, schwz_gmres_create_basis: fp32 basis vectors,
+    # fp64 arithmetic, blocked classical Gram-Schmidt applied twice in three passes, a constant number of launches
+    # per Krylov vector and half the basis memory).  The stop test inside a cycle is on the recurred norm, which the
+    # true residual follows only down to about 2^-24 of the cycle's start residual; restarts recompute it in fp64.
+    # Without non_symmetric_matrix, with a direct local solver or with non_symmetric_solver "bicgstab" the field has
+    # no effect, like restart_iter; any other name is refused.
+    gmres_basis: str = "double"
     # extension (no field of the reference's Metadata): the method of the iterative local solve of a symmetric matrix:
     # "cg" (the reference's) or "chebyshev" (schwz_cheb: a fixed polynomial in the Jacobi-preconditioned matrix, one
     # reduction-free launch per inner iteration; local_precond 'null' or block-jacobi of block size 1, double precision).
@@ -285,7 +293,8 @@ def _precision_code(settings, metadata):
     if settings.non_symmetric_matrix:
         raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
                                        "local_solver_precision 'single' is not implemented for GMRES "
-                                       "(non_symmetric_matrix)")
+                                       "(non_symmetric_matrix): GMRES keeps fp64 arithmetic; its mixed-precision "
+                                       "form is the compressed basis, gmres_basis = 'single'")
     if _precond_name_code(metadata) not in (capi.PRECOND_NONE, capi.PRECOND_JACOBI):
         raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
                                        "local_solver_precision 'single' is implemented for local_precond 'null' and "
@@ -304,6 +313,20 @@ def _nonsym_solver_code(settings, metadata):
             and _local_solver_code(settings) == capi.SOLVER_ITERATIVE:
         return capi.NONSYM_BICGSTAB
     return capi.NONSYM_GMRES
+
+
+def _gmres_basis_code(settings, metadata):
+    """capi.GMRES_BASIS_* of metadata.gmres_basis.  The name is checked whatever the other settings are; it selects
+    the fp32 basis only where the local solver is GMRES: the iterative local solver of a non-symmetric matrix with
+    non_symmetric_solver "gmres".  Runs before any device call."""
+    name = getattr(metadata, "gmres_basis", "double")
+    if not isinstance(name, str) or name not in ("double", "single"):
+        raise capi.SchwzError(capi.ERR_INVALID, "gmres_basis must be 'double' or 'single', not %r" % (name,))
+    if name == "single" and settings.non_symmetric_matrix \
+            and _local_solver_code(settings) == capi.SOLVER_ITERATIVE \
+            and _nonsym_solver_code(settings, metadata) == capi.NONSYM_GMRES:
+        return capi.GMRES_BASIS_F32
+    return capi.GMRES_BASIS_F64
 
 
 def _sym_solver_code(settings, metadata):
@@ -605,6 +628,7 @@ class SolverRAS:
         precision_code = _precision_code(s, m)
         nonsym_code = _nonsym_solver_code(s, m)
         sym_code = _sym_solver_code(s, m)
+        basis_code = _gmres_basis_code(s, m)
         coarse_on = _coarse_enabled(s, m)
         self._coarse = None
         if self._distributed_ingest():
@@ -644,6 +668,8 @@ class SolverRAS:
                 sd.set_local_precision(precision_code)
             if nonsym_code != capi.NONSYM_GMRES:  # (GMRES is what to_device creates: the setter is not called)
                 sd.set_nonsym_solver(nonsym_code)
+            if basis_code != capi.GMRES_BASIS_F64:  # (the fp64 basis is what to_device creates: the setter is not called)
+                sd.set_gmres_basis(basis_code)
             if sym_code != capi.SYM_CG:  # (CG is what to_device creates: the setter is not called)
                 sd.set_sym_solver(sym_code)
                 sd.set_cheb_bounds(*_cheb_bounds(m, sd.cheb_bounds()[1]))
@@ -687,6 +713,8 @@ class SolverRAS:
                 self._print(" Local max iters %d (BiCGSTAB)" % lmi)
             elif sym_code == capi.SYM_CHEBYSHEV:
                 self._print(" Local max iters %d (Chebyshev)" % lmi)
+            elif basis_code == capi.GMRES_BASIS_F32:
+                self._print(" Local max iters %d with restart iter %d (fp32 basis)" % (lmi, s.restart_iter))
             else:
                 self._print(" Local max iters %d with restart iter %d" % (lmi, s.restart_iter))
         else:
