@@ -782,6 +782,54 @@ int schwz_ras_coarse_residual(schwz_subdomain *sd, schwz_coarse *c, schwz_stream
 int schwz_coarse_solve(schwz_coarse *c, schwz_stream stream);
 int schwz_ras_coarse_apply(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream);
 
+/* ---- One matrix, many right-hand sides (an extension: the reference solves the one system its initialize was handed,
+ * SchwarzBase::initialize at source/schwarz_base.cpp:128-271, and has no call that replaces b, so no line of it is
+ * replaced).  Everything schwz_subdomain_to_device and schwz_ras_coarse_set_aggregates build follows from the matrix
+ * and the partition, except the local right-hand side (schwz_ras_vector id 3), its copy in b~ (id 1), the sums beta of
+ * the coarse part and the iteration state.  These calls replace exactly those, in a few vector passes; the solver
+ * SELECTION -- precision, non-symmetric solver, GMRES basis, symmetric solver, Chebyshev bounds, the cap of
+ * schwz_ras_set_local_max_iters -- survives all of them.  A new solve is: rhs_set or rhs_gather, rhs_aggregate (coarse
+ * space on), restart, then the outer iteration as after the upload.  All of them obey `stream`, none synchronises the
+ * device; SCHWZ_ERR_INVALID for a null argument and for a subdomain that is not on the device.
+ *
+ * schwz_ras_rhs_set: `rhs` holds local_size_x values in local order, [interior; overlap rows], the layout of
+ * h_local_rhs; a host pointer (on_device = 0: one copy on `stream`, waited for, so the array is the caller's again on
+ * return) or a device pointer (one copy launch).  The vector
+ * of id 3 is overwritten in place: its pointer does not move.
+ * schwz_ras_rhs_gather: for a right-hand side that already lives in HBM as ONE global vector of n_global = N doubles:
+ * rhs[i] = d_global[index[i]], one indexed load per row.  index is the subdomain's own local-to-global list, or the map
+ * schwz_ras_rhs_index sets (a caller that permuted the rows passes permutation[local_to_global[i]]; NULL: back to the
+ * own list).  The map is checked on the host when it is set -- an index outside [0, N): SCHWZ_ERR_INVALID -- and
+ * uploaded, 8 B per local row, by the first gather and not before: a subdomain that never solves again allocates
+ * nothing.  rhs_index waits for the device only where it releases an uploaded map.
+ * schwz_ras_rhs_aggregate: beta_a = sum_{i in a} b_i of the coarse part, from the vector of id 3 into the buffer the
+ * residual launches of schwz_ras_coarse_residual read.  One lane per aggregate, the rows of an aggregate in ascending
+ * order into one accumulator, no atomics: the order of the host plan, so the bits are those of a fresh
+ * schwz_ras_coarse_set_aggregates on that b.  The rows grouped by aggregate (4 B per interior row) are built and
+ * uploaded by the first call (it waits for `stream` once).  Without aggregates: SCHWZ_OK, nothing launched.
+ * schwz_ras_rhs_norm_sq: sum of b_i^2 over the local_size interior rows in a fixed order, for the norm of a b that was
+ * given on the device; waits for `stream`, like every call that hands a value to the host.  schwz_ras_rhs_norm_sq_local:
+ * the same over all local_size_x rows, overlap rows included -- the square of the check residual of step 2 for a zero
+ * x~, which a host layer that keeps the start vector measures its convergence against.
+ * schwz_ras_restart, keep_x = 0: the state schwz_subdomain_to_device leaves -- both x~ buffers zero, b~ = b, y zero
+ * where it is a vector of its own, schwz_ras_y_form what an upload followed by the same setters gives.  Every solver
+ * object forgets its last solve first: a postponed last iteration and the stream handle saved for it are DROPPED
+ * before any buffer is rewritten (never run later on the new data), likewise a pending Chebyshev norm, the second
+ * output of the restriction and the state schwz_ras_last_inner_stats reports (0 iterations, norm 0, as before the first
+ * solve); schwz_ras_cg_flavour answers 0 until the next solve.  The pointers of ids 1 and 3 do not move; ask for ids 0
+ * and 2 again.  keep_x = 1: every vector keeps its values, x~ halos included, so the next solve starts from the last
+ * iterate; only what refers to the old b goes: the solvers' memory as above and b~ (= b again; the next
+ * schwz_ras_update_boundary rewrites its overlap rows).  Another value of keep_x: SCHWZ_ERR_INVALID.
+ * Not offered: new matrix values on the old pattern, several right-hand sides in one batched solve, a start vector
+ * other than zero or the kept one (write through the pointers of schwz_ras_vector at your own risk). */
+int schwz_ras_rhs_set(schwz_subdomain *sd, const double *rhs, int on_device, schwz_stream stream);
+int schwz_ras_rhs_index(schwz_subdomain *sd, const int64_t *h_index);
+int schwz_ras_rhs_gather(schwz_subdomain *sd, const double *d_global, int64_t n_global, schwz_stream stream);
+int schwz_ras_rhs_aggregate(schwz_subdomain *sd, schwz_stream stream);
+int schwz_ras_rhs_norm_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream);
+int schwz_ras_rhs_norm_sq_local(schwz_subdomain *sd, double *h_out, schwz_stream stream);
+int schwz_ras_restart(schwz_subdomain *sd, int keep_x, schwz_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -430,6 +430,10 @@ int bicgstab_create_adopt(const schwz_csr *A, schwz_pcg *pre, schwz_bicgstab **o
 
 schwz_pcg *bicgstab_precond(schwz_bicgstab *s) { return s->pre; }
 
+// schwz_ras_restart: the state of the last solve (what schwz_bicgstab_last_stats and schwz_bicgstab_breakdown report)
+// back to zeros, as created
+int bicgstab_forget(schwz_bicgstab *s, hipStream_t st) { return s ? s->state.reset(st) : SCHWZ_OK; }
+
 schwz_pcg *bicgstab_release_precond(schwz_bicgstab *s)
 {
     schwz_pcg *pre = s->pre;

@@ -918,6 +918,27 @@ int pcg_finish_lazy(schwz_pcg *s)
     return s->lazy_run ? s->lazy_run(s->lazy.stream) : SCHWZ_OK;
 }
 
+// Between two solves of a set-up subdomain (schwz_ras_restart): everything the object remembers of its last solve
+// is forgotten, as after creation.  The postponed launches are DROPPED, never run -- they would update a residual of
+// the old right-hand side -- and with them the saved stream handle; the second outputs belong to buffers the caller
+// is about to rewrite; the device state goes back to zeros behind what `st` holds.  What follows from the matrix
+// stays: the plan's buffers, the recorded graphs, the priority rows and their event.
+int pcg_forget(schwz_pcg *s, hipStream_t st)
+{
+    if (!s) return SCHWZ_OK;
+    s->lazy = schwz_pcg::LazyLast();
+    s->lazy_run = nullptr;
+    s->x2_written = false;
+    s->x2_out = nullptr;
+    s->x2_src = nullptr;
+    s->x_out = nullptr;
+    s->p_pending = false;
+    s->init = schwz_pcg::InitFold();
+    s->init_event = nullptr;
+    s->last_flavour = 0;
+    return s->state.reset(st);
+}
+
 int pcg_last_stats(schwz_pcg *s, int *h_iters, double *h_resnorm)
 {
     const int rc_lazy = pcg_finish_lazy(s);

@@ -345,6 +345,9 @@ struct schwz_pcg_f32 {
     double *part_vec() const { return part + 2 * kMaxGrid; }
 };
 
+// schwz_ras_restart: the state of the last solve (what schwz_pcg_f32_last_stats reports) back to zeros, as created
+int schwz::pcg_f32_forget(schwz_pcg_f32 *s, hipStream_t st) { return s ? s->state.reset(st) : SCHWZ_OK; }
+
 static int pcg_f32_build(schwz_pcg_f32 *s)
 {
     const CsrView &A = s->A->v;

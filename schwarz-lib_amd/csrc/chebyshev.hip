@@ -305,6 +305,19 @@ struct schwz_cheb {
     double last_rr = 0.0;       // ||r_m||^2 once computed (NaN: never computable, max_iters = 0 and nobody asked)
 };
 
+// schwz_ras_restart: what the object remembers of its last solve is forgotten, as created -- the pending norm is
+// DROPPED (it would be the norm of a residual of the old right-hand side), the counters and the device state are zero
+int schwz::cheb_forget(schwz_cheb *s, hipStream_t st)
+{
+    if (!s) return SCHWZ_OK;
+    s->fixed = false;
+    s->last_iters = 0;
+    s->norm_pending = false;
+    s->norm_d = 0;
+    s->last_rr = 0.0;
+    return s->state.reset(st);
+}
+
 template <int FORM, bool NORM>
 static void cheb_launch_form(const schwz_cheb *s, const ChebArgs &a, hipStream_t st)
 {

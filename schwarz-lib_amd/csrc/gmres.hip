@@ -524,6 +524,9 @@ int gmres_create_adopt(const schwz_csr *A, int restart, int basis, schwz_pcg *pr
 
 schwz_pcg *gmres_precond(schwz_gmres *s) { return s->pre; }
 
+// schwz_ras_restart: the state of the last solve (what schwz_gmres_last_stats reports) back to zeros, as created
+int gmres_forget(schwz_gmres *s, hipStream_t st) { return s ? s->state.reset(st) : SCHWZ_OK; }
+
 int gmres_basis(const schwz_gmres *s) { return s->basis; }
 
 schwz_pcg *gmres_release_precond(schwz_gmres *s)

@@ -689,6 +689,14 @@ int bicgstab_create_adopt(const schwz_csr *A, schwz_pcg *pre, schwz_bicgstab **o
 schwz_pcg *bicgstab_precond(schwz_bicgstab *s);
 schwz_pcg *bicgstab_release_precond(schwz_bicgstab *s);
 int pcg_finish_lazy(schwz_pcg *s);  // the postponed residual update / state advance of the last solve, if any  // ILU(0) sweeps: trs_take_error of the factor solves
+// schwz_ras_restart: what a solver object remembers of its last solve -- postponed launches and their saved stream,
+// second outputs, pending norms, the state schwz_ras_last_inner_stats reads -- is forgotten, as after creation;
+// nothing postponed is run.  The device state is zeroed on `st`.  A null solver is fine.
+int pcg_forget(schwz_pcg *s, hipStream_t st);
+int pcg_f32_forget(schwz_pcg_f32 *s, hipStream_t st);
+int cheb_forget(schwz_cheb *s, hipStream_t st);
+int gmres_forget(schwz_gmres *s, hipStream_t st);
+int bicgstab_forget(schwz_bicgstab *s, hipStream_t st);
 }  // namespace schwz
 
 // ---- opaque ABI types -------------------------------------------------------
@@ -908,6 +916,10 @@ struct schwz_coarse_part {
     schwz::Dev<int32_t> w_slot, piece, piece_ptr;  // piece: {aggregate, begin, end} per piece
     schwz::Dev<uint16_t> id16;
     std::vector<double> rows;  // m x nc: the subdomain's rows of A0 (schwz_ras_coarse_rows)
+    // schwz_ras_rhs_aggregate (rhs.hip), built at its first call: the interior rows grouped by aggregate, ascending
+    // inside each (agg_rows, 4 B per interior row), aggregate a's rows at [agg_ptr[a], agg_ptr[a + 1])
+    schwz::Dev<int32_t> agg_rows, agg_ptr;
+    bool agg_ready = false;
 };
 
 namespace schwz {
@@ -990,7 +1002,18 @@ struct schwz_subdomain {
     hipEvent_t ev_scalar = nullptr;
     // aggregation coarse correction (schwz_ras_coarse_set_aggregates); null: one-level RAS, nothing of it runs
     schwz_coarse_part *coarse = nullptr;
+    // schwz_ras_rhs_gather (rhs.hip): the global position of every local row's right-hand side.  rhs_index holds the
+    // caller's map (schwz_ras_rhs_index; empty: l2g itself); the device copy is made at the first gather, not before
+    std::vector<int64_t> rhs_index;
+    bool rhs_index_custom = false;
+    int64_t *d_rhs_index = nullptr;
 };
+
+namespace schwz {
+// rhs.hip: one pass that puts the vectors of a subdomain back to what the upload left -- x (nx entries) and, where
+// they exist, x_alt (nx) and y (n) zero, bt[0:n] = b[0:n]
+int launch_restart(int64_t n, int64_t nx, const double *b, double *bt, double *x, double *x_alt, double *y, hipStream_t st);
+}  // namespace schwz
 
 namespace schwz {
 int trs_take_error(schwz_trs *t);  // trs.hip: SCHWZ_ERR_HIP (and the reason) if a flag-driven sweep timed out

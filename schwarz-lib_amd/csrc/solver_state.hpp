@@ -33,6 +33,14 @@ public:
         pending_ = -1;
         bank_ = 0;
     }
+    // between two solves (schwz_ras_restart): the device state back to what create() left, zeros, behind everything
+    // enqueued on `st`; no copy is in flight
+    int reset(hipStream_t st)
+    {
+        SCHWZ_HIP_TRY(hipMemsetAsync(d_, 0, sizeof(State), st));
+        begin();
+        return SCHWZ_OK;
+    }
     // One step behind the launches: waits for the copy the last poll() enqueued and sets *stopped if the device had
     // decided by then; enqueues the next copy and its event on `st`.  The queue behind the launches never drains.
     int poll(hipStream_t st, bool *stopped)

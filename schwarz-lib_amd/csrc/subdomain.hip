@@ -268,7 +268,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
         schwz_trs_destroy(sd->trs);
         schwz_csr_destroy(sd->A);
         void *ptrs[] = {sd->d_i_rp, sd->d_i_col, sd->d_i_val, sd->d_put_idx, sd->d_get_idx, sd->d_x, sd->d_x_alt,
-                        sd->d_rhs, sd->d_btilde, sd->d_y, sd->d_partials, sd->d_stream_part};
+                        sd->d_rhs, sd->d_btilde, sd->d_y, sd->d_partials, sd->d_stream_part, sd->d_rhs_index};
         for (void *p : ptrs) (void)hipFree(p);
         if (sd->h_scalar) (void)hipHostFree(sd->h_scalar);
         if (sd->ev_scalar) (void)hipEventDestroy(sd->ev_scalar);
@@ -678,6 +678,33 @@ int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream)
         return SCHWZ_OK;
     }
     return launch_copy(sd->local_size, sd->d_y, sd->d_x, (hipStream_t)stream);
+}
+
+// Between two solves on a set-up subdomain (an extension; the right-hand side itself is replaced by the calls of
+// rhs.hip).  First the solver objects forget their last solve -- a postponed launch is dropped BEFORE any buffer is
+// rewritten, never run later on the new data.  keep_x = 0 then leaves what schwz_subdomain_to_device leaves: the form
+// the upload would choose for the solver that is selected now (a setter that changed the kind has already moved y to
+// a vector of its own, as it does behind a fresh upload), y where that form keeps it, and one pass over the vectors.
+// keep_x = 1 keeps every vector and both form flags -- a y that is ahead of x~ stays ahead -- and only copies b to
+// b~: its interior rows are written nowhere else (schwz_ras_update_boundary rewrites the overlap rows alone).
+int schwz_ras_restart(schwz_subdomain *sd, int keep_x, schwz_stream stream)
+{
+    REQUIRE_DEVICE(sd, "schwz_ras_restart");
+    SCHWZ_REQUIRE(keep_x == 0 || keep_x == 1, "schwz_ras_restart: keep_x must be 0 or 1");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = pcg_forget(sd->cg, st)) || (rc = pcg_f32_forget(sd->cg32, st)) || (rc = cheb_forget(sd->cheb, st)) ||
+        (rc = gmres_forget(sd->gmres, st)) || (rc = bicgstab_forget(sd->bicg, st)))
+        return rc;
+    const int64_t n = sd->local_size_x;
+    if (keep_x) return launch_copy(n, sd->d_rhs, sd->d_btilde, st);
+    const bool uni = want_unified(sd) && ensure_x_alt(sd);
+    // (the pass below zeroes it: no memset of its own)
+    if (!uni && !sd->d_y) SCHWZ_HIP_TRY(hipMalloc((void **)&sd->d_y, (size_t)(n ? n : 1) * sizeof(double)));
+    sd->unified = uni;
+    sd->y_in_alt = false;
+    sd->y_ahead = false;
+    return launch_restart(n, n + sd->halo_size, sd->d_rhs, sd->d_btilde, sd->d_x, sd->d_x_alt, sd->d_y, st);
 }
 
 // The coarse correction c (schwz_coarse_solve) added to every copy of every row this subdomain holds: all slots of

@@ -851,6 +851,51 @@ class Subdomain:
     def coarse_apply(self, coarse, stream=0):
         check(lib.schwz_ras_coarse_apply(self.h, coarse.h, _stream_arg(stream)))
 
+    # ---- a new right-hand side on a set-up subdomain (schwz_ras_rhs_*, schwz_ras_restart) ----
+
+    def rhs_set(self, rhs, stream=0):
+        """The local right-hand side (vector id 3) from `rhs`: a host array of local_size_x values in local order,
+        or the integer address of as many doubles in HBM."""
+        if isinstance(rhs, np.ndarray):
+            rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+            assert len(rhs) == self.local_size_x
+            check(lib.schwz_ras_rhs_set(self.h, ptr(rhs), 0, _stream_arg(stream)))
+        else:
+            check(lib.schwz_ras_rhs_set(self.h, ptr(rhs), 1, _stream_arg(stream)))
+
+    def rhs_index(self, index=None):
+        """The map of rhs_gather: the global position of every local row's right-hand side (None: the subdomain's own
+        local-to-global list).  Checked on the host here, uploaded by the first gather."""
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.int64)
+            assert len(index) == self.local_size_x
+        check(lib.schwz_ras_rhs_index(self.h, ptr(index)))
+
+    def rhs_gather(self, d_global, n_global, stream=0):
+        """The local right-hand side gathered from a global vector of n_global doubles in HBM."""
+        check(lib.schwz_ras_rhs_gather(self.h, ptr(d_global), int(n_global), _stream_arg(stream)))
+
+    def rhs_aggregate(self, stream=0):
+        """beta of the coarse part recomputed from the local right-hand side (nothing without aggregates)."""
+        check(lib.schwz_ras_rhs_aggregate(self.h, _stream_arg(stream)))
+
+    def rhs_norm_sq(self, stream=0):
+        """Sum of the squares of the right-hand side over the interior rows (waits for the stream)."""
+        out = C.c_double(0.0)
+        check(lib.schwz_ras_rhs_norm_sq(self.h, C.byref(out), _stream_arg(stream)))
+        return out.value
+
+    def rhs_norm_sq_local(self, stream=0):
+        """The same over all local_size_x rows: the square of the check residual of a zero x~."""
+        out = C.c_double(0.0)
+        check(lib.schwz_ras_rhs_norm_sq_local(self.h, C.byref(out), _stream_arg(stream)))
+        return out.value
+
+    def restart(self, keep_x=False, stream=0):
+        """The iteration state back to "just uploaded" (keep_x: every vector keeps its values); the solver objects
+        forget their last solve either way (schwz_ras_restart)."""
+        check(lib.schwz_ras_restart(self.h, int(bool(keep_x)), _stream_arg(stream)))
+
     def close(self):
         if getattr(self, "h", None) and lib is not None:
             lib.schwz_subdomain_destroy(self.h)

@@ -472,6 +472,7 @@ class SolverRAS:
                 "executor '%s' is not available: only 'hip' (MI355X) exists and there is "
                 "no CPU fallback" % settings.executor_string)
         self._user_matrix, self._user_rhs = None, None
+        self._device_rhs = None  # set_rhs(tensor): the right-hand side lives in HBM, _user_rhs is not used
         self.comm = comm if comm is not None else InProcessComm(max(metadata.num_subdomains, 1))
         self.backend = backend if backend is not None else HipBackend(
             getattr(self.comm, "device_index", 0))
@@ -623,6 +624,7 @@ class SolverRAS:
         s, m, be, comm = self.settings, self.metadata, self.backend, self.comm
         self._user_matrix = matrix
         self._user_rhs = None if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
+        self._device_rhs, self._gather_index_set, self._start_ref = None, False, None
         solver_code = _factor_solver_code(s, m)
         precond_code = _precond_code(m)
         precision_code = _precision_code(s, m)
@@ -966,6 +968,10 @@ class SolverRAS:
         self._lres0 = {me: -1.0 for me in self.subdomains}
         self._flags = {me: False for me in self.subdomains}
         self._gres, self._gres0 = 0.0, -1.0
+        if getattr(self, "_start_ref", None) is not None:
+            # set_rhs(..., "keep"): the tests measure against the residual of a ZERO start vector, as a fresh solver's
+            # do -- relative to a kept iterate's own, already small, residual no tolerance could be met
+            self._lres0, self._gres0 = dict(self._start_ref[0]), self._start_ref[1]
         self._num_converged = 0
         self._timings = [[] for _ in range(5)]
         # overlapped one-sided mode: flooded convergence state and the messages in flight
@@ -1470,9 +1476,12 @@ class SolverRAS:
         self._exchange()
         parts = {me: sd.true_residual_sq(stream) for me, sd in locals_}
         res_sq = sum(comm.allgather_scalars(parts))
-        rhs_sq = sum(comm.allgather_scalars(
-            {me: float(np.sum(self._rhs_first_rows(sd, sd.local_size) ** 2))
-             for me, sd in locals_}))
+        if self._device_rhs is not None:  # set_rhs(tensor): b is in HBM only
+            rhs_sq = sum(comm.allgather_scalars({me: sd.rhs_norm_sq(stream) for me, sd in locals_}))
+        else:
+            rhs_sq = sum(comm.allgather_scalars(
+                {me: float(np.sum(self._rhs_first_rows(sd, sd.local_size) ** 2))
+                 for me, sd in locals_}))
         out["residual_norm"] = float(np.sqrt(res_sq))
         out["rhs_norm"] = float(np.sqrt(rhs_sq))
         if gather_solution:
@@ -1487,6 +1496,92 @@ class SolverRAS:
                         (out["residual_norm"], out["residual_norm"] / out["rhs_norm"], elapsed))
         self.result = out
         return out
+
+    # ------------------------------------------------- one matrix, many right-hand sides
+    def _check_new_rhs(self, rhs, initial_guess):
+        """The refusals of set_rhs, all before any device call: (host array or None, device tensor or None)."""
+        def refuse(msg):
+            raise capi.SchwzError(capi.ERR_INVALID, "set_rhs: " + msg)
+        if self.problem is None or not self.subdomains:
+            refuse("the solver is not set up: call initialize() first")
+        if initial_guess not in ("zero", "keep"):
+            refuse("initial_guess must be 'zero' or 'keep', not %r" % (initial_guess,))
+        if rhs is None:
+            return None, None
+        N = int(self.metadata.global_size)
+        if type(rhs).__module__.split(".")[0] == "torch":
+            torch = self.backend._torch
+            if rhs.dtype != torch.float64:
+                refuse("a device right-hand side must be a float64 tensor, not %s" % rhs.dtype)
+            if rhs.dim() != 1 or rhs.shape[0] != N:
+                refuse("the right-hand side must have shape (%d,), not %s" % (N, tuple(rhs.shape)))
+            if rhs.device != self.backend.device:
+                refuse("the tensor lives on %s, the solver on %s" % (rhs.device, self.backend.device))
+            return None, rhs.contiguous()
+        arr = np.asarray(rhs)
+        if arr.dtype.kind != "f":
+            refuse("the right-hand side must hold floating-point values, not %s" % arr.dtype)
+        if arr.ndim != 1 or arr.shape[0] != N:
+            refuse("the right-hand side must have shape (%d,), not %s" % (N, arr.shape))
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if not np.isfinite(arr).all():
+            refuse("the right-hand side holds a value that is not finite")
+        return arr, None
+
+    def set_rhs(self, rhs=None, initial_guess="zero"):
+        """A new right-hand side on the solver as initialize() set it up -- partition, index sets, matrices, codings,
+        factors, solver objects and the coarse plan stay -- and the iteration state of a fresh solver
+        (initial_guess="zero": run() then computes, bit for bit, what initialize(rhs=...) + run() computes) or the
+        last iterate as the start vector ("keep"; the convergence tests of the runs that follow then measure against
+        the residual of a zero start vector, the norm of b per subdomain, as a fresh solver's do).  An extension: the reference has no such call.
+        `rhs`: None (as in initialize: ones, or the random right-hand side the settings ask for), a host array of
+        global_size floats, the same on every rank, indexed by the caller's row ids like initialize(rhs=...), or a
+        float64 torch tensor of that length on the solver's device, which is gathered on the device and never copied
+        to the host.  Collective like initialize(): every rank calls it."""
+        host, dev = self._check_new_rhs(rhs, initial_guess)
+        keep = initial_guess == "keep"
+        be, comm = self.backend, self.comm
+        stream = be.stream()
+        # messages of an interrupted run: completed either way; applied (unpacked) only where x~ is kept
+        if getattr(self, "_early", None) is not None:
+            if keep:
+                self._exchange()
+            else:
+                handle, self._early = self._early, None
+                comm.finish_exchange(handle)
+        pending, self._pending = getattr(self, "_pending", None), None
+        if pending is not None:
+            comm.finish_exchange(pending["halo"])
+            comm.finish_flags(pending["flags"])
+            if keep:
+                for me, sd in self.subdomains.items():
+                    self._unpack(me, sd, stream)
+        self._user_rhs, self._device_rhs = host, dev
+        if dev is not None and not self._gather_index_set:
+            perm = self.metadata.permutation
+            for sd in self.subdomains.values():
+                if perm is None:
+                    sd.rhs_index(None)
+                else:  # exactly as _rhs indexes a right-hand side handed to initialize()
+                    sd.rhs_index(np.asarray(perm, dtype=np.int64)[sd.local_to_global[:sd.local_size_x]])
+            self._gather_index_set = True
+        for sd in self.subdomains.values():
+            if dev is not None:
+                sd.rhs_gather(dev.data_ptr(), dev.shape[0], stream)
+            else:
+                sd.rhs_set(self._rhs_first_rows(sd, sd.local_size_x), stream)
+            if getattr(self, "_coarse", None) is not None:
+                sd.rhs_aggregate(stream)
+            sd.restart(keep, stream)
+        self._start_ref = None
+        if keep:
+            norms = {me: float(np.sqrt(sd.rhs_norm_sq_local(stream))) for me, sd in self.subdomains.items()}
+            self._start_ref = (norms, float(sum(comm.allgather_scalars(norms))))
+
+    def solve(self, rhs=None, initial_guess="zero", gather_solution=True):
+        """set_rhs(rhs, initial_guess) followed by run(gather_solution)."""
+        self.set_rhs(rhs, initial_guess)
+        return self.run(gather_solution)
 
     def run(self, gather_solution=True):
         """SchwarzBase::run (schwarz_base.cpp:323-506).  Returns a dict with the
