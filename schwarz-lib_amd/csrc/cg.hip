@@ -167,16 +167,7 @@ __global__ __launch_bounds__(kBlock) void cg_direction_kernel(int64_t n, double 
         const double z = dg.mode ? diag_one(dg, ddict, i) * r[i] : r[i];
         p_out[i] = z + beta * p[i];
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // other workgroups read rho[it&1] concurrently: the slot written here is the other one
-        st->rho[(it + 1) & 1] = rho_new;
-        st->rr = rr;
-        st->iters = st->iters + 1;
-        // 0, not it + 1: every later launch leaves at once whatever iteration index it carries (the
-        // recorded launches of a replayed hipGraph carry 0..15 again and again).  Workgroups of THIS
-        // launch that read the 0 early skip their part of p, which nobody will read any more.
-        if (sqrt(rr) <= rtol * st->r0) st->stop_iter = 0;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) cg_advance_state(st, it, rho_new, rr, rtol);
 }
 
 // What workgroup 0 of cg_direction_kernel does, alone: the LAST iteration of a solve needs the state
@@ -189,12 +180,7 @@ __global__ __launch_bounds__(kBlock) void cg_state_advance_kernel(const double *
     if (it >= st->stop_iter) return;
     const double rho_new = fold_partials(partials_in, nparts, red);
     const double rr = fold_partials(partials_in + nparts, nparts, red);
-    if (threadIdx.x == 0) {
-        st->rho[(it + 1) & 1] = rho_new;
-        st->rr = rr;
-        st->iters = st->iters + 1;
-        if (sqrt(rr) <= rtol * st->r0) st->stop_iter = 0;
-    }
+    if (threadIdx.x == 0) cg_advance_state(st, it, rho_new, rr, rtol);
 }
 
 // The last direction of a fixed-work solve is never stored (pcg_iterate, vlast_on): when somebody asks for the

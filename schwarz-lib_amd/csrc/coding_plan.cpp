@@ -1030,7 +1030,7 @@ WalkPlan plan_walk(const CodingOptions &opt, const PairPlan &P, int64_t nrows, i
     // Measured in-box (tools/tdir_ab.sh): 256-wide planes, update bands of 512 rows: 1024-row bands for the fused
     // launch -3 % per step (2048: +5 %); 512-wide planes, 1024 / 2048: +3 % (two workgroups per CU); 1024-wide
     // planes, where a 1024-row band is a single x line, 2048: fused launch 0.773 -> 0.696 ms, -4 % per step -- in
-    // round 2.  With the halo schedule of round 3 (SCHWZ_DD) the halo lines hit L2 and what counts on 1024-wide
+    // round 2.  With the halo three positions ahead (round 3) the halo lines hit L2 and what counts on 1024-wide
     // planes is the second workgroup per CU a 1024-row band leaves room for: 1024 x 1024 x 128 slab, fused launch
     // 0.681 ms with 2048-row bands, 0.640 ms with 1024 (step 16.5 -> 16.0 ms; profiles/r03_c5slab_ab.txt).
     int T_dir = opt.sweep_Tdir ? *opt.sweep_Tdir : (T == 512 ? 1024 : T);

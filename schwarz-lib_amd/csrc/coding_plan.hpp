@@ -34,13 +34,11 @@ inline size_t sweep_update_lds(int64_t T, int64_t nx, int npat)
     return (size_t)(4 * T + 4 * nx) * sizeof(double) + (size_t)npat * (9 * 16 + 4);
 }
 
-// Build-time switch of spmv_pair.hip (described there; `make variant DEFS=-DSCHWZ_DD=...` recompiles that file
-// alone): its default, and the NX-row halo lines of r and p the direction walk's window carries under it.  The
-// planning functions never read the constant -- spmv_pair.hip hands plan_walk the value of ITS build.
-#ifndef SCHWZ_DD
-#define SCHWZ_DD 7
-#endif
-constexpr int kDirdotHaloLines = (SCHWZ_DD & 2) ? 3 : 2;
+// NX-row halo lines of p' in the fused direction walk's LDS window: the halo of a position is requested three
+// positions ahead -- in the step in which the neighbouring band fetches the same lines as its own window, so they hit
+// L2 (spmv_pair.hip, profiles/r03_dd_ab.txt) -- and each of the three in flight needs a slot.  The planning functions
+// never read the constant: spmv_pair.hip hands it to plan_walk.
+constexpr int kDirdotHaloLines = 3;
 
 // ... of the fused direction walk: `halo_lines` halo lines in its window, the upper triangle's five slots in its tables
 inline size_t sweep_dirdot_lds(int64_t T_dir, int64_t nx, int npat, int halo_lines)

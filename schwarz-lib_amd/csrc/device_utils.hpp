@@ -117,6 +117,19 @@ __device__ __forceinline__ void cg_init_state(CgState *st, const double *partial
     }
 }
 
+// One iteration's advance of CgState by the one lane that holds the folded rho = r.z and ||r||^2 of the new residual
+// (cg_direction_kernel, cg_state_advance_kernel and the fused direction launches of spmv_pair.hip).  Other workgroups read
+// rho[it & 1] concurrently: the slot written is the other one.  stop_iter = 0, not it + 1: every later launch leaves
+// at once whatever iteration index it carries (the recorded launches of a replayed hipGraph carry 0..15 again and
+// again); workgroups of THIS launch that read the 0 early skip their part of p, which nobody will read any more.
+__device__ __forceinline__ void cg_advance_state(CgState *st, int it, double rho_new, double rr, double rtol)
+{
+    st->rho[(it + 1) & 1] = rho_new;
+    st->rr = rr;
+    st->iters = st->iters + 1;
+    if (sqrt(rr) <= rtol * st->r0) st->stop_iter = 0;
+}
+
 // ---------------------------------------------------------------------------
 // streaming vector kernels (cg.hip, bicgstab.hip): 16-byte accesses, the Jacobi diagonal in its DiagView forms
 // ---------------------------------------------------------------------------

@@ -398,36 +398,36 @@ struct CsrView {
     int pair_canon[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // z-sweep ("brick") walk of a canonical 3-D stencil layout {-PL, -NX, -1, 0, +1, +NX, +PL} (spmv_pair.hip):
     // a workgroup keeps a band of sweep_T rows and walks it through consecutive planes (stride PL), the
-    // window [band - NX, band + T + NX) of each plane staged once in an LDS ring.  sweep_seg: one
-    // {band, z0, z1, 0} per workgroup slot (z0 == z1: empty); sweep_gen: the chunks of 512 rows no segment
-    // covers (boundary planes of a subdomain, overlap rows), walked the generic way by sweep_gen_blocks more
-    // workgroups of the same launch.  sweep_nslots == 0: not built.
+    // window [band - NX, band + T + NX) of each plane staged once in an LDS ring.  sweep_rec: one WalkRecord per
+    // workgroup slot -- the segment {band, z0, z1, rows of the band} (z0 == z1: empty) and the planes of its first
+    // five chain positions; sweep_gen: the chunks of 512 rows no segment covers (boundary planes of a subdomain,
+    // overlap rows), walked the generic way by sweep_gen_blocks more workgroups of the same launch.
+    // sweep_nslots == 0: not built.
+    // (unused_*: seven tables the walks read in earlier forms -- segments as int4, slot values and presence masks.
+    // Nothing uploads or reads them; the pointers keep their places, and stay null, because the argument block of
+    // every kernel that takes a CsrView is laid out by this struct: without them the compiler schedules some of those
+    // kernels differently (spmv_dict.hip: other VGPR counts, profiles/r25_walk_forms.txt).)
     int sweep_T = 0, sweep_nx = 0, sweep_nslots = 0, sweep_ngen = 0, sweep_gen_blocks = 0;
     int64_t sweep_pl = 0;
-    const int4 *sweep_seg = nullptr;
-    // the fused direction launch's own band height and segment table (spmv_pair_dirdot_sweep_kernel); equal to
-    // the update launch's unless SCHWZ_SWEEP_TDIR asks for taller bands
+    const void *unused_seg = nullptr;
+    // the fused direction launch's own band height and records (spmv_pair_dirdot_sweep_kernel); equal to the update
+    // launch's unless SCHWZ_SWEEP_TDIR asks for taller bands
     int sweep_T_dir = 0, sweep_nslots_dir = 0;
-    const int4 *sweep_seg_dir = nullptr;
+    const void *unused_seg_dir = nullptr;
     // ... and the first-direction launch of a solve (one vector read, bound by latency: more, shorter workgroups)
     int sweep_T_first = 0, sweep_nslots_first = 0;
-    const int4 *sweep_seg_first = nullptr;
-    // the three tables once more as records that also carry the first five chain rows of the segment (WalkRecord):
-    // what the kernels read; the int4 tables stay for whoever reads segments alone
+    const void *unused_seg_first = nullptr;
     const WalkRecord *sweep_rec = nullptr, *sweep_rec_dir = nullptr, *sweep_rec_first = nullptr;
     const schwz_idx *sweep_gen = nullptr;
+    const void *unused_canon_val = nullptr, *unused_canon_mask = nullptr;
+    int canon_npat = 0;  // patterns of table 0
+    const void *unused_canon_sym_val = nullptr, *unused_canon_sym_mask = nullptr;
     // per pattern of table 0: its entries in the nine slots [far before 0, far before 1, -NX, -1, 0, +1, +NX,
-    // far after 0, far after 1] (9 PairVal) and the presence mask (bit k: row r has slot k, bit 16 + k: row r + 1)
-    const double *canon_val = nullptr;
-    const int *canon_mask = nullptr;
-    int canon_npat = 0;
-    // the same for the upper-triangle twin of the table (symmetric matrices): slots [0, +1, +NX, far after 0,
-    // far after 1], 5 PairVal
-    const double *canon_sym_val = nullptr;
-    const int *canon_sym_mask = nullptr;
-    // both tables in the form the walks keep in LDS when they sum every slot (SCHWZ_WALK_ZEROCOEF, spmv_pair.hip):
-    // canon_npat x 9 and canon_npat x 5 pairs, +0.0 where the mask has no bit -- one 16-byte load per staged entry
+    // far after 0, far after 1] as 9 pairs (row r, row r + 1), +0.0 where the pattern has no entry: the form the
+    // walks keep in LDS (they sum every slot, spmv_pair.hip) -- one 16-byte load per staged entry
     const double *canon_ready = nullptr;
+    // the same for the upper-triangle twin of the table (symmetric matrices; nullptr: none): slots [0, +1, +NX,
+    // far after 0, far after 1], 5 pairs
     const double *canon_sym_ready = nullptr;
     // chains of planes (see plan_walk, coding_plan.cpp): plane index per chain position (-1: none) and, per position, which
     // window each far slot reads (2 bits per slot B0, B1, A0, A1: 0 none, 1 previous position, 2 next)
@@ -713,8 +713,7 @@ struct schwz_csr {
         struct { schwz::DevBuf code, vptr, dptr, vdict, ddict; } dict;
         struct { schwz::DevBuf pair_id, rle, chunk_ptable, ptbl_desc, ptbl_len, ptbl_val, ptbl_meta; } pair;
         struct {
-            schwz::DevBuf seg, seg_dir, seg_first, gen, canon_val, canon_mask, canon_sym_val, canon_sym_mask, chain_plane,
-                chain_far, rec, rec_dir, rec_first, canon_ready, canon_sym_ready;
+            schwz::DevBuf gen, chain_plane, chain_far, rec, rec_dir, rec_first, canon_ready, canon_sym_ready;
         } walk;
         struct { schwz::DevBuf chunk_dual, chain_dual, dual_chunks; } dual;
     } coding;

@@ -572,69 +572,49 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_kernel(CsrView A, SpmvArgs a
         }
     }
     if (kDir && blockIdx.x == 0 && tid == 0 && !a.sweep) {  // (the z-sweep kernel does it for its companion launch)
-        // what cg_direction_kernel's workgroup 0 does: the rho slot written is the one no launch of
-        // this iteration reads; stop_iter = 0 makes every later launch leave at once
-        CgState *st = const_cast<CgState *>(a.cg_state);
-        st->rho[(a.it + 1) & 1] = cg_rho_new;
-        st->rr = cg_rr;
-        st->iters = st->iters + 1;
-        if (sqrt(cg_rr) <= a.cg_rtol * st->r0) st->stop_iter = 0;
+        // what cg_direction_kernel's workgroup 0 does
+        cg_advance_state(const_cast<CgState *>(a.cg_state), a.it, cg_rho_new, cg_rr, a.cg_rtol);
     }
 }
 
-// SCHWZ_WALK_ZEROCOEF (build-time switch, round 3): the walks stage the slot tables into LDS with a coefficient of
-// +0.0 wherever a pattern has no entry and sum EVERY slot's product, instead of selecting +0.0 for the absent ones
-// by a mask bit (two bit tests and two 64-bit selects per slot and row pair: a third of the vector instructions of a
-// step).  The same bits: a sum that began at +0.0 is never -0.0, so adding the +-0.0 that (+0.0 x a finite operand)
-// yields leaves it unchanged, exactly like adding the selected +0.0.  The operands of absent slots are loaded vector
-// data (clamped addresses, windows of real planes), finite whenever the vector is; a vector holding Inf / NaN has a
-// NaN p.(A p) either way.  0 restores the masked sums.
-#ifndef SCHWZ_WALK_ZEROCOEF
-#define SCHWZ_WALK_ZEROCOEF 1
-#endif
+// The z-sweep walks below have one form each.  The alternatives they were measured against (masked sums, plain or
+// hinted streams, the earlier prologues, the two-slot halo ring) were build-time switches until commit 1043a3a;
+// DESIGN.md section 3 and profiles/ keep the measurements.
+//
+// Sums.  The slot tables hold a coefficient of +0.0 wherever a pattern has no entry (CsrView::canon_ready, made once by
+// the plan) and the walks sum EVERY slot's product instead of selecting +0.0 for the absent ones by a mask bit (two bit
+// tests and two 64-bit selects per slot and row pair: a third of the vector instructions of a step).  The same bits: a
+// sum that began at +0.0 is never -0.0, so adding the +-0.0 that (+0.0 x a finite operand) yields leaves it unchanged,
+// exactly like adding a selected +0.0.  The operands of absent slots are loaded vector data (clamped addresses, windows
+// of real planes), finite whenever the vector is; a vector holding Inf / NaN has a NaN p.(A p) either way.
+//
+// Streams.  The update walk's r is a non-temporal load and store and p' leaves the fused launch with non-temporal stores.
+// On vectors of 135 MB (256^3, 512 x 512 x 64) the hints win: in-box a plain r load in the update launch costs the
+// FOLLOWING fused launch 4 us of 74, a plain r store the update launch 3 us of 69.  Where r, p and p' fit the 256 MiB
+// Infinity Cache together (192^3: 3 x 57 MB) they LOSE 5 % of the step -- they give up the on-die copy the next launch
+// would have read (profiles/r03_cache_hints.txt).  A per-launch choice was built and dropped: as a workgroup-uniform
+// branch around the three accesses it cost 2.5 % of the 256^3 step (the loop body is no longer one block), as a template
+// parameter it doubles ~100 instantiations; no configuration of BASELINE.json has vectors that small.
+// r0 leaves the START walk with a plain store: its next two readers (first direction, first update) follow at once and
+// find part of it on die: -0.5 ... -0.75 % per step at 256^3 / 512 x 512 x 64, neutral on 1 GB vectors (same file).
+//
+// Prologue: what a walk workgroup does before its first step -- a constant per launch that does not depend on the bytes
+// (profiles/r16_walk_timeline.txt, r21_walk_prologue.txt).  Two steps:
+// 1. Everything that depends on nothing but the kernel arguments and blockIdx.x is requested at kernel entry before
+//    anything is waited for -- stop_iter, rho, the slot's WalkRecord (segment AND its first five chain rows, read through
+//    the constant address space: scalar loads that do not queue behind the vector loads), the table entries in their
+//    staged form (one unconditional 16-byte load per entry, kept in registers) and the lane's strided sums of the
+//    previous launch's partial sums, eight per bank at a time (fold_lane_sums) -- and the early return and the
+//    empty-slot branch follow that one wait.  The loads in front of the return have no side effect and valid addresses
+//    whether or not the launch is live.
+// 2. Then the windows are requested, and BEHIND those requests the tables go to LDS and the cross-wave part of the fold
+//    gives alpha / beta, behind barriers that order LDS alone (block_sum_lds; the fused direction walk's two folds
+//    share them).  Requested behind the windows, tables and partial sums came back behind them (vector loads return in
+//    order), and a fold's __syncthreads() waited for every prefetched plane, not only for those of the first position.
+// Every sum keeps its order: the same bits as folding one partial sum after the other.
 
-// SCHWZ_WALK_HINTS (build-time switch): 1 = the update walk's r is a non-temporal load and store and p' leaves the
-// fused launch with non-temporal stores; 0 = plain loads and stores.  On vectors of 135 MB (256^3, 512 x 512 x 64) the
-// hints win: in-box a plain r load in the update launch costs the FOLLOWING fused launch 4 us of 74, a plain r store
-// the update launch 3 us of 69.  Where r, p and p' fit the 256 MiB Infinity Cache together (192^3: 3 x 57 MB) they
-// LOSE 5 % of the step -- they give up the on-die copy the next launch would have read (profiles/r03_cache_hints.txt).
-// A per-launch choice was built and dropped: as a workgroup-uniform branch around the three accesses it cost 2.5 % of
-// the 256^3 step (the loop body is no longer one block), as a template parameter it doubles ~100 instantiations; no
-// configuration of BASELINE.json has vectors that small.
-#ifndef SCHWZ_WALK_HINTS
-#define SCHWZ_WALK_HINTS 1
-#endif
-#ifndef SCHWZ_INIT_PLAIN_STORE
-#define SCHWZ_INIT_PLAIN_STORE 1  // start walk: r0 leaves with a plain store -- its next two readers (first direction, first update) follow at once and find part of it on die: -0.5 ... -0.75 % per step at 256^3 / 512 x 512 x 64, neutral on 1 GB vectors (profiles/r03_cache_hints.txt)
-#endif
-
-// SCHWZ_WALK_PRO (build-time switch, tools/walk_ab.sh): what a walk workgroup does before its first step -- a constant
-// per launch that does not depend on the bytes (profiles/r16_walk_timeline.txt: 8.6 us of the update walk's life, 14 us
-// of the fused direction walk's, of which the tables and the fold took 4.9 and 6.9 us).
-// bit 0: the slot tables are staged and the lane's strided sums of the previous launch's partial sums are taken at
-//   kernel entry, while the scalar loads of the segment and its chain rows are on their way and BEFORE the windows
-//   are requested; only the cross-wave part of the fold follows the window requests, behind barriers that order LDS
-//   alone (block_sum_lds; the fused direction walk's two folds share them).  Before, tables and partial sums were
-//   requested behind the windows, came back behind them (vector loads return in order), and each fold's two
-//   __syncthreads() waited for every prefetched plane, not only for those of the first position.
-// bit 1: the partial sums are requested eight per bank at a time (fold_lane_sums) instead of one after the other.
-// bit 2 (needs bits 0 and 1): everything that depends on nothing but the kernel arguments and blockIdx.x is requested
-//   at kernel entry before anything is waited for -- stop_iter, the slot's WalkRecord (segment AND its first five
-//   chain rows, read through the constant address space: scalar loads that do not queue behind the vector loads), rho,
-//   the table entries in their staged form (CsrView::canon_ready: one unconditional 16-byte load per entry, kept in
-//   registers) and the lane sums -- and the early return and the empty-slot branch follow that one wait.  Then the
-//   windows are requested; the LDS stores of the tables join the cross-wave part of the fold behind them.  Before,
-//   stop_iter, the segment (a vector load), the sums, the mask, the values behind branches on the mask bits, the mask
-//   again and the chain rows were each waited for in turn.  The loads in front of the return have no side effect and
-//   valid addresses whether or not the launch is live.  With SCHWZ_WALK_ZEROCOEF=0 the tables are staged from
-//   canon_val / canon_mask as under bit 0.
-// Every sum keeps its order: the same bits.  3 restores the prologue of round 16, 0 the one before it.
-#ifndef SCHWZ_WALK_PRO
-#define SCHWZ_WALK_PRO 7
-#endif
-static_assert((SCHWZ_WALK_PRO & 4) == 0 || (SCHWZ_WALK_PRO & 3) == 3, "SCHWZ_WALK_PRO bit 2 builds on bits 0 and 1");
-// table entries a lane keeps in registers between kernel entry and the LDS stores (bit 2): kPairPats patterns of nine
-// slots at the most, of five in the fused direction walk
+// table entries a lane keeps in registers between kernel entry and the LDS stores: kPairPats patterns of nine slots at
+// the most, of five in the fused direction walk
 constexpr int kWalkTabPerLane = (kPairPats * 9 + kBlock - 1) / kBlock;
 constexpr int kWalkSymTabPerLane = (kPairPats * 5 + kBlock - 1) / kBlock;
 
@@ -681,6 +661,29 @@ __device__ __forceinline__ void walk_stamp_positions(const SpmvArgs &a, int npos
 #define SCHWZ_STAMP_LANDED() ((void)0)
 #endif
 
+// Workgroup 0 of a walk zeroes the partial-sum slots no workgroup of the launch or of its companion writes, in
+// BANKS banks of a.part_stride slots
+template <int BANKS>
+__device__ __forceinline__ void zero_unused_partials(const SpmvArgs &a)
+{
+    if (blockIdx.x == 0)
+        for (int i = (int)gridDim.x + a.part_offset + (int)threadIdx.x; i < a.part_stride; i += kBlock) {
+            a.partials[i] = a.partials[a.part_stride + i] = 0.0;
+            if (BANKS == 3) a.partials[2 * a.part_stride + i] = 0.0;
+        }
+}
+
+// Row of a 16-byte piece clamped into the vector: pieces beyond its ends (first / last band of a plane) read a valid
+// address; no row has an entry there and the zero coefficients drop what they deliver
+__device__ __forceinline__ int clamp_piece(int g, int64_t gmax) { return g < 0 ? 0 : (g > (int)gmax ? (int)gmax : g); }
+
+// Window a far slot reads at a chain position, from its two bits of chain_far: 1 the previous position's, 2 the
+// next one's, 0 none -- the slot then reads the position's own window, and its coefficients are zero
+__device__ __forceinline__ const double *far_window(int sel, const double *prv, const double *nxt, const double *cur)
+{
+    return (sel & 3) == 1 ? prv : ((sel & 3) == 2 ? nxt : cur);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // z-sweep ("brick") walk of the q-free CG update launch for matrices in the canonical 3-D stencil layout
 // {-PL, -NX, -1, 0, +1, +NX, +PL} (CsrView::sweep_*).  tools/probes/brick_probe.hip priced the memory
@@ -692,7 +695,7 @@ __device__ __forceinline__ void walk_stamp_positions(const SpmvArgs &a, int npos
 // lane's pairs and the chunk's pattern-id record are requested one plane ahead.  The loop body is
 // straight-line code (addresses are clamped instead of guarded, every count is a template
 // parameter), so the compiler can give each wait its own vmcnt instead of draining the queue.
-// Products, order and presence masks are those of accumulate_canon: the same bits per row.
+// Products and their order are those of accumulate_canon: the same bits per row.
 // NL: 16-byte pieces of a window per lane; NH: chunks of 512 rows per band; DIAGVEC: Jacobi diagonal
 // as a full vector.  x is not touched (deferred x update only).
 // INIT: the same walk as the CG start launch (kSpmvResidInit without its p store): the ring holds the
@@ -724,35 +727,22 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     double *const own_ring = reinterpret_cast<double *>(sweep_lds);
     double *const halo_ring = own_ring + 4 * T;
     PairVal *const cpv = reinterpret_cast<PairVal *>(halo_ring + 4 * NX);
-    int *const cmask = reinterpret_cast<int *>(cpv + A.canon_npat * 9);
+    const int ntab = A.canon_npat * 9;  // entries of the slot tables
     __shared__ double red[4];
     double cg_alpha = 1.0;
     const int tid = threadIdx.x;
     [[maybe_unused]] constexpr int kForm = INIT ? kFormStart : kFormUpdate;
     SCHWZ_STAMP(kForm, kStampEntry);
-    constexpr bool kPro2 = (SCHWZ_WALK_PRO & 4) != 0;            // one wait for everything but the windows (see SCHWZ_WALK_PRO)
-    constexpr bool kReady = kPro2 && SCHWZ_WALK_ZEROCOEF != 0;  // ... the tables among it, from their staged form
-    if (!kPro2 && !INIT) {
-        if (a.it >= a.cg_state->stop_iter) return;
-    }
     // INIT reads the right-hand side where the update launch reads r (the caller's b need only be 8-byte
     // aligned) and stores r to a.y
     typedef double pvd2u __attribute__((ext_vector_type(2), aligned(8)));
     const double *const r_in = INIT ? a.b : a.cg_r;
     double *const r_out = INIT ? a.y : (a.cg_r_out ? a.cg_r_out : a.cg_r);
     const pvd2 ring_scale = {a.ring_scale, a.ring_scale};  // 1.0 except in the first update of a solve with a virtual p0
-    // What a workgroup needs before its first step besides its windows -- the slot tables in LDS and the step
-    // length alpha (every workgroup folds the partial sums of the previous launch itself) -- is fetched AFTER the
-    // first windows have been requested (round 3): the two latencies overlap instead of adding up at the start of
-    // every workgroup's life.
-    // (SCHWZ_WALK_PRO bit 0: tables and the lane's strided sums of the partial sums at kernel entry -- `early` --, the
-    // cross-wave part of the fold behind the window requests -- `late`; without it both where `late` is called)
-    constexpr bool kEarly = (SCHWZ_WALK_PRO & 1) != 0;
     double fold_lane = 0.0, rho_it = 0.0;
-    // (kReady) the lane's table entries between their request and their LDS stores: rounds of kBlock entries, a round
-    // that exists is loaded by every lane (the lanes past the table's end repeat its last entry and store nothing)
+    // the lane's table entries between their request and their LDS stores: rounds of kBlock entries, a round that
+    // exists is loaded by every lane (the lanes past the table's end repeat its last entry and store nothing)
     pvd2 tab[kWalkTabPerLane];
-    const int ntab = A.canon_npat * 9;
     auto request_tables = [&]() {
 #pragma unroll
         for (int k = 0; k < kWalkTabPerLane; ++k) {
@@ -765,18 +755,15 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         for (int k = 0; k < kWalkTabPerLane; ++k)
             if (tid + k * kBlock < ntab) cpv[tid + k * kBlock] = PairVal{tab[k].x, tab[k].y};
     };
-    auto stage_tables = [&]() {
-        for (int i = tid; i < A.canon_npat * 9; i += kBlock) {
-            if (SCHWZ_WALK_ZEROCOEF) {
-                const int m = A.canon_mask[i / 9], k = i % 9;
-                cpv[i] = PairVal{((m >> k) & 1) ? A.canon_val[2 * i] : 0.0, ((m >> (16 + k)) & 1) ? A.canon_val[2 * i + 1] : 0.0};
-            } else {
-                cpv[i] = PairVal{A.canon_val[2 * i], A.canon_val[2 * i + 1]};
-            }
-        }
-        if (tid < A.canon_npat) cmask[tid] = A.canon_mask[tid];
-    };
-    // (kPro2) the slot's record, through the constant address space: scalar loads
+    // Prologue, step 1: request everything that depends only on the arguments and blockIdx.x -- stop_iter, rho and the
+    // record (scalar), the ready tables, the lane sums -- in front of the first wait
+    int stop_iter = 0;
+    if (!INIT) {
+        stop_iter = a.cg_state->stop_iter;
+        rho_it = a.cg_state->rho[a.it & 1];
+    }
+    // the slot's record -- the segment and the planes of its chain positions z0 - 1 .. z0 + 3 -- through the constant
+    // address space: scalar loads
     typedef const WalkRecord __attribute__((address_space(4))) *const_record;
     int4 sg;
     int rec_plane[5] = {0, 0, 0, 0, 0};
@@ -786,57 +773,32 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
 #pragma unroll
         for (int k = 0; k < 5; ++k) rec_plane[k] = rec->plane[k];
     };
-    auto tables_and_alpha = [&](bool early) {
-        if (kEarly && early) {
-            if (!INIT) rho_it = a.cg_state->rho[a.it & 1];
-            if (kPro2) {
-                request_record();
-                // (no instruction: keeps the compiler from moving the scalar requests above behind the vector requests
-                // below, where they landed behind a second wait for kernel arguments -- the arguments those need are
-                // operands here, so they arrive with the first batch)
-                asm volatile("" ::"s"(a.pq_partials), "s"(a.pq_nparts), "s"(A.canon_ready), "s"(ntab) : "memory");
-            }
-            if (kReady) request_tables();  // (before the sums: the first wait for a vector load is inside fold_lane_sums)
-            if (!INIT) {
-                if (SCHWZ_WALK_PRO & 2) {
-                    double s[1] = {0.0};
-                    fold_lane_sums(a.pq_partials, a.pq_nparts, s);
-                    fold_lane = s[0];
-                } else {
-                    for (int i = tid; i < a.pq_nparts; i += kBlock) fold_lane += a.pq_partials[i];  // fold_partials' sums
-                }
-            }
-            if (!kReady) stage_tables();
-            return;
-        }
-        if (!kEarly) stage_tables();
-        if (kReady) store_tables();
+    request_record();
+    // (no instruction: keeps the compiler from moving the scalar requests above behind the vector requests below, where
+    // they landed behind a second wait for kernel arguments -- the arguments those need are operands here, so they
+    // arrive with the first batch)
+    asm volatile("" ::"s"(a.pq_partials), "s"(a.pq_nparts), "s"(A.canon_ready), "s"(ntab) : "memory");
+    request_tables();  // (before the sums: the first wait for a vector load is inside fold_lane_sums)
+    if (!INIT) {
+        double s[1] = {0.0};
+        fold_lane_sums(a.pq_partials, a.pq_nparts, s);
+        fold_lane = s[0];
+    }
+    if (!INIT && a.it >= stop_iter) return;
+    // Prologue, step 2, called behind the window requests so that the two latencies overlap instead of adding up at the
+    // start of every workgroup's life: tables to LDS, cross-wave fold, alpha (every workgroup folds the partial sums of
+    // the previous launch itself)
+    auto tables_and_alpha = [&]() {
+        store_tables();
         if (!INIT) {
-            if (kEarly) {
-                double v[1] = {fold_lane};
-                block_sum_lds(v, red);
-                cg_alpha = rho_it / v[0];
-            } else {
-                cg_alpha = a.cg_state->rho[a.it & 1] / fold_partials(a.pq_partials, a.pq_nparts, red);
-            }
+            double v[1] = {fold_lane};
+            block_sum_lds(v, red);
+            cg_alpha = rho_it / v[0];
             if (blockIdx.x == 0 && tid == 0 && a.alpha_out) *a.alpha_out = cg_alpha;
         }
         lds_barrier();
     };
-    if (kPro2) {
-        // requests only, in front of the first wait: stop_iter, rho and the record (scalar), the tables, the lane sums
-        int stop_iter = 0;
-        if (!INIT) stop_iter = a.cg_state->stop_iter;
-        tables_and_alpha(true);
-        if (!INIT && a.it >= stop_iter) return;
-    }
-    // partial-sum slots no workgroup of this launch or of its companion writes
-    if (blockIdx.x == 0)
-        for (int i = (int)gridDim.x + a.part_offset + tid; i < a.part_stride; i += kBlock) {
-            a.partials[i] = a.partials[a.part_stride + i] = 0.0;
-            if (DUAL) a.partials[2 * a.part_stride + i] = 0.0;
-        }
-    if (!kPro2) sg = A.sweep_seg[blockIdx.x];
+    zero_unused_partials<DUAL ? 3 : 2>(a);
     const int64_t PL = A.sweep_pl;
     const int band = sg.x, z0 = sg.y, z1 = sg.z;  // chain positions z0 <= z < z1
     constexpr bool GEN = RUNS == 0;
@@ -845,19 +807,16 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
     double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
     typedef const unsigned __attribute__((address_space(4))) *const_words;
     typedef const int __attribute__((address_space(4))) *const_ints;
-    if (!kPro2 && kEarly && (z0 < z1 || blockIdx.x == 0)) tables_and_alpha(true);
     if (z0 < z1) {
         // first row of the band at a chain position (scalar loads: the position is workgroup-uniform); a
-        // position without a plane (the ends of a chain) reads plane 0 -- valid memory no mask lets through
+        // position without a plane (the ends of a chain) reads plane 0 -- valid memory whose slots have zero coefficients
         const const_ints chain = (const_ints)(uintptr_t)A.chain_plane;
         const const_ints chain_far = (const_ints)(uintptr_t)A.chain_far;
         auto band_row = [&](int z) -> int {  // rows fit 32 bits (the launch is for ncols < 2^28)
             const int k = chain[z];
             return (k < 0 ? 0 : k) * (int)PL + band * T;
         };
-        // Pieces beyond the vector's ends (first / last band of a plane) are clamped to a valid address: no
-        // row has an entry there, the masks drop what they deliver.
-        auto clampg = [&](int g) -> int { return g < 0 ? 0 : (g > (int)gmax ? (int)gmax : g); };
+        auto clampg = [&](int g) -> int { return clamp_piece(g, gmax); };
         auto load_own = [&](int base, pvd2 (&reg)[NH]) {
 #pragma unroll
             for (int k = 0; k < NH; ++k) __builtin_memcpy(&reg[k], a.x + clampg(base + 2 * (tid + k * kBlock)), 16);
@@ -900,10 +859,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
 #pragma unroll
                 for (int k = 0; k < (GEN ? 1 : RUNS / 2); ++k) f.w[k] = q[k];
             }
-            if (SCHWZ_WALK_HINTS)
-                f.r = __builtin_nontemporal_load(reinterpret_cast<const pvd2u *>(r_in + ra));
-            else
-                f.r = *reinterpret_cast<const pvd2u *>(r_in + ra);
+            f.r = __builtin_nontemporal_load(reinterpret_cast<const pvd2u *>(r_in + ra));
             if (DIAGVEC) f.d = __builtin_nontemporal_load(reinterpret_cast<const pvd2 *>(a.dinv + ra));
             return f;
         };
@@ -917,7 +873,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         int brow[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k)
-            brow[k] = kPro2 ? (rec_plane[k] < 0 ? 0 : rec_plane[k]) * (int)PL + band * T : band_row(z0 - 1 + k);
+            brow[k] = (rec_plane[k] < 0 ? 0 : rec_plane[k]) * (int)PL + band * T;  // band_row(z0 - 1 + k), from the record
         SCHWZ_STAMP_AFTER(brow[0] + brow[1] + brow[2] + brow[3] + brow[4]);
         SCHWZ_STAMP(kForm, kStampSegment);
         SCHWZ_STAMP_POSITIONS(z1 - z0);
@@ -936,7 +892,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
             }
             SCHWZ_STAMP_LANDED();
             SCHWZ_STAMP(kForm, kStampWindows);
-            tables_and_alpha(false);
+            tables_and_alpha();
             SCHWZ_STAMP(kForm, kStampTables);
             store_own(z0 - 1, first);
             store_own(z0, second);
@@ -955,11 +911,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
             const double *prv = own_ring + (size_t)((z + 3) & 3) * T;
             const double *nxt = own_ring + (size_t)((z + 1) & 3) * T;
             const double *hlo = halo_ring + (size_t)(z & 1) * 2 * NX, *hup = hlo + NX;
-            // window each far slot reads (slots of a plane without that coupling read `cur`: masked anyway)
-            const double *fb0 = (far & 3) == 1 ? prv : ((far & 3) == 2 ? nxt : cur);
-            const double *fb1 = ((far >> 2) & 3) == 1 ? prv : (((far >> 2) & 3) == 2 ? nxt : cur);
-            const double *fa0 = ((far >> 4) & 3) == 1 ? prv : (((far >> 4) & 3) == 2 ? nxt : cur);
-            const double *fa1 = ((far >> 6) & 3) == 1 ? prv : (((far >> 6) & 3) == 2 ? nxt : cur);
+            const double *fb0 = far_window(far, prv, nxt, cur), *fb1 = far_window(far >> 2, prv, nxt, cur);
+            const double *fa0 = far_window(far >> 4, prv, nxt, cur), *fa1 = far_window(far >> 6, prv, nxt, cur);
             const int rbase = z + 2 < z1 ? brow[3] : brow[1];  // past the segment: a valid plane, never used
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
@@ -975,7 +928,6 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
                     const unsigned e = (f.w[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
                     if ((unsigned)tid >= (e & 0xffu)) pid = (int)(e >> 8);
                 }
-                const int mask = SCHWZ_WALK_ZEROCOEF ? 0 : cmask[pid];
                 pvd2 t[8];
                 t[4] = *reinterpret_cast<const pvd2 *>(cur + i0);
                 t[3].x = i0 > 0 ? cur[i0 - 1] : hlo[NX - 1];
@@ -986,20 +938,15 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
                 t[6] = *reinterpret_cast<const pvd2 *>(i0 + NX < T ? cur + (i0 + NX) : hup + (i0 + NX - T));
                 t[0] = *reinterpret_cast<const pvd2 *>(fb0 + i0);
                 t[7] = *reinterpret_cast<const pvd2 *>(fa0 + i0);
-                // masked sums without branches: an absent entry adds +0.0, which leaves a sum that began
-                // at +0.0 unchanged bit for bit (such a sum is never -0.0).  The second far slots exist on a
-                // subdomain's boundary planes only: a plane without them skips both (workgroup-uniform).
+                // sums without branches or selects: an absent entry has a coefficient of +0.0 (see "Sums" above).
+                // The second far slots exist on a subdomain's boundary planes only: a plane without them skips both
+                // (workgroup-uniform).
                 double s0 = 0.0, s1 = 0.0;
                 auto add = [&](int k, pvd2 tv) {
                     const PairVal v = cpv[pid * 9 + k];
                     const double p0 = v.a * tv.x, p1 = v.b * tv.y;
-                    if (SCHWZ_WALK_ZEROCOEF) {
-                        s0 += p0;
-                        s1 += p1;
-                    } else {
-                        s0 += ((mask >> k) & 1) ? p0 : 0.0;
-                        s1 += ((mask >> (16 + k)) & 1) ? p1 : 0.0;
-                    }
+                    s0 += p0;
+                    s1 += p1;
                 };
                 add(0, t[0]);
                 if (far & 0x0c) add(1, *reinterpret_cast<const pvd2 *>(fb1 + i0));
@@ -1029,10 +976,10 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
                     acc2 += plain_pos ? q1 : 0.0;
                 }
                 const pvd2 rn = {r0, r1};
-                if (SCHWZ_WALK_HINTS && !(INIT && SCHWZ_INIT_PLAIN_STORE))
-                    __builtin_nontemporal_store(rn, reinterpret_cast<pvd2 *>(r_out + ra));
-                else
+                if (INIT)  // r0: a plain store, its readers follow at once ("Streams" above)
                     *reinterpret_cast<pvd2 *>(r_out + ra) = rn;
+                else
+                    __builtin_nontemporal_store(rn, reinterpret_cast<pvd2 *>(r_out + ra));
                 rr[h] = fetch(rbase, h);
             }
 #pragma unroll
@@ -1048,7 +995,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
         if (z < z1) step(z, own_b, r_a);
         SCHWZ_STAMP(kForm, kStampLastStep);
     } else if (!INIT && blockIdx.x == 0) {
-        tables_and_alpha(false);  // (an empty first slot still reports alpha)
+        tables_and_alpha();  // (an empty first slot still reports alpha)
     }
     // (one reduction of all the sums behind a single pair of LDS-only barriers was measured here: inside the noise,
     // profiles/r16_walk_launch_constant.txt.  Not kept.)
@@ -1077,16 +1024,14 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_sweep_kernel(CsrView A, Spmv
 // FIRST: the first direction of a solve whose start launch was the INIT walk above: p' = z (nothing is
 // read from p, beta does not exist yet), the partial sums of p'.(A p'), CgState untouched.
 // ---------------------------------------------------------------------------------------------------
-// SCHWZ_DD (build-time switch, tools/dd_ab.sh; round 3): bit 0 p' leaves with non-temporal stores; bit 1 the halo
-// of a position is requested THREE positions ahead, i.e. in the same step in which the neighbouring band
-// requests the same lines as its own window (a third halo slot in LDS); bit 2 the own r lines are plain loads
-// (they are the neighbouring band's halo: a non-temporal load marks them for early eviction).  Before, the halo
-// was asked for two steps after the neighbour had fetched the lines -- longer than a line lives in the 4 MiB L2
-// at this stream rate -- and the PMC traffic of the launch was 1.17 x (256-wide planes) / 1.25 x (512-wide) its
-// bytes: exactly the halo, fetched twice.  All three together, in-box (profiles/r03_dd_ab.txt): launch 0.0789 ->
-// 0.0740 ms on the cube, 0.0861 -> 0.0729 ms on the 512 x 512 x 64 slab (0.585 -> 0.69 of peak; the step
-// 1.95 -> 1.82 ms), the same bits.  0 restores the round-2 schedule.
-// (default: 7, set in coding_plan.hpp together with the halo-line count kDirdotHaloLines that follows from it)
+// Halo schedule and streams (profiles/r03_dd_ab.txt).  The halo of a position is requested THREE positions ahead, i.e.
+// in the same step in which the neighbouring band requests the same lines as its own window (hence the third halo slot
+// in LDS, kDirdotHaloLines); the own r lines are plain loads (they are the neighbouring band's halo: a non-temporal
+// load marks them for early eviction); p' leaves with non-temporal stores.  Asked for two steps after the neighbour had
+// fetched the lines -- longer than a line lives in the 4 MiB L2 at this stream rate -- the halo was fetched twice: the
+// PMC traffic of the launch was 1.17 x (256-wide planes) / 1.25 x (512-wide) its bytes.  All three together, in-box:
+// launch 0.0789 -> 0.0740 ms on the cube, 0.0861 -> 0.0729 ms on the 512 x 512 x 64 slab (0.585 -> 0.69 of peak; the
+// step 1.95 -> 1.82 ms), the same bits.
 template <int NHL, int NH, bool FIRST = false, int RUNS = 8>
 __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView A, SpmvArgs a)
 {
@@ -1095,18 +1040,12 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     constexpr int T = NH * kPairRows;
     const int NX = A.sweep_nx;
     double *const own_ring = reinterpret_cast<double *>(sweep_lds);  // p' of four chain positions [4][T]
-    constexpr int kHaloSlots = (SCHWZ_DD & 2) ? 3 : 2;
-    double *const halo_ring = own_ring + 4 * T;                       // p' of the NX rows above the band [kHaloSlots][NX]
-    PairVal *const cpv = reinterpret_cast<PairVal *>(halo_ring + kHaloSlots * NX);
-    int *const cmask = reinterpret_cast<int *>(cpv + A.canon_npat * 5);
+    double *const halo_ring = own_ring + 4 * T;                       // p' of the NX rows above the band [kDirdotHaloLines][NX]
+    PairVal *const cpv = reinterpret_cast<PairVal *>(halo_ring + kDirdotHaloLines * NX);
+    const int ntab = A.canon_npat * 5;  // entries of the slot tables
     __shared__ double red[8];
     [[maybe_unused]] constexpr int kForm = FIRST ? kFormFirst : kFormDirdot;
     SCHWZ_STAMP(kForm, kStampEntry);
-    constexpr bool kPro2 = (SCHWZ_WALK_PRO & 4) != 0;            // as in the update walk
-    constexpr bool kReady = kPro2 && SCHWZ_WALK_ZEROCOEF != 0;
-    // (FIRST reads nothing of CgState: with init_fold its own workgroup 0 is still to write it.  After a zero start
-    // residual the launch is needless; the update launch behind it sees stop_iter == 0 and leaves.)
-    if (!kPro2 && !FIRST && a.it >= a.cg_state->stop_iter) return;
     double cg_rho_new = 0.0, cg_rr = 0.0, cg_beta = 0.0;
     const int tid = threadIdx.x;
     // FIRST, workgroup 0: CgState and the check norm from the start walk's partial sums, which the kernel boundary
@@ -1116,16 +1055,9 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             cg_init_state(const_cast<CgState *>(a.cg_state), a.pq_partials, a.pq_nparts, a.cg_rtol, a.norm_sq_out,
                           a.norm_bank, red);
     };
-    // the slot tables and beta (folded from the previous launch's partial sums by every workgroup): fetched after
-    // the first windows have been requested, like in the update walk above
-    // (SCHWZ_WALK_PRO bit 0, as in the update walk: `early` at kernel entry, `late` behind the window requests, where
-    // the two folds share one pair of LDS-only barriers)
-    constexpr bool kEarly = (SCHWZ_WALK_PRO & 1) != 0;
     double fold_rho = 0.0, fold_rr = 0.0, rho_it = 0.0;
-    // (kReady) the lane's table entries between their request and their LDS stores: rounds of kBlock entries, a round
-    // that exists is loaded by every lane (the lanes past the table's end repeat its last entry and store nothing)
+    // the lane's table entries between their request and their LDS stores (as in the update walk)
     pvd2 tab[kWalkSymTabPerLane];
-    const int ntab = A.canon_npat * 5;
     auto request_tables = [&]() {
 #pragma unroll
         for (int k = 0; k < kWalkSymTabPerLane; ++k) {
@@ -1138,18 +1070,16 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         for (int k = 0; k < kWalkSymTabPerLane; ++k)
             if (tid + k * kBlock < ntab) cpv[tid + k * kBlock] = PairVal{tab[k].x, tab[k].y};
     };
-    auto stage_tables = [&]() {
-        for (int i = tid; i < A.canon_npat * 5; i += kBlock) {
-            if (SCHWZ_WALK_ZEROCOEF) {
-                const int m = A.canon_sym_mask[i / 5], k = i % 5;
-                cpv[i] = PairVal{((m >> k) & 1) ? A.canon_sym_val[2 * i] : 0.0, ((m >> (16 + k)) & 1) ? A.canon_sym_val[2 * i + 1] : 0.0};
-            } else {
-                cpv[i] = PairVal{A.canon_sym_val[2 * i], A.canon_sym_val[2 * i + 1]};
-            }
-        }
-        if (tid < A.canon_npat) cmask[tid] = A.canon_sym_mask[tid];
-    };
-    // (kPro2) the slot's record, through the constant address space: scalar loads
+    // Prologue, step 1 (as in the update walk): requests only, in front of the first wait.
+    // (FIRST reads nothing of CgState: with init_fold its own workgroup 0 is still to write it.  After a zero start
+    // residual the launch is needless; the update launch behind it sees stop_iter == 0 and leaves.)
+    int stop_iter = 0;
+    if (!FIRST) {
+        stop_iter = a.cg_state->stop_iter;
+        rho_it = a.cg_state->rho[a.it & 1];
+    }
+    // the slot's record -- the segment and the planes of its chain positions z0 - 1 .. z0 + 3 -- through the constant
+    // address space: scalar loads (of its own table: the band height may differ from the update launch's)
     typedef const WalkRecord __attribute__((address_space(4))) *const_record;
     int4 sg;
     int rec_plane[5] = {0, 0, 0, 0, 0};
@@ -1159,59 +1089,32 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
 #pragma unroll
         for (int k = 0; k < 5; ++k) rec_plane[k] = rec->plane[k];
     };
-    auto tables_and_beta = [&](bool early) {
-        if (kEarly && early) {
-            if (!FIRST) rho_it = a.cg_state->rho[a.it & 1];
-            if (kPro2) {
-                request_record();
-                asm volatile("" ::"s"(a.pq_partials), "s"(a.pq_nparts), "s"(A.canon_sym_ready), "s"(ntab) : "memory");  // (as in the update walk)
-            }
-            if (kReady) request_tables();  // (before the sums, as in the update walk)
-            if (!FIRST) {
-                if (SCHWZ_WALK_PRO & 2) {
-                    double s[2] = {0.0, 0.0};
-                    fold_lane_sums(a.pq_partials, a.pq_nparts, s);
-                    fold_rho = s[0];
-                    fold_rr = s[1];
-                } else {
-                    for (int i = tid; i < a.pq_nparts; i += kBlock) {  // fold_partials' sums of both banks
-                        fold_rho += a.pq_partials[i];
-                        fold_rr += a.pq_partials[a.pq_nparts + i];
-                    }
-                }
-            }
-            if (!kReady) stage_tables();
-            return;
-        }
-        if (!kEarly) stage_tables();
-        if (kReady) store_tables();
+    request_record();
+    asm volatile("" ::"s"(a.pq_partials), "s"(a.pq_nparts), "s"(A.canon_sym_ready), "s"(ntab) : "memory");  // (as in the update walk)
+    request_tables();  // (before the sums, as in the update walk)
+    if (!FIRST) {
+        double s[2] = {0.0, 0.0};
+        fold_lane_sums(a.pq_partials, a.pq_nparts, s);
+        fold_rho = s[0];
+        fold_rr = s[1];
+    }
+    if (!FIRST && a.it >= stop_iter) return;
+    // Prologue, step 2, behind the window requests: tables to LDS, the two cross-wave folds behind one pair of LDS-only
+    // barriers, beta.  (The captures are named -- what the step reads, then what it writes -- and keep this order: the
+    // compiler's output follows it, down to the order of two assembler comments; profiles/r25_walk_forms.txt.)
+    auto tables_and_beta = [&rho_it, &store_tables, &fold_rho, &fold_rr, &cg_rho_new, &cg_rr, &cg_beta, &init_fold]() {
+        store_tables();
         if (!FIRST) {
-            if (kEarly) {
-                double v[2] = {fold_rho, fold_rr};
-                block_sum_lds(v, red);
-                cg_rho_new = v[0];
-                cg_rr = v[1];
-                cg_beta = cg_rho_new / rho_it;
-            } else {
-                cg_rho_new = fold_partials(a.pq_partials, a.pq_nparts, red);
-                cg_rr = fold_partials(a.pq_partials + a.pq_nparts, a.pq_nparts, red);
-                cg_beta = cg_rho_new / a.cg_state->rho[a.it & 1];
-            }
+            double v[2] = {fold_rho, fold_rr};
+            block_sum_lds(v, red);
+            cg_rho_new = v[0];
+            cg_rr = v[1];
+            cg_beta = cg_rho_new / rho_it;
         }
         init_fold();
         lds_barrier();
     };
-    if (kPro2) {
-        // requests only, in front of the first wait (as in the update walk)
-        int stop_iter = 0;
-        if (!FIRST) stop_iter = a.cg_state->stop_iter;
-        tables_and_beta(true);
-        if (!FIRST && a.it >= stop_iter) return;
-    }
-    if (blockIdx.x == 0)
-        for (int i = (int)gridDim.x + a.part_offset + tid; i < a.part_stride; i += kBlock)
-            a.partials[i] = a.partials[a.part_stride + i] = 0.0;
-    if (!kPro2) sg = A.sweep_seg_dir[blockIdx.x];  // (its own table: the band height may differ from the update launch's)
+    zero_unused_partials<2>(a);
     const int64_t PL = A.sweep_pl;
     const int band = sg.x, z0 = sg.y, z1 = sg.z;
     constexpr bool GEN = RUNS == 0;          // planes that are not whole chunks: byte ids, partial last band (see above)
@@ -1221,7 +1124,6 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     double acc0 = 0.0;
     typedef const unsigned __attribute__((address_space(4))) *const_words;
     typedef const int __attribute__((address_space(4))) *const_ints;
-    if (!kPro2 && kEarly && (z0 < z1 || (!FIRST && blockIdx.x == 0))) tables_and_beta(true);
     if (z0 < z1) {
         const const_ints chain = (const_ints)(uintptr_t)A.chain_plane;
         const const_ints chain_far = (const_ints)(uintptr_t)A.chain_far;
@@ -1229,7 +1131,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             const int k = chain[z];
             return (k < 0 ? 0 : k) * (int)PL + band * T;
         };
-        auto clampg = [&](int g) -> int { return g < 0 ? 0 : (g > (int)gmax ? (int)gmax : g); };
+        auto clampg = [&](int g) -> int { return clamp_piece(g, gmax); };
         // p' at one 16-byte piece: the expression of dir2 / cg_direction_kernel
         const pvd2 p_scale = {a.p_scale, a.p_scale};  // 1.0 except where a.x is r0 and p0 = p_scale x r0 (virtual p0)
         auto newp = [&](pvd2 rv, pvd2 pv) -> pvd2 {
@@ -1253,10 +1155,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
 #pragma unroll
             for (int k = 0; k < NH; ++k) {
                 const int g = clampg(base + 2 * piece_of(k));
-                if (SCHWZ_DD & 4)
-                    o.r[k] = *reinterpret_cast<const pvd2 *>(a.cg_r + g);
-                else
-                    o.r[k] = __builtin_nontemporal_load(reinterpret_cast<const pvd2 *>(a.cg_r + g));
+                o.r[k] = *reinterpret_cast<const pvd2 *>(a.cg_r + g);  // (plain: the neighbouring band's halo)
                 if (FIRST)
                     o.p[k] = o.r[k];
                 else
@@ -1271,12 +1170,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             for (int k = 0; k < NH; ++k) {
                 const pvd2 v = newp(o.r[k], o.p[k]);
                 *reinterpret_cast<pvd2 *>(slot_p + 2 * (tid + k * kBlock)) = v;
-                if (out && a.y) {  // (a.y == nullptr: a direction nobody reads from memory -- windows and sums only)
-                    if ((SCHWZ_DD & 1) && SCHWZ_WALK_HINTS)
-                        __builtin_nontemporal_store(v, reinterpret_cast<pvd2 *>(a.y + base + 2 * piece_of(k)));
-                    else
-                        __builtin_memcpy(a.y + base + 2 * piece_of(k), &v, 16);
-                }
+                // (a.y == nullptr: a direction nobody reads from memory -- windows and sums only)
+                if (out && a.y) __builtin_nontemporal_store(v, reinterpret_cast<pvd2 *>(a.y + base + 2 * piece_of(k)));
             }
         };
         auto load_halo = [&](int base, Halo &hh) {
@@ -1292,7 +1187,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
                     __builtin_memcpy(&hh.p[k], a.x + g, 16);
             }
         };
-        // (with three slots the slot of a position is passed in: position modulo 3, kept incrementally)
+        // (the slot of a position is passed in: position modulo 3, kept incrementally)
         auto store_halo = [&](int hslot, const Halo &hh) {
             double *slot_p = halo_ring + (size_t)hslot * NX;
 #pragma unroll
@@ -1321,7 +1216,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         int brow[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k)
-            brow[k] = kPro2 ? (rec_plane[k] < 0 ? 0 : rec_plane[k]) * (int)PL + band * T : band_row(z0 - 1 + k);
+            brow[k] = (rec_plane[k] < 0 ? 0 : rec_plane[k]) * (int)PL + band * T;  // band_row(z0 - 1 + k), from the record
         SCHWZ_STAMP_AFTER(brow[0] + brow[1] + brow[2] + brow[3] + brow[4]);
         SCHWZ_STAMP(kForm, kStampSegment);
         SCHWZ_STAMP_POSITIONS(z1 - z0);
@@ -1331,19 +1226,17 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             Halo h0;
             load_own(brow[0], before);
             load_own(brow[1], first);
-            load_halo(brow[1], (SCHWZ_DD & 2) ? h0 : hreg);
+            load_halo(brow[1], h0);
             load_own(brow[2], own_b);
             load_own(brow[3], own_a);
-            if (SCHWZ_DD & 2) {
-                // halo of the first position goes to its slot now; the next two stay in flight like the own windows
-                load_halo(brow[2], hreg);    // position z0 + 1
-                load_halo(brow[3], hreg_b);  // position z0 + 2
-            }
+            // halo of the first position goes to its slot now; the next two stay in flight like the own windows
+            load_halo(brow[2], hreg);    // position z0 + 1
+            load_halo(brow[3], hreg_b);  // position z0 + 2
             SCHWZ_STAMP_LANDED();
             SCHWZ_STAMP(kForm, kStampWindows);
-            tables_and_beta(false);
+            tables_and_beta();
             SCHWZ_STAMP(kForm, kStampTables);
-            if (SCHWZ_DD & 2) store_halo(0, h0);
+            store_halo(0, h0);
             store_own(z0 - 1, brow[0], before, false);
             store_own(z0, brow[1], first, true);
         }
@@ -1352,29 +1245,22 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
             rle_a[h] = fetch_rle(brow[1], h);
             rle_b[h] = fetch_rle(z0 + 1 < z1 ? brow[2] : brow[1], h);
         }
-        int hs = 0;  // halo slot of the position being computed (three-slot form)
-        // one position: `own_next` holds r, p of position z + 1 on entry and of position z + 3 on exit; in the
-        // three-slot form `hal_next` holds the halo of position z + 1 on entry and of position z + 3 on exit
+        int hs = 0;  // halo slot of the position being computed
+        // one position: `own_next` holds r, p of position z + 1 on entry and of position z + 3 on exit, `hal_next`
+        // the halo of position z + 1 on entry and of position z + 3 on exit
         auto step = [&](int z, Own &own_next, Rle (&rl)[NH], Halo &hal_next) {
             store_own(z + 1, brow[2], own_next, z + 1 < z1);
             const int hs_next = hs == 2 ? 0 : hs + 1;
-            if (SCHWZ_DD & 2)
-                store_halo(hs_next, hal_next);
-            else
-                store_halo(z & 1, hreg);
+            store_halo(hs_next, hal_next);
             lds_barrier();
-            if (SCHWZ_DD & 2)
-                load_halo(brow[4], hal_next);
-            else
-                load_halo(brow[2], hreg);
+            load_halo(brow[4], hal_next);
             load_own(brow[4], own_next);
             const int far = chain_far[z];
             const double *cur = own_ring + (size_t)(z & 3) * T;
             const double *prv = own_ring + (size_t)((z + 3) & 3) * T;
             const double *nxt = own_ring + (size_t)((z + 1) & 3) * T;
-            const double *hup = halo_ring + (size_t)((SCHWZ_DD & 2) ? hs : (z & 1)) * NX;
-            const double *fa0 = ((far >> 4) & 3) == 1 ? prv : (((far >> 4) & 3) == 2 ? nxt : cur);
-            const double *fa1 = ((far >> 6) & 3) == 1 ? prv : (((far >> 6) & 3) == 2 ? nxt : cur);
+            const double *hup = halo_ring + (size_t)hs * NX;
+            const double *fa0 = far_window(far >> 4, prv, nxt, cur), *fa1 = far_window(far >> 6, prv, nxt, cur);
             const int rbase = z + 2 < z1 ? brow[3] : brow[1];
 #pragma unroll
             for (int h = 0; h < NH; ++h) {
@@ -1388,7 +1274,6 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
                     const unsigned e = (f.w[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
                     if ((unsigned)tid >= (e & 0xffu)) pid = (int)(e >> 8);
                 }
-                const int mask = SCHWZ_WALK_ZEROCOEF ? 0 : cmask[pid];
                 pvd2 t[4];
                 t[0] = *reinterpret_cast<const pvd2 *>(cur + i0);
                 t[1].x = t[0].y;
@@ -1399,13 +1284,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
                 auto add = [&](int k, pvd2 tv) {
                     const PairVal v = cpv[pid * 5 + k];
                     const double p0 = v.a * tv.x, p1 = v.b * tv.y;
-                    if (SCHWZ_WALK_ZEROCOEF) {
-                        s0 += p0;
-                        s1 += p1;
-                    } else {
-                        s0 += ((mask >> k) & 1) ? p0 : 0.0;
-                        s1 += ((mask >> (16 + k)) & 1) ? p1 : 0.0;
-                    }
+                    s0 += p0;
+                    s1 += p1;
                 };
 #pragma unroll
                 for (int k = 0; k < 4; ++k) add(k, t[k]);
@@ -1434,7 +1314,7 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
         if (z < z1) step(z, own_b, rle_a, hreg);
         SCHWZ_STAMP(kForm, kStampLastStep);
     } else if (!FIRST && blockIdx.x == 0) {
-        tables_and_beta(false);  // (an empty first slot still advances the CG state below)
+        tables_and_beta();  // (an empty first slot still advances the CG state below)
     } else {
         init_fold();  // (... or initialises it)
     }
@@ -1445,12 +1325,8 @@ __global__ __launch_bounds__(kBlock) void spmv_pair_dirdot_sweep_kernel(CsrView 
     }
     SCHWZ_STAMP(kForm, kStampDone);
     if (!FIRST && blockIdx.x == 0 && tid == 0) {
-        // what cg_direction_kernel's workgroup 0 does (see the chunk-by-chunk kernel's epilogue)
-        CgState *st = const_cast<CgState *>(a.cg_state);
-        st->rho[(a.it + 1) & 1] = cg_rho_new;
-        st->rr = cg_rr;
-        st->iters = st->iters + 1;
-        if (sqrt(cg_rr) <= a.cg_rtol * st->r0) st->stop_iter = 0;
+        // what cg_direction_kernel's workgroup 0 does
+        cg_advance_state(const_cast<CgState *>(a.cg_state), a.it, cg_rho_new, cg_rr, a.cg_rtol);
     }
 }
 
@@ -1476,7 +1352,7 @@ bool pair_sweep_update_ok(const CsrView &A, int grid, int diag_mode)
 bool pair_sweep_dirdot_ok(const CsrView &A, int grid, int diag_mode)
 {
     const int nh = A.sweep_T_dir / kPairRows, nhl = (A.sweep_nx / 2 + kBlock - 1) / kBlock;
-    return pair_sweep_update_ok(A, grid, diag_mode) && A.canon_sym_val && diag_mode != 1 &&
+    return pair_sweep_update_ok(A, grid, diag_mode) && A.canon_sym_ready && diag_mode != 1 &&
            A.sweep_nslots_dir + A.sweep_gen_blocks <= grid && (nh == 1 || nh == 2 || nh == 4) && nhl <= 2 &&
            sweep_dirdot_lds(A.sweep_T_dir, A.sweep_nx, A.canon_npat, kDirdotHaloLines) <= kSweepLdsLimit;
 }
@@ -1634,12 +1510,11 @@ int launch_spmv_pair(const CsrView &A, int mode, const SpmvArgs &a, int grid, hi
             set_error("launch_spmv_pair: the z-sweep first-direction launch does not apply to this matrix");
             return SCHWZ_ERR_INVALID;
         }
-        // (the kernel reads its segments from sweep_seg_dir: this launch gets a view whose direction table IS the
+        // (the kernel reads its records from sweep_rec_dir: this launch gets a view whose direction table IS the
         // first-direction table)
         CsrView Af = A;
-        if (A.sweep_seg_first && A.sweep_nslots_first <= grid) {
+        if (A.sweep_rec_first && A.sweep_nslots_first <= grid) {
             Af.sweep_T_dir = A.sweep_T_first;
-            Af.sweep_seg_dir = A.sweep_seg_first;
             Af.sweep_rec_dir = A.sweep_rec_first;
             Af.sweep_nslots_dir = A.sweep_nslots_first;
         }
@@ -1754,7 +1629,7 @@ static void bind_pair(schwz_csr *A, const PairPlan &P)
     A->pair_code_bytes = P.code_bytes;
 }
 
-// ... the z-sweep walk's; a launch without a segment table of its own reads the table before it
+// ... the z-sweep walk's; a launch without records of its own reads the table before it
 static void bind_walk(schwz_csr *A, const WalkPlan &W)
 {
     CsrView &v = A->v;
@@ -1766,19 +1641,12 @@ static void bind_walk(schwz_csr *A, const WalkPlan &W)
     v.sweep_nslots = W.nslots();
     v.sweep_ngen = (int)W.gen.size();
     v.sweep_gen_blocks = W.gen_blocks;
-    v.sweep_seg = b.seg.as<int4>();
     v.sweep_gen = b.gen.as<schwz_idx>();
     v.sweep_T_dir = W.T_dir;
     v.sweep_nslots_dir = W.nslots_dir();
-    v.sweep_seg_dir = b.seg_dir.p ? b.seg_dir.as<int4>() : v.sweep_seg;
     v.sweep_T_first = W.T_first;
     v.sweep_nslots_first = W.nslots_first();
-    v.sweep_seg_first = b.seg_first.p ? b.seg_first.as<int4>() : v.sweep_seg_dir;
-    v.canon_val = b.canon_val.as<double>();
-    v.canon_mask = b.canon_mask.as<int>();
     v.canon_npat = W.npat;
-    v.canon_sym_val = b.canon_sym_val.as<double>();
-    v.canon_sym_mask = b.canon_sym_mask.as<int>();
     v.chain_plane = b.chain_plane.as<int>();
     v.chain_far = b.chain_far.as<int>();
     v.sweep_rec = b.rec.as<WalkRecord>();
@@ -1805,13 +1673,10 @@ static int upload_walk(schwz_csr *A, const WalkPlan &W)
     if (!W.built()) return SCHWZ_OK;
     auto &b = A->coding.walk;
     int rc = SCHWZ_OK;
-    if ((!W.seg_dir.empty() && (rc = b.seg_dir.put(W.seg_dir))) || (!W.seg_first.empty() && (rc = b.seg_first.put(W.seg_first))) ||
-        (rc = b.seg.put(W.seg)) || (rc = b.gen.put(W.gen)) || (rc = b.canon_val.put(W.canon_val)) ||
-        (rc = b.canon_mask.put(W.canon_mask)) || (rc = b.chain_plane.put(W.chain_plane)) ||
-        (rc = b.chain_far.put(W.chain_far)) ||
-        (!W.canon_sym_val.empty() && ((rc = b.canon_sym_val.put(W.canon_sym_val)) || (rc = b.canon_sym_mask.put(W.canon_sym_mask)))))
+    // what the kernels read: the companion's chunk list, the chains, and at entry the records and the ready tables
+    // (the plan's segment tables, values and masks, from which those are derived, stay on the host)
+    if ((rc = b.gen.put(W.gen)) || (rc = b.chain_plane.put(W.chain_plane)) || (rc = b.chain_far.put(W.chain_far)))
         return rc;
-    // the records and ready tables the kernels read at entry (every build uploads them; SCHWZ_WALK_PRO bit 2 reads them)
     if ((!W.rec_dir.empty() && (rc = b.rec_dir.put(W.rec_dir))) || (!W.rec_first.empty() && (rc = b.rec_first.put(W.rec_first))) ||
         (rc = b.rec.put(W.rec)) || (rc = b.canon_ready.put(W.canon_ready)) ||
         (!W.canon_sym_ready.empty() && (rc = b.canon_sym_ready.put(W.canon_sym_ready))))

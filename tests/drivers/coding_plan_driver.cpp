@@ -276,10 +276,10 @@ int main(int argc, char **argv)
 
     const CodingOptions opt = coding_options_from_env();
     const HostCsr M{nrows, nrows, A.rp.data(), A.col.data(), A.val.data(), tiles};
-    // The driver always plans with the halo lines of the DEFAULT SCHWZ_DD (coding_plan.hpp), whatever variant
-    // libraries exist: tests/golden/coding_plan_parent.json was recorded from a default build.  Whoever changes the
-    // default moves the direction tables the record pins, and has to record it anew.
-    static_assert(kDirdotHaloLines == 3, "the recorded plans assume the default SCHWZ_DD (bit 1 set: 3 halo lines)");
+    // The driver plans with the halo lines of the fused direction walk (coding_plan.hpp):
+    // tests/golden/coding_plan_parent.json was recorded with three.  Whoever changes the number moves the direction
+    // tables the record pins, and has to record it anew.
+    static_assert(kDirdotHaloLines == 3, "the recorded plans assume the three halo lines of the fused direction walk");
     const int grid = walk_grid(ntl), halo_lines = kDirdotHaloLines;
     // the plans in the order, and under the conditions, of build_spmv_dict / build_spmv_pair
     PatternPlan pat = plan_patterns(opt, M);

@@ -1,4 +1,4 @@
-"""The z-sweep walks' entry (spmv_pair.hip, SCHWZ_WALK_PRO bit 2): stop_iter, the slot's record -- segment and first
+"""The z-sweep walks' entry (spmv_pair.hip, step 1 of the prologue): stop_iter, the slot's record -- segment and first
 five chain rows --, rho, the lane sums and the table entries in their staged form are requested before anything is
 waited for, the early return and the empty-slot branch follow that wait, and the tables reach LDS behind the window
 requests.  A record with a wrong plane moves a whole window, a table entry that lost its value or kept one it should

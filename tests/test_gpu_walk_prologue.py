@@ -1,4 +1,4 @@
-"""What a z-sweep walk workgroup does before its first and after its last step (spmv_pair.hip, SCHWZ_WALK_PRO): the
+"""What a z-sweep walk workgroup does before its first and after its last step (spmv_pair.hip, "Prologue"): the
 fold of the previous launch's partial sums -- alpha in the update walk, rho and beta in the fused direction walk --
 taken in two parts around the window requests, and the reductions of the epilogue behind one pair of barriers.  alpha
 and beta feed every row of every later iterate, so a fold that dropped, doubled or misplaced a partial sum shows in x.

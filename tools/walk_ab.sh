@@ -1,10 +1,11 @@
 #!/bin/bash
-# In-box A/B of library builds (make variant NAME=.. DEFS=..): cube, 512 x 512 x 64 slab, optionally the configs[4] slab.
-#   LIBS="libschwz_hip.so libschwz_hip_zc0.so" SHAPES="cube slab" bash tools/walk_ab.sh
+# In-box A/B of library builds under schwarz-lib_amd/lib (another checkout's library copied there, or make variant
+# NAME=.. DEFS=..): cube, 512 x 512 x 64 slab, optionally the configs[4] slab.
+#   LIBS="libschwz_hip.so libschwz_hip_parent.so" SHAPES="cube slab" bash tools/walk_ab.sh
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/walk_ab.txt
 : > $OUT
-LIBS=${LIBS:-"libschwz_hip.so libschwz_hip_zc0.so libschwz_hip.so libschwz_hip_zc0.so"}
+LIBS=${LIBS:-"libschwz_hip.so libschwz_hip_parent.so libschwz_hip.so libschwz_hip_parent.so"}
 for shape in ${SHAPES:-cube slab}; do
     case $shape in cube) ARGS="";; slab) ARGS="--strong 512,512,64";; wide) ARGS="--strong 1024,1024,16";; c5) ARGS="--strong 1024,1024,128";; *) ARGS="--size $shape";; esac
     for LE in $LIBS; do
