@@ -321,6 +321,44 @@ int schwz_cheb_solve(schwz_cheb *s, const double *d_b, double *d_x, double rtol,
 /* iterations and residual norm of the last solve (device synchronisation) */
 int schwz_cheb_last_stats(schwz_cheb *s, int *h_iters, double *h_resnorm);
 
+/* ---- Block vectors: K right-hand sides against one matrix (an extension: the reference solves one system, so no
+ * line of it is replaced; csrc/batch.hip).  A block vector of n rows and k columns is stored row-interleaved, element
+ * (i, j) at i * k + j, k = 2, 4 or 8 -- any other k: SCHWZ_ERR_INVALID, checked before anything else.  The kernels
+ * read plain CSR, whatever coding the upload chose for the single-vector path: values and columns come from HBM once
+ * per tile, independent of k, and every row sum runs in CSR order without contraction, so column j of a result
+ * depends on column j of the operands alone, bit for bit.  All entry points obey `stream`.
+ *
+ * schwz_csr_spmm: Y = alpha A X + beta Y (beta == 0: Y is not read).  X holds ncols * k values, Y nrows * k.
+ *
+ * schwz_bcg: k independent CG recurrences that share the matrix pass, fp64, precond SCHWZ_PRECOND_NONE or
+ * SCHWZ_PRECOND_JACOBI (another known code: SCHWZ_ERR_NOT_IMPLEMENTED; an unknown one, a null `out`, a matrix that is
+ * not square: SCHWZ_ERR_INVALID; with Jacobi a row without a positive finite diagonal entry: SCHWZ_ERR_NOT_SPD).
+ * alpha_j, beta_j and the freeze mask stay on the device; an iteration is three launches (Q = A P with the partial
+ * sums of p.q; the update of x and r; the direction), and every reduction is a set of per-workgroup partial sums the
+ * next launch folds in a fixed order.
+ * solve: X is the warm start on entry.  Column j is FROZEN -- its x_j and r_j stop changing, bit for bit -- once
+ * ||r_j|| <= rtol ||r_0,j|| (the loop-top test of schwz_pcg_solve, per column), where r_0,j = 0, p_j.q_j = 0 or
+ * r_j.z_j = 0 would be divided by (a zero column stays exactly zero), and from the first launch on where bit j of
+ * `frozen` is set (bits >= k: SCHWZ_ERR_INVALID).  rtol <= 0: exactly max_iters iterations are launched, the host
+ * polls nothing.  rtol > 0: the solve ends when every column is frozen or at max_iters; the host polls the pinned copy
+ * of the state one chunk of launches behind, as schwz_cheb_solve does, and launches past the stop return at once.
+ * h_iters / h_resnorm (k values each; may be NULL) are the updates applied to each column and the recurred residual
+ * norms, written behind a synchronisation of `stream` only when asked for; schwz_bcg_last_stats reports the same at
+ * any later time (device synchronisation).
+ * schwz_bcg_residual: h_norm_sq[j] = ||b_j - A x_j||^2 (k values; waits for `stream`), and R = B - A X stored to d_r
+ * where d_r is not NULL (NULL: the norm-only form, nothing stored).  Uses the solver's scratch: not beside a solve of
+ * the same object on another stream. */
+typedef struct schwz_bcg schwz_bcg;
+int schwz_csr_spmm(const schwz_csr *A, int k, double alpha, const double *d_x, double beta, double *d_y,
+                   schwz_stream stream);
+int schwz_bcg_create(const schwz_csr *A, int precond, int k, schwz_bcg **out);
+void schwz_bcg_destroy(schwz_bcg *s);
+int schwz_bcg_solve(schwz_bcg *s, const double *d_b, double *d_x, double rtol, int max_iters, unsigned frozen,
+                    int *h_iters, double *h_resnorm, schwz_stream stream);
+int schwz_bcg_last_stats(schwz_bcg *s, int *h_iters, double *h_resnorm);
+int schwz_bcg_residual(schwz_bcg *s, const double *d_b, const double *d_x, double *d_r, double *h_norm_sq,
+                       schwz_stream stream);
+
 /* Profiling hooks for bench.py's roofline leg: between begin and end, every
  * launch of the dominant kernel (the CSR SpMV inside schwz_pcg_solve) is
  * bracketed by a HIP event pair on its launch stream; end synchronises and
@@ -820,7 +858,8 @@ int schwz_ras_coarse_apply(schwz_subdomain *sd, schwz_coarse *c, schwz_stream st
  * and 2 again.  keep_x = 1: every vector keeps its values, x~ halos included, so the next solve starts from the last
  * iterate; only what refers to the old b goes: the solvers' memory as above and b~ (= b again; the next
  * schwz_ras_update_boundary rewrites its overlap rows).  Another value of keep_x: SCHWZ_ERR_INVALID.
- * Not offered: new matrix values on the old pattern, several right-hand sides in one batched solve, a start vector
+ * Not offered: new matrix values on the old pattern, several right-hand sides in one batched solve (the block entry
+ * points further down do that, on a state of their own), a start vector
  * other than zero or the kept one (write through the pointers of schwz_ras_vector at your own risk). */
 int schwz_ras_rhs_set(schwz_subdomain *sd, const double *rhs, int on_device, schwz_stream stream);
 int schwz_ras_rhs_index(schwz_subdomain *sd, const int64_t *h_index);
@@ -829,6 +868,43 @@ int schwz_ras_rhs_aggregate(schwz_subdomain *sd, schwz_stream stream);
 int schwz_ras_rhs_norm_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 int schwz_ras_rhs_norm_sq_local(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 int schwz_ras_restart(schwz_subdomain *sd, int keep_x, schwz_stream stream);
+
+/* ---- The steps of a RAS iteration on block vectors (an extension, see "Block vectors" above: the reference solves
+ * one system, so no line of it is replaced).  schwz_ras_batch_begin allocates the block state of a subdomain that is on
+ * the device: x~ [interior | overlap | halo], b, b~ and y with k columns each, row-interleaved, all zero, and a schwz_bcg
+ * on the local matrix.  It is separate from the single-vector state: these calls read the local matrix, the interface
+ * rows and the index lists, and write nothing the other entry points read or write, so a single-vector run before or
+ * after computes what it computes without them.  begin with the k the state already has keeps it; another k replaces
+ * it; schwz_ras_batch_end (and schwz_subdomain_destroy) releases it.
+ * k other than 2, 4, 8: SCHWZ_ERR_INVALID (checked first).  The block path exists for the fp64 CG local solve of a
+ * symmetric matrix without a preconditioner or with scalar Jacobi (block-Jacobi of block size 1 included) on one level;
+ * a direct or non-symmetric local solver, another preconditioner, the ParILU options, the fp32 or Chebyshev local
+ * solve and a subdomain with aggregates: SCHWZ_ERR_NOT_IMPLEMENTED.  Every other call: SCHWZ_ERR_INVALID without a
+ * block state.  All obey `stream`; those that hand values to the host wait for it.
+ * rhs_set: h_rhs holds local_size_x * k values, [interior; overlap rows] with the columns innermost (host memory; the
+ * copy is waited for); x~ and y go back to zero and b~ = b: the state of a fresh upload.
+ * pack / unpack: the send and receive buffers are [neighbour][entry][column]: the layouts of schwz_ras_pack /
+ * schwz_ras_unpack with k values per entry.
+ * update_boundary: b~ = b - A_Gamma x~ on the overlap rows, per column, the row sum in CSR order.
+ * local_residual: h_resnorm[j] = ||b~_j - A x~_j||_2 over the local_size_x rows (k values).
+ * local_solve: A y_j = b~_j by schwz_bcg_solve from the last y, with the subdomain's local tolerance and iteration cap;
+ * the columns named by `frozen` are left alone.  h_inner_iters: k counts (waits for `stream`), or NULL.
+ * restrict: x~[interior] = y[interior] in the columns `frozen` does not name.
+ * vector: 0 x~ (len (local_size_x + halo) * k), 1 b~, 2 y, 3 b (len local_size_x * k).
+ * get_interior: local_size * k values of x~ to the host.  true_residual_sq: h_out[j] = sum over the interior rows of
+ * (b_j - A x~_j)^2 (k values). */
+int schwz_ras_batch_begin(schwz_subdomain *sd, int k);
+int schwz_ras_batch_end(schwz_subdomain *sd);
+int schwz_ras_batch_rhs_set(schwz_subdomain *sd, const double *h_rhs, schwz_stream stream);
+int schwz_ras_batch_pack(schwz_subdomain *sd, double *d_send, schwz_stream stream);
+int schwz_ras_batch_unpack(schwz_subdomain *sd, const double *d_recv, schwz_stream stream);
+int schwz_ras_batch_update_boundary(schwz_subdomain *sd, schwz_stream stream);
+int schwz_ras_batch_local_residual(schwz_subdomain *sd, double *h_resnorm, schwz_stream stream);
+int schwz_ras_batch_local_solve(schwz_subdomain *sd, unsigned frozen, int *h_inner_iters, schwz_stream stream);
+int schwz_ras_batch_restrict(schwz_subdomain *sd, unsigned frozen, schwz_stream stream);
+int schwz_ras_batch_vector(schwz_subdomain *sd, int which, double **d_ptr, int64_t *len);
+int schwz_ras_batch_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stream);
+int schwz_ras_batch_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 
 #ifdef __cplusplus
 }

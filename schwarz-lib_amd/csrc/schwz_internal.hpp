@@ -1006,6 +1006,9 @@ struct schwz_subdomain {
     std::vector<int64_t> rhs_index;
     bool rhs_index_custom = false;
     int64_t *d_rhs_index = nullptr;
+    // block state (schwz_ras_batch_begin, csrc/batch.hip): k right-hand sides at once, vectors and a solver of its
+    // own; null until asked for.  Nothing above is read-write shared with it: it reads the matrix and the index lists
+    struct schwz_ras_batch *batch = nullptr;
 };
 
 namespace schwz {

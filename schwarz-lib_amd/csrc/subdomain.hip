@@ -260,6 +260,7 @@ void schwz_subdomain_destroy(schwz_subdomain *sd)
 {
     if (!sd) return;
     if (sd->on_device) {
+        (void)schwz_ras_batch_end(sd);
         schwz_pcg_destroy(sd->cg);
         schwz_pcg_f32_destroy(sd->cg32);
         schwz_cheb_destroy(sd->cheb);

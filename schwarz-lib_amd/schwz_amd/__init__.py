@@ -8,10 +8,10 @@ from . import _capi as capi  # noqa: F401  (loads libschwz_hip.so)
 from ._capi import SchwzError, NotImplementedSchwz  # noqa: F401
 from .comm import InProcessComm, TorchDistComm, WindowComm  # noqa: F401
 from .core import Coarse, dense_inverse  # noqa: F401
-from .core import (Bicgstab, Chebyshev, Csr, DeviceWindow, Gmres, Pcg, PcgF32, PeerWindow, Problem, Subdomain, Trs, TrsLU, TrsSweeps, cholesky, gather, ilu0, isai, lu, parilu,  # noqa: F401
+from .core import (BatchCg, Bicgstab, Chebyshev, Csr, DeviceWindow, Gmres, Pcg, PcgF32, PeerWindow, Problem, Subdomain, Trs, TrsLU, TrsSweeps, cholesky, gather, ilu0, isai, lu, parilu,  # noqa: F401
                    scatter,
                    partition_regular, partition_regular2d, rhs_random)
-from .solver import (HipBackend, Metadata, Settings, SolverRAS,  # noqa: F401
+from .solver import (HipBackend, Metadata, Settings, SolverRAS, batch_blocks,  # noqa: F401
                      PARTITION_CUSTOM, PARTITION_METIS, PARTITION_REGULAR, PARTITION_REGULAR2D,
                      SOLVER_DIRECT_CHOLMOD, SOLVER_DIRECT_GINKGO, SOLVER_DIRECT_UMFPACK,
                      SOLVER_ITERATIVE_GINKGO)

@@ -79,7 +79,14 @@ SYMBOLS = [
     "schwz_ras_rhs_set", "schwz_ras_rhs_index", "schwz_ras_rhs_gather", "schwz_ras_rhs_aggregate", "schwz_ras_rhs_norm_sq",
     "schwz_ras_rhs_norm_sq_local",
     "schwz_ras_restart",
+    "schwz_csr_spmm", "schwz_bcg_create", "schwz_bcg_destroy", "schwz_bcg_solve", "schwz_bcg_last_stats",
+    "schwz_bcg_residual",
+    "schwz_ras_batch_begin", "schwz_ras_batch_end", "schwz_ras_batch_rhs_set", "schwz_ras_batch_pack",
+    "schwz_ras_batch_unpack", "schwz_ras_batch_update_boundary", "schwz_ras_batch_local_residual",
+    "schwz_ras_batch_local_solve", "schwz_ras_batch_restrict", "schwz_ras_batch_vector", "schwz_ras_batch_get_interior",
+    "schwz_ras_batch_true_residual_sq",
 ]
+BATCH_WIDTHS = (2, 4, 8)  # the block-vector widths the device code is instantiated for
 COARSE_MAX_DOFS = 4096    # aggregates of a coarse space: two bytes per x~ slot, the explicit inverse at most 128 MB
 
 
@@ -280,6 +287,24 @@ _sig("schwz_ras_rhs_aggregate", i32, [vp, vp])
 _sig("schwz_ras_rhs_norm_sq", i32, [vp, C.POINTER(dbl), vp])
 _sig("schwz_ras_rhs_norm_sq_local", i32, [vp, C.POINTER(dbl), vp])
 _sig("schwz_ras_restart", i32, [vp, i32, vp])
+_sig("schwz_csr_spmm", i32, [vp, i32, dbl, vp, dbl, vp, vp])
+_sig("schwz_bcg_create", i32, [vp, i32, i32, pvp])
+_sig("schwz_bcg_destroy", None, [vp])
+_sig("schwz_bcg_solve", i32, [vp, vp, vp, dbl, i32, C.c_uint, C.POINTER(C.c_int), C.POINTER(dbl), vp])
+_sig("schwz_bcg_last_stats", i32, [vp, C.POINTER(C.c_int), C.POINTER(dbl)])
+_sig("schwz_bcg_residual", i32, [vp, vp, vp, vp, C.POINTER(dbl), vp])
+_sig("schwz_ras_batch_begin", i32, [vp, i32])
+_sig("schwz_ras_batch_end", i32, [vp])
+_sig("schwz_ras_batch_rhs_set", i32, [vp, vp, vp])
+_sig("schwz_ras_batch_pack", i32, [vp, vp, vp])
+_sig("schwz_ras_batch_unpack", i32, [vp, vp, vp])
+_sig("schwz_ras_batch_update_boundary", i32, [vp, vp])
+_sig("schwz_ras_batch_local_residual", i32, [vp, C.POINTER(dbl), vp])
+_sig("schwz_ras_batch_local_solve", i32, [vp, C.c_uint, C.POINTER(C.c_int), vp])
+_sig("schwz_ras_batch_restrict", i32, [vp, C.c_uint, vp])
+_sig("schwz_ras_batch_vector", i32, [vp, i32, pvp, C.POINTER(i64)])
+_sig("schwz_ras_batch_get_interior", i32, [vp, vp, vp])
+_sig("schwz_ras_batch_true_residual_sq", i32, [vp, C.POINTER(dbl), vp])
 
 
 def check(rc):

@@ -49,6 +49,11 @@ class Csr:
         check(lib.schwz_csr_spmv(self.h, alpha, ptr(d_x), beta, ptr(d_y), variant,
                                  _stream_arg(stream)))
 
+    def spmm(self, d_x, d_y, k, alpha=1.0, beta=0.0, stream=0):
+        """Y = alpha A X + beta Y on block vectors of k = 2, 4 or 8 columns, element (i, j) at i * k + j
+        (schwz_csr_spmm, an extension); plain CSR whatever format() says."""
+        check(lib.schwz_csr_spmm(self.h, int(k), alpha, ptr(d_x), beta, ptr(d_y), _stream_arg(stream)))
+
     def format(self):
         """Coding variant 0 uses: 0 plain CSR, 1 per-entry dictionaries, 2 row patterns, 3 row pairs."""
         return int(lib.schwz_csr_format(self.h))
@@ -228,6 +233,47 @@ class Chebyshev:
     def close(self):
         if getattr(self, "h", None) and lib is not None:
             lib.schwz_cheb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+class BatchCg:
+    """k = 2, 4 or 8 independent CG recurrences that share one pass over the matrix per iteration (schwz_bcg, an
+    extension: the reference solves one system).  precond: PRECOND_NONE or PRECOND_JACOBI.  Block vectors are
+    row-interleaved, element (i, j) at i * k + j.  solve() returns per-column lists (updates applied, recurred residual
+    norm); a column is frozen -- its x stops changing -- once its own test fires, where it would divide by zero, or
+    from the start where bit j of `frozen` is set."""
+
+    def __init__(self, csr, precond=capi.PRECOND_NONE, k=8):
+        self.csr, self.k = csr, int(k)
+        h = C.c_void_p()
+        check(lib.schwz_bcg_create(csr.h, precond, self.k, C.byref(h)))
+        self.h = h
+
+    def solve(self, d_b, d_x, rtol, max_iters, frozen=0, stream=0, want_stats=True):
+        it = (C.c_int * self.k)()
+        rn = (C.c_double * self.k)()
+        check(lib.schwz_bcg_solve(self.h, ptr(d_b), ptr(d_x), rtol, max_iters, int(frozen),
+                                  it if want_stats else None, rn if want_stats else None, _stream_arg(stream)))
+        return list(it), list(rn)
+
+    def last_stats(self):
+        it = (C.c_int * self.k)()
+        rn = (C.c_double * self.k)()
+        check(lib.schwz_bcg_last_stats(self.h, it, rn))
+        return list(it), list(rn)
+
+    def residual(self, d_b, d_x, d_r=None, stream=0):
+        """Per column ||b_j - A x_j||^2 (waits for the stream); R = B - A X goes to d_r where one is given."""
+        out = (C.c_double * self.k)()
+        check(lib.schwz_bcg_residual(self.h, ptr(d_b), ptr(d_x), ptr(d_r), out, _stream_arg(stream)))
+        return list(out)
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.schwz_bcg_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -592,6 +638,8 @@ class Subdomain:
     iteration state.  Mirrors what SolverRAS::setup_local_matrices /
     setup_comm_buffers build (restricted_schwarz.cpp:56-604)."""
 
+    batch_k = 0  # columns of the block state (batch_begin); 0: none
+
     def __init__(self, problem, P, me, overlap, first_row):
         self.problem = problem
         self.P, self.me, self.overlap = P, me, overlap
@@ -895,6 +943,63 @@ class Subdomain:
         """The iteration state back to "just uploaded" (keep_x: every vector keeps its values); the solver objects
         forget their last solve either way (schwz_ras_restart)."""
         check(lib.schwz_ras_restart(self.h, int(bool(keep_x)), _stream_arg(stream)))
+
+    # ---- the steps of a RAS iteration on block vectors (schwz_ras_batch_*): k columns, element (i, j) at i * k + j ----
+
+    def batch_begin(self, k):
+        """The block state of k = 2, 4 or 8 columns: vectors and a block CG of its own, beside the single-vector state."""
+        check(lib.schwz_ras_batch_begin(self.h, int(k)))
+        self.batch_k = int(k)
+
+    def batch_end(self):
+        check(lib.schwz_ras_batch_end(self.h))
+        self.batch_k = 0
+
+    def batch_rhs_set(self, rhs, stream=0):
+        """rhs: host array of shape (local_size_x, k), local order; x~ and y go back to zero, b~ = b."""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        assert rhs.shape == (self.local_size_x, self.batch_k)
+        check(lib.schwz_ras_batch_rhs_set(self.h, ptr(rhs), _stream_arg(stream)))
+
+    def batch_pack(self, d_send, stream=0):
+        check(lib.schwz_ras_batch_pack(self.h, ptr(d_send), _stream_arg(stream)))
+
+    def batch_unpack(self, d_recv, stream=0):
+        check(lib.schwz_ras_batch_unpack(self.h, ptr(d_recv), _stream_arg(stream)))
+
+    def batch_update_boundary(self, stream=0):
+        check(lib.schwz_ras_batch_update_boundary(self.h, _stream_arg(stream)))
+
+    def batch_local_residual(self, stream=0):
+        """Per column ||b~_j - A x~_j||_2 (waits for the stream)."""
+        out = (C.c_double * self.batch_k)()
+        check(lib.schwz_ras_batch_local_residual(self.h, out, _stream_arg(stream)))
+        return list(out)
+
+    def batch_local_solve(self, frozen=0, stream=0, want_iters=False):
+        it = (C.c_int * self.batch_k)()
+        check(lib.schwz_ras_batch_local_solve(self.h, int(frozen), it if want_iters else None, _stream_arg(stream)))
+        return list(it)
+
+    def batch_restrict(self, frozen=0, stream=0):
+        check(lib.schwz_ras_batch_restrict(self.h, int(frozen), _stream_arg(stream)))
+
+    def batch_vector(self, which):
+        """(device pointer, length) of the block x~ (0), b~ (1), y (2) or b (3)."""
+        p = C.c_void_p()
+        n = C.c_int64(0)
+        check(lib.schwz_ras_batch_vector(self.h, which, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def batch_get_interior(self, stream=0):
+        out = np.zeros((max(self.local_size, 1), self.batch_k), dtype=np.float64)
+        check(lib.schwz_ras_batch_get_interior(self.h, ptr(out), _stream_arg(stream)))
+        return out[:self.local_size]
+
+    def batch_true_residual_sq(self, stream=0):
+        out = (C.c_double * self.batch_k)()
+        check(lib.schwz_ras_batch_true_residual_sq(self.h, out, _stream_arg(stream)))
+        return list(out)
 
     def close(self):
         if getattr(self, "h", None) and lib is not None:

@@ -228,6 +228,16 @@ def _ratio(a, b):
     return a / b
 
 
+def batch_blocks(nrhs):
+    """The block widths solve_many runs nrhs columns in: blocks of 8, the last one padded up to 2, 4 or 8 (the widths
+    the device code is instantiated for, capi.BATCH_WIDTHS)."""
+    nrhs = int(nrhs)
+    if nrhs < 1:
+        raise capi.SchwzError(capi.ERR_INVALID, "solve_many: nrhs must be at least 1")
+    full, rest = divmod(nrhs, 8)
+    return (8,) * full + ((min(w for w in capi.BATCH_WIDTHS if w >= rest),) if rest else ())
+
+
 def _local_solver_code(settings):
     ls = settings.local_solver
     if ls == SOLVER_ITERATIVE_GINKGO:
@@ -1582,6 +1592,179 @@ class SolverRAS:
         """set_rhs(rhs, initial_guess) followed by run(gather_solution)."""
         self.set_rhs(rhs, initial_guess)
         return self.run(gather_solution)
+
+    # ------------------------------------------------- a block of right-hand sides at once
+    def _check_batch(self, rhs):
+        """The refusals of solve_many, all before any device allocation.  Returns the (N, nrhs) float64 array."""
+        s, m = self.settings, self.metadata
+        cs = s.comm_settings
+
+        def unavailable(what):
+            raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED, "solve_many: the block path does not exist for " + what)
+
+        def refuse(msg):
+            raise capi.SchwzError(capi.ERR_INVALID, "solve_many: " + msg)
+        if s.non_symmetric_matrix:
+            unavailable("non_symmetric_matrix")
+        if _local_solver_code(s) != capi.SOLVER_ITERATIVE:
+            unavailable("a direct local solver")
+        if any(_sweep_counts(m)):
+            unavailable("the ParILU options (par_ilu_sweeps / trisolve_sweeps)")
+        if _precond_name_code(m) not in (capi.PRECOND_NONE, capi.PRECOND_JACOBI):
+            unavailable("local_precond '%s' (null, or block-jacobi with precond_max_block_size = 1)" % m.local_precond)
+        if m.local_solver_precision != "double":
+            unavailable("local_solver_precision '%s'" % m.local_solver_precision)
+        if m.symmetric_solver != "cg":
+            unavailable("symmetric_solver '%s'" % m.symmetric_solver)
+        if m.coarse_space != "none":
+            unavailable("coarse_space '%s' (two-level RAS)" % m.coarse_space)
+        if cs.enable_onesided:
+            unavailable("enable_onesided")
+        if s.use_mixed_precision:
+            unavailable("use_mixed_precision (fp32 halos)")
+        if s.reset_local_crit_iter != -1:
+            unavailable("reset_local_crit_iter (the two-stage local criterion)")
+        if self.problem is None or not self.subdomains:
+            refuse("the solver is not set up: call initialize() first")
+        N = int(m.global_size)
+        if type(rhs).__module__.split(".")[0] == "torch":
+            refuse("the right-hand sides must be a host array (device tensors are not taken)")
+        arr = np.asarray(rhs)
+        if arr.dtype.kind != "f":
+            refuse("the right-hand sides must hold floating-point values, not %s" % arr.dtype)
+        if arr.ndim != 2 or arr.shape[0] != N:
+            refuse("the right-hand sides must have shape (%d, nrhs), not %s" % (N, arr.shape))
+        if arr.shape[1] < 1:
+            refuse("nrhs must be at least 1")
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if not np.isfinite(arr).all():
+            refuse("the right-hand sides hold a value that is not finite")
+        return arr
+
+    def _batch_exchange(self, bufs, stream):
+        send_buf, recv_buf, sends, recvs = bufs
+        for me, sd in self.subdomains.items():
+            sd.batch_pack(send_buf[me].data_ptr(), stream)
+        self.comm.exchange(sends, recvs)
+        for me, sd in self.subdomains.items():
+            sd.batch_unpack(recv_buf[me].data_ptr(), stream)
+
+    def _solve_block(self, B, k, gather_solution):
+        """One block: B is (N, nreal) in the caller's row ids, nreal <= k, the other columns are zero padding."""
+        s, m, be, comm = self.settings, self.metadata, self.backend, self.comm
+        cv = s.convergence_settings
+        P, tol, nreal = m.num_subdomains, m.tolerance, B.shape[1]
+        stream = be.stream()
+        locals_ = list(self.subdomains.items())
+        perm = None if m.permutation is None else np.asarray(m.permutation, dtype=np.int64)
+        interior = {}
+        send_buf, recv_buf, sends, recvs = {}, {}, {}, {}
+        for me, sd in locals_:
+            sd.batch_begin(k)
+            ids = np.asarray(sd.local_to_global[:sd.local_size_x], dtype=np.int64)
+            rows = ids if perm is None else perm[ids]      # exactly as _rhs indexes a right-hand side
+            local = np.zeros((sd.local_size_x, k))
+            local[:, :nreal] = B[rows]
+            sd.batch_rhs_set(local, stream)
+            interior[me] = local[:sd.local_size, :nreal]
+            # [neighbour][entry][column]: the slices of the single-vector buffers, k times as long
+            send_buf[me], recv_buf[me] = be.empty(sd.num_send * k), be.empty(sd.num_recv * k)
+            off = sd.send_offsets()
+            for q_at, (q, _) in enumerate(sd.put_lists()):
+                sends[(me, q)] = send_buf[me][off[q_at] * k:off[q_at + 1] * k]
+            off = sd.recv_offsets()
+            for p_at, (p, _) in enumerate(sd.get_lists()):
+                recvs[(p, me)] = recv_buf[me][off[p_at] * k:off[p_at + 1] * k]
+        bufs = (send_buf, recv_buf, sends, recvs)
+        padding = sum(1 << j for j in range(nreal, k))
+        fired = [False] * nreal
+        iters = [0] * nreal
+        gres0 = [-1.0] * nreal
+        history = [[] for _ in range(nreal)]
+        be.synchronize()
+        comm.barrier()
+        start = time.perf_counter()
+        it = 0
+        while it < m.max_iters:
+            self._batch_exchange(bufs, stream)
+            for _, sd in locals_:
+                sd.batch_update_boundary(stream)
+            # the per-column test is the project's own (step(), solve.cpp:890-915): the sum over the subdomains of
+            # the local residual norms, relative to its value at iteration 0
+            lres = {me: (sd.batch_local_residual(stream) if tol >= 0.0 else [-1.0] * k) for me, sd in locals_}
+            iter_cond = ((it > m.max_iters * 0.05) or m.max_iters < 1000) if cv.enable_global_check_iter_offset else True
+            for j in range(nreal):
+                if fired[j]:
+                    continue
+                if any(np.isnan(lres[me][j]) for me, _ in locals_):
+                    raise capi.SchwzError(capi.ERR_DIVERGED, "local residual of column %d is NaN" % j)
+                if tol > 0.0 and iter_cond and cv.enable_global_check:
+                    gres = 0.0
+                    for v in comm.allgather_scalars({me: lres[me][j] for me, _ in locals_}):
+                        gres += v
+                    history[j].append(gres)
+                    if gres0[j] < 0.0:
+                        gres0[j] = gres
+                    if np.isnan(gres) or gres > 1e12:
+                        raise capi.SchwzError(capi.ERR_DIVERGED, " Rank %d: column %d diverged in %d iters " % (comm.rank, j, it))
+                    if _ratio(gres, gres0[j]) <= tol:
+                        fired[j] = True
+                        iters[j] = it
+            if all(fired):
+                break
+            frozen = padding | sum(1 << j for j in range(nreal) if fired[j])
+            for _, sd in locals_:
+                sd.batch_local_solve(frozen, stream)
+            for _, sd in locals_:
+                sd.batch_restrict(frozen, stream)
+            it += 1
+        for j in range(nreal):
+            if not fired[j]:
+                iters[j] = it
+        be.synchronize()
+        comm.barrier()
+        elapsed = time.perf_counter() - start
+        # as finish_run: (A x) on the interior rows needs fresh overlap values, hence one more exchange
+        self._batch_exchange(bufs, stream)
+        parts = {me: sd.batch_true_residual_sq(stream) for me, sd in locals_}
+        out = dict(iter_count=iters, converged=fired, history=history, elapsed=elapsed, residual_norm=[], rhs_norm=[],
+                   solution=None)
+        for j in range(nreal):
+            res_sq = sum(comm.allgather_scalars({me: parts[me][j] for me, _ in locals_}))
+            rhs_sq = sum(comm.allgather_scalars({me: float(np.sum(interior[me][:, j] ** 2)) for me, _ in locals_}))
+            out["residual_norm"].append(float(np.sqrt(res_sq)))
+            out["rhs_norm"].append(float(np.sqrt(rhs_sq)))
+        if gather_solution:
+            pieces = {me: np.ascontiguousarray(sd.batch_get_interior(stream)[:, :nreal]) for me, sd in locals_}
+            out["solution"] = comm.gather_vectors(pieces)
+        return out
+
+    def solve_many(self, rhs, gather_solution=True):
+        """Several right-hand sides against the matrix initialize() set up, solved in blocks of up to eight columns that
+        share every pass over the local matrices and every launch of the outer step (an extension: the reference
+        solves one system).  `rhs`: a host array of shape (global_size, nrhs), the same on every rank, indexed by the
+        caller's row ids like initialize(rhs=...).  The columns run in blocks of 8, the last block padded to 2, 4 or 8
+        with zero columns whose results are dropped.  Per block a synchronous loop of its own: exchange, boundary
+        update, per-column check, local solve, restriction -- no speculative solve, no early exchange.  A column whose
+        convergence test fires is frozen from then on, in the local solves and in the restriction: its solution is the
+        iterate at which a run on that column alone would have stopped.  The single-right-hand-side state is untouched.
+        Returns per-column lists iter_count, converged, residual_norm, rhs_norm and history (the global residual sum
+        per iteration), solution of shape (global_size, nrhs) on the root rank, and elapsed (the loops of the blocks).
+        Collective like run(): every rank calls it."""
+        B = self._check_batch(rhs)
+        nrhs = B.shape[1]
+        out = dict(iter_count=[], converged=[], residual_norm=[], rhs_norm=[], history=[], elapsed=0.0, solution=None)
+        sols, at = [], 0
+        for k in batch_blocks(nrhs):
+            part = self._solve_block(B[:, at:at + min(k, nrhs - at)], k, gather_solution)
+            at += k
+            for key in ("iter_count", "converged", "residual_norm", "rhs_norm", "history"):
+                out[key] += part[key]
+            out["elapsed"] += part["elapsed"]
+            sols.append(part["solution"])
+        if gather_solution and all(p is not None for p in sols):
+            out["solution"] = np.concatenate(sols, axis=1)
+        return out
 
     def run(self, gather_solution=True):
         """SchwarzBase::run (schwarz_base.cpp:323-506).  Returns a dict with the
