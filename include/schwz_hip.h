@@ -121,7 +121,11 @@ int schwz_scatter_typed(int64_t n, const void *d_idx, int index_type, const void
                         int value_type, int op, schwz_stream stream);
 
 /* CSR matrix resident in HBM, with the row-tile table the SpMV kernel needs.
- * Replaces gko::matrix::Csr<double,int> on the device executor. */
+ * Replaces gko::matrix::Csr<double,int> on the device executor.
+ * The arrays are uploaded as they are.  SpMV sums every stored entry, but the preconditioned solvers read the
+ * diagonal as ONE stored entry per row (Jacobi, block-Jacobi) and the symmetry check bisects the rows: a matrix
+ * uploaded directly must hold every column once per row, ascending.  The problem sources of section 2
+ * (schwz_problem_from_csr, schwz_problem_from_matrix_market) guarantee that for everything they feed. */
 typedef struct schwz_csr schwz_csr;
 int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_row_ptr,
                      const schwz_idx *h_col, const double *h_val, schwz_csr **out);
@@ -450,7 +454,12 @@ typedef struct schwz_problem schwz_problem;
  * stencil on an nx*nx grid; dim=3 is the 7-point extension on nx*ny*nz. */
 int schwz_problem_laplacian(int dim, int64_t nx, int64_t ny, int64_t nz,
                             schwz_problem **out);
-/* explicit CSR with int64 row_ptr (copied) */
+/* explicit CSR with int64 row_ptr (copied).  The arrays are checked before anything is read through them:
+ * h_row_ptr[0] != 0, a row_ptr that decreases or is negative anywhere, a column < 0 or >= N: SCHWZ_ERR_INVALID.
+ * Rows may be unsorted (deal.II stores the diagonal first): they are stable-sorted by column.  Rows may hold a
+ * column more than once: those entries are summed in their stored order and stored once.  The pattern does not
+ * depend on the values (explicit zeros, and sums that vanish, stay stored).  Every problem therefore has
+ * strictly ascending columns in every row. */
 int schwz_problem_from_csr(int64_t N, const int64_t *h_row_ptr,
                            const schwz_idx *h_col, const double *h_val,
                            schwz_problem **out);
@@ -459,13 +468,27 @@ int schwz_problem_from_csr(int64_t N, const int64_t *h_row_ptr,
  * subdomain reads -- its interior and overlap rows, schwz_problem_extract_rows -- and hand each rank a row
  * source that holds only that part (row ids ascending, CSR over those rows, columns global and ascending);
  * schwz_subdomain_setup on it gives the same subdomain as on the whole matrix and fails if it needs a row
- * that is not there.  extract_rows: first call with h_col == NULL fills h_row_ptr (nrows + 1 entries). */
+ * that is not there.  extract_rows: first call with h_col == NULL fills h_row_ptr (nrows + 1 entries).
+ * from_rows sorts and sums nothing: row ids that are not strictly ascending or lie outside [0, N), a row_ptr that
+ * does not start at 0 or decreases anywhere, columns that are not strictly ascending or lie outside [0, N):
+ * SCHWZ_ERR_INVALID (what extract_rows hands out always passes). */
 int schwz_problem_from_rows(int64_t N, int64_t nrows, const int64_t *h_row_ids, const int64_t *h_row_ptr,
                             const schwz_idx *h_col, const double *h_val, schwz_problem **out);
 int schwz_problem_extract_rows(const schwz_problem *p, int64_t nrows, const int64_t *h_row_ids,
                                int64_t *h_row_ptr, schwz_idx *h_col, double *h_val);
 /* Matrix-Market file branch (initialization.cpp:204-213): gko::read +
- * sort_by_column_index */
+ * sort_by_column_index.  The banner is the five words "%%MatrixMarket matrix coordinate <field> <symmetry>" in
+ * any letter case, field real | integer | pattern, symmetry general | symmetric | skew-symmetric; array, complex,
+ * hermitian, any other word and a missing banner are refused.  Comment lines ('%') before the size line and blank
+ * lines anywhere are skipped; LF or CRLF.  The matrix must be square with 1 <= n < 2^31 - 1.  Every entry line
+ * holds exactly "row col value" ("row col" in a pattern file, value 1.0), indices 1-based inside the matrix, the
+ * value wholly a finite number (an integer in an integer file).  symmetric and skew-symmetric files hold the lower
+ * triangle only (skew-symmetric: no diagonal entry); the mirror of (i, j, v) is (j, i, v), skew-symmetric
+ * (j, i, -v).  Entries of one (row, col) are summed in file order and stored once (schwz_problem_from_csr).
+ * Refused with SCHWZ_ERR_IO and a message that names the entry or the word: an index outside the matrix, an
+ * entry line with another number of fields, a value that is not a finite number, an entry above the diagonal or on
+ * the diagonal of a skew-symmetric file, fewer entries than the size line announces, content after the last one,
+ * a negative count.  Nothing is allocated from the announced count beyond what the bytes of the file can hold. */
 int schwz_problem_from_matrix_market(const char *path, schwz_problem **out);
 void schwz_problem_destroy(schwz_problem *p);
 int64_t schwz_problem_size(const schwz_problem *p);
@@ -504,6 +527,7 @@ int schwz_partition_graph(const schwz_problem *p, int P, uint32_t *h_part);
  * setup_comm_buffers (:308-604). */
 typedef struct schwz_subdomain schwz_subdomain;
 
+/* h_first_row: P + 1 entries from 0 to N that never decrease, else SCHWZ_ERR_INVALID. */
 int schwz_subdomain_setup(const schwz_problem *p, int P, int me, int overlap,
                           const int64_t *h_first_row, schwz_subdomain **out);
 void schwz_subdomain_destroy(schwz_subdomain *sd);
@@ -537,7 +561,10 @@ int schwz_subdomain_recv_offset(const schwz_subdomain *sd, int k, int64_t *offse
 
 /* Host sparse LL^T of the local matrix, standing in for CHOLMOD simplicial
  * LL^T (Solve::compute_local_factors, source/solve.cpp:75-143): identity
- * A(perm,perm) = L L^T.  Outputs are malloc'd; free with schwz_free. */
+ * A(perm,perm) = L L^T.  Outputs are malloc'd; free with schwz_free.
+ * schwz_cholesky, schwz_lu and schwz_isai, like schwz_ilu0: rows whose columns are not strictly ascending
+ * (unsorted, or a column stored twice) or lie outside [0, n): SCHWZ_ERR_INVALID.  No exception leaves a function
+ * of this section: an allocation that fails, or a length no container holds, is SCHWZ_ERR_INVALID too. */
 int schwz_cholesky(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col,
                    const double *h_val, int natural_ordering, schwz_idx **l_rp,
                    schwz_idx **l_col, double **l_val, schwz_idx **u_rp,

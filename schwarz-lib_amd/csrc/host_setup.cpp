@@ -9,6 +9,8 @@
 #include <omp.h>
 
 #include <algorithm>
+#include <cctype>
+#include <charconv>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -17,8 +19,10 @@
 #include <numeric>
 #include <queue>
 #include <set>
+#include <stdexcept>
+#include <string_view>
+#include <system_error>
 #include <unordered_map>
-#include <sstream>
 
 #include "schwz_internal.hpp"
 
@@ -67,7 +71,61 @@ bool csr_is_symmetric(int64_t nrows, int64_t ncols, const schwz_idx *rp, const s
     return ok && upper == lower;
 }
 
+// Every row of an n x ncols CSR matrix has strictly ascending columns inside [0, ncols) and row_ptr starts at 0
+// and never decreases: what the factorizations below index with.  On failure `what` says which rule broke.
+static bool csr_rows_strictly_ascending(int64_t n, int64_t ncols, const schwz_idx *rp, const schwz_idx *col,
+                                        std::string *what)
+{
+    if (n > 0 && rp[0] != 0) {
+        *what = "row_ptr must start at 0";
+        return false;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        if (rp[i + 1] < rp[i]) {
+            *what = "row_ptr decreases at row " + std::to_string(i);
+            return false;
+        }
+        if (rp[i + 1] > rp[i] && !col) {
+            *what = "null column array";
+            return false;
+        }
+        for (schwz_idx j = rp[i]; j < rp[i + 1]; ++j) {
+            if (col[j] < 0 || col[j] >= ncols) {
+                *what = "column index out of range in row " + std::to_string(i);
+                return false;
+            }
+            if (j > rp[i] && col[j - 1] >= col[j]) {
+                *what = "columns must be strictly ascending (sorted, each stored once) in row " + std::to_string(i);
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
+// What an exception becomes at the C boundary (SCHWZ_GUARD below): allocation failures and lengths no container
+// can hold are the caller's sizes gone wrong.
+static int caught(const char *fn)
+{
+    try {
+        throw;
+    } catch (const std::bad_alloc &) {
+        set_error(std::string(fn) + ": out of memory (a size in the arguments is too large)");
+    } catch (const std::length_error &e) {
+        set_error(std::string(fn) + ": a size in the arguments is negative or too large (" + e.what() + ")");
+    } catch (const std::exception &e) {
+        set_error(std::string(fn) + ": " + e.what());
+    } catch (...) {
+        set_error(std::string(fn) + ": unknown exception");
+    }
+    return SCHWZ_ERR_INVALID;
+}
+
 }  // namespace schwz
+
+// No exception leaves an extern "C" function of this file: its body is a function-try-block closed by this handler.
+#define SCHWZ_GUARD(fn) \
+    catch (...) { return ::schwz::caught(fn); }
 
 using namespace schwz;
 
@@ -152,6 +210,38 @@ static T *to_malloc(const std::vector<T> &v)
     return p;
 }
 
+// ---- the words of a Matrix-Market line (schwz_problem_from_matrix_market) ----
+namespace {
+
+void split_words(const std::string &line, std::vector<std::string_view> &words)
+{
+    words.clear();
+    const char *s = line.data(), *e = s + line.size();
+    while (s < e) {
+        while (s < e && std::isspace((unsigned char)*s)) ++s;
+        const char *b = s;
+        while (s < e && !std::isspace((unsigned char)*s)) ++s;
+        if (s > b) words.emplace_back(b, (size_t)(s - b));
+    }
+}
+
+// the number a word spells, all of it: an optional sign, then what std::from_chars reads (no locale)
+template <typename T>
+bool whole_number(std::string_view w, T *out)
+{
+    if (!w.empty() && w[0] == '+') {
+        w.remove_prefix(1);
+        if (w.empty() || w[0] == '+' || w[0] == '-') return false;
+    }
+    if (w.empty()) return false;
+    const auto r = std::from_chars(w.data(), w.data() + w.size(), *out);
+    return r.ec == std::errc() && r.ptr == w.data() + w.size();
+}
+
+std::string quoted(std::string_view w) { return "\"" + std::string(w.substr(0, 60)) + "\""; }
+
+}  // namespace
+
 extern "C" {
 
 const char *schwz_last_error(void) { return g_last_error.c_str(); }
@@ -160,7 +250,7 @@ int schwz_setup_threads(void) { return schwz::setup_threads(); }
 void schwz_free(void *p) { std::free(p); }
 
 int schwz_problem_laplacian(int dim, int64_t nx, int64_t ny, int64_t nz, schwz_problem **out)
-{
+try {
     SCHWZ_REQUIRE(out, "schwz_problem_laplacian: null output");
     SCHWZ_REQUIRE(dim == 2 || dim == 3, "schwz_problem_laplacian: dim must be 2 or 3");
     SCHWZ_REQUIRE(nx > 0, "schwz_problem_laplacian: grid size must be positive");
@@ -182,48 +272,48 @@ int schwz_problem_laplacian(int dim, int64_t nx, int64_t ny, int64_t nz, schwz_p
     *out = p;
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_problem_laplacian")
 
 // Distributed ingest: a process holds the rows its subdomain reads -- interior and overlap
 // rows -- of a matrix one rank parsed and partitioned; the rest of the setup (index sets, local and
 // interface matrices, lists) runs on that part exactly as on the whole matrix.
 int schwz_problem_from_rows(int64_t N, int64_t nrows, const int64_t *row_ids, const int64_t *rp,
                             const schwz_idx *col, const double *val, schwz_problem **out)
-{
+try {
     SCHWZ_REQUIRE(out && N >= 0 && nrows >= 0 && nrows <= N && rp && (nrows == 0 || row_ids),
                   "schwz_problem_from_rows: bad arguments");
     SCHWZ_REQUIRE(rp[0] == 0, "schwz_problem_from_rows: row_ptr must start at 0");
-    for (int64_t i = 0; i < nrows; ++i) {
+    // (all of row_ptr before anything is read through it)
+    for (int64_t i = 0; i < nrows; ++i)
+        SCHWZ_REQUIRE(rp[i + 1] >= rp[i] && rp[i + 1] - rp[i] <= INT_MAX / 2,
+                      "schwz_problem_from_rows: row_ptr not monotone (row " + std::to_string(i) + ")");
+    for (int64_t i = 0; i < nrows; ++i)
         SCHWZ_REQUIRE(row_ids[i] >= 0 && row_ids[i] < N && (i == 0 || row_ids[i - 1] < row_ids[i]),
                       "schwz_problem_from_rows: row ids must be ascending and inside the matrix");
-        SCHWZ_REQUIRE(rp[i + 1] >= rp[i], "schwz_problem_from_rows: row_ptr not monotone");
-    }
     const int64_t nnz = rp[nrows];
     SCHWZ_REQUIRE(nnz == 0 || (col && val), "schwz_problem_from_rows: null column / value array");
-    auto *p = new schwz_problem();
+    for (int64_t i = 0; i < nrows; ++i)
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j)
+            SCHWZ_REQUIRE(col[j] >= 0 && col[j] < N && (j == rp[i] || col[j - 1] < col[j]),
+                          "schwz_problem_from_rows: columns must be ascending and inside the matrix");
+    std::unique_ptr<schwz_problem> p(new schwz_problem());
     p->kind = 1;
     p->N = N;
     p->present.assign(row_ids, row_ids + nrows);
     p->rp.assign(rp, rp + nrows + 1);
     p->col.assign(col, col + nnz);
     p->val.assign(val, val + nnz);
-    for (int64_t i = 0; i < nrows; ++i) {
-        p->max_row_nnz = std::max(p->max_row_nnz, (int)(rp[i + 1] - rp[i]));
-        for (int64_t j = rp[i]; j < rp[i + 1]; ++j)
-            if (col[j] < 0 || col[j] >= N || (j > rp[i] && col[j - 1] >= col[j])) {
-                delete p;
-                set_error("schwz_problem_from_rows: columns must be ascending and inside the matrix");
-                return SCHWZ_ERR_INVALID;
-            }
-    }
-    *out = p;
+    for (int64_t i = 0; i < nrows; ++i) p->max_row_nnz = std::max(p->max_row_nnz, (int)(rp[i + 1] - rp[i]));
+    *out = p.release();
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_problem_from_rows")
 
 // The rows `row_ids` of a problem as CSR arrays (what the parsing rank sends to the others).  Call once
 // with col_out == nullptr for the row pointers (rp_out[nrows] = entries needed), then with the arrays.
 int schwz_problem_extract_rows(const schwz_problem *p, int64_t nrows, const int64_t *row_ids, int64_t *rp_out,
                                schwz_idx *col_out, double *val_out)
-{
+try {
     SCHWZ_REQUIRE(p && nrows >= 0 && rp_out && (nrows == 0 || row_ids), "schwz_problem_extract_rows: bad arguments");
     std::vector<int64_t> c((size_t)p->max_row_nnz + 1);
     std::vector<double> v((size_t)p->max_row_nnz + 1);
@@ -247,112 +337,211 @@ int schwz_problem_extract_rows(const schwz_problem *p, int64_t nrows, const int6
     }
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_problem_extract_rows")
 
 int schwz_problem_from_csr(int64_t N, const int64_t *rp, const schwz_idx *col, const double *val,
                            schwz_problem **out)
-{
+try {
+    // Both explicit problem sources end here (the file reader calls this).  The arrays are checked before anything is
+    // read through them.  Rows come out with strictly ascending columns: a row that is not is stable-sorted
+    // (sort_by_column_index, initialization.cpp:212) and the entries of one column are summed in their stored order
+    // into one entry -- the diagonal extractors and the block-Jacobi builder read one stored entry per (row, column).
+    // The pattern does not depend on the values: explicit zeros and sums that vanish stay stored.
     SCHWZ_REQUIRE(out && rp && N >= 0, "schwz_problem_from_csr: bad arguments");
-    auto *p = new schwz_problem();
+    SCHWZ_REQUIRE(rp[0] == 0, "schwz_problem_from_csr: row_ptr must start at 0");
+    for (int64_t i = 0; i < N; ++i)
+        SCHWZ_REQUIRE(rp[i + 1] >= rp[i] && rp[i + 1] - rp[i] <= INT_MAX / 2,
+                      "schwz_problem_from_csr: row_ptr not monotone (row " + std::to_string(i) + ")");
+    const int64_t nnz = rp[N];
+    SCHWZ_REQUIRE(nnz == 0 || (col && val), "schwz_problem_from_csr: null column / value array");
+    bool ascending = true;
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+            SCHWZ_REQUIRE(col[j] >= 0 && col[j] < N,
+                          "schwz_problem_from_csr: column index out of range (row " + std::to_string(i) + ")");
+            if (j > rp[i] && col[j - 1] >= col[j]) ascending = false;
+        }
+    std::unique_ptr<schwz_problem> p(new schwz_problem());
     p->kind = 0;
     p->N = N;
-    p->rp.assign(rp, rp + N + 1);
-    const int64_t nnz = rp[N];
-    p->col.assign(col, col + nnz);
-    p->val.assign(val, val + nnz);
-    for (int64_t i = 0; i < N; ++i) {
-        const int len = (int)(rp[i + 1] - rp[i]);
-        p->max_row_nnz = std::max(p->max_row_nnz, len);
-        // sort_by_column_index (initialization.cpp:212)
-        bool sorted = true;
-        for (int64_t j = rp[i] + 1; j < rp[i + 1]; ++j)
-            if (p->col[j - 1] > p->col[j]) sorted = false;
-        if (!sorted) {
-            std::vector<std::pair<schwz_idx, double>> tmp((size_t)len);
-            for (int k = 0; k < len; ++k) tmp[k] = {p->col[rp[i] + k], p->val[rp[i] + k]};
-            std::stable_sort(tmp.begin(), tmp.end(),
-                             [](const auto &a, const auto &b) { return a.first < b.first; });
-            for (int k = 0; k < len; ++k) {
-                p->col[rp[i] + k] = tmp[k].first;
-                p->val[rp[i] + k] = tmp[k].second;
+    if (ascending) {
+        p->rp.assign(rp, rp + N + 1);
+        p->col.assign(col, col + nnz);
+        p->val.assign(val, val + nnz);
+        for (int64_t i = 0; i < N; ++i) p->max_row_nnz = std::max(p->max_row_nnz, (int)(rp[i + 1] - rp[i]));
+    } else {
+        p->rp.assign((size_t)N + 1, 0);
+        p->col.reserve((size_t)nnz);
+        p->val.reserve((size_t)nnz);
+        std::vector<std::pair<schwz_idx, double>> tmp;
+        for (int64_t i = 0; i < N; ++i) {
+            tmp.clear();
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) tmp.push_back({col[j], val[j]});
+            std::stable_sort(tmp.begin(), tmp.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+            for (size_t k = 0; k < tmp.size(); ++k) {
+                if (k > 0 && tmp[k].first == tmp[k - 1].first) {
+                    p->val.back() += tmp[k].second;
+                } else {
+                    p->col.push_back(tmp[k].first);
+                    p->val.push_back(tmp[k].second);
+                }
             }
+            p->rp[(size_t)i + 1] = (int64_t)p->col.size();
+            p->max_row_nnz = std::max(p->max_row_nnz, (int)(p->rp[(size_t)i + 1] - p->rp[(size_t)i]));
         }
     }
-    for (int64_t j = 0; j < nnz; ++j) {
-        if (p->col[j] < 0 || p->col[j] >= N) {
-            delete p;
-            set_error("schwz_problem_from_csr: column index out of range");
-            return SCHWZ_ERR_INVALID;
-        }
-    }
-    *out = p;
+    *out = p.release();
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_problem_from_csr")
 
-// Matrix-Market coordinate real/integer/pattern, general/symmetric
+// Matrix-Market coordinate files, read line by line.  The banner is "%%MatrixMarket matrix coordinate <field>
+// <symmetry>", five words in any letter case: field real | integer | pattern, symmetry general | symmetric |
+// skew-symmetric (array, complex, hermitian and any other word are refused by name).  '%' lines before the size line
+// and blank lines anywhere are skipped, LF or CRLF.  Every entry line holds exactly "row col value" ("row col" for
+// pattern), the indices 1-based inside the matrix, the value wholly a finite number; symmetric and skew-symmetric
+// files hold the lower triangle only (skew-symmetric: no diagonal) and every off-diagonal entry is followed by its
+// mirror (skew-symmetric: negated).  Entries of one (row, col) are summed in file order (schwz_problem_from_csr).
+// Every refusal is SCHWZ_ERR_IO and names the entry or the word; nothing is allocated from the announced count beyond
+// what the bytes of the file can hold.
 int schwz_problem_from_matrix_market(const char *path, schwz_problem **out)
-{
+try {
     SCHWZ_REQUIRE(path && out, "schwz_problem_from_matrix_market: null argument");
-    std::ifstream in(path);
+    std::ifstream in(path, std::ios::binary);
     if (!in) {
         set_error(std::string("Could not find the file \"") + path + "\"");
         return SCHWZ_ERR_IO;
     }
+    auto refuse = [](const std::string &why) {
+        set_error("matrix market: " + why);
+        return (int)SCHWZ_ERR_IO;
+    };
+    in.seekg(0, std::ios::end);
+    const int64_t file_bytes = (int64_t)in.tellg();
+    in.seekg(0, std::ios::beg);
     std::string line;
-    std::getline(in, line);
-    std::string low = line;
-    std::transform(low.begin(), low.end(), low.begin(), ::tolower);
-    if (low.find("%%matrixmarket") != 0 || low.find("coordinate") == std::string::npos) {
-        set_error("matrix market: only coordinate format is supported");
-        return SCHWZ_ERR_IO;
+    std::vector<std::string_view> w;
+    // ---- banner
+    if (!std::getline(in, line)) line.clear();
+    split_words(line, w);
+    auto lower = [](std::string_view s) {
+        std::string t(s);
+        std::transform(t.begin(), t.end(), t.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+        return t;
+    };
+    if (w.empty() || lower(w[0]) != "%%matrixmarket")
+        return refuse("missing banner: the first line must be \"%%MatrixMarket matrix coordinate <field> <symmetry>\", found " +
+                      quoted(line));
+    if (w.size() != 5) return refuse("the banner must hold five words, found " + quoted(line));
+    const std::string object = lower(w[1]), format = lower(w[2]), field = lower(w[3]), symm = lower(w[4]);
+    if (object != "matrix") return refuse("unsupported object " + quoted(w[1]) + " (matrix only)");
+    if (format != "coordinate") return refuse("unsupported format " + quoted(w[2]) + " (coordinate only)");
+    if (field != "real" && field != "integer" && field != "pattern")
+        return refuse("unsupported field " + quoted(w[3]) + " (real, integer or pattern)");
+    if (symm != "general" && symm != "symmetric" && symm != "skew-symmetric")
+        return refuse("unsupported symmetry " + quoted(w[4]) + " (general, symmetric or skew-symmetric)");
+    const bool pattern = field == "pattern", integer = field == "integer";
+    const bool skew = symm == "skew-symmetric", lower_only = skew || symm == "symmetric";
+    if (pattern && skew) return refuse("a \"pattern\" file cannot be \"skew-symmetric\"");
+    // ---- size line: the first line that is neither a comment nor blank
+    bool have = false;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line[0] == '%') continue;
+        split_words(line, w);
+        if (!w.empty()) {
+            have = true;
+            break;
+        }
     }
-    const bool symmetric = low.find("symmetric") != std::string::npos;
-    const bool pattern = low.find("pattern") != std::string::npos;
-    while (std::getline(in, line))
-        if (!line.empty() && line[0] != '%') break;
+    if (!have) return refuse("truncated file: no size line");
     int64_t nr = 0, nc = 0, nz = 0;
+    if (w.size() != 3 || !whole_number(w[0], &nr) || !whole_number(w[1], &nc) || !whole_number(w[2], &nz))
+        return refuse("the size line must hold three integers (rows, columns, entries), found " + quoted(line));
+    if (nr != nc || nr <= 0)
+        return refuse("need a square matrix with at least one row, the size line says " + std::to_string(nr) + " x " +
+                      std::to_string(nc));
+    if (nr >= INT32_MAX)  // (before anything of length n exists)
+        return refuse("the matrix has " + std::to_string(nr) + " rows, indices here are 32-bit");
+    if (nz < 0) return refuse("the size line announces " + std::to_string(nz) + " entries");
     {
-        std::istringstream ss(line);
-        ss >> nr >> nc >> nz;
+        // an entry takes at least "1 1\n" / "1 1 1\n" (the last line may lack its end)
+        const int64_t pos = (int64_t)in.tellg();
+        const int64_t left = pos < 0 ? 0 : file_bytes - pos;
+        const int64_t most = (left + 1) / (pattern ? 4 : 6);
+        if (nz > most)
+            return refuse("truncated file: the size line announces " + std::to_string(nz) + " entries, the " +
+                          std::to_string(left) + " bytes after it hold at most " + std::to_string(most));
     }
-    if (nr <= 0 || nr != nc) {
-        set_error("matrix market: need a square matrix");
-        return SCHWZ_ERR_IO;
-    }
-    std::vector<int64_t> ri, ci;
+    std::vector<schwz_idx> ri, ci;
     std::vector<double> vv;
-    ri.reserve((size_t)nz * (symmetric ? 2 : 1));
+    ri.reserve((size_t)nz * (lower_only ? 2 : 1));
     ci.reserve(ri.capacity());
     vv.reserve(ri.capacity());
+    const size_t want = pattern ? 2 : 3;
     for (int64_t k = 0; k < nz; ++k) {
-        int64_t r, c;
-        double v = 1.0;
-        if (!(in >> r >> c)) {
-            set_error("matrix market: truncated file");
-            return SCHWZ_ERR_IO;
+        const std::string entry = "entry " + std::to_string(k + 1);
+        have = false;
+        while (std::getline(in, line)) {
+            split_words(line, w);
+            if (!w.empty()) {
+                have = true;
+                break;
+            }
         }
-        if (!pattern) in >> v;
-        ri.push_back(r - 1);
-        ci.push_back(c - 1);
+        if (!have) return refuse("truncated file: " + entry + " of " + std::to_string(nz) + " is missing");
+        if (w.size() != want)
+            return refuse(entry + " must hold " + std::to_string(want) + " fields (" + field + "), found " +
+                          std::to_string(w.size()) + ": " + quoted(line));
+        int64_t r = 0, c = 0;
+        if (!whole_number(w[0], &r) || !whole_number(w[1], &c))
+            return refuse(entry + ": " + quoted(!whole_number(w[0], &r) ? w[0] : w[1]) + " is not an integer index");
+        if (r < 1 || r > nr || c < 1 || c > nr)
+            return refuse(entry + ": index (" + std::to_string(r) + ", " + std::to_string(c) + ") outside the " +
+                          std::to_string(nr) + " x " + std::to_string(nr) + " matrix (indices are 1-based)");
+        double v = 1.0;
+        if (integer) {
+            int64_t iv = 0;
+            if (!whole_number(w[2], &iv)) return refuse(entry + ": " + quoted(w[2]) + " is not an integer value");
+            v = (double)iv;
+        } else if (!pattern) {
+            if (!whole_number(w[2], &v) || !std::isfinite(v))
+                return refuse(entry + ": " + quoted(w[2]) + " is not a finite number");
+        }
+        if (lower_only && c > r)
+            return refuse(entry + ": (" + std::to_string(r) + ", " + std::to_string(c) + ") lies above the diagonal of a " +
+                          symm + " file (lower triangle only)");
+        if (skew && c == r)
+            return refuse(entry + ": (" + std::to_string(r) + ", " + std::to_string(c) +
+                          ") is a diagonal entry of a skew-symmetric file");
+        ri.push_back((schwz_idx)(r - 1));
+        ci.push_back((schwz_idx)(c - 1));
         vv.push_back(v);
-        if (symmetric && r != c) {
-            ri.push_back(c - 1);
-            ci.push_back(r - 1);
-            vv.push_back(v);
+        if (lower_only && r != c) {
+            ri.push_back((schwz_idx)(c - 1));
+            ci.push_back((schwz_idx)(r - 1));
+            vv.push_back(skew ? -v : v);
         }
     }
+    while (std::getline(in, line)) {
+        split_words(line, w);
+        if (!w.empty())
+            return refuse("content after the last of the " + std::to_string(nz) + " announced entries: " + quoted(line));
+    }
+    // rows in file order (a mirror right behind its entry); schwz_problem_from_csr sorts and sums
     std::vector<int64_t> rp((size_t)nr + 1, 0);
-    for (int64_t r : ri) rp[r + 1]++;
-    for (int64_t i = 0; i < nr; ++i) rp[i + 1] += rp[i];
+    for (schwz_idx r : ri) rp[(size_t)r + 1]++;
+    for (int64_t i = 0; i < nr; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
     std::vector<schwz_idx> col(ri.size());
     std::vector<double> val(ri.size());
     std::vector<int64_t> fill(rp.begin(), rp.end() - 1);
     for (size_t k = 0; k < ri.size(); ++k) {
-        col[fill[ri[k]]] = (schwz_idx)ci[k];
-        val[fill[ri[k]]] = vv[k];
-        fill[ri[k]]++;
+        const int64_t at = fill[(size_t)ri[k]]++;
+        col[(size_t)at] = ci[k];
+        val[(size_t)at] = vv[k];
     }
     return schwz_problem_from_csr(nr, rp.data(), col.data(), val.data(), out);
 }
+SCHWZ_GUARD("schwz_problem_from_matrix_market")
 
 void schwz_problem_destroy(schwz_problem *p) { delete p; }
 int64_t schwz_problem_size(const schwz_problem *p) { return p ? p->N : 0; }
@@ -369,7 +558,7 @@ int schwz_problem_row(const schwz_problem *p, int64_t row, int *n, int64_t *cols
 // source/restricted_schwarz.cpp:105-152
 int schwz_problem_permute(const schwz_problem *p, int P, const uint32_t *part, int64_t *perm,
                           int64_t *first_row, schwz_problem **out)
-{
+try {
     SCHWZ_REQUIRE(p && part && perm && first_row && out && P > 0, "schwz_problem_permute: bad arguments");
     const int64_t N = p->N;
     std::vector<int64_t> cnt((size_t)P, 0);
@@ -403,6 +592,7 @@ int schwz_problem_permute(const schwz_problem *p, int P, const uint32_t *part, i
     // by local column index later anyway, restricted_schwarz.cpp:297-298)
     return schwz_problem_from_csr(N, rp.data(), col.data(), val.data(), out);
 }
+SCHWZ_GUARD("schwz_problem_permute")
 
 // minstd_rand0 (x <- 16807 x mod 2^31-1, seed 1) and libstdc++'s generate_canonical<double,53>
 // with two draws, evaluated in the same floating-point order
@@ -928,7 +1118,7 @@ static void ml_recurse(const MlGraph &g, const std::vector<int64_t> &ids, int pa
 }  // namespace
 
 int schwz_partition_graph(const schwz_problem *p, int P, uint32_t *part)
-{
+try {
     SCHWZ_REQUIRE(p && part && P > 0, "schwz_partition_graph: bad arguments");
     static const bool multilevel = [] {
         const char *e = std::getenv("SCHWZ_PART_MULTILEVEL");
@@ -977,6 +1167,7 @@ int schwz_partition_graph(const schwz_problem *p, int P, uint32_t *part)
     if (p->N > 0) bisect(p, nodes, P, 0, part, mark, stamp);
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_partition_graph")
 
 // ---------------------------------------------------------------------------
 // subdomain index sets (restricted_schwarz.cpp:56-304) and get lists (:336-371)
@@ -984,14 +1175,18 @@ int schwz_partition_graph(const schwz_problem *p, int P, uint32_t *part)
 
 int schwz_subdomain_setup(const schwz_problem *p, int P, int me, int overlap, const int64_t *first_row,
                           schwz_subdomain **out)
-{
+try {
     SCHWZ_REQUIRE(p && out && first_row, "schwz_subdomain_setup: null argument");
     SCHWZ_REQUIRE(P > 0 && me >= 0 && me < P, "schwz_subdomain_setup: bad rank / subdomain count");
     SCHWZ_REQUIRE(overlap >= 1, "schwz_subdomain_setup: overlap must be >= 1");
     SCHWZ_REQUIRE(first_row[0] == 0 && first_row[P] == p->N, "schwz_subdomain_setup: first_row must cover all rows");
+    for (int q = 0; q < P; ++q)  // (with both ends fixed: every entry inside [0, N])
+        SCHWZ_REQUIRE(first_row[q] <= first_row[q + 1],
+                      "schwz_subdomain_setup: first_row must not decrease (subdomain " + std::to_string(q) + ")");
     StageTimer timer_all("subdomain_setup (index sets, local / interface matrices, get lists)");
     p->missing_row = -1;  // see schwz_problem_extract_rows
-    auto *sd = new schwz_subdomain();
+    std::unique_ptr<schwz_subdomain> owner(new schwz_subdomain());
+    schwz_subdomain *const sd = owner.get();
     sd->P = P;
     sd->me = me;
     sd->overlap = overlap;
@@ -1000,7 +1195,6 @@ int schwz_subdomain_setup(const schwz_problem *p, int P, int me, int overlap, co
     const int64_t lo = first_row[me], hi = first_row[me + 1];
     sd->local_size = hi - lo;
     if (sd->local_size >= INT32_MAX / 2) {
-        delete sd;
         set_error("schwz_subdomain_setup: subdomain too large for int32 local indices");
         return SCHWZ_ERR_INVALID;
     }
@@ -1102,8 +1296,7 @@ int schwz_subdomain_setup(const schwz_problem *p, int P, int me, int overlap, co
         for (int64_t r = 0; r < n; ++r) {
             nnz_l += cnt[(size_t)r];
             if (nnz_l >= INT32_MAX) {
-                delete sd;
-                set_error("schwz_subdomain_setup: local matrix exceeds 2^31-1 nonzeros");
+                        set_error("schwz_subdomain_setup: local matrix exceeds 2^31-1 nonzeros");
                 return SCHWZ_ERR_INVALID;
             }
             sd->l_rp[(size_t)r + 1] = (schwz_idx)nnz_l;
@@ -1181,15 +1374,15 @@ int schwz_subdomain_setup(const schwz_problem *p, int P, int me, int overlap, co
         }
     }
     if (p->missing_row >= 0) {  // a row source that holds part of the matrix only (schwz_problem_from_rows)
-        delete sd;
         set_error("schwz_subdomain_setup: the problem does not hold a row this subdomain reads (row " +
                   std::to_string(p->missing_row) + ")");
         p->missing_row = -1;
         return SCHWZ_ERR_INVALID;
     }
-    *out = sd;
+    *out = owner.release();
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_subdomain_setup")
 
 int schwz_subdomain_sizes(const schwz_subdomain *sd, int64_t *s)
 {
@@ -1255,7 +1448,7 @@ int schwz_subdomain_put_list(const schwz_subdomain *sd, int k, int *rank, int64_
 }
 
 int schwz_subdomain_add_put_list(schwz_subdomain *sd, int p, int64_t count, const int64_t *ids)
-{
+try {
     SCHWZ_REQUIRE(sd && (ids || count == 0), "schwz_subdomain_add_put_list: null argument");
     SCHWZ_REQUIRE(!sd->on_device, "schwz_subdomain_add_put_list: lists are frozen after to_device");
     SCHWZ_REQUIRE(p >= 0 && p < sd->P && p != sd->me, "schwz_subdomain_add_put_list: bad neighbour rank");
@@ -1270,6 +1463,7 @@ int schwz_subdomain_add_put_list(schwz_subdomain *sd, int p, int64_t count, cons
     sd->num_send += count;
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_subdomain_add_put_list")
 
 static int offset_of(const std::vector<std::vector<int64_t>> &lists, int k, int64_t *off)
 {
@@ -1334,9 +1528,13 @@ static void rcm(int64_t n, const schwz_idx *rp, const schwz_idx *col, std::vecto
 int schwz_cholesky(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double *val, int natural,
                    schwz_idx **l_rp_o, schwz_idx **l_col_o, double **l_val_o, schwz_idx **u_rp_o,
                    schwz_idx **u_col_o, double **u_val_o, schwz_idx **perm_o)
-{
+try {
     SCHWZ_REQUIRE(rp && l_rp_o && l_col_o && l_val_o && u_rp_o && u_col_o && u_val_o && perm_o && n >= 0,
                   "schwz_cholesky: bad arguments");
+    {
+        std::string what;
+        SCHWZ_REQUIRE(csr_rows_strictly_ascending(n, n, rp, col, &what), "schwz_cholesky: " + what);
+    }
     std::vector<schwz_idx> perm;
     if (natural) {
         perm.resize((size_t)n);
@@ -1457,6 +1655,7 @@ int schwz_cholesky(int64_t n, const schwz_idx *rp, const schwz_idx *col, const d
     *perm_o = to_malloc(perm);
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_cholesky")
 
 // ---------------------------------------------------------------------------
 // sparse LU with threshold partial pivoting (left-looking, Gilbert-Peierls)
@@ -1469,14 +1668,15 @@ int schwz_cholesky(int64_t n, const schwz_idx *rp, const schwz_idx *col, const d
 int schwz_lu(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double *val, int natural,
              schwz_idx **l_rp_o, schwz_idx **l_col_o, double **l_val_o, schwz_idx **u_rp_o, schwz_idx **u_col_o,
              double **u_val_o, schwz_idx **row_perm_o, schwz_idx **col_perm_o)
-{
+try {
     SCHWZ_REQUIRE(rp && l_rp_o && l_col_o && l_val_o && u_rp_o && u_col_o && u_val_o && row_perm_o && col_perm_o &&
                       n >= 0 && n < INT_MAX,
                   "schwz_lu: bad arguments");
     const size_t N = (size_t)n;
-    for (int64_t i = 0; i < n; ++i)
-        for (schwz_idx t = rp[i]; t < rp[i + 1]; ++t)
-            SCHWZ_REQUIRE(col[t] >= 0 && col[t] < n, "schwz_lu: column index out of range");
+    {
+        std::string what;
+        SCHWZ_REQUIRE(csr_rows_strictly_ascending(n, n, rp, col, &what), "schwz_lu: " + what);
+    }
     // A in CSC: column c's rows and values
     std::vector<schwz_idx> cp(N + 1, 0), ci((size_t)rp[n]);
     std::vector<double> cx((size_t)rp[n]);
@@ -1646,14 +1846,19 @@ int schwz_lu(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double 
     *col_perm_o = to_malloc(q);
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_lu")
 
 // ISAI of a triangular factor on its own pattern (Anzt, Huckle, Braeckle, Dongarra 2018): per row
 // one small triangular substitution with T(S,S), S the row's pattern; rows are independent.
 int schwz_isai(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double *val, int lower, double **w_val)
-{
+try {
     if (!rp || !w_val || n < 0 || (n > 0 && (!col || !val))) {
         set_error("schwz_isai: bad arguments");
         return SCHWZ_ERR_INVALID;
+    }
+    {
+        std::string what;  // (entry() below finds a column by bisection)
+        SCHWZ_REQUIRE(csr_rows_strictly_ascending(n, n, rp, col, &what), "schwz_isai: " + what);
     }
     const int64_t nnz = n ? rp[n] : 0;
     std::vector<double> w((size_t)nnz);
@@ -1693,12 +1898,13 @@ int schwz_isai(int64_t n, const schwz_idx *rp, const schwz_idx *col, const doubl
     *w_val = to_malloc(w);
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_isai")
 
 // ILU(0), row by row (IKJ): for every k < i in row i: l_ik = a_ik / u_kk, then row i loses
 // l_ik * (row k of U) on the positions it stores.
 int schwz_ilu0(int64_t n, const schwz_idx *rp, const schwz_idx *col, const double *val, schwz_idx **l_rp_o,
                schwz_idx **l_col_o, double **l_val_o, schwz_idx **u_rp_o, schwz_idx **u_col_o, double **u_val_o)
-{
+try {
     SCHWZ_REQUIRE(rp && l_rp_o && l_col_o && l_val_o && u_rp_o && u_col_o && u_val_o && n >= 0,
                   "schwz_ilu0: bad arguments");
     const int64_t nnz = rp[n];
@@ -1755,6 +1961,7 @@ int schwz_ilu0(int64_t n, const schwz_idx *rp, const schwz_idx *col, const doubl
     *u_val_o = to_malloc(u_val);
     return SCHWZ_OK;
 }
+SCHWZ_GUARD("schwz_ilu0")
 
 }  // extern "C"
 

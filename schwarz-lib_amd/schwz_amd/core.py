@@ -527,11 +527,23 @@ class Problem:
         check(lib.schwz_problem_laplacian(dim, nx, ny, nz, C.byref(h)))
         return cls(h)
 
+    @staticmethod
+    def _check_lengths(who, rp, col, val):
+        """The library reads col and val up to row_ptr[-1]: arrays that end before that are refused here."""
+        if rp.ndim != 1 or col.ndim != 1 or val.ndim != 1 or len(rp) < 1:
+            raise capi.SchwzError(capi.ERR_INVALID, who + ": row_ptr, col and val must be 1-D, row_ptr not empty")
+        if min(len(col), len(val)) < int(rp[-1]):
+            raise capi.SchwzError(capi.ERR_INVALID, "%s: row_ptr ends at %d, col holds %d and val %d entries"
+                             % (who, int(rp[-1]), len(col), len(val)))
+
     @classmethod
     def from_csr(cls, rp, col, val):
+        """Rows may be unsorted and may hold a column more than once: they are stable-sorted and the entries of one
+        column summed in stored order (schwz_problem_from_csr)."""
         rp = np.ascontiguousarray(rp, dtype=np.int64)
         col = np.ascontiguousarray(col, dtype=IDX)
         val = np.ascontiguousarray(val, dtype=np.float64)
+        cls._check_lengths("Problem.from_csr", rp, col, val)
         h = C.c_void_p()
         check(lib.schwz_problem_from_csr(len(rp) - 1, ptr(rp), ptr(col), ptr(val), C.byref(h)))
         return cls(h)
@@ -544,6 +556,9 @@ class Problem:
         rp = np.ascontiguousarray(rp, dtype=np.int64)
         col = np.ascontiguousarray(col, dtype=IDX)
         val = np.ascontiguousarray(val, dtype=np.float64)
+        cls._check_lengths("Problem.from_rows", rp, col, val)
+        if row_ids.ndim != 1 or len(rp) != len(row_ids) + 1:
+            raise capi.SchwzError(capi.ERR_INVALID, "Problem.from_rows: row_ptr must hold len(row_ids) + 1 entries")
         h = C.c_void_p()
         check(lib.schwz_problem_from_rows(int(N), len(row_ids), ptr(row_ids), ptr(rp), ptr(col), ptr(val),
                                           C.byref(h)))

@@ -345,3 +345,97 @@ def test_partial_problem_recovers_after_a_missing_row(schwz, oracle):
         schwz.Subdomain(part, 2, 0, 2, schwz.partition_regular(full.N, 2))
     got = part.extract_rows(held[:3])
     assert np.array_equal(got[0], full.extract_rows(held[:3])[0])
+
+
+# ---- the ingest boundary through the product library (ctypes): the error code, and the process survives.  The same
+# ---- cases and many more run under the sanitizers in tests/test_ingest.py.
+
+_MM = "%%MatrixMarket matrix coordinate "
+
+
+def _read(schwz, tmp_path, text):
+    path = tmp_path / "m.mtx"
+    path.write_bytes(text.encode())
+    return schwz.Problem.from_matrix_market(str(path)).to_csr()
+
+
+@pytest.mark.parametrize("name,text,word", [
+    ("row_index_past_n", _MM + "real general\n3 3 3\n1 1 1.0\n4 2 2.0\n3 3 3.0\n", "entry 2"),
+    ("row_index_0", _MM + "real general\n3 3 3\n1 1 1.0\n0 2 2.0\n3 3 3.0\n", "entry 2"),
+    ("negative_count", _MM + "real general\n3 3 -1\n1 1 1.0\n", "-1 entries"),
+    ("count_beyond_the_file", _MM + "real general\n3 3 4000000000000000000\n1 1 1.0\n", "truncated"),
+    ("n_beyond_32_bits", _MM + "real general\n4294967297 4294967297 1\n1 1 1.0\n", "4294967297"),
+    ("complex", _MM + "complex general\n2 2 2\n1 1 2 0\n2 2 3 0\n", "\"complex\""),
+    ("missing_value", _MM + "real general\n3 3 3\n1 1 1.0\n3 3 3.0\n2 2\n", "entry 3"),
+    ("value_nan", _MM + "real general\n3 3 1\n1 1 nan\n", "\"nan\""),
+    ("above_the_diagonal", _MM + "real symmetric\n3 3 2\n1 1 1.0\n1 2 5.0\n", "entry 2"),
+    ("content_after_the_last_entry", _MM + "real general\n3 3 1\n1 1 1.0\n2 2 2.0\n", "after the last"),
+])
+def test_matrix_market_refusals_through_the_library(schwz, tmp_path, name, text, word):
+    with pytest.raises(schwz.SchwzError) as e:
+        _read(schwz, tmp_path, text)
+    assert e.value.code == schwz.capi.ERR_IO and word in str(e.value)
+    # the process is alive and the library still reads a file
+    rp, col, val = _read(schwz, tmp_path, _MM + "real general\n1 1 1\n1 1 2.5\n")
+    assert rp.tolist() == [0, 1] and col.tolist() == [0] and val.tolist() == [2.5]
+
+
+def test_matrix_market_accepted_forms_through_the_library(schwz, tmp_path):
+    # skew-symmetric: the mirror is -v ("symmetric" inside the word is not the symmetry)
+    rp, col, val = _read(schwz, tmp_path, _MM + "real skew-symmetric\n3 3 2\n2 1 5\n3 2 7\n")
+    assert rp.tolist() == [0, 1, 3, 4] and col.tolist() == [1, 0, 2, 1] and val.tolist() == [-5.0, 5.0, -7.0, 7.0]
+    # symmetric with duplicates: summed in file order ((1e16 + 1) + -1e16 == 0, stored), the mirror alike
+    rp, col, val = _read(schwz, tmp_path,
+                         _MM + "real symmetric\n2 2 5\n1 1 1.0\n1 1 2.0\n2 1 1e16\n2 1 1.0\n2 1 -1e16\n")
+    assert rp.tolist() == [0, 2, 3] and col.tolist() == [0, 1, 0] and val.tolist() == [3.0, 0.0, 0.0]
+    # pattern and integer fields, mixed case, CRLF
+    rp, col, val = _read(schwz, tmp_path, "%%MatrixMarket MATRIX Coordinate PATTERN General\r\n% c\r\n\r\n2 2 2\r\n2 1\r\n1 2\r\n\r\n")
+    assert rp.tolist() == [0, 1, 2] and col.tolist() == [1, 0] and val.tolist() == [1.0, 1.0]
+    rp, col, val = _read(schwz, tmp_path, _MM + "integer symmetric\n2 2 3\n1 1 4\n2 1 -1\n2 2 4\n")
+    assert col.tolist() == [0, 1, 0, 1] and val.tolist() == [4.0, -1.0, -1.0, 4.0]
+
+
+def test_problem_from_arrays_refusals_through_the_library(schwz):
+    col3, val3 = np.array([0, 1, 2], dtype=np.int32), np.ones(3)
+    bad = [(np.array([0, 3, 1, 2]), col3, val3),           # not monotone
+           (np.array([0, -2, -1]), col3[:1], val3[:1]),   # negative
+           (np.array([1, 2, 3]), col3, val3),             # does not start at 0
+           (np.array([0, 1, 2, 3]), np.array([0, 3, 2], dtype=np.int32), val3),   # column >= N
+           (np.array([0, 1, 2, 3]), np.array([0, -1, 2], dtype=np.int32), val3),  # column < 0
+           (np.array([], dtype=np.int64), col3, val3),    # the wrapper: no row_ptr at all
+           (np.array([0, 2, 4, 6]), col3, val3),          # the wrapper: col ends before row_ptr[-1]
+           (np.array([0, 1, 2, 3]), col3, val3[:2])]      # the wrapper: val ends before row_ptr[-1]
+    for rp, col, val in bad:
+        with pytest.raises(schwz.SchwzError) as e:
+            schwz.Problem.from_csr(rp, col, val)
+        assert e.value.code == schwz.capi.ERR_INVALID, (rp, str(e.value))
+    with pytest.raises(schwz.SchwzError) as e:
+        schwz.Problem.from_rows(6, np.array([1, 3]), np.array([0, 2, 4, 6]), col3, val3)
+    assert e.value.code == schwz.capi.ERR_INVALID
+    with pytest.raises(schwz.SchwzError) as e:
+        schwz.Problem.from_rows(6, np.array([1, 3]), np.array([0, 2, 1]), col3, val3)
+    assert e.value.code == schwz.capi.ERR_INVALID
+    # unsorted rows are sorted, duplicates summed in stored order, and the library is still usable
+    rp, col, val = schwz.Problem.from_csr(np.array([0, 5, 6]), np.array([1, 0, 1, 0, 1, 1], dtype=np.int32),
+                                          np.array([1e16, 5.0, 1.0, 7.0, -1e16, 2.0])).to_csr()
+    assert rp.tolist() == [0, 2, 3] and col.tolist() == [0, 1, 1] and val.tolist() == [12.0, 0.0, 2.0]
+
+
+def test_setup_and_factorization_refusals_through_the_library(schwz, oracle):
+    rp, col, val = oracle.laplacian2d(6)
+    prob = schwz.Problem.from_csr(rp, col, val)
+    with pytest.raises(schwz.SchwzError) as e:
+        schwz.Subdomain(prob, 3, 0, 2, np.array([0, 40, 20, 36], dtype=np.int64))
+    assert e.value.code == schwz.capi.ERR_INVALID and "first_row" in str(e.value)
+    urp = np.array([0, 1, 3, 5], dtype=np.int32)
+    good = (urp, np.array([0, 0, 1, 1, 2], dtype=np.int32), np.array([2.0, -1.0, 2.0, -1.0, 2.0]))
+    unsorted = (urp, np.array([0, 1, 0, 1, 2], dtype=np.int32), np.array([2.0, 2.0, -1.0, -1.0, 2.0]))
+    twice = (urp, np.array([0, 1, 1, 1, 2], dtype=np.int32), np.array([2.0, 1.0, 1.0, -1.0, 2.0]))
+    past = (urp, np.array([0, 0, 1, 1, 3], dtype=np.int32), np.array([2.0, -1.0, 2.0, -1.0, 2.0]))
+    calls = (lambda a: schwz.cholesky(*a, True), lambda a: schwz.lu(*a, natural=True), lambda a: schwz.isai(*a, True))
+    for call in calls:
+        call(good)
+        for rows in (unsorted, twice, past):
+            with pytest.raises(schwz.SchwzError) as e:
+                call(rows)
+            assert e.value.code == schwz.capi.ERR_INVALID
