@@ -674,13 +674,6 @@ int schwz_bcg_residual(schwz_bcg *s, const double *d_b, const double *d_x, doubl
 // lists and write nothing the single-vector entry points read.
 // ===========================================================================
 
-struct schwz_ras_batch {
-    int k = 0;
-    schwz_bcg *cg = nullptr;
-    Dev<double> x, rhs, bt, y;
-    ~schwz_ras_batch() { schwz_bcg_destroy(cg); }
-};
-
 namespace schwz {
 
 // into[e * k + j] = from[idx[e] * k + j] (PACK) or into[idx[e] * k + j] = from[e * k + j]: send and receive buffers are
@@ -731,42 +724,42 @@ __global__ __launch_bounds__(kBlock) void batch_restrict_kernel(int64_t count, i
 
 }  // namespace schwz
 
-#define REQUIRE_BATCH(sd, name)                                                                   \
-    SCHWZ_REQUIRE((sd) && (sd)->on_device, name ": subdomain is not on the device");              \
-    SCHWZ_REQUIRE((sd)->batch, name ": the subdomain has no block state (schwz_ras_batch_begin)")
+#define REQUIRE_BATCH(sd, name)                                                 \
+    SCHWZ_REQUIRE((sd) && (sd)->dev, name ": subdomain is not on the device"); \
+    SCHWZ_REQUIRE((sd)->dev->batch, name ": the subdomain has no block state (schwz_ras_batch_begin)")
 
 extern "C" {
 
 int schwz_ras_batch_begin(schwz_subdomain *sd, int k)
 {
     SCHWZ_REQUIRE(batch_k_ok(k), "schwz_ras_batch_begin: k must be 2, 4 or 8");
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_batch_begin: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_batch_begin: subdomain is not on the device");
     const schwz_solver_options &o = sd->opt;
     const bool jacobi = o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1);
-    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || sd->gmres || sd->bicg ||
+    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || sd->dev->gmres || sd->dev->bicg ||
         !(jacobi || o.precond == SCHWZ_PRECOND_NONE) || o.par_ilu_sweeps || o.trisolve_sweeps ||
-        sd->precision != SCHWZ_PRECISION_F64 || sd->sym_solver != SCHWZ_SYM_CG || sd->coarse) {
+        sd->precision != SCHWZ_PRECISION_F64 || sd->sym_solver != SCHWZ_SYM_CG || sd->dev->coarse) {
         set_error("schwz_ras_batch_begin: the block path exists for the fp64 CG local solve of a symmetric matrix, without a "
                   "preconditioner or with scalar Jacobi, on one level");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
-    if (sd->batch && sd->batch->k != k) {
-        delete sd->batch;
-        sd->batch = nullptr;
+    if (sd->dev->batch && sd->dev->batch->k != k) {
+        delete sd->dev->batch;
+        sd->dev->batch = nullptr;
     }
     const int64_t n = sd->local_size_x, nx = n + sd->halo_size;
-    if (!sd->batch) {
+    if (!sd->dev->batch) {
         schwz_ras_batch *b = new schwz_ras_batch();
         b->k = k;
         int rc;
-        if ((rc = schwz_bcg_create(sd->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, k, &b->cg)) ||
+        if ((rc = schwz_bcg_create(sd->dev->A, jacobi ? SCHWZ_PRECOND_JACOBI : SCHWZ_PRECOND_NONE, k, &b->cg)) ||
             (rc = b->x.alloc((size_t)nx * k, true)) || (rc = b->rhs.alloc((size_t)n * k, true)) ||
             (rc = b->bt.alloc((size_t)n * k, true)) || (rc = b->y.alloc((size_t)n * k, true))) {
             delete b;
             return rc;
         }
         SCHWZ_HIP_TRY(hipDeviceSynchronize());
-        sd->batch = b;
+        sd->dev->batch = b;
     }
     return SCHWZ_OK;
 }
@@ -774,8 +767,9 @@ int schwz_ras_batch_begin(schwz_subdomain *sd, int k)
 int schwz_ras_batch_end(schwz_subdomain *sd)
 {
     SCHWZ_REQUIRE(sd, "schwz_ras_batch_end: null subdomain");
-    delete sd->batch;
-    sd->batch = nullptr;
+    if (!sd->dev) return SCHWZ_OK;
+    delete sd->dev->batch;
+    sd->dev->batch = nullptr;
     return SCHWZ_OK;
 }
 
@@ -783,7 +777,7 @@ int schwz_ras_batch_rhs_set(schwz_subdomain *sd, const double *h_rhs, schwz_stre
 {
     REQUIRE_BATCH(sd, "schwz_ras_batch_rhs_set");
     SCHWZ_REQUIRE(h_rhs || sd->local_size_x == 0, "schwz_ras_batch_rhs_set: null right-hand side");
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     hipStream_t st = (hipStream_t)stream;
     const size_t nk = (size_t)sd->local_size_x * b->k, nxk = (size_t)(sd->local_size_x + sd->halo_size) * b->k;
     // the state a fresh upload leaves: x~ and y zero, b~ = b
@@ -803,9 +797,9 @@ int schwz_ras_batch_pack(schwz_subdomain *sd, double *d_send, schwz_stream strea
     REQUIRE_BATCH(sd, "schwz_ras_batch_pack");
     if (sd->num_send == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_send, "schwz_ras_batch_pack: null send buffer");
-    const int k = sd->batch->k;
+    const int k = sd->dev->batch->k;
     hipLaunchKernelGGL(batch_halo_kernel<true>, dim3(grid_for(sd->num_send * k)), dim3(kBlock), 0, (hipStream_t)stream,
-                       sd->num_send, k, (const schwz_idx *)sd->d_put_idx, (const double *)sd->batch->x, d_send);
+                       sd->num_send, k, (const schwz_idx *)sd->dev->d_put_idx, (const double *)sd->dev->batch->x, d_send);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }
@@ -815,9 +809,9 @@ int schwz_ras_batch_unpack(schwz_subdomain *sd, const double *d_recv, schwz_stre
     REQUIRE_BATCH(sd, "schwz_ras_batch_unpack");
     if (sd->num_recv == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_recv, "schwz_ras_batch_unpack: null recv buffer");
-    const int k = sd->batch->k;
+    const int k = sd->dev->batch->k;
     hipLaunchKernelGGL(batch_halo_kernel<false>, dim3(grid_for(sd->num_recv * k)), dim3(kBlock), 0, (hipStream_t)stream,
-                       sd->num_recv, k, (const schwz_idx *)sd->d_get_idx, d_recv, (double *)sd->batch->x);
+                       sd->num_recv, k, (const schwz_idx *)sd->dev->d_get_idx, d_recv, (double *)sd->dev->batch->x);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }
@@ -827,10 +821,10 @@ int schwz_ras_batch_update_boundary(schwz_subdomain *sd, schwz_stream stream)
     REQUIRE_BATCH(sd, "schwz_ras_batch_update_boundary");
     // as schwz_ras_update_boundary: rows < local_size have no interface entries, b~ = b there
     if (sd->P <= 1 || sd->nnz_interface == 0 || sd->overlap_size == 0) return SCHWZ_OK;
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     hipLaunchKernelGGL(batch_interface_kernel, dim3(grid_for(sd->overlap_size * b->k)), dim3(kBlock), 0, (hipStream_t)stream,
-                       sd->overlap_size, sd->local_size, b->k, (const schwz_idx *)sd->d_i_rp, (const schwz_idx *)sd->d_i_col,
-                       (const double *)sd->d_i_val, (const double *)b->x, (const double *)b->rhs, (double *)b->bt);
+                       sd->overlap_size, sd->local_size, b->k, (const schwz_idx *)sd->dev->d_i_rp, (const schwz_idx *)sd->dev->d_i_col,
+                       (const double *)sd->dev->d_i_val, (const double *)b->x, (const double *)b->rhs, (double *)b->bt);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }
@@ -839,7 +833,7 @@ int schwz_ras_batch_local_residual(schwz_subdomain *sd, double *h_resnorm, schwz
 {
     REQUIRE_BATCH(sd, "schwz_ras_batch_local_residual");
     SCHWZ_REQUIRE(h_resnorm, "schwz_ras_batch_local_residual: null output");
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     const int rc = bcg_residual_impl(b->cg, b->bt, b->x, nullptr, INT64_MAX, h_resnorm, (hipStream_t)stream);
     if (rc) return rc;
     for (int j = 0; j < b->k; ++j) h_resnorm[j] = std::sqrt(h_resnorm[j]);
@@ -849,7 +843,7 @@ int schwz_ras_batch_local_residual(schwz_subdomain *sd, double *h_resnorm, schwz
 int schwz_ras_batch_local_solve(schwz_subdomain *sd, unsigned frozen, int *h_inner_iters, schwz_stream stream)
 {
     REQUIRE_BATCH(sd, "schwz_ras_batch_local_solve");
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     const int maxit = sd->opt.local_max_iters == -1 ? (int)sd->local_size_x : sd->opt.local_max_iters;
     return schwz_bcg_solve(b->cg, b->bt, b->y, sd->opt.local_tol, maxit, frozen, h_inner_iters, nullptr, stream);
 }
@@ -857,7 +851,7 @@ int schwz_ras_batch_local_solve(schwz_subdomain *sd, unsigned frozen, int *h_inn
 int schwz_ras_batch_restrict(schwz_subdomain *sd, unsigned frozen, schwz_stream stream)
 {
     REQUIRE_BATCH(sd, "schwz_ras_batch_restrict");
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     SCHWZ_REQUIRE((frozen >> b->k) == 0, "schwz_ras_batch_restrict: the mask names a column >= k");
     const int64_t count = sd->local_size * b->k;
     if (count == 0) return SCHWZ_OK;
@@ -872,7 +866,7 @@ int schwz_ras_batch_vector(schwz_subdomain *sd, int which, double **d_ptr, int64
     REQUIRE_BATCH(sd, "schwz_ras_batch_vector");
     SCHWZ_REQUIRE(d_ptr && len, "schwz_ras_batch_vector: null output");
     SCHWZ_REQUIRE(which >= 0 && which <= 3, "schwz_ras_batch_vector: which must be 0 (x~), 1 (b~), 2 (y) or 3 (b)");
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     const int64_t n = sd->local_size_x * b->k;
     *d_ptr = which == 0 ? b->x : which == 1 ? b->bt : which == 2 ? b->y : b->rhs;
     *len = which == 0 ? n + sd->halo_size * b->k : n;
@@ -884,7 +878,7 @@ int schwz_ras_batch_get_interior(schwz_subdomain *sd, double *h_out, schwz_strea
     REQUIRE_BATCH(sd, "schwz_ras_batch_get_interior");
     SCHWZ_REQUIRE(h_out || sd->local_size == 0, "schwz_ras_batch_get_interior: null output");
     if (sd->local_size == 0) return SCHWZ_OK;
-    SCHWZ_HIP_TRY(hipMemcpyAsync(h_out, sd->batch->x, (size_t)sd->local_size * sd->batch->k * sizeof(double),
+    SCHWZ_HIP_TRY(hipMemcpyAsync(h_out, sd->dev->batch->x, (size_t)sd->local_size * sd->dev->batch->k * sizeof(double),
                                  hipMemcpyDeviceToHost, (hipStream_t)stream));
     SCHWZ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return SCHWZ_OK;
@@ -894,7 +888,7 @@ int schwz_ras_batch_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_s
 {
     REQUIRE_BATCH(sd, "schwz_ras_batch_true_residual_sq");
     SCHWZ_REQUIRE(h_out, "schwz_ras_batch_true_residual_sq: null output");
-    schwz_ras_batch *b = sd->batch;
+    schwz_ras_batch *b = sd->dev->batch;
     return bcg_residual_impl(b->cg, b->rhs, b->x, nullptr, sd->local_size, h_out, (hipStream_t)stream);
 }
 

@@ -727,7 +727,7 @@ static int pcg_build(schwz_pcg *s, const schwz_csr *A, int precond)
     int rc;
     if ((rc = s->r.alloc(n)) || (rc = s->p.alloc(n)) || (rc = s->q.alloc(n)) || (rc = s->partials.alloc(8 * kMaxGrid)))
         return rc;
-    s->stream_part.p = stream_part_alloc(A->v);
+    s->stream_part = stream_part_alloc(A->v);
     if ((rc = s->norm_sq_own.alloc(2)) || (rc = s->state.create())) return rc;
     s->d_norm_sq = s->norm_sq_own;
     if (precond == SCHWZ_PRECOND_JACOBI) {
@@ -1474,17 +1474,13 @@ struct CgSolve {
         if (hipStreamBeginCapture(s->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             int rc = SCHWZ_OK;
             for (int k = 0; k < kGraphIters && !rc; ++k) rc = iterate(k, s->capture_stream, false);
-            hipGraph_t graph = nullptr;
-            const hipError_t e1 = hipStreamEndCapture(s->capture_stream, &graph);
-            if (rc) {
-                if (graph) (void)hipGraphDestroy(graph);
-                return rc;
-            }
+            Graph graph;
+            const hipError_t e1 = hipStreamEndCapture(s->capture_stream, &graph.h);
+            if (rc) return rc;
             if (e1 == hipSuccess && hipGraphInstantiate(out, graph, nullptr, nullptr, 0) == hipSuccess)
                 s->graphs.push_back({d_x, rtol, s->variant, pl.flavour, GraphExec(*out)});
             else
                 *out = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
         }
         (void)hipGetLastError();
         return SCHWZ_OK;

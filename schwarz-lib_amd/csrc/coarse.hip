@@ -177,7 +177,7 @@ int schwz_coarse_solve(schwz_coarse *c, schwz_stream stream)
 
 int schwz_ras_coarse_set_aggregates(schwz_subdomain *sd, const int32_t *h_slot_agg, int32_t first_agg, int32_t m, int32_t nc)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_coarse_set_aggregates: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_coarse_set_aggregates: subdomain is not on the device");
     if (sd->P > 1 && sd->overlap < 2) {
         // the local matrix of such a subdomain drops the couplings of its interior rows to other subdomains
         set_error("schwz_ras_coarse_set_aggregates: the coarse correction needs overlap >= 2 on more than one subdomain");
@@ -186,7 +186,7 @@ int schwz_ras_coarse_set_aggregates(schwz_subdomain *sd, const int32_t *h_slot_a
     StageTimer timer("coarse plan + upload");
     const int64_t n = sd->local_size, nslots = sd->local_size_x + sd->halo_size;
     std::vector<double> rhs((size_t)n);
-    if (n) SCHWZ_HIP_TRY(hipMemcpy(rhs.data(), sd->d_rhs, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (n) SCHWZ_HIP_TRY(hipMemcpy(rhs.data(), sd->dev->d_rhs, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     CoarsePlan plan;
     int rc = plan_coarse(n, nslots, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), rhs.data(), h_slot_agg, first_agg, m,
                          nc, &plan);
@@ -208,30 +208,30 @@ int schwz_ras_coarse_set_aggregates(schwz_subdomain *sd, const int32_t *h_slot_a
         return rc;
     part->rows = std::move(plan.rows);
     SCHWZ_HIP_TRY(hipDeviceSynchronize());
-    delete sd->coarse;
-    sd->coarse = part.release();
+    delete sd->dev->coarse;
+    sd->dev->coarse = part.release();
     return SCHWZ_OK;
 }
 
 int schwz_ras_coarse_rows(const schwz_subdomain *sd, double *h_rows)
 {
-    SCHWZ_REQUIRE(sd && sd->coarse, "schwz_ras_coarse_rows: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
-    SCHWZ_REQUIRE(h_rows || sd->coarse->rows.empty(), "schwz_ras_coarse_rows: null output");
-    std::copy(sd->coarse->rows.begin(), sd->coarse->rows.end(), h_rows);
+    SCHWZ_REQUIRE(sd && sd->dev && sd->dev->coarse, "schwz_ras_coarse_rows: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
+    SCHWZ_REQUIRE(h_rows || sd->dev->coarse->rows.empty(), "schwz_ras_coarse_rows: null output");
+    std::copy(sd->dev->coarse->rows.begin(), sd->dev->coarse->rows.end(), h_rows);
     return SCHWZ_OK;
 }
 
 int schwz_ras_coarse_residual(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device && sd->coarse,
+    SCHWZ_REQUIRE(sd && sd->dev && sd->dev->coarse,
                   "schwz_ras_coarse_residual: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
-    const schwz_coarse_part *p = sd->coarse;
+    const schwz_coarse_part *p = sd->dev->coarse;
     SCHWZ_REQUIRE(c && c->nc == p->nc, "schwz_ras_coarse_residual: the coarse object has another number of aggregates");
     if (p->m == 0) return SCHWZ_OK;
     hipStream_t st = (hipStream_t)stream;
     if (p->npieces > 0) {
         hipLaunchKernelGGL(coarse_partial_kernel, dim3(p->npieces), dim3(kBlock), 0, st, (const int32_t *)p->piece,
-                           (const int32_t *)p->w_slot, (const double *)p->w_val, (const double *)sd->d_x,
+                           (const int32_t *)p->w_slot, (const double *)p->w_val, (const double *)sd->dev->d_x,
                            (double *)p->partial);
         SCHWZ_HIP_TRY(hipGetLastError());
     }

@@ -1450,7 +1450,7 @@ int schwz_subdomain_put_list(const schwz_subdomain *sd, int k, int *rank, int64_
 int schwz_subdomain_add_put_list(schwz_subdomain *sd, int p, int64_t count, const int64_t *ids)
 try {
     SCHWZ_REQUIRE(sd && (ids || count == 0), "schwz_subdomain_add_put_list: null argument");
-    SCHWZ_REQUIRE(!sd->on_device, "schwz_subdomain_add_put_list: lists are frozen after to_device");
+    SCHWZ_REQUIRE(!sd->dev, "schwz_subdomain_add_put_list: lists are frozen after to_device");
     SCHWZ_REQUIRE(p >= 0 && p < sd->P && p != sd->me, "schwz_subdomain_add_put_list: bad neighbour rank");
     SCHWZ_REQUIRE(sd->nbr_out.empty() || sd->nbr_out.back() < p,
                   "schwz_subdomain_add_put_list: neighbours must be added in ascending rank order");

@@ -528,11 +528,9 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
     StageTimer timer_up("csr_create: upload of rp / col / val");
     schwz_csr *A = new schwz_csr();
     int rc;
-    if ((rc = upload(tile_nz.data(), tile_nz.size(), &A->d_tile_nz)) ||
-        (rc = upload(h_rp, (size_t)nrows + 1, &A->d_rp)) || (rc = upload(h_col, (size_t)nnz, &A->d_col, 4)) ||
-        (rc = upload(h_val, (size_t)nnz, &A->d_val, 4)) || (rc = upload(tiles.data(), tiles.size(), &A->d_tile)) ||
-        (rc = upload(wtiles.data(), wtiles.size(), &A->d_wtile)) ||
-        (!order.empty() && (rc = upload(order.data(), order.size(), &A->d_order)))) {
+    if ((rc = A->d_tile_nz.put(tile_nz)) || (rc = A->d_rp.put(h_rp, (size_t)nrows + 1)) ||
+        (rc = A->d_col.put(h_col, (size_t)nnz, 4)) || (rc = A->d_val.put(h_val, (size_t)nnz, 4)) ||
+        (rc = A->d_tile.put(tiles)) || (rc = A->d_wtile.put(wtiles)) || (!order.empty() && (rc = A->d_order.put(order)))) {
         schwz_csr_destroy(A);
         return rc;
     }
@@ -540,13 +538,13 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
     A->v.nrows = nrows;
     A->v.ncols = ncols;
     A->v.nnz = nnz;
-    A->v.rp = (const schwz_idx *)A->d_rp;
-    A->v.col = (const schwz_idx *)A->d_col;
-    A->v.val = (const double *)A->d_val;
+    A->v.rp = A->d_rp;
+    A->v.col = A->d_col;
+    A->v.val = A->d_val;
     A->v.ntiles = (int)tiles.size() - 1;
     A->h_tiles = tiles;
-    A->v.tile_row = (const schwz_idx *)A->d_tile;
-    A->v.tile_nz = (const schwz_idx *)A->d_tile_nz;
+    A->v.tile_row = A->d_tile;
+    A->v.tile_nz = A->d_tile_nz;
     A->v.stream_cap = stream_cap;
     // Wide planes (more than 2048 tiles = 512 K rows per plane, e.g. 1024 x 1024): with the block-cyclic deal an XCD
     // sweeps its share of a whole plane before it comes back to the same in-plane position of the next one -- 512
@@ -580,8 +578,8 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
             if (total == (size_t)ntl_s) {
                 std::vector<schwz_idx> flat((size_t)kXcds * nper, -1);
                 for (int x = 0; x < kXcds; ++x) std::copy(seq[(size_t)x].begin(), seq[(size_t)x].end(), flat.begin() + (size_t)x * nper);
-                if (upload(flat.data(), flat.size(), &A->d_stream_order) == SCHWZ_OK) {
-                    A->v.stream_order = (const schwz_idx *)A->d_stream_order;
+                if (A->d_stream_order.put(flat) == SCHWZ_OK) {
+                    A->v.stream_order = A->d_stream_order;
                     A->v.stream_nper = (int)nper;
                 }
             }
@@ -622,7 +620,7 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
         A->v.xcd_block = 1 << sh;
     }
     A->v.nwtiles = (int)wtiles.size() - 1;
-    A->v.wtile_row = (const schwz_idx *)A->d_wtile;
+    A->v.wtile_row = A->d_wtile;
     StageTimer timer_code("csr_create: matrix codings (patterns, pairs, walk tables)");
     if ((rc = build_spmv_dict(A, h_rp, h_col, h_val, tiles))) {
         schwz_csr_destroy(A);
@@ -634,18 +632,7 @@ int schwz_csr_create(int64_t nrows, int64_t ncols, const schwz_idx *h_rp, const 
 
 void schwz_csr_destroy(schwz_csr *A)
 {
-    if (!A) return;
-    (void)hipFree(A->d_rp);
-    (void)hipFree(A->d_col);
-    (void)hipFree(A->d_val);
-    (void)hipFree(A->d_tile);
-    (void)hipFree(A->d_tile_nz);
-    (void)hipFree(A->d_stream_order);
-    (void)hipFree(A->d_wtile);
-    (void)hipFree(A->d_order);
-    (void)hipFree(A->d_tile_dual);
-    free_spmv_dict(A);
-    delete A;
+    delete A;  // (the arrays and the codings free themselves)
 }
 
 int64_t schwz_csr_nnz(const schwz_csr *A) { return A ? A->v.nnz : 0; }
@@ -755,11 +742,9 @@ int csr_set_dual_split(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_c
         for (int64_t j = h_rp[r0]; j < h_rp[r1] && !f; ++j) f = h_col[j] >= split;
         flag[(size_t)t] = f ? 1 : 0;
     }
-    (void)hipFree(A->d_tile_dual);
-    A->d_tile_dual = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc(&A->d_tile_dual, flag.size()));
-    SCHWZ_HIP_TRY(hipMemcpy(A->d_tile_dual, flag.data(), flag.size(), hipMemcpyHostToDevice));
-    A->v.tile_dual = (const uint8_t *)A->d_tile_dual;
+    A->v.tile_dual = nullptr;
+    if (int rc = A->d_tile_dual.put(flag)) return rc;
+    A->v.tile_dual = A->d_tile_dual;
     return pair_set_dual_split(A, h_rp, h_col, split);
 }
 

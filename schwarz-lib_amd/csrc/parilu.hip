@@ -152,10 +152,10 @@ int trs_sweeps_solve(schwz_trs *t, const double *b, double *y, hipStream_t st)
 
 // ParILU symbolic pass + sweeps.  h_rp / h_col: the pattern of A on the host (columns sorted, diagonal
 // present); d_val: A's values in HBM.  Outputs: the L / U patterns (malloc'd host arrays) and their values
-// in HBM (hipMalloc'd).
+// in HBM.
 static int parilu_run(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, const double *d_val, int sweeps,
-                      schwz_idx **l_rp_o, schwz_idx **l_col_o, double **d_l_val_o, schwz_idx **u_rp_o,
-                      schwz_idx **u_col_o, double **d_u_val_o)
+                      schwz_idx **l_rp_o, schwz_idx **l_col_o, Dev<double> *d_l_val_o, schwz_idx **u_rp_o,
+                      schwz_idx **u_col_o, Dev<double> *d_u_val_o)
 {
     SCHWZ_REQUIRE(sweeps >= 1, "schwz_parilu: sweeps must be >= 1");
     SCHWZ_REQUIRE(n >= 0 && n < INT32_MAX, "schwz_parilu: bad size");
@@ -252,70 +252,48 @@ static int parilu_run(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, 
     timer_sym.stop();
     StageTimer timer_sw("parilu: upload + sweeps + pivot check");
     const int64_t lnz = l_rp[(size_t)n], unz = u_rp[(size_t)n];
-    void *d_dst = nullptr, *d_pp = nullptr, *d_pairs = nullptr, *d_lrp = nullptr, *d_urp = nullptr;
-    double *lv[2] = {nullptr, nullptr}, *uv[2] = {nullptr, nullptr};
-    int *d_bad = nullptr;
-    int rc = SCHWZ_OK;
-    auto cleanup = [&] {
-        for (void *p : {d_dst, d_pp, d_pairs, d_lrp, d_urp, (void *)d_bad}) (void)hipFree(p);
-    };
-    if ((rc = upload(dst.data(), dst.size(), &d_dst)) || (rc = upload(pp.data(), pp.size(), &d_pp)) ||
-        (rc = upload(pairs.data(), (size_t)npairs, &d_pairs)) || (rc = upload(l_rp.data(), l_rp.size(), &d_lrp)) ||
-        (rc = upload(u_rp.data(), u_rp.size(), &d_urp))) {
-        cleanup();
+    Dev<int2> d_dst, d_pairs;
+    Dev<schwz_idx> d_pp, d_lrp, d_urp;
+    Dev<double> lv[2], uv[2];
+    Dev<int> d_bad;
+    int rc;
+    if ((rc = d_dst.put(dst)) || (rc = d_pp.put(pp)) || (rc = d_pairs.put(pairs.data(), (size_t)npairs)) ||
+        (rc = d_lrp.put(l_rp)) || (rc = d_urp.put(u_rp)))
         return rc;
-    }
-    for (int b = 0; b < 2 && !rc; ++b) {
-        if (hipMalloc((void **)&lv[b], sizeof(double) * (size_t)(lnz ? lnz : 1)) != hipSuccess ||
-            hipMalloc((void **)&uv[b], sizeof(double) * (size_t)(unz ? unz : 1)) != hipSuccess)
-            rc = SCHWZ_ERR_HIP;
-    }
-    if (!rc && hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess) rc = SCHWZ_ERR_HIP;
-    auto free_vals = [&] {
-        for (int b = 0; b < 2; ++b) {
-            (void)hipFree(lv[b]);
-            (void)hipFree(uv[b]);
-        }
-    };
+    for (int b = 0; b < 2 && !rc; ++b)
+        if (!(rc = lv[b].alloc((size_t)(lnz ? lnz : 1)))) rc = uv[b].alloc((size_t)(unz ? unz : 1));
+    if (!rc) rc = d_bad.alloc(1);
     if (rc) {
         (void)hipGetLastError();
         set_error("schwz_parilu: out of device memory");
-        free_vals();
-        cleanup();
         return rc;
     }
     const int g_e = grid_for(nnz), g_n = grid_for(n);
     const hipStream_t st = nullptr;
-    hipLaunchKernelGGL(parilu_init_kernel, dim3(g_e), dim3(kBlock), 0, st, nnz, d_val, (const int2 *)d_dst, lv[0],
-                       uv[0]);
-    hipLaunchKernelGGL(parilu_unit_kernel, dim3(g_n), dim3(kBlock), 0, st, n, (const schwz_idx *)d_lrp, lv[0], lv[1]);
+    hipLaunchKernelGGL(parilu_init_kernel, dim3(g_e), dim3(kBlock), 0, st, nnz, d_val, (const int2 *)d_dst,
+                       (double *)lv[0], (double *)uv[0]);
+    hipLaunchKernelGGL(parilu_unit_kernel, dim3(g_n), dim3(kBlock), 0, st, n, (const schwz_idx *)d_lrp, (double *)lv[0],
+                       (double *)lv[1]);
     for (int s = 0; s < sweeps; ++s) {
         const int o = s & 1;
         hipLaunchKernelGGL(parilu_sweep_kernel, dim3(g_e), dim3(kBlock), 0, st, nnz, d_val, (const int2 *)d_dst,
                            (const schwz_idx *)d_pp, (const int2 *)d_pairs, (const double *)lv[o],
-                           (const double *)uv[o], lv[o ^ 1], uv[o ^ 1]);
+                           (const double *)uv[o], (double *)lv[o ^ 1], (double *)uv[o ^ 1]);
     }
     const int fin = sweeps & 1;
     int bad = 0;
     hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(parilu_pivot_kernel, dim3(g_n), dim3(kBlock), 0, st, n, (const schwz_idx *)d_urp,
-                           (const double *)uv[fin], d_bad);
+                           (const double *)uv[fin], (int *)d_bad);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(lv[fin ^ 1]);
-    (void)hipFree(uv[fin ^ 1]);
-    cleanup();
     if (e != hipSuccess) {
-        (void)hipFree(lv[fin]);
-        (void)hipFree(uv[fin]);
         set_error(std::string("schwz_parilu: ") + hipGetErrorString(e));
         return SCHWZ_ERR_HIP;
     }
     if (bad) {
-        (void)hipFree(lv[fin]);
-        (void)hipFree(uv[fin]);
         set_error("schwz_parilu: zero or non-finite pivot after " + std::to_string(sweeps) + " ParILU sweep" +
                   (sweeps == 1 ? "" : "s"));
         return SCHWZ_ERR_NOT_SPD;
@@ -329,15 +307,13 @@ static int parilu_run(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, 
     *l_col_o = to_malloc(l_col);
     *u_rp_o = to_malloc(u_rp);
     *u_col_o = to_malloc(u_col);
-    *d_l_val_o = lv[fin];
-    *d_u_val_o = uv[fin];
     if (!*l_rp_o || !*l_col_o || !*u_rp_o || !*u_col_o) {
         for (void *p : {(void *)*l_rp_o, (void *)*l_col_o, (void *)*u_rp_o, (void *)*u_col_o}) std::free(p);
-        (void)hipFree(lv[fin]);
-        (void)hipFree(uv[fin]);
         set_error("schwz_parilu: out of host memory");
         return SCHWZ_ERR_INVALID;
     }
+    *d_l_val_o = std::move(lv[fin]);
+    *d_u_val_o = std::move(uv[fin]);
     return SCHWZ_OK;
 }
 
@@ -347,7 +323,7 @@ int parilu_host_factors(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col
                         schwz_idx **l_rp, schwz_idx **l_col, double **l_val, schwz_idx **u_rp, schwz_idx **u_col,
                         double **u_val)
 {
-    double *dl = nullptr, *du = nullptr;
+    Dev<double> dl, du;
     int rc = parilu_run(n, h_rp, h_col, d_val, sweeps, l_rp, l_col, &dl, u_rp, u_col, &du);
     if (rc) return rc;
     const size_t lnz = (size_t)(*l_rp)[n], unz = (size_t)(*u_rp)[n];
@@ -358,8 +334,6 @@ int parilu_host_factors(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col
         e = hipMemcpy(*l_val, dl, sizeof(double) * lnz, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(*u_val, du, sizeof(double) * unz, hipMemcpyDeviceToHost);
     }
-    (void)hipFree(dl);
-    (void)hipFree(du);
     if (!*l_val || !*u_val || e != hipSuccess) {
         for (void *p : {(void *)*l_rp, (void *)*l_col, (void *)*l_val, (void *)*u_rp, (void *)*u_col, (void *)*u_val})
             std::free(p);
@@ -387,7 +361,12 @@ int schwz_parilu(const schwz_csr *A, int sweeps, schwz_idx **l_rp, schwz_idx **l
     SCHWZ_HIP_TRY(hipMemcpy(rp.data(), A->v.rp, rp.size() * sizeof(schwz_idx), hipMemcpyDeviceToHost));
     if (!col.empty())
         SCHWZ_HIP_TRY(hipMemcpy(col.data(), A->v.col, col.size() * sizeof(schwz_idx), hipMemcpyDeviceToHost));
-    return parilu_run(n, rp.data(), col.data(), A->v.val, sweeps, l_rp, l_col, d_l_val, u_rp, u_col, d_u_val);
+    Dev<double> dl, du;
+    if (int rc = parilu_run(n, rp.data(), col.data(), A->v.val, sweeps, l_rp, l_col, &dl, u_rp, u_col, &du)) return rc;
+    // success only: the values leave their owners for the caller (schwz_device_free)
+    *d_l_val = (double *)dl.release();
+    *d_u_val = (double *)du.release();
+    return SCHWZ_OK;
 }
 
 int schwz_parilu_host(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, const double *h_val, int sweeps,
@@ -396,12 +375,9 @@ int schwz_parilu_host(int64_t n, const schwz_idx *h_rp, const schwz_idx *h_col, 
 {
     SCHWZ_REQUIRE(h_rp && l_rp && l_col && l_val && u_rp && u_col && u_val && n >= 0, "schwz_parilu_host: bad arguments");
     SCHWZ_REQUIRE(h_rp[0] == 0 && h_rp[n] >= 0 && (h_rp[n] == 0 || (h_col && h_val)), "schwz_parilu_host: bad arguments");
-    void *d_val = nullptr;
-    int rc = upload(h_val, (size_t)h_rp[n], &d_val);
-    if (rc) return rc;
-    rc = parilu_host_factors(n, h_rp, h_col, (const double *)d_val, sweeps, l_rp, l_col, l_val, u_rp, u_col, u_val);
-    (void)hipFree(d_val);
-    return rc;
+    Dev<double> d_val;
+    if (int rc = d_val.put(h_val, (size_t)h_rp[n])) return rc;
+    return parilu_host_factors(n, h_rp, h_col, d_val, sweeps, l_rp, l_col, l_val, u_rp, u_col, u_val);
 }
 
 void schwz_device_free(void *d_ptr) { (void)hipFree(d_ptr); }
@@ -448,33 +424,19 @@ int schwz_trs_create_sweeps(int64_t n, const schwz_idx *l_rp, const schwz_idx *l
     schwz_trs *t = new schwz_trs();
     t->n = n;
     t->sweeps = sweeps;
-    int rc = 0;
-    void *d;
-#define UP(dst, vec)                                    \
-    if (!rc) {                                          \
-        rc = upload((vec).data(), (vec).size(), &d);    \
-        dst = (decltype(dst))d;                         \
-    }
-    UP(t->js_l_rp, lrp)
-    UP(t->js_l_col, lcol)
-    UP(t->js_l_val, lval)
-    UP(t->js_l_dinv, ldi)
-    UP(t->js_u_rp, urp)
-    UP(t->js_u_col, ucol)
-    UP(t->js_u_val, uval)
-    UP(t->js_u_dinv, udi)
-#undef UP
-    for (double **w : {&t->w0, &t->w1, &t->w2})
-        if (!rc && hipMalloc((void **)w, sizeof(double) * (size_t)(n ? n : 1)) != hipSuccess) {
+    std::unique_ptr<schwz_trs> own(t);
+    int rc;
+    if ((rc = t->js_l_rp.put(lrp)) || (rc = t->js_l_col.put(lcol)) || (rc = t->js_l_val.put(lval)) ||
+        (rc = t->js_l_dinv.put(ldi)) || (rc = t->js_u_rp.put(urp)) || (rc = t->js_u_col.put(ucol)) ||
+        (rc = t->js_u_val.put(uval)) || (rc = t->js_u_dinv.put(udi)))
+        return rc;
+    for (Dev<double> *w : {&t->w0, &t->w1, &t->w2})
+        if (w->alloc((size_t)(n ? n : 1))) {
             (void)hipGetLastError();
             set_error("schwz_trs_create_sweeps: out of device memory");
-            rc = SCHWZ_ERR_HIP;
+            return SCHWZ_ERR_HIP;
         }
-    if (rc) {
-        schwz_trs_destroy(t);
-        return rc;
-    }
-    *out = t;
+    *out = own.release();
     return SCHWZ_OK;
 }
 

@@ -99,18 +99,15 @@ int launch_restart(int64_t n, int64_t nx, const double *b, double *bt, double *x
 // waited for, once)
 static int ensure_rhs_index(schwz_subdomain *sd, hipStream_t st)
 {
-    if (sd->d_rhs_index) return SCHWZ_OK;
+    if (sd->dev->d_rhs_index) return SCHWZ_OK;
     const size_t n = (size_t)sd->local_size_x;
     const int64_t *h = sd->rhs_index_custom ? sd->rhs_index.data() : sd->l2g.data();
-    int64_t *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc((void **)&d, (n ? n : 1) * sizeof(int64_t)));
-    hipError_t e = n ? hipMemcpyAsync(d, h, n * sizeof(int64_t), hipMemcpyHostToDevice, st) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        SCHWZ_HIP_TRY(e);
-    }
-    sd->d_rhs_index = d;
+    Dev<int64_t> d;
+    int rc;
+    if ((rc = d.alloc(n ? n : 1))) return rc;
+    if (n) SCHWZ_HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    SCHWZ_HIP_TRY(hipStreamSynchronize(st));
+    sd->dev->d_rhs_index = std::move(d);
     return SCHWZ_OK;
 }
 
@@ -118,7 +115,7 @@ static int ensure_rhs_index(schwz_subdomain *sd, hipStream_t st)
 // aggregate stay ascending, as in plan_coarse)
 static int ensure_agg_rows(schwz_subdomain *sd, hipStream_t st)
 {
-    schwz_coarse_part *p = sd->coarse;
+    schwz_coarse_part *p = sd->dev->coarse;
     if (p->agg_ready) return SCHWZ_OK;
     const int64_t n = sd->local_size;
     const int32_t m = p->m;
@@ -154,29 +151,28 @@ extern "C" {
 
 int schwz_ras_rhs_set(schwz_subdomain *sd, const double *rhs, int on_device, schwz_stream stream)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_rhs_set: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_rhs_set: subdomain is not on the device");
     SCHWZ_REQUIRE(rhs, "schwz_ras_rhs_set: null right-hand side");
     const int64_t n = sd->local_size_x;
     if (n == 0) return SCHWZ_OK;
-    if (on_device) return launch_copy(n, rhs, sd->d_rhs, (hipStream_t)stream);
+    if (on_device) return launch_copy(n, rhs, sd->dev->d_rhs, (hipStream_t)stream);
     // (waited for: the runtime may read pageable memory after the call returns, and the array is the caller's again)
-    SCHWZ_HIP_TRY(hipMemcpyAsync(sd->d_rhs, rhs, (size_t)n * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
+    SCHWZ_HIP_TRY(hipMemcpyAsync(sd->dev->d_rhs, rhs, (size_t)n * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
     SCHWZ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return SCHWZ_OK;
 }
 
 int schwz_ras_rhs_index(schwz_subdomain *sd, const int64_t *h_index)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_rhs_index: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_rhs_index: subdomain is not on the device");
     const size_t n = (size_t)sd->local_size_x;
     if (h_index)
         for (size_t i = 0; i < n; ++i)
             SCHWZ_REQUIRE(h_index[i] >= 0 && h_index[i] < sd->N, "schwz_ras_rhs_index: an index lies outside [0, n_global)");
     // (a gather that still reads the old map on some stream must finish before the map is released)
-    if (sd->d_rhs_index) {
+    if (sd->dev->d_rhs_index) {
         SCHWZ_HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(sd->d_rhs_index);
-        sd->d_rhs_index = nullptr;
+        sd->dev->d_rhs_index = Dev<int64_t>();
     }
     sd->rhs_index_custom = h_index != nullptr;
     if (h_index)
@@ -188,7 +184,7 @@ int schwz_ras_rhs_index(schwz_subdomain *sd, const int64_t *h_index)
 
 int schwz_ras_rhs_gather(schwz_subdomain *sd, const double *d_global, int64_t n_global, schwz_stream stream)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_rhs_gather: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_rhs_gather: subdomain is not on the device");
     SCHWZ_REQUIRE(d_global, "schwz_ras_rhs_gather: null global vector");
     SCHWZ_REQUIRE(n_global == sd->N, "schwz_ras_rhs_gather: the global vector must have one entry per global row");
     const int64_t n = sd->local_size_x;
@@ -196,22 +192,22 @@ int schwz_ras_rhs_gather(schwz_subdomain *sd, const double *d_global, int64_t n_
     hipStream_t st = (hipStream_t)stream;
     const int rc = ensure_rhs_index(sd, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(rhs_gather_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, n, (const int64_t *)sd->d_rhs_index, d_global,
-                       sd->d_rhs);
+    hipLaunchKernelGGL(rhs_gather_kernel, dim3(grid_for(n)), dim3(kBlock), 0, st, n, (const int64_t *)sd->dev->d_rhs_index, d_global,
+                       sd->dev->d_rhs);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }
 
 int schwz_ras_rhs_aggregate(schwz_subdomain *sd, schwz_stream stream)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_rhs_aggregate: subdomain is not on the device");
-    schwz_coarse_part *p = sd->coarse;
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_rhs_aggregate: subdomain is not on the device");
+    schwz_coarse_part *p = sd->dev->coarse;
     if (!p || p->m == 0) return SCHWZ_OK;
     hipStream_t st = (hipStream_t)stream;
     const int rc = ensure_agg_rows(sd, st);
     if (rc) return rc;
     hipLaunchKernelGGL(rhs_aggregate_kernel, dim3((p->m + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (int)p->m,
-                       (const int32_t *)p->agg_ptr, (const int32_t *)p->agg_rows, (const double *)sd->d_rhs, (double *)p->beta);
+                       (const int32_t *)p->agg_ptr, (const int32_t *)p->agg_rows, (const double *)sd->dev->d_rhs, (double *)p->beta);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }
@@ -223,26 +219,26 @@ static int rhs_norm_sq_rows(schwz_subdomain *sd, int64_t n, double *h_out, schwz
     if (n == 0) return SCHWZ_OK;
     hipStream_t st = (hipStream_t)stream;
     const int g = grid_for((n + 1) / 2);
-    hipLaunchKernelGGL(rhs_norm_sq_kernel, dim3(g), dim3(kBlock), 0, st, n, (const double *)sd->d_rhs, sd->d_partials);
+    hipLaunchKernelGGL(rhs_norm_sq_kernel, dim3(g), dim3(kBlock), 0, st, n, (const double *)sd->dev->d_rhs, sd->dev->d_partials);
     SCHWZ_HIP_TRY(hipGetLastError());
     // (slot 1 of the mapped scalars: slot 0 may hold a check norm somebody has not waited for yet)
-    const int rc = launch_final_norm(sd->d_partials, g, sd->d_h_scalar + 1, st);
+    const int rc = launch_final_norm(sd->dev->d_partials, g, sd->dev->d_h_scalar + 1, st);
     if (rc) return rc;
     SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-    *h_out = sd->h_scalar[1];
+    *h_out = sd->dev->h_scalar.p[1];
     return SCHWZ_OK;
 }
 
 int schwz_ras_rhs_norm_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_rhs_norm_sq: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_rhs_norm_sq: subdomain is not on the device");
     SCHWZ_REQUIRE(h_out, "schwz_ras_rhs_norm_sq: null output");
     return rhs_norm_sq_rows(sd, sd->local_size, h_out, stream);
 }
 
 int schwz_ras_rhs_norm_sq_local(schwz_subdomain *sd, double *h_out, schwz_stream stream)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_rhs_norm_sq_local: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_rhs_norm_sq_local: subdomain is not on the device");
     SCHWZ_REQUIRE(h_out, "schwz_ras_rhs_norm_sq_local: null output");
     return rhs_norm_sq_rows(sd, sd->local_size_x, h_out, stream);
 }

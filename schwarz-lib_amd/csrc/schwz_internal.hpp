@@ -192,18 +192,6 @@ void set_error(const std::string &msg);
         }                                             \
     } while (0)
 
-// host vector -> fresh device allocation; `pad` extra zeroed elements follow the data (the 16-byte
-// SpMV loads may touch them)
-template <typename T>
-inline int upload(const T *h, size_t count, void **d, size_t pad = 0)
-{
-    *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc(d, (count + pad ? count + pad : 1) * sizeof(T)));
-    if (count) SCHWZ_HIP_TRY(hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice));
-    if (pad) SCHWZ_HIP_TRY(hipMemset((char *)*d + count * sizeof(T), 0, pad * sizeof(T)));
-    return SCHWZ_OK;
-}
-
 // A device allocation that frees itself.  The buffers of the matrix codings live in structs of these
 // (schwz_csr::coding): releasing a coding is assigning a fresh struct, and no pointer can be forgotten.
 struct DevBuf {
@@ -229,12 +217,28 @@ struct DevBuf {
         if (zero) SCHWZ_HIP_TRY(hipMemset(p, 0, bytes));
         return SCHWZ_OK;
     }
-    // replaces the allocation by a copy of h (plus `pad` zeroed elements)
+    // replaces the allocation by a copy of h[0:count]; `pad` extra zeroed elements follow the data (the 16-byte
+    // SpMV loads may touch them)
     template <typename T>
-    int put(const std::vector<T> &h, size_t pad = 0)
+    int put(const T *h, size_t count, size_t pad = 0)
     {
         *this = DevBuf();
-        return upload(h.data(), h.size(), &p, pad);
+        SCHWZ_HIP_TRY(hipMalloc(&p, (count + pad ? count + pad : 1) * sizeof(T)));
+        if (count) SCHWZ_HIP_TRY(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
+        if (pad) SCHWZ_HIP_TRY(hipMemset((char *)p + count * sizeof(T), 0, pad * sizeof(T)));
+        return SCHWZ_OK;
+    }
+    template <typename T, typename A>
+    int put(const std::vector<T, A> &h, size_t pad = 0)
+    {
+        return put(h.data(), h.size(), pad);
+    }
+    // hands the allocation to the caller, who frees it (the C ABI's out pointers: schwz_device_free)
+    void *release()
+    {
+        void *q = p;
+        p = nullptr;
+        return q;
     }
     template <typename T>
     const T *as() const { return static_cast<const T *>(p); }
@@ -245,6 +249,10 @@ struct DevBuf {
 template <typename T>
 struct Dev : DevBuf {
     int alloc(size_t count, bool zero = false) { return DevBuf::alloc(count * sizeof(T), zero); }
+    // (of T only: these hide DevBuf's put of any element type)
+    int put(const T *h, size_t count, size_t pad = 0) { return DevBuf::put(h, count, pad); }
+    template <typename A>
+    int put(const std::vector<T, A> &h, size_t pad = 0) { return DevBuf::put(h.data(), h.size(), pad); }
     operator T *() const { return static_cast<T *>(p); }
 };
 
@@ -258,9 +266,9 @@ struct Pinned {
     {
         if (p) (void)hipHostFree(p);
     }
-    int alloc(size_t count)  // zeroed
+    int alloc(size_t count, unsigned flags = hipHostMallocDefault)  // zeroed
     {
-        SCHWZ_HIP_TRY(hipHostMalloc((void **)&p, count * sizeof(T), hipHostMallocDefault));
+        SCHWZ_HIP_TRY(hipHostMalloc((void **)&p, count * sizeof(T), flags));
         std::memset(p, 0, count * sizeof(T));
         return SCHWZ_OK;
     }
@@ -299,6 +307,7 @@ struct Stream : Handle<hipStream_t, hipStreamDestroy> {
     }
 };
 using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
+using Graph = Handle<hipGraph_t, hipGraphDestroy>;  // the temporary of a stream capture
 
 }  // namespace schwz
 
@@ -554,17 +563,13 @@ struct SpmvArgs {
     unsigned long long *walk_probe = nullptr;
 };
 
-// SpmvArgs::stream_part for launches on A: nullptr where A needs none, or where the allocation fails (those launches
-// keep the persistent form); hipFree releases it (a solver adopts it into a Dev<double>)
-inline double *stream_part_alloc(const CsrView &A)
+// SpmvArgs::stream_part for launches on A: empty where A needs none, or where the allocation fails (those launches
+// keep the persistent form).  The solver or subdomain that launches moves it in
+inline Dev<double> stream_part_alloc(const CsrView &A)
 {
-    void *p = nullptr;
-    if (A.stream_part_cap <= 0) return nullptr;
-    if (hipMalloc(&p, (size_t)2 * A.stream_part_cap * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return (double *)p;
+    Dev<double> part;
+    if (A.stream_part_cap > 0 && part.alloc((size_t)2 * A.stream_part_cap)) (void)hipGetLastError();
+    return part;
 }
 
 // launch grid of the streaming vector kernels: one lane per element up to kMaxGrid workgroups
@@ -629,7 +634,6 @@ namespace schwz {
 // per-entry dictionaries), uploads what was accepted and binds it to A->v; the switches are read here, once
 int build_spmv_dict(schwz_csr *A, const schwz_idx *h_rp, const schwz_idx *h_col, const double *h_val,
                     const std::vector<schwz_idx> &tiles);
-void free_spmv_dict(schwz_csr *A);
 struct CodingOptions;
 struct HostCsr;
 int build_spmv_pair(schwz_csr *A, const CodingOptions &opt, const HostCsr &M);
@@ -703,9 +707,9 @@ int bicgstab_forget(schwz_bicgstab *s, hipStream_t st);
 
 struct schwz_csr {
     schwz::CsrView v;
-    void *d_rp = nullptr, *d_col = nullptr, *d_val = nullptr, *d_tile = nullptr, *d_wtile = nullptr, *d_order = nullptr;
-    void *d_tile_nz = nullptr;
-    void *d_stream_order = nullptr;
+    // (every device array frees itself: schwz_csr_destroy is `delete`)
+    schwz::Dev<schwz_idx> d_rp, d_col, d_tile, d_wtile, d_order, d_tile_nz, d_stream_order;
+    schwz::Dev<double> d_val;
     // device arrays of the codings, one struct per plan of coding_plan.hpp (uploaded and bound to `v` by
     // spmv_dict.hip / spmv_pair.hip)
     struct Coding {
@@ -717,7 +721,7 @@ struct schwz_csr {
         } walk;
         struct { schwz::DevBuf chunk_dual, chain_dual, dual_chunks; } dual;
     } coding;
-    void *d_tile_dual = nullptr;
+    schwz::Dev<uint8_t> d_tile_dual;
     std::vector<int> h_chain_plane;  // host copy of CsrView::chain_plane (z-sweep walk built)
     std::vector<schwz_idx> h_tiles;  // host copy of the tile boundaries
     int pair_deal_shift = 0;         // log2 of the run length (in tiles) of the XCD deal the pair kernels derive theirs from
@@ -822,15 +826,18 @@ struct schwz_pcg {
 
 struct schwz_trs {
     int64_t n = 0;
-    schwz_idx *l_rp = nullptr, *l_col = nullptr, *u_rp = nullptr, *u_col = nullptr;
-    double *l_val = nullptr, *u_val = nullptr;
+    // (every device array, the capture stream and the graphs free themselves: schwz_trs_destroy is `delete`)
+    schwz::Dev<schwz_idx> l_rp, l_col, u_rp, u_col;
+    schwz::Dev<double> l_val, u_val;
     // w[i] = b[perm[i]] before the sweeps, y[perm_out[i]] = w[i] after them: the same array for LL^T and
-    // ILU (perm_out == perm), the row and the column permutation of an LU (schwz_trs_create_lu)
-    schwz_idx *perm = nullptr, *perm_out = nullptr;
+    // ILU (perm_out points at perm), the row and the column permutation of an LU (schwz_trs_create_lu: perm_out
+    // points at perm_col)
+    schwz::Dev<schwz_idx> perm, perm_col;
+    const schwz_idx *perm_out = nullptr;  // borrowed
     // level schedules: rows sorted by level, level pointers
-    schwz_idx *l_order = nullptr, *l_lvl = nullptr, *u_order = nullptr, *u_lvl = nullptr;
+    schwz::Dev<schwz_idx> l_order, l_lvl, u_order, u_lvl;
     int l_nlvl = 0, u_nlvl = 0;
-    double *w0 = nullptr, *w1 = nullptr;
+    schwz::Dev<double> w0, w1;
     // launch plan for factors too large for the one-workgroup kernel: runs of narrow levels
     // (one workgroup, barriers in between) and wide levels (one multi-workgroup launch each)
     struct Seg {
@@ -845,28 +852,28 @@ struct schwz_trs {
     struct Captured {
         const double *b;
         double *y;
-        hipGraphExec_t exec;
+        schwz::GraphExec exec;
     };
     std::vector<Captured> graphs;
-    hipStream_t capture_stream = nullptr;
+    schwz::Stream capture_stream;
     bool graphs_failed = false;  // capture / instantiate refused once: launch by launch from then on
     // flag-driven sweeps (trs_flag_kernel): the two solution vectors that double as per-row flags
     bool flags = false;
-    unsigned long long *f0 = nullptr, *f1 = nullptr;
-    int *d_err = nullptr;
+    schwz::Dev<unsigned long long> f0, f1;
+    schwz::Dev<int> d_err;
     // the factors in level order (rows at their position in the level-sorted order, columns = positions)
-    schwz_idx *fl_rp = nullptr, *fl_col = nullptr, *fu_rp = nullptr, *fu_col = nullptr;
-    double *fl_val = nullptr, *fu_val = nullptr;
-    schwz_idx *fl_src = nullptr, *fu_src = nullptr, *fu_dst = nullptr;  // rhs gather / y scatter per position
+    schwz::Dev<schwz_idx> fl_rp, fl_col, fu_rp, fu_col;
+    schwz::Dev<double> fl_val, fu_val;
+    schwz::Dev<schwz_idx> fl_src, fu_src, fu_dst;  // rhs gather / y scatter per position
     int flag_grid = 0;
     // LU factors (schwz_trs_create_lu) with rows beyond one lane each: trs_flag_wave_kernel, one wave per row
     bool wave = false;
     // Jacobi-sweep mode (schwz_trs_create_sweeps, csrc/parilu.hip): `sweeps` passes per factor over the strict
     // parts (CSR) with the reciprocal diagonals; w0, w1, w2 double-buffer the passes.  0: exact solves.
     int sweeps = 0;
-    schwz_idx *js_l_rp = nullptr, *js_l_col = nullptr, *js_u_rp = nullptr, *js_u_col = nullptr;
-    double *js_l_val = nullptr, *js_u_val = nullptr, *js_l_dinv = nullptr, *js_u_dinv = nullptr;
-    double *w2 = nullptr;
+    schwz::Dev<schwz_idx> js_l_rp, js_l_col, js_u_rp, js_u_col;
+    schwz::Dev<double> js_l_val, js_u_val, js_l_dinv, js_u_dinv;
+    schwz::Dev<double> w2;
 };
 
 namespace schwz {
@@ -959,34 +966,61 @@ struct schwz_subdomain {
         return it == g2l_x.end() ? -1 : it->second;
     }
     // ---- device state -----------------------------------------------------
-    bool on_device = false;
+    // Everything in HBM, and every object that owns HIP resources, lives in schwz_subdomain_device (below), reached
+    // through this one plain pointer: null until schwz_subdomain_to_device, deleted by schwz_subdomain_destroy.
+    // "On the device" is `dev != nullptr`.  (A pointer, not a member: host_setup.cpp and the host-only test drivers
+    // create and delete subdomains in programs linked without the HIP runtime, so no destructor that frees device
+    // memory may be reachable from ~schwz_subdomain.)
+    struct schwz_subdomain_device *dev = nullptr;
     schwz_solver_options opt{};
+    int gmres_basis = 0;  // SCHWZ_GMRES_BASIS_*: the basis type of dev->gmres, and of the one a return from bicg creates
+    int precision = 0;    // schwz_ras_set_local_precision
+    int sym_solver = 0;   // schwz_ras_set_sym_solver
+    int64_t nnz_interface = 0;
+    // schwz_ras_rhs_gather (rhs.hip): the global position of every local row's right-hand side.  rhs_index holds the
+    // caller's map (schwz_ras_rhs_index; empty: l2g itself); the device copy is made at the first gather, not before
+    std::vector<int64_t> rhs_index;
+    bool rhs_index_custom = false;
+};
+
+// block state of a subdomain (schwz_ras_batch_begin, csrc/batch.hip): k right-hand sides at once, vectors and a solver
+// of its own.  Nothing of the subdomain is read-write shared with it: it reads the matrix and the index lists
+struct schwz_ras_batch {
+    int k = 0;
+    schwz_bcg *cg = nullptr;
+    schwz::Dev<double> x, rhs, bt, y;
+    ~schwz_ras_batch() { schwz_bcg_destroy(cg); }
+};
+
+// The device half of a subdomain.  Every buffer, the pinned scalar and the event free themselves; the destructor
+// (subdomain.hip) destroys the matrix and the adopted solver objects through their schwz_*_destroy functions and
+// deletes `coarse` and `batch`.  Only .hip translation units may create or delete one.
+struct schwz_subdomain_device {
+    schwz_subdomain_device() = default;
+    schwz_subdomain_device(const schwz_subdomain_device &) = delete;
+    ~schwz_subdomain_device();
     schwz_csr *A = nullptr;  // local_matrix
     // The solver objects.  Which of them the next local solve runs is local_kind's answer (subdomain.hip); nothing
     // else chooses a path by these pointers or by `precision` / `sym_solver`.
     schwz_pcg *cg = nullptr;       // symmetric local matrix, iterative (LocalKind::Cg, and the two below beside it)
     schwz_gmres *gmres = nullptr;  // non-symmetric local matrix (Gmres)
     schwz_bicgstab *bicg = nullptr;  // ... once schwz_ras_set_nonsym_solver asked for BiCGSTAB (Bicgstab; gmres is null then)
-    int gmres_basis = 0;             // SCHWZ_GMRES_BASIS_*: the basis type of gmres, and of the one a return from bicg creates
     // mixed-precision local solve (schwz_ras_set_local_precision, csrc/cg_f32.hip): created at first use, CgF32 while
     // `precision` is SCHWZ_PRECISION_F32; `cg` stays what it is, so that F64 restores the fp64 path exactly
     schwz_pcg_f32 *cg32 = nullptr;
-    int precision = 0;
     // Chebyshev local solve (schwz_ras_set_sym_solver, csrc/chebyshev.hip): created at first use, Chebyshev while
     // `sym_solver` is SCHWZ_SYM_CHEBYSHEV; `cg` stays what it is, so that SCHWZ_SYM_CG restores the CG path exactly
     schwz_cheb *cheb = nullptr;
-    int sym_solver = 0;
     schwz_trs *trs = nullptr;  // the direct solvers' factors (Direct)
     // interface rows: only overlap rows are non-empty; stored compactly
-    schwz_idx *d_i_rp = nullptr, *d_i_col = nullptr;  // cols index x~ directly
-    double *d_i_val = nullptr;
-    int64_t nnz_interface = 0;
-    schwz_idx *d_put_idx = nullptr, *d_get_idx = nullptr;  // local ids, packed
-    double *d_x = nullptr;       // x~ [interior|overlap|halo]
-    double *d_x_alt = nullptr;   // the other x~ buffer: the last x update of a CG solve writes its interior, the restriction swaps the two
-    double *d_rhs = nullptr;     // b_loc
-    double *d_btilde = nullptr;  // b~ = local_solution on entry of the solve
-    double *d_y = nullptr;       // init_guess / solve result of the separate form (allocated at first need)
+    schwz::Dev<schwz_idx> d_i_rp, d_i_col;  // cols index x~ directly
+    schwz::Dev<double> d_i_val;
+    schwz::Dev<schwz_idx> d_put_idx, d_get_idx;  // local ids, packed
+    schwz::Dev<double> d_x;       // x~ [interior|overlap|halo]
+    schwz::Dev<double> d_x_alt;   // the other x~ buffer: the last x update of a CG solve writes its interior, the restriction swaps the two
+    schwz::Dev<double> d_rhs;     // b_loc
+    schwz::Dev<double> d_btilde;  // b~ = local_solution on entry of the solve
+    schwz::Dev<double> d_y;       // init_guess / solve result of the separate form (allocated at first need)
     // Unified form (subdomain.hip, want_unified): no overlap, no halo, CG with x deferred -- y and x~ are the same n
     // values, and y lives in one of the two x~ buffers.  State A: y IS x~ (d_x).  State B (y_in_alt): y is d_x_alt,
     // after a solve that has not been restricted.
@@ -994,21 +1028,15 @@ struct schwz_subdomain {
     bool y_in_alt = false;
     // separate form: a solve has run since the last restriction (y is ahead of x~)
     bool y_ahead = false;
-    double *d_partials = nullptr;
-    double *d_stream_part = nullptr;  // SpmvArgs::stream_part of the subdomain's own norm launches
-    double *h_scalar = nullptr;  // pinned, mapped
-    double *d_h_scalar = nullptr;  // device alias of h_scalar
-    hipEvent_t ev_scalar = nullptr;
+    schwz::Dev<double> d_partials;
+    schwz::Dev<double> d_stream_part;  // SpmvArgs::stream_part of the subdomain's own norm launches
+    schwz::Pinned<double> h_scalar;  // mapped
+    double *d_h_scalar = nullptr;    // device alias of h_scalar (borrowed)
+    schwz::Event ev_scalar;
     // aggregation coarse correction (schwz_ras_coarse_set_aggregates); null: one-level RAS, nothing of it runs
     schwz_coarse_part *coarse = nullptr;
-    // schwz_ras_rhs_gather (rhs.hip): the global position of every local row's right-hand side.  rhs_index holds the
-    // caller's map (schwz_ras_rhs_index; empty: l2g itself); the device copy is made at the first gather, not before
-    std::vector<int64_t> rhs_index;
-    bool rhs_index_custom = false;
-    int64_t *d_rhs_index = nullptr;
-    // block state (schwz_ras_batch_begin, csrc/batch.hip): k right-hand sides at once, vectors and a solver of its
-    // own; null until asked for.  Nothing above is read-write shared with it: it reads the matrix and the index lists
-    struct schwz_ras_batch *batch = nullptr;
+    schwz::Dev<int64_t> d_rhs_index;  // device copy of the map of schwz_ras_rhs_gather (schwz_subdomain::rhs_index)
+    schwz_ras_batch *batch = nullptr;  // null until asked for
 };
 
 namespace schwz {

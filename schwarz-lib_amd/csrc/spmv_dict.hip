@@ -503,6 +503,16 @@ static int upload_dict(schwz_csr *A, const DictPlan &P)
     return SCHWZ_OK;
 }
 
+// what build_spmv_dict releases when an upload fails
+static void free_spmv_dict(schwz_csr *A)
+{
+    A->coding.pattern = {};
+    A->coding.dict = {};
+    bind_pattern(A, PatternPlan());
+    bind_dict(A, DictPlan());
+    free_spmv_pair(A);
+}
+
 // Row patterns; row pairs and the walk only over accepted patterns (stencil-like matrices); per-entry dictionaries
 // only without patterns or when forced.  A coding that is not accepted leaves its fields null and its fraction
 // known.  If an upload fails, everything uploaded so far is released and the error returned.
@@ -523,15 +533,6 @@ int build_spmv_dict(schwz_csr *A, const schwz_idx *rp, const schwz_idx *col, con
     if (!rc) rc = upload_dict(A, plan_dict(opt, M, A->v.pat_id != nullptr));
     if (rc) free_spmv_dict(A);
     return rc;
-}
-
-void free_spmv_dict(schwz_csr *A)
-{
-    A->coding.pattern = {};
-    A->coding.dict = {};
-    bind_pattern(A, PatternPlan());
-    bind_dict(A, DictPlan());
-    free_spmv_pair(A);
 }
 
 }  // namespace schwz

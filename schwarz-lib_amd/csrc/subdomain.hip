@@ -9,6 +9,9 @@
 //   b_loc, b~, y (CG warm start), r, p, q, 1/diag : local_size_x doubles each
 //           (y: a vector of its own, or -- unified form, below -- one of the two x~ buffers)
 //   put / get lists: int32 local ids, packed in neighbour order
+// All of it belongs to schwz_subdomain_device (schwz_internal.hpp), which the subdomain reaches through sd->dev:
+// the buffers free themselves, its destructor (below) destroys the matrix and the solver objects, and
+// schwz_subdomain_destroy deletes it.  sd->dev is null on a host-only subdomain.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -18,23 +21,6 @@
 #include "schwz_internal.hpp"
 
 using namespace schwz;
-
-template <typename T>
-static int dev_upload(const std::vector<T> &h, T **d)
-{
-    *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc((void **)d, (h.empty() ? 1 : h.size()) * sizeof(T)));
-    if (!h.empty()) SCHWZ_HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return SCHWZ_OK;
-}
-
-static int dev_zeros(int64_t n, double **d)
-{
-    *d = nullptr;
-    SCHWZ_HIP_TRY(hipMalloc((void **)d, (size_t)(n ? n : 1) * sizeof(double)));
-    SCHWZ_HIP_TRY(hipMemset(*d, 0, (size_t)(n ? n : 1) * sizeof(double)));
-    return SCHWZ_OK;
-}
 
 // ---- where the solver's vector y lives -----------------------------------------------------------------------
 // On a subdomain without overlap and without halo (one subdomain) y and x~ are the same local_size_x values: the
@@ -62,8 +48,8 @@ static int dev_zeros(int64_t n, double **d)
 static LocalKind local_kind(const schwz_subdomain *sd)
 {
     if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE) return LocalKind::Direct;
-    if (sd->gmres) return LocalKind::Gmres;
-    if (sd->bicg) return LocalKind::Bicgstab;
+    if (sd->dev && sd->dev->gmres) return LocalKind::Gmres;
+    if (sd->dev && sd->dev->bicg) return LocalKind::Bicgstab;
     if (sd->precision == SCHWZ_PRECISION_F32) return LocalKind::CgF32;
     if (sd->sym_solver == SCHWZ_SYM_CHEBYSHEV) return LocalKind::Chebyshev;
     return LocalKind::Cg;
@@ -83,20 +69,19 @@ static bool restrict_fuse_on()
 
 static bool want_unified(schwz_subdomain *sd)
 {
-    return local_kind(sd) == LocalKind::Cg && sd->cg && restrict_fuse_on() && sd->overlap_size == 0 &&
-           sd->halo_size == 0 && sd->local_size > 0 && !sd->cg->prio_on && pcg_defers_x(sd->cg);
+    schwz_subdomain_device *d = sd->dev;
+    return local_kind(sd) == LocalKind::Cg && d->cg && restrict_fuse_on() && sd->overlap_size == 0 &&
+           sd->halo_size == 0 && sd->local_size > 0 && !d->cg->prio_on && pcg_defers_x(d->cg);
 }
 
 // the second x~ buffer, allocated at first need (zeroed); false: no room
 static bool ensure_x_alt(schwz_subdomain *sd)
 {
-    if (sd->d_x_alt) return true;
-    const size_t nx = (size_t)std::max<int64_t>(sd->local_size_x + sd->halo_size, 1);
-    if (hipMalloc((void **)&sd->d_x_alt, nx * sizeof(double)) != hipSuccess ||
-        hipMemset(sd->d_x_alt, 0, nx * sizeof(double)) != hipSuccess) {
+    Dev<double> &alt = sd->dev->d_x_alt;
+    if (alt) return true;
+    if (alt.alloc((size_t)std::max<int64_t>(sd->local_size_x + sd->halo_size, 1), true)) {
         (void)hipGetLastError();
-        (void)hipFree(sd->d_x_alt);
-        sd->d_x_alt = nullptr;
+        alt = Dev<double>();
         return false;
     }
     return true;
@@ -104,28 +89,30 @@ static bool ensure_x_alt(schwz_subdomain *sd)
 
 static double *y_of(const schwz_subdomain *sd)
 {
-    return sd->unified ? (sd->y_in_alt ? sd->d_x_alt : sd->d_x) : sd->d_y;
+    const schwz_subdomain_device *d = sd->dev;
+    return d->unified ? (d->y_in_alt ? d->d_x_alt : d->d_x) : d->d_y;
 }
 
 // the form of the solve about to be launched; y moves with one copy where it differs from the current one
 static int choose_form(schwz_subdomain *sd, hipStream_t st)
 {
     const bool uni = want_unified(sd) && ensure_x_alt(sd);
-    if (uni == sd->unified) return SCHWZ_OK;
+    schwz_subdomain_device *d = sd->dev;
+    if (uni == d->unified) return SCHWZ_OK;
     const int64_t n = sd->local_size_x;
     int rc;
     if (uni) {
         // y ahead of x~ (a solve that was not restricted): state B.  Otherwise state A, where y is x~: the copy makes
         // it so even where the caller wrote into y -- which the separate form, too, takes for x~ in its check residual.
-        if ((rc = launch_copy(n, sd->d_y, sd->y_ahead ? sd->d_x_alt : sd->d_x, st))) return rc;
-        sd->y_in_alt = sd->y_ahead;
+        if ((rc = launch_copy(n, d->d_y, d->y_ahead ? d->d_x_alt : d->d_x, st))) return rc;
+        d->y_in_alt = d->y_ahead;
     } else {
-        if (!sd->d_y && (rc = dev_zeros(n, &sd->d_y))) return rc;
-        if ((rc = launch_copy(n, y_of(sd), sd->d_y, st))) return rc;
-        sd->y_ahead = sd->y_in_alt;
-        sd->y_in_alt = false;
+        if (!d->d_y && (rc = d->d_y.alloc((size_t)(n ? n : 1), true))) return rc;
+        if ((rc = launch_copy(n, y_of(sd), d->d_y, st))) return rc;
+        d->y_ahead = d->y_in_alt;
+        d->y_in_alt = false;
     }
-    sd->unified = uni;
+    d->unified = uni;
     return SCHWZ_OK;
 }
 
@@ -138,22 +125,23 @@ static int choose_form(schwz_subdomain *sd, hipStream_t st)
 template <typename Solve>
 static int cg_solve_in_form(schwz_subdomain *sd, Solve solve)
 {
-    schwz_pcg *cg = sd->cg;
+    schwz_subdomain_device *d = sd->dev;
+    schwz_pcg *cg = d->cg;
     cg->x2_out = nullptr;
-    if (sd->unified) {
-        cg->x_out = sd->y_in_alt ? nullptr : sd->d_x_alt;
+    if (d->unified) {
+        cg->x_out = d->y_in_alt ? nullptr : d->d_x_alt;
     } else {
-        sd->y_ahead = true;
+        d->y_ahead = true;
         if (restrict_fuse_on() && sd->local_size > 0 && ensure_x_alt(sd)) {
-            cg->x2_out = sd->d_x_alt;
+            cg->x2_out = d->d_x_alt;
             cg->x2_rows = sd->local_size;
-            cg->x2_src = sd->d_x;
+            cg->x2_src = d->d_x;
             cg->x2_total = sd->local_size_x + sd->halo_size;
         }
     }
     const int rc = solve(y_of(sd));
     cg->x_out = nullptr;
-    if (sd->unified && !rc) sd->y_in_alt = true;
+    if (d->unified && !rc) d->y_in_alt = true;
     return rc;
 }
 
@@ -161,23 +149,24 @@ static int cg_solve_in_form(schwz_subdomain *sd, Solve solve)
 // breakdown simply ends this local solve: the next outer iteration starts again from y with a fresh rhat.)
 static int solve_in_place(schwz_subdomain *sd, int *h_iters, schwz_stream stream)
 {
-    if (sd->cg) {
+    schwz_subdomain_device *d = sd->dev;
+    if (d->cg) {
         const int rc = choose_form(sd, (hipStream_t)stream);  // -> separate: want_unified is false for these kinds
         if (rc) return rc;
-        sd->cg->x2_out = nullptr;
-        sd->cg->x2_written = false;  // (or schwz_ras_restrict would swap in a stale buffer)
+        d->cg->x2_out = nullptr;
+        d->cg->x2_written = false;  // (or schwz_ras_restrict would swap in a stale buffer)
     }
-    sd->y_ahead = true;
+    d->y_ahead = true;
     const double tol = sd->opt.local_tol;
     const int maxit = local_maxit(sd);
     switch (local_kind(sd)) {
     case LocalKind::Direct:
         if (h_iters) *h_iters = 0;
-        return schwz_trs_solve(sd->trs, sd->d_btilde, sd->d_y, stream);
-    case LocalKind::Gmres: return schwz_gmres_solve(sd->gmres, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
-    case LocalKind::Bicgstab: return schwz_bicgstab_solve(sd->bicg, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
-    case LocalKind::CgF32: return schwz_pcg_f32_solve(sd->cg32, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
-    case LocalKind::Chebyshev: return schwz_cheb_solve(sd->cheb, sd->d_btilde, sd->d_y, tol, maxit, h_iters, nullptr, stream);
+        return schwz_trs_solve(d->trs, d->d_btilde, d->d_y, stream);
+    case LocalKind::Gmres: return schwz_gmres_solve(d->gmres, d->d_btilde, d->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::Bicgstab: return schwz_bicgstab_solve(d->bicg, d->d_btilde, d->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::CgF32: return schwz_pcg_f32_solve(d->cg32, d->d_btilde, d->d_y, tol, maxit, h_iters, nullptr, stream);
+    case LocalKind::Chebyshev: return schwz_cheb_solve(d->cheb, d->d_btilde, d->d_y, tol, maxit, h_iters, nullptr, stream);
     case LocalKind::Cg: break;  // not in place: schwz_ras_local_solve takes it through cg_solve_in_form
     }
     return SCHWZ_ERR_INVALID;
@@ -211,9 +200,10 @@ static bool priority_rows(const std::vector<schwz_idx> &ids, int64_t n, int64_t 
     return true;
 }
 
-// the solver object of sd->opt around sd->A: what local_kind then finds
+// the solver object of sd->opt around sd->dev->A: what local_kind then finds
 static int create_local_solver(schwz_subdomain *sd, std::vector<schwz_idx> put_idx)
 {
+    schwz_subdomain_device *d = sd->dev;
     const schwz_solver_options &o = sd->opt;
     const int64_t n = sd->local_size_x;
     int rc;
@@ -221,17 +211,17 @@ static int create_local_solver(schwz_subdomain *sd, std::vector<schwz_idx> put_i
         const int bsz = o.precond_block_size < 1 ? 1 : o.precond_block_size;
         // solve.cpp:486-520: GMRES(restart_iter); the preconditioner objects are the CG's
         if (o.non_symmetric)
-            return schwz_gmres_create_ex(sd->A, o.precond, bsz, o.restart_iter < 1 ? 1 : o.restart_iter, o.par_ilu_sweeps,
-                                         o.trisolve_sweeps, &sd->gmres);
+            return schwz_gmres_create_ex(d->A, o.precond, bsz, o.restart_iter < 1 ? 1 : o.restart_iter, o.par_ilu_sweeps,
+                                         o.trisolve_sweeps, &d->gmres);
         if ((rc = o.par_ilu_sweeps || o.trisolve_sweeps
-                      ? schwz_pcg_create_ilu(sd->A, o.precond, o.par_ilu_sweeps, o.trisolve_sweeps, &sd->cg)
-                      : schwz_pcg_create_ex(sd->A, o.precond, bsz, &sd->cg)))
+                      ? schwz_pcg_create_ilu(d->A, o.precond, o.par_ilu_sweeps, o.trisolve_sweeps, &d->cg)
+                      : schwz_pcg_create_ex(d->A, o.precond, bsz, &d->cg)))
             return rc;
-        sd->cg->variant = o.spmv_variant;
+        d->cg->variant = o.spmv_variant;
         std::sort(put_idx.begin(), put_idx.end());
-        if (priority_rows(put_idx, n, sd->local_size, &sd->cg->prio_lo, &sd->cg->prio_hi)) {
-            if ((rc = sd->cg->prio_event.create())) return rc;
-            sd->cg->prio_on = true;
+        if (priority_rows(put_idx, n, sd->local_size, &d->cg->prio_lo, &d->cg->prio_hi)) {
+            if ((rc = d->cg->prio_event.create())) return rc;
+            d->cg->prio_on = true;
         }
         return SCHWZ_OK;
     }
@@ -246,61 +236,32 @@ static int create_local_solver(schwz_subdomain *sd, std::vector<schwz_idx> put_i
                  : schwz_cholesky(n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), o.natural_factor_ordering,
                                   &l_rp, &l_col, &l_val, &u_rp, &u_col, &u_val, &perm)))
         return rc;
-    rc = lu ? schwz_trs_create_lu(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, col_perm, &sd->trs)
-            : schwz_trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, &sd->trs);
+    rc = lu ? schwz_trs_create_lu(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, col_perm, &d->trs)
+            : schwz_trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, perm, &d->trs);
     for (void *p : {(void *)l_rp, (void *)l_col, (void *)l_val, (void *)u_rp, (void *)u_col, (void *)u_val, (void *)perm,
                     (void *)col_perm})
         schwz_free(p);
     return rc;
 }
 
-extern "C" {
-
-void schwz_subdomain_destroy(schwz_subdomain *sd)
+// (the buffers, the pinned scalar and the event free themselves)
+schwz_subdomain_device::~schwz_subdomain_device()
 {
-    if (!sd) return;
-    if (sd->on_device) {
-        (void)schwz_ras_batch_end(sd);
-        schwz_pcg_destroy(sd->cg);
-        schwz_pcg_f32_destroy(sd->cg32);
-        schwz_cheb_destroy(sd->cheb);
-        schwz_gmres_destroy(sd->gmres);
-        schwz_bicgstab_destroy(sd->bicg);
-        schwz_trs_destroy(sd->trs);
-        schwz_csr_destroy(sd->A);
-        void *ptrs[] = {sd->d_i_rp, sd->d_i_col, sd->d_i_val, sd->d_put_idx, sd->d_get_idx, sd->d_x, sd->d_x_alt,
-                        sd->d_rhs, sd->d_btilde, sd->d_y, sd->d_partials, sd->d_stream_part, sd->d_rhs_index};
-        for (void *p : ptrs) (void)hipFree(p);
-        if (sd->h_scalar) (void)hipHostFree(sd->h_scalar);
-        if (sd->ev_scalar) (void)hipEventDestroy(sd->ev_scalar);
-        delete sd->coarse;
-    }
-    delete sd;
+    delete batch;
+    schwz_pcg_destroy(cg);
+    schwz_pcg_f32_destroy(cg32);
+    schwz_cheb_destroy(cheb);
+    schwz_gmres_destroy(gmres);
+    schwz_bicgstab_destroy(bicg);
+    schwz_trs_destroy(trs);
+    schwz_csr_destroy(A);
+    delete coarse;
 }
 
-int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, const schwz_solver_options *opt)
+// the uploads of schwz_subdomain_to_device into the fresh sd->dev
+static int upload_device_state(schwz_subdomain *sd, const double *h_local_rhs)
 {
-    StageTimer timer_all("subdomain_to_device total");
-    SCHWZ_REQUIRE(sd && h_local_rhs && opt, "schwz_subdomain_to_device: null argument");
-    SCHWZ_REQUIRE(!sd->on_device, "schwz_subdomain_to_device: already on the device");
-    SCHWZ_REQUIRE(opt->local_solver == SCHWZ_SOLVER_ITERATIVE || opt->local_solver == SCHWZ_SOLVER_DIRECT ||
-                      opt->local_solver == SCHWZ_SOLVER_DIRECT_LU,
-                  "schwz_subdomain_to_device: unknown local solver");
-    SCHWZ_REQUIRE(opt->par_ilu_sweeps >= 0 && opt->trisolve_sweeps >= 0,
-                  "schwz_subdomain_to_device: par_ilu_sweeps / trisolve_sweeps must be >= 0");
-    if ((opt->par_ilu_sweeps || opt->trisolve_sweeps) && opt->local_solver != SCHWZ_SOLVER_ITERATIVE) {
-        set_error("schwz_subdomain_to_device: par_ilu_sweeps / trisolve_sweeps apply to the iterative local solver only");
-        return SCHWZ_ERR_NOT_IMPLEMENTED;
-    }
-    if (opt->local_solver == SCHWZ_SOLVER_ITERATIVE) {
-        const int rc_sw = pcg_check_ilu_sweeps(opt->precond, opt->par_ilu_sweeps, opt->trisolve_sweeps);
-        if (rc_sw) return rc_sw;
-    }
-    if (schwz_device_count() < 1) {
-        set_error("schwz_subdomain_to_device: no HIP device visible (there is no CPU fallback)");
-        return SCHWZ_ERR_HIP;
-    }
-    sd->opt = *opt;
+    schwz_subdomain_device *d = sd->dev;
     const int64_t n = sd->local_size_x;
     const int64_t nx = n + sd->halo_size;
     int rc;
@@ -326,40 +287,80 @@ int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, co
         i_col[k] = l;
     }
     sd->nnz_interface = (int64_t)i_col.size();
-    if ((rc = schwz_csr_create(n, n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), &sd->A))) return rc;
-    sd->on_device = true;  // from here on destroy() releases device memory
+    if ((rc = schwz_csr_create(n, n, sd->l_rp.data(), sd->l_col.data(), sd->l_val.data(), &d->A))) return rc;
     // x~ and the CG iterate coincide on the interior: only tiles reaching the overlap need the
     // second product of the fused check+start residual kernel
-    if (sd->overlap_size > 0 && (rc = csr_set_dual_split(sd->A, sd->l_rp.data(), sd->l_col.data(), sd->local_size))) return rc;
-    if ((rc = dev_upload(i_rp, &sd->d_i_rp)) || (rc = dev_upload(i_col, &sd->d_i_col)) ||
-        (rc = dev_upload(sd->i_val, &sd->d_i_val)) || (rc = dev_upload(put_idx, &sd->d_put_idx)) ||
-        (rc = dev_upload(get_idx, &sd->d_get_idx)))
+    if (sd->overlap_size > 0 && (rc = csr_set_dual_split(d->A, sd->l_rp.data(), sd->l_col.data(), sd->local_size))) return rc;
+    if ((rc = d->d_i_rp.put(i_rp)) || (rc = d->d_i_col.put(i_col)) || (rc = d->d_i_val.put(sd->i_val)) ||
+        (rc = d->d_put_idx.put(put_idx)) || (rc = d->d_get_idx.put(get_idx)))
         return rc;
-    if ((rc = dev_zeros(nx, &sd->d_x))) return rc;  // (y: at the end, once the solver is known)
-    std::vector<double> rhs(h_local_rhs, h_local_rhs + n);
-    if ((rc = dev_upload(rhs, &sd->d_rhs)) || (rc = dev_upload(rhs, &sd->d_btilde))) return rc;
-    SCHWZ_HIP_TRY(hipMalloc((void **)&sd->d_partials, sizeof(double) * (2 * kMaxGrid + 2)));
-    sd->d_stream_part = stream_part_alloc(sd->A->v);
-    SCHWZ_HIP_TRY(hipHostMalloc((void **)&sd->h_scalar, 4 * sizeof(double), hipHostMallocMapped));
-    SCHWZ_HIP_TRY(hipHostGetDevicePointer((void **)&sd->d_h_scalar, sd->h_scalar, 0));
-    SCHWZ_HIP_TRY(hipEventCreateWithFlags(&sd->ev_scalar, hipEventDisableTiming));
+    if ((rc = d->d_x.alloc((size_t)(nx ? nx : 1), true))) return rc;  // (y: at the end, once the solver is known)
+    if ((rc = d->d_rhs.put(h_local_rhs, (size_t)n)) || (rc = d->d_btilde.put(h_local_rhs, (size_t)n))) return rc;
+    if ((rc = d->d_partials.alloc(2 * kMaxGrid + 2))) return rc;
+    d->d_stream_part = stream_part_alloc(d->A->v);
+    // (Pinned::alloc zeroes the scalars, which nothing relies on: a slot is written by a kernel before it is read)
+    if ((rc = d->h_scalar.alloc(4, hipHostMallocMapped))) return rc;
+    SCHWZ_HIP_TRY(hipHostGetDevicePointer((void **)&d->d_h_scalar, d->h_scalar.p, 0));
+    if ((rc = d->ev_scalar.create())) return rc;
     if ((rc = create_local_solver(sd, put_idx))) return rc;
     // y: inside the x~ buffers where the two coincide (state A), else a vector of its own
-    sd->unified = want_unified(sd) && ensure_x_alt(sd);
-    if (!sd->unified && (rc = dev_zeros(n, &sd->d_y))) return rc;
+    d->unified = want_unified(sd) && ensure_x_alt(sd);
+    if (!d->unified && (rc = d->d_y.alloc((size_t)(n ? n : 1), true))) return rc;
     SCHWZ_HIP_TRY(hipDeviceSynchronize());
     return SCHWZ_OK;
 }
 
+extern "C" {
+
+void schwz_subdomain_destroy(schwz_subdomain *sd)
+{
+    if (!sd) return;
+    delete sd->dev;
+    delete sd;
+}
+
+int schwz_subdomain_to_device(schwz_subdomain *sd, const double *h_local_rhs, const schwz_solver_options *opt)
+{
+    StageTimer timer_all("subdomain_to_device total");
+    SCHWZ_REQUIRE(sd && h_local_rhs && opt, "schwz_subdomain_to_device: null argument");
+    SCHWZ_REQUIRE(!sd->dev, "schwz_subdomain_to_device: already on the device");
+    SCHWZ_REQUIRE(opt->local_solver == SCHWZ_SOLVER_ITERATIVE || opt->local_solver == SCHWZ_SOLVER_DIRECT ||
+                      opt->local_solver == SCHWZ_SOLVER_DIRECT_LU,
+                  "schwz_subdomain_to_device: unknown local solver");
+    SCHWZ_REQUIRE(opt->par_ilu_sweeps >= 0 && opt->trisolve_sweeps >= 0,
+                  "schwz_subdomain_to_device: par_ilu_sweeps / trisolve_sweeps must be >= 0");
+    if ((opt->par_ilu_sweeps || opt->trisolve_sweeps) && opt->local_solver != SCHWZ_SOLVER_ITERATIVE) {
+        set_error("schwz_subdomain_to_device: par_ilu_sweeps / trisolve_sweeps apply to the iterative local solver only");
+        return SCHWZ_ERR_NOT_IMPLEMENTED;
+    }
+    if (opt->local_solver == SCHWZ_SOLVER_ITERATIVE) {
+        const int rc_sw = pcg_check_ilu_sweeps(opt->precond, opt->par_ilu_sweeps, opt->trisolve_sweeps);
+        if (rc_sw) return rc_sw;
+    }
+    if (schwz_device_count() < 1) {
+        set_error("schwz_subdomain_to_device: no HIP device visible (there is no CPU fallback)");
+        return SCHWZ_ERR_HIP;
+    }
+    sd->opt = *opt;
+    // a failure half way leaves nothing behind: the half-built device state is deleted here, not by a later destroy
+    sd->dev = new schwz_subdomain_device();
+    const int rc = upload_device_state(sd, h_local_rhs);
+    if (rc) {
+        delete sd->dev;
+        sd->dev = nullptr;
+    }
+    return rc;
+}
+
 #define REQUIRE_DEVICE(sd, name) \
-    SCHWZ_REQUIRE((sd) && (sd)->on_device, name ": subdomain is not on the device")
+    SCHWZ_REQUIRE((sd) && (sd)->dev, name ": subdomain is not on the device")
 
 int schwz_ras_pack(schwz_subdomain *sd, double *d_send, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_pack");
     if (sd->num_send == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_send, "schwz_ras_pack: null send buffer");
-    return schwz_gather(sd->num_send, sd->d_put_idx, sd->d_x, d_send, SCHWZ_OP_COPY, stream);
+    return schwz_gather(sd->num_send, sd->dev->d_put_idx, sd->dev->d_x, d_send, SCHWZ_OP_COPY, stream);
 }
 
 int schwz_ras_unpack(schwz_subdomain *sd, const double *d_recv, schwz_stream stream)
@@ -367,7 +368,7 @@ int schwz_ras_unpack(schwz_subdomain *sd, const double *d_recv, schwz_stream str
     REQUIRE_DEVICE(sd, "schwz_ras_unpack");
     if (sd->num_recv == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_recv, "schwz_ras_unpack: null recv buffer");
-    return schwz_scatter(sd->num_recv, sd->d_get_idx, d_recv, sd->d_x, SCHWZ_OP_COPY, stream);
+    return schwz_scatter(sd->num_recv, sd->dev->d_get_idx, d_recv, sd->dev->d_x, SCHWZ_OP_COPY, stream);
 }
 
 int schwz_ras_pack_f32(schwz_subdomain *sd, float *d_send, schwz_stream stream)
@@ -375,7 +376,7 @@ int schwz_ras_pack_f32(schwz_subdomain *sd, float *d_send, schwz_stream stream)
     REQUIRE_DEVICE(sd, "schwz_ras_pack_f32");
     if (sd->num_send == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_send, "schwz_ras_pack_f32: null send buffer");
-    return launch_gather_f32(sd->num_send, sd->d_put_idx, sd->d_x, d_send, (hipStream_t)stream);
+    return launch_gather_f32(sd->num_send, sd->dev->d_put_idx, sd->dev->d_x, d_send, (hipStream_t)stream);
 }
 
 int schwz_ras_unpack_f32(schwz_subdomain *sd, const float *d_recv, schwz_stream stream)
@@ -383,7 +384,7 @@ int schwz_ras_unpack_f32(schwz_subdomain *sd, const float *d_recv, schwz_stream 
     REQUIRE_DEVICE(sd, "schwz_ras_unpack_f32");
     if (sd->num_recv == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_recv, "schwz_ras_unpack_f32: null recv buffer");
-    return launch_scatter_f32(sd->num_recv, sd->d_get_idx, d_recv, sd->d_x, (hipStream_t)stream);
+    return launch_scatter_f32(sd->num_recv, sd->dev->d_get_idx, d_recv, sd->dev->d_x, (hipStream_t)stream);
 }
 
 // The pack of the NEXT exchange, beside the tail of the running local solve: waits (on `stream`, typically a
@@ -392,7 +393,7 @@ int schwz_ras_unpack_f32(schwz_subdomain *sd, const float *d_recv, schwz_stream 
 // schwz_ras_pack would read after schwz_ras_restrict.
 int schwz_ras_early_pack_ok(const schwz_subdomain *sd)
 {
-    return sd && sd->on_device && local_kind(sd) == LocalKind::Cg && sd->cg && sd->cg->prio_on && sd->cg->prio_event ? 1 : 0;
+    return sd && sd->dev && local_kind(sd) == LocalKind::Cg && sd->dev->cg && sd->dev->cg->prio_on && sd->dev->cg->prio_event ? 1 : 0;
 }
 
 int schwz_ras_pack_early(schwz_subdomain *sd, void *d_send, int single, schwz_stream stream)
@@ -401,9 +402,9 @@ int schwz_ras_pack_early(schwz_subdomain *sd, void *d_send, int single, schwz_st
     SCHWZ_REQUIRE(schwz_ras_early_pack_ok(sd), "schwz_ras_pack_early: this subdomain's solver records no boundary event");
     if (sd->num_send == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_send, "schwz_ras_pack_early: null send buffer");
-    SCHWZ_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, sd->cg->prio_event, 0));
-    if (single) return launch_gather_f32(sd->num_send, sd->d_put_idx, y_of(sd), (float *)d_send, (hipStream_t)stream);
-    return schwz_gather(sd->num_send, sd->d_put_idx, y_of(sd), (double *)d_send, SCHWZ_OP_COPY, stream);
+    SCHWZ_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, sd->dev->cg->prio_event, 0));
+    if (single) return launch_gather_f32(sd->num_send, sd->dev->d_put_idx, y_of(sd), (float *)d_send, (hipStream_t)stream);
+    return schwz_gather(sd->num_send, sd->dev->d_put_idx, y_of(sd), (double *)d_send, SCHWZ_OP_COPY, stream);
 }
 
 // One neighbour's part of the halo, to / from ANY device address -- the receiver's window in the
@@ -418,8 +419,8 @@ int schwz_ras_pack_neighbor(schwz_subdomain *sd, int k, void *d_dst, int single,
     const int64_t cnt = (int64_t)sd->put[(size_t)k].size();
     if (cnt == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_dst, "schwz_ras_pack_neighbor: null destination");
-    if (single) return launch_gather_f32(cnt, sd->d_put_idx + off, sd->d_x, (float *)d_dst, (hipStream_t)stream);
-    return schwz_gather(cnt, sd->d_put_idx + off, sd->d_x, (double *)d_dst, SCHWZ_OP_COPY, stream);
+    if (single) return launch_gather_f32(cnt, sd->dev->d_put_idx + off, sd->dev->d_x, (float *)d_dst, (hipStream_t)stream);
+    return schwz_gather(cnt, sd->dev->d_put_idx + off, sd->dev->d_x, (double *)d_dst, SCHWZ_OP_COPY, stream);
 }
 
 int schwz_ras_unpack_neighbor(schwz_subdomain *sd, int k, const void *d_src, int single, schwz_stream stream)
@@ -431,8 +432,8 @@ int schwz_ras_unpack_neighbor(schwz_subdomain *sd, int k, const void *d_src, int
     const int64_t cnt = (int64_t)sd->get[(size_t)k].size();
     if (cnt == 0) return SCHWZ_OK;
     SCHWZ_REQUIRE(d_src, "schwz_ras_unpack_neighbor: null source");
-    if (single) return launch_scatter_f32(cnt, sd->d_get_idx + off, (const float *)d_src, sd->d_x, (hipStream_t)stream);
-    return schwz_scatter(cnt, sd->d_get_idx + off, (const double *)d_src, sd->d_x, SCHWZ_OP_COPY, stream);
+    if (single) return launch_scatter_f32(cnt, sd->dev->d_get_idx + off, (const float *)d_src, sd->dev->d_x, (hipStream_t)stream);
+    return schwz_scatter(cnt, sd->dev->d_get_idx + off, (const double *)d_src, sd->dev->d_x, SCHWZ_OP_COPY, stream);
 }
 
 // ---- windows: device buffers other rank processes map (the MPI_Win_create of communicate.hpp:67-224) ----
@@ -485,8 +486,8 @@ int schwz_ras_update_boundary(schwz_subdomain *sd, schwz_stream stream)
     // rows < local_size have no interface entries: b~ = b there, set at upload.
     // restricted_schwarz.cpp:1007: only applied when num_subdomains > 1 && overlap > 0
     if (sd->P <= 1 || sd->nnz_interface == 0) return SCHWZ_OK;
-    return launch_interface_update(sd->overlap_size, sd->local_size, sd->d_i_rp, sd->d_i_col, sd->d_i_val,
-                                   sd->d_x, sd->d_rhs, sd->d_btilde, (hipStream_t)stream);
+    return launch_interface_update(sd->overlap_size, sd->local_size, sd->dev->d_i_rp, sd->dev->d_i_col, sd->dev->d_i_val,
+                                   sd->dev->d_x, sd->dev->d_rhs, sd->dev->d_btilde, (hipStream_t)stream);
 }
 
 // Launches the residual-norm kernels and the 8-byte device->host copy, then records
@@ -494,19 +495,20 @@ int schwz_ras_update_boundary(schwz_subdomain *sd, schwz_stream stream)
 // solve) already run behind it on the same stream.
 static int residual_norm_sq_launch(schwz_subdomain *sd, const double *b, int64_t row_limit, hipStream_t st)
 {
+    schwz_subdomain_device *d = sd->dev;
     SpmvArgs a;
-    a.x = sd->d_x;
+    a.x = d->d_x;
     a.b = b;
-    a.partials = sd->d_partials;
-    a.stream_part = sd->d_stream_part;
+    a.partials = d->d_partials;
+    a.stream_part = d->d_stream_part;
     a.row_limit = row_limit;
-    int rc = launch_spmv(sd->A->v, kSpmvResidNorm, a, sd->opt.spmv_variant, st);
+    int rc = launch_spmv(d->A->v, kSpmvResidNorm, a, sd->opt.spmv_variant, st);
     if (rc) return rc;
-    const int g = spmv_grid(sd->A->v, sd->opt.spmv_variant);
+    const int g = spmv_grid(d->A->v, sd->opt.spmv_variant);
     // the scalar lands in mapped pinned host memory straight from the kernel: no
     // copy engine hop between this kernel and the next one in the stream
-    if ((rc = launch_final_norm(sd->d_partials + g, g, sd->d_h_scalar, st))) return rc;
-    SCHWZ_HIP_TRY(hipEventRecord(sd->ev_scalar, st));
+    if ((rc = launch_final_norm(d->d_partials + g, g, d->d_h_scalar, st))) return rc;
+    SCHWZ_HIP_TRY(hipEventRecord(d->ev_scalar, st));
     return SCHWZ_OK;
 }
 
@@ -514,7 +516,7 @@ int schwz_ras_local_residual_launch(schwz_subdomain *sd, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_local_residual_launch");
     if (sd->local_size_x == 0) return SCHWZ_OK;
-    return residual_norm_sq_launch(sd, sd->d_btilde, sd->local_size_x, (hipStream_t)stream);
+    return residual_norm_sq_launch(sd, sd->dev->d_btilde, sd->local_size_x, (hipStream_t)stream);
 }
 
 int schwz_ras_local_residual_wait(schwz_subdomain *sd, double *h_resnorm)
@@ -525,12 +527,12 @@ int schwz_ras_local_residual_wait(schwz_subdomain *sd, double *h_resnorm)
         *h_resnorm = 0.0;
         return SCHWZ_OK;
     }
-    SCHWZ_HIP_TRY(hipEventSynchronize(sd->ev_scalar));
-    *h_resnorm = std::sqrt(sd->h_scalar[0]);
+    SCHWZ_HIP_TRY(hipEventSynchronize(sd->dev->ev_scalar));
+    *h_resnorm = std::sqrt(sd->dev->h_scalar.p[0]);
     if (*h_resnorm != *h_resnorm) {
         // a NaN norm: say so specifically when it comes from a triangular sweep that gave up waiting
-        int rc = sd->cg ? pcg_take_trs_error(sd->cg) : SCHWZ_OK;
-        if (!rc && sd->trs) rc = trs_take_error(sd->trs);
+        int rc = sd->dev->cg ? pcg_take_trs_error(sd->dev->cg) : SCHWZ_OK;
+        if (!rc && sd->dev->trs) rc = trs_take_error(sd->dev->trs);
         if (rc) return rc;
     }
     return SCHWZ_OK;
@@ -552,8 +554,8 @@ int schwz_ras_norm_sq_to_device(schwz_subdomain *sd, double *d_norm_sq, schwz_st
         SCHWZ_HIP_TRY(hipMemsetAsync(d_norm_sq, 0, sizeof(double), st));
         return SCHWZ_OK;
     }
-    SCHWZ_HIP_TRY(hipStreamWaitEvent(st, sd->ev_scalar, 0));
-    hipLaunchKernelGGL(schwz::copy_scalar_kernel, dim3(1), dim3(1), 0, st, (const double *)sd->d_h_scalar, d_norm_sq);
+    SCHWZ_HIP_TRY(hipStreamWaitEvent(st, sd->dev->ev_scalar, 0));
+    hipLaunchKernelGGL(schwz::copy_scalar_kernel, dim3(1), dim3(1), 0, st, (const double *)sd->dev->d_h_scalar, d_norm_sq);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }
@@ -573,16 +575,16 @@ int schwz_ras_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream 
         *h_out = 0.0;
         return SCHWZ_OK;
     }
-    int rc = residual_norm_sq_launch(sd, sd->d_rhs, sd->local_size, (hipStream_t)stream);
+    int rc = residual_norm_sq_launch(sd, sd->dev->d_rhs, sd->local_size, (hipStream_t)stream);
     if (rc) return rc;
-    SCHWZ_HIP_TRY(hipEventSynchronize(sd->ev_scalar));
-    *h_out = sd->h_scalar[0];
+    SCHWZ_HIP_TRY(hipEventSynchronize(sd->dev->ev_scalar));
+    *h_out = sd->dev->h_scalar.p[0];
     return SCHWZ_OK;
 }
 
 int schwz_ras_set_local_max_iters(schwz_subdomain *sd, int max_iters)
 {
-    SCHWZ_REQUIRE(sd && sd->on_device, "schwz_ras_set_local_max_iters: subdomain is not on the device");
+    SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_set_local_max_iters: subdomain is not on the device");
     SCHWZ_REQUIRE(max_iters >= -1, "schwz_ras_set_local_max_iters: max_iters must be -1 or >= 0");
     sd->opt.local_max_iters = max_iters;
     return SCHWZ_OK;
@@ -591,17 +593,18 @@ int schwz_ras_set_local_max_iters(schwz_subdomain *sd, int max_iters)
 int schwz_ras_last_inner_stats(schwz_subdomain *sd, int *h_iters, double *h_resnorm)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_last_inner_stats");
+    schwz_subdomain_device *d = sd->dev;
     SCHWZ_REQUIRE(h_iters && h_resnorm, "schwz_ras_last_inner_stats: null output");
     *h_iters = 0;
     *h_resnorm = 0.0;
     if (sd->local_size_x == 0) return SCHWZ_OK;
     switch (local_kind(sd)) {
     case LocalKind::Direct: return SCHWZ_OK;
-    case LocalKind::Gmres: return schwz_gmres_last_stats(sd->gmres, h_iters, h_resnorm);
-    case LocalKind::Bicgstab: return schwz_bicgstab_last_stats(sd->bicg, h_iters, h_resnorm);
-    case LocalKind::CgF32: return schwz_pcg_f32_last_stats(sd->cg32, h_iters, h_resnorm);
-    case LocalKind::Chebyshev: return schwz_cheb_last_stats(sd->cheb, h_iters, h_resnorm);
-    case LocalKind::Cg: return sd->cg ? pcg_last_stats(sd->cg, h_iters, h_resnorm) : SCHWZ_OK;
+    case LocalKind::Gmres: return schwz_gmres_last_stats(d->gmres, h_iters, h_resnorm);
+    case LocalKind::Bicgstab: return schwz_bicgstab_last_stats(d->bicg, h_iters, h_resnorm);
+    case LocalKind::CgF32: return schwz_pcg_f32_last_stats(d->cg32, h_iters, h_resnorm);
+    case LocalKind::Chebyshev: return schwz_cheb_last_stats(d->cheb, h_iters, h_resnorm);
+    case LocalKind::Cg: return d->cg ? pcg_last_stats(d->cg, h_iters, h_resnorm) : SCHWZ_OK;
     }
     return SCHWZ_OK;
 }
@@ -610,43 +613,44 @@ int schwz_ras_local_solve(schwz_subdomain *sd, int *h_inner_iters, schwz_stream 
 {
     REQUIRE_DEVICE(sd, "schwz_ras_local_solve");
     if (local_kind(sd) != LocalKind::Cg) return solve_in_place(sd, h_inner_iters, stream);
-    SCHWZ_REQUIRE(sd->cg, "schwz_ras_local_solve: the subdomain has no iterative solver");
+    SCHWZ_REQUIRE(sd->dev->cg, "schwz_ras_local_solve: the subdomain has no iterative solver");
     const int rc = choose_form(sd, (hipStream_t)stream);
     if (rc) return rc;
     return cg_solve_in_form(sd, [&](double *y) {
-        return schwz_pcg_solve(sd->cg, sd->d_btilde, y, sd->opt.local_tol, local_maxit(sd), h_inner_iters, nullptr, stream);
+        return schwz_pcg_solve(sd->dev->cg, sd->dev->d_btilde, y, sd->opt.local_tol, local_maxit(sd), h_inner_iters, nullptr, stream);
     });
 }
 
 int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_check_and_solve_launch");
+    schwz_subdomain_device *d = sd->dev;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = sd->local_size_x;
     if (n == 0) return SCHWZ_OK;
     // the check residual shares the matrix pass of the CG start residual (kSpmvResidDual) ...
-    if (local_kind(sd) == LocalKind::Cg && sd->cg && spmv_variant_has_dual(sd->opt.spmv_variant)) {
+    if (local_kind(sd) == LocalKind::Cg && d->cg && spmv_variant_has_dual(sd->opt.spmv_variant)) {
         int rc = choose_form(sd, st);
         if (rc) return rc;
         // x~ and y coincide on [interior|overlap] when there is no overlap at all
         // (single subdomain): the check residual is then the CG start residual ...
-        const double *x2 = (sd->overlap_size == 0) ? nullptr : sd->d_x;
+        const double *x2 = (sd->overlap_size == 0) ? nullptr : d->d_x;
         // ... unless a solve has run since the last restriction (a discarded solve, x~ kept): y has moved on and the
         // check residual, which belongs to x~, gets its own launch
-        if (x2 || !(sd->unified ? sd->y_in_alt : sd->y_ahead))
+        if (x2 || !(d->unified ? d->y_in_alt : d->y_ahead))
             return cg_solve_in_form(sd, [&](double *y) {
-                schwz_pcg *cg = sd->cg;
+                schwz_pcg *cg = d->cg;
                 double *keep = cg->d_norm_sq;
-                cg->d_norm_sq = sd->d_h_scalar;  // mapped pinned host memory, written by the kernel
-                int rc = pcg_begin(cg, sd->d_btilde, y, sd->opt.local_tol, true, x2, n, st);
+                cg->d_norm_sq = d->d_h_scalar;  // mapped pinned host memory, written by the kernel
+                int rc = pcg_begin(cg, d->d_btilde, y, sd->opt.local_tol, true, x2, n, st);
                 cg->d_norm_sq = keep;
                 if (!rc) {
                     // the norm is final behind the start launch's fold: a kernel of pcg_begin, or the first launch of
                     // pcg_iterate, which then records the event (nothing on the device waits for it earlier:
                     // schwz_ras_norm_sq_to_device is enqueued after this function)
                     if (cg->init.pending)
-                        cg->init_event = sd->ev_scalar;
-                    else if (hipEventRecord(sd->ev_scalar, st) != hipSuccess)
+                        cg->init_event = d->ev_scalar;
+                    else if (hipEventRecord(d->ev_scalar, st) != hipSuccess)
                         rc = SCHWZ_ERR_HIP;
                 }
                 if (!rc) rc = pcg_iterate(cg, y, sd->opt.local_tol, local_maxit(sd), st);
@@ -663,22 +667,23 @@ int schwz_ras_check_and_solve_launch(schwz_subdomain *sd, schwz_stream stream)
 int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_restrict");
+    schwz_subdomain_device *d = sd->dev;
     if (sd->local_size == 0) return SCHWZ_OK;
-    if (sd->unified) {
+    if (d->unified) {
         // state B: the buffer the solve filled becomes x~ (and y stays where it is: state A).  State A: y is x~.
-        if (sd->y_in_alt) std::swap(sd->d_x, sd->d_x_alt);
-        sd->y_in_alt = false;
+        if (d->y_in_alt) std::swap(d->d_x, d->d_x_alt);
+        d->y_in_alt = false;
         return SCHWZ_OK;
     }
-    sd->y_ahead = false;
-    if (sd->cg && sd->cg->x2_written && sd->d_x_alt && sd->cg->x2_out == sd->d_x_alt) {
+    d->y_ahead = false;
+    if (d->cg && d->cg->x2_written && d->d_x_alt && d->cg->x2_out == d->d_x_alt) {
         // the solve's last x update wrote y[interior] into the other buffer: it becomes x~
-        std::swap(sd->d_x, sd->d_x_alt);
-        sd->cg->x2_written = false;
-        sd->cg->x2_out = sd->d_x_alt;
+        std::swap(d->d_x, d->d_x_alt);
+        d->cg->x2_written = false;
+        d->cg->x2_out = d->d_x_alt;
         return SCHWZ_OK;
     }
-    return launch_copy(sd->local_size, sd->d_y, sd->d_x, (hipStream_t)stream);
+    return launch_copy(sd->local_size, d->d_y, d->d_x, (hipStream_t)stream);
 }
 
 // Between two solves on a set-up subdomain (an extension; the right-hand side itself is replaced by the calls of
@@ -691,21 +696,22 @@ int schwz_ras_restrict(schwz_subdomain *sd, schwz_stream stream)
 int schwz_ras_restart(schwz_subdomain *sd, int keep_x, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_restart");
+    schwz_subdomain_device *d = sd->dev;
     SCHWZ_REQUIRE(keep_x == 0 || keep_x == 1, "schwz_ras_restart: keep_x must be 0 or 1");
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = pcg_forget(sd->cg, st)) || (rc = pcg_f32_forget(sd->cg32, st)) || (rc = cheb_forget(sd->cheb, st)) ||
-        (rc = gmres_forget(sd->gmres, st)) || (rc = bicgstab_forget(sd->bicg, st)))
+    if ((rc = pcg_forget(d->cg, st)) || (rc = pcg_f32_forget(d->cg32, st)) || (rc = cheb_forget(d->cheb, st)) ||
+        (rc = gmres_forget(d->gmres, st)) || (rc = bicgstab_forget(d->bicg, st)))
         return rc;
     const int64_t n = sd->local_size_x;
-    if (keep_x) return launch_copy(n, sd->d_rhs, sd->d_btilde, st);
+    if (keep_x) return launch_copy(n, d->d_rhs, d->d_btilde, st);
     const bool uni = want_unified(sd) && ensure_x_alt(sd);
     // (the pass below zeroes it: no memset of its own)
-    if (!uni && !sd->d_y) SCHWZ_HIP_TRY(hipMalloc((void **)&sd->d_y, (size_t)(n ? n : 1) * sizeof(double)));
-    sd->unified = uni;
-    sd->y_in_alt = false;
-    sd->y_ahead = false;
-    return launch_restart(n, n + sd->halo_size, sd->d_rhs, sd->d_btilde, sd->d_x, sd->d_x_alt, sd->d_y, st);
+    if (!uni && !d->d_y && (rc = d->d_y.alloc((size_t)(n ? n : 1)))) return rc;
+    d->unified = uni;
+    d->y_in_alt = false;
+    d->y_ahead = false;
+    return launch_restart(n, n + sd->halo_size, d->d_rhs, d->d_btilde, d->d_x, d->d_x_alt, d->d_y, st);
 }
 
 // The coarse correction c (schwz_coarse_solve) added to every copy of every row this subdomain holds: all slots of
@@ -717,11 +723,12 @@ int schwz_ras_restart(schwz_subdomain *sd, int keep_x, schwz_stream stream)
 int schwz_ras_coarse_apply(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_coarse_apply");
-    SCHWZ_REQUIRE(sd->coarse, "schwz_ras_coarse_apply: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
+    schwz_subdomain_device *d = sd->dev;
+    SCHWZ_REQUIRE(d->coarse, "schwz_ras_coarse_apply: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
     SCHWZ_REQUIRE(c, "schwz_ras_coarse_apply: null coarse object");
     double *y = y_of(sd);
-    if (y == sd->d_x) y = nullptr;
-    return launch_coarse_apply(sd->coarse, c, sd->d_x, sd->local_size_x + sd->halo_size, y, y ? sd->local_size_x : 0,
+    if (y == d->d_x) y = nullptr;
+    return launch_coarse_apply(d->coarse, c, d->d_x, sd->local_size_x + sd->halo_size, y, y ? sd->local_size_x : 0,
                                (hipStream_t)stream);
 }
 
@@ -730,10 +737,10 @@ int schwz_ras_vector(schwz_subdomain *sd, int which, double **d_ptr, int64_t *le
     REQUIRE_DEVICE(sd, "schwz_ras_vector");
     SCHWZ_REQUIRE(d_ptr && len, "schwz_ras_vector: null output");
     switch (which) {
-    case 0: *d_ptr = sd->d_x; *len = sd->local_size_x + sd->halo_size; break;
-    case 1: *d_ptr = sd->d_btilde; *len = sd->local_size_x; break;
+    case 0: *d_ptr = sd->dev->d_x; *len = sd->local_size_x + sd->halo_size; break;
+    case 1: *d_ptr = sd->dev->d_btilde; *len = sd->local_size_x; break;
     case 2: *d_ptr = y_of(sd); *len = sd->local_size_x; break;
-    case 3: *d_ptr = sd->d_rhs; *len = sd->local_size_x; break;
+    case 3: *d_ptr = sd->dev->d_rhs; *len = sd->local_size_x; break;
     default: set_error("schwz_ras_vector: unknown vector id"); return SCHWZ_ERR_INVALID;
     }
     return SCHWZ_OK;
@@ -743,18 +750,18 @@ int schwz_ras_local_csr(schwz_subdomain *sd, schwz_csr **out)
 {
     REQUIRE_DEVICE(sd, "schwz_ras_local_csr");
     SCHWZ_REQUIRE(out, "schwz_ras_local_csr: null output");
-    *out = sd->A;
+    *out = sd->dev->A;
     return SCHWZ_OK;
 }
 
 // 0 none, 1 full 1/diag vector, 2 one-byte codes into a dictionary, 3 one scalar (schwz::DiagView)
-int schwz_ras_jacobi_form(const schwz_subdomain *sd) { return sd && sd->cg ? sd->cg->diag.mode : 0; }
+int schwz_ras_jacobi_form(const schwz_subdomain *sd) { return sd && sd->dev && sd->dev->cg ? sd->dev->cg->diag.mode : 0; }
 
-int schwz_ras_y_form(const schwz_subdomain *sd) { return sd && sd->on_device && sd->unified ? (sd->y_in_alt ? 2 : 1) : 0; }
+int schwz_ras_y_form(const schwz_subdomain *sd) { return sd && sd->dev && sd->dev->unified ? (sd->dev->y_in_alt ? 2 : 1) : 0; }
 
 int schwz_ras_cg_flavour(const schwz_subdomain *sd)
 {
-    return sd && local_kind(sd) == LocalKind::Cg && sd->cg ? schwz_pcg_flavour(sd->cg) : 0;
+    return sd && sd->dev && local_kind(sd) == LocalKind::Cg && sd->dev->cg ? schwz_pcg_flavour(sd->dev->cg) : 0;
 }
 
 int schwz_ras_local_precision(const schwz_subdomain *sd) { return sd ? sd->precision : SCHWZ_PRECISION_F64; }
@@ -765,7 +772,7 @@ int schwz_ras_local_precision(const schwz_subdomain *sd) { return sd ? sd->preci
 static int plain_cg_precond(const schwz_subdomain *sd)
 {
     const schwz_solver_options &o = sd->opt;
-    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->cg) return -1;
+    if (o.local_solver != SCHWZ_SOLVER_ITERATIVE || o.non_symmetric || !sd->dev->cg) return -1;
     if (o.precond == SCHWZ_PRECOND_NONE) return SCHWZ_PRECOND_NONE;
     if (o.precond == SCHWZ_PRECOND_JACOBI || (o.precond == SCHWZ_PRECOND_BLOCK_JACOBI && o.precond_block_size <= 1))
         return SCHWZ_PRECOND_JACOBI;
@@ -804,7 +811,7 @@ int schwz_ras_set_local_precision(schwz_subdomain *sd, int precision)
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
     int rc;
-    if (!sd->cg32 && (rc = schwz_pcg_f32_create(sd->A, precond, &sd->cg32))) return rc;
+    if (!sd->dev->cg32 && (rc = schwz_pcg_f32_create(sd->dev->A, precond, &sd->dev->cg32))) return rc;
     sd->precision = precision;
     return settle_form(sd);
 }
@@ -831,24 +838,24 @@ int schwz_ras_set_sym_solver(schwz_subdomain *sd, int which)
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
     int rc;
-    if (!sd->cheb && (rc = schwz_cheb_create(sd->A, precond, &sd->cheb))) return rc;
+    if (!sd->dev->cheb && (rc = schwz_cheb_create(sd->dev->A, precond, &sd->dev->cheb))) return rc;
     sd->sym_solver = which;
     return settle_form(sd);
 }
 
 int schwz_ras_cheb_bounds(const schwz_subdomain *sd, double *lmin, double *lmax)
 {
-    SCHWZ_REQUIRE(sd && sd->cheb, "schwz_ras_cheb_bounds: the subdomain has no Chebyshev solver (schwz_ras_set_sym_solver)");
-    return schwz_cheb_bounds(sd->cheb, lmin, lmax);
+    SCHWZ_REQUIRE(sd && sd->dev && sd->dev->cheb, "schwz_ras_cheb_bounds: the subdomain has no Chebyshev solver (schwz_ras_set_sym_solver)");
+    return schwz_cheb_bounds(sd->dev->cheb, lmin, lmax);
 }
 
 int schwz_ras_set_cheb_bounds(schwz_subdomain *sd, double lmin, double lmax)
 {
-    SCHWZ_REQUIRE(sd && sd->cheb, "schwz_ras_set_cheb_bounds: the subdomain has no Chebyshev solver (schwz_ras_set_sym_solver)");
-    return schwz_cheb_set_bounds(sd->cheb, lmin, lmax);
+    SCHWZ_REQUIRE(sd && sd->dev && sd->dev->cheb, "schwz_ras_set_cheb_bounds: the subdomain has no Chebyshev solver (schwz_ras_set_sym_solver)");
+    return schwz_cheb_set_bounds(sd->dev->cheb, lmin, lmax);
 }
 
-int schwz_ras_nonsym_solver(const schwz_subdomain *sd) { return sd && sd->bicg ? SCHWZ_NONSYM_BICGSTAB : SCHWZ_NONSYM_GMRES; }
+int schwz_ras_nonsym_solver(const schwz_subdomain *sd) { return sd && sd->dev && sd->dev->bicg ? SCHWZ_NONSYM_BICGSTAB : SCHWZ_NONSYM_GMRES; }
 
 int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which)
 {
@@ -856,8 +863,9 @@ int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which)
     SCHWZ_REQUIRE(which == SCHWZ_NONSYM_GMRES || which == SCHWZ_NONSYM_BICGSTAB,
                   "schwz_ras_set_nonsym_solver: unknown solver");
     REQUIRE_DEVICE(sd, "schwz_ras_set_nonsym_solver");
+    schwz_subdomain_device *d = sd->dev;
     // (exactly one of gmres / bicg and no cg: what local_kind relies on)
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !sd->gmres == !sd->bicg || sd->cg) {
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !d->gmres == !d->bicg || d->cg) {
         set_error("schwz_ras_set_nonsym_solver: the choice exists for the iterative local solver of a non-symmetric "
                   "matrix only");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
@@ -870,18 +878,18 @@ int schwz_ras_set_nonsym_solver(schwz_subdomain *sd, int which)
     // the old one still owns it; a failure (no memory for the work vectors) leaves the subdomain as it was.
     int rc;
     if (which == SCHWZ_NONSYM_BICGSTAB) {
-        if ((rc = bicgstab_create_adopt(sd->A, gmres_precond(sd->gmres), &sd->bicg))) return rc;
-        (void)gmres_release_precond(sd->gmres);
-        schwz_gmres_destroy(sd->gmres);
-        sd->gmres = nullptr;
+        if ((rc = bicgstab_create_adopt(d->A, gmres_precond(d->gmres), &d->bicg))) return rc;
+        (void)gmres_release_precond(d->gmres);
+        schwz_gmres_destroy(d->gmres);
+        d->gmres = nullptr;
         return SCHWZ_OK;
     }
-    if ((rc = gmres_create_adopt(sd->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, sd->gmres_basis,
-                                 bicgstab_precond(sd->bicg), &sd->gmres)))
+    if ((rc = gmres_create_adopt(d->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, sd->gmres_basis,
+                                 bicgstab_precond(d->bicg), &d->gmres)))
         return rc;
-    (void)bicgstab_release_precond(sd->bicg);
-    schwz_bicgstab_destroy(sd->bicg);
-    sd->bicg = nullptr;
+    (void)bicgstab_release_precond(d->bicg);
+    schwz_bicgstab_destroy(d->bicg);
+    d->bicg = nullptr;
     return SCHWZ_OK;
 }
 
@@ -893,23 +901,24 @@ int schwz_ras_set_gmres_basis(schwz_subdomain *sd, int which)
     SCHWZ_REQUIRE(which == SCHWZ_GMRES_BASIS_F64 || which == SCHWZ_GMRES_BASIS_F32,
                   "schwz_ras_set_gmres_basis: unknown basis type");
     REQUIRE_DEVICE(sd, "schwz_ras_set_gmres_basis");
-    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !sd->gmres == !sd->bicg || sd->cg) {
+    schwz_subdomain_device *d = sd->dev;
+    if (sd->opt.local_solver != SCHWZ_SOLVER_ITERATIVE || !sd->opt.non_symmetric || !d->gmres == !d->bicg || d->cg) {
         set_error("schwz_ras_set_gmres_basis: the choice exists for the iterative local solver of a non-symmetric "
                   "matrix only");
         return SCHWZ_ERR_NOT_IMPLEMENTED;
     }
     if (which == sd->gmres_basis) return SCHWZ_OK;
-    if (sd->gmres) {
+    if (d->gmres) {
         // as in schwz_ras_set_nonsym_solver: the new solver is created around the preconditioner while the old one
         // still owns it, so a failure leaves the subdomain as it was
         SCHWZ_HIP_TRY(hipDeviceSynchronize());
         schwz_gmres *fresh = nullptr;
-        const int rc = gmres_create_adopt(sd->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, which,
-                                          gmres_precond(sd->gmres), &fresh);
+        const int rc = gmres_create_adopt(d->A, sd->opt.restart_iter < 1 ? 1 : sd->opt.restart_iter, which,
+                                          gmres_precond(d->gmres), &fresh);
         if (rc) return rc;
-        (void)gmres_release_precond(sd->gmres);
-        schwz_gmres_destroy(sd->gmres);
-        sd->gmres = fresh;
+        (void)gmres_release_precond(d->gmres);
+        schwz_gmres_destroy(d->gmres);
+        d->gmres = fresh;
     }
     sd->gmres_basis = which;  // (while BiCGSTAB is set: what a return to GMRES creates)
     return SCHWZ_OK;
@@ -920,7 +929,7 @@ int schwz_ras_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stre
     REQUIRE_DEVICE(sd, "schwz_ras_get_interior");
     SCHWZ_REQUIRE(h_out || sd->local_size == 0, "schwz_ras_get_interior: null output");
     if (sd->local_size == 0) return SCHWZ_OK;
-    SCHWZ_HIP_TRY(hipMemcpyAsync(h_out, sd->d_x, (size_t)sd->local_size * sizeof(double), hipMemcpyDeviceToHost,
+    SCHWZ_HIP_TRY(hipMemcpyAsync(h_out, sd->dev->d_x, (size_t)sd->local_size * sizeof(double), hipMemcpyDeviceToHost,
                                  (hipStream_t)stream));
     SCHWZ_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return SCHWZ_OK;
@@ -937,10 +946,10 @@ int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which)
         // the coarse step of this subdomain (coarse.hip): W (value, slot, gathered x~) and the aggregates' beta and s;
         // its m rows of the GEMV over the explicit inverse with s read and c written; the apply pass -- x~ read and
         // written and two bytes of id per slot, and y read and written where it is a buffer of its own
-        const schwz_coarse_part *p = sd->coarse;
+        const schwz_coarse_part *p = sd->dev ? sd->dev->coarse : nullptr;
         if (!p) return 0;
         const int64_t slots = p->nslots;
-        const bool own_y = !(sd->unified && !sd->y_in_alt);
+        const bool own_y = !(sd->dev->unified && !sd->dev->y_in_alt);
         return 20 * p->nw + 16 * (int64_t)p->m + 8 * (int64_t)p->m * p->nc + 16 * (int64_t)p->nc + 16 * slots + 2 * slots +
                (own_y ? 16 * n : 0);
     }

@@ -450,38 +450,17 @@ static int trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, 
     plan(ul, t->u_plan);
     t->h_l_lvl = ll;
     t->h_u_lvl = ul;
-    int rc = 0;
-    void *d;
-#define UP(dst, src, cnt, T)                        \
-    if (!rc) {                                      \
-        rc = upload<T>((src), (size_t)(cnt), &d);   \
-        dst = (decltype(dst))d;                     \
-    }
-    UP(t->l_rp, l_rp, n + 1, schwz_idx)
-    UP(t->l_col, l_col, l_rp[n], schwz_idx)
-    UP(t->l_val, l_val, l_rp[n], double)
-    UP(t->u_rp, u_rp, n + 1, schwz_idx)
-    UP(t->u_col, u_col, u_rp[n], schwz_idx)
-    UP(t->u_val, u_val, u_rp[n], double)
-    if (perm) {
-        UP(t->perm, perm, n, schwz_idx)
-    }
-    if (perm_out == perm) {
-        t->perm_out = t->perm;
-    } else {
-        UP(t->perm_out, perm_out, n, schwz_idx)
-    }
-    UP(t->l_order, lo.data(), lo.size(), schwz_idx)
-    UP(t->l_lvl, ll.data(), ll.size(), schwz_idx)
-    UP(t->u_order, uo.data(), uo.size(), schwz_idx)
-    UP(t->u_lvl, ul.data(), ul.size(), schwz_idx)
-#undef UP
-    if (rc) {
-        schwz_trs_destroy(t);
+    std::unique_ptr<schwz_trs> own(t);  // (a failure below leaves nothing behind)
+    int rc;
+    if ((rc = t->l_rp.put(l_rp, (size_t)n + 1)) || (rc = t->l_col.put(l_col, (size_t)l_rp[n])) ||
+        (rc = t->l_val.put(l_val, (size_t)l_rp[n])) || (rc = t->u_rp.put(u_rp, (size_t)n + 1)) ||
+        (rc = t->u_col.put(u_col, (size_t)u_rp[n])) || (rc = t->u_val.put(u_val, (size_t)u_rp[n])) ||
+        (perm && (rc = t->perm.put(perm, (size_t)n))) ||
+        (perm_out != perm && (rc = t->perm_col.put(perm_out, (size_t)n))) || (rc = t->l_order.put(lo)) ||
+        (rc = t->l_lvl.put(ll)) || (rc = t->u_order.put(uo)) || (rc = t->u_lvl.put(ul)) ||
+        (rc = t->w0.alloc((size_t)(n ? n : 1))) || (rc = t->w1.alloc((size_t)(n ? n : 1))))
         return rc;
-    }
-    SCHWZ_HIP_TRY(hipMalloc((void **)&t->w0, sizeof(double) * (size_t)(n ? n : 1)));
-    SCHWZ_HIP_TRY(hipMalloc((void **)&t->w1, sizeof(double) * (size_t)(n ? n : 1)));
+    t->perm_out = perm_out == perm ? t->perm : t->perm_col;
     // flag-driven sweeps (one persistent launch per factor) for factors beyond the one-workgroup kernel
     // whose rows are short enough for one lane each, and for LU factors with longer rows one wave per
     // row (trs_flag_wave_kernel); SCHWZ_TRS_FLAGS=0: the level-by-level plan
@@ -516,38 +495,20 @@ static int trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, 
             };
             std::vector<schwz_idx> prp, pcol, lsrc((size_t)n), usrc((size_t)n), udst((size_t)n);
             std::vector<double> pval;
-            int rc2 = 0;
             permuted(l_rp, l_col, l_val, lo, lpos, prp, pcol, pval);
-            if (!rc2) rc2 = upload(prp.data(), prp.size(), &d), t->fl_rp = (schwz_idx *)d;
-            if (!rc2) rc2 = upload(pcol.data(), pcol.size(), &d), t->fl_col = (schwz_idx *)d;
-            if (!rc2) rc2 = upload(pval.data(), pval.size(), &d), t->fl_val = (double *)d;
+            if ((rc = t->fl_rp.put(prp)) || (rc = t->fl_col.put(pcol)) || (rc = t->fl_val.put(pval))) return rc;
             permuted(u_rp, u_col, u_val, uo, upos, prp, pcol, pval);
-            if (!rc2) rc2 = upload(prp.data(), prp.size(), &d), t->fu_rp = (schwz_idx *)d;
-            if (!rc2) rc2 = upload(pcol.data(), pcol.size(), &d), t->fu_col = (schwz_idx *)d;
-            if (!rc2) rc2 = upload(pval.data(), pval.size(), &d), t->fu_val = (double *)d;
+            if ((rc = t->fu_rp.put(prp)) || (rc = t->fu_col.put(pcol)) || (rc = t->fu_val.put(pval))) return rc;
             for (int64_t k = 0; k < n; ++k) {
                 lsrc[(size_t)k] = perm ? perm[lo[(size_t)k]] : lo[(size_t)k];
                 usrc[(size_t)k] = lpos[(size_t)uo[(size_t)k]];
                 udst[(size_t)k] = perm_out ? perm_out[uo[(size_t)k]] : uo[(size_t)k];
             }
-            if (!rc2) rc2 = upload(lsrc.data(), lsrc.size(), &d), t->fl_src = (schwz_idx *)d;
-            if (!rc2) rc2 = upload(usrc.data(), usrc.size(), &d), t->fu_src = (schwz_idx *)d;
-            if (!rc2) rc2 = upload(udst.data(), udst.size(), &d), t->fu_dst = (schwz_idx *)d;
-            std::vector<unsigned long long> unset((size_t)n, kTrsUnset);
-            if (!rc2) rc2 = upload(unset.data(), unset.size(), &d), t->f0 = (unsigned long long *)d;
-            if (!rc2) {
-                rc2 = upload(unset.data(), unset.size(), &d);
-                t->f1 = (unsigned long long *)d;
-            }
+            const std::vector<unsigned long long> unset((size_t)n, kTrsUnset);
             const int zero = 0;
-            if (!rc2) {
-                rc2 = upload(&zero, 1, &d);
-                t->d_err = (int *)d;
-            }
-            if (rc2) {
-                schwz_trs_destroy(t);
-                return rc2;
-            }
+            if ((rc = t->fl_src.put(lsrc)) || (rc = t->fu_src.put(usrc)) || (rc = t->fu_dst.put(udst)) ||
+                (rc = t->f0.put(unset)) || (rc = t->f1.put(unset)) || (rc = t->d_err.put(&zero, 1)))
+                return rc;
             t->flags = true;
             int dev = 0, cus = 256;
             hipDeviceProp_t prop;
@@ -577,7 +538,7 @@ static int trs_create(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col, 
             if (per_cu < 1) t->flags = false;
         }
     }
-    *out = t;
+    *out = own.release();
     return SCHWZ_OK;
 }
 
@@ -596,20 +557,7 @@ int schwz_trs_create_lu(int64_t n, const schwz_idx *l_rp, const schwz_idx *l_col
     return trs_create(n, l_rp, l_col, l_val, u_rp, u_col, u_val, row_perm, col_perm, true, out);
 }
 
-void schwz_trs_destroy(schwz_trs *t)
-{
-    if (!t) return;
-    if (t->perm_out != t->perm) (void)hipFree(t->perm_out);
-    void *ptrs[] = {t->l_rp, t->l_col, t->l_val, t->u_rp, t->u_col, t->u_val, t->perm,
-                    t->l_order, t->l_lvl, t->u_order, t->u_lvl, t->w0, t->w1, t->f0, t->f1, t->d_err,
-                    t->fl_rp, t->fl_col, t->fl_val, t->fu_rp, t->fu_col, t->fu_val, t->fl_src, t->fu_src, t->fu_dst,
-                    t->w2, t->js_l_rp, t->js_l_col, t->js_l_val, t->js_l_dinv, t->js_u_rp, t->js_u_col, t->js_u_val,
-                    t->js_u_dinv};
-    for (void *p : ptrs) (void)hipFree(p);
-    for (auto &g : t->graphs) (void)hipGraphExecDestroy(g.exec);
-    if (t->capture_stream) (void)hipStreamDestroy(t->capture_stream);
-    delete t;
-}
+void schwz_trs_destroy(schwz_trs *t) { delete t; }
 
 int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream stream)
 {
@@ -630,7 +578,7 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
                            t->fl_col, t->fl_val, d_b, t->fl_src, t->f1, t->f0, (double *)nullptr,
                            (const schwz_idx *)nullptr, t->d_err);
         hipLaunchKernelGGL((trs_flag_wave_kernel<false>), dim3(t->flag_grid), dim3(kBlock), 0, st, t->n, t->fu_rp,
-                           t->fu_col, t->fu_val, reinterpret_cast<const double *>(t->f1), t->fu_src, t->f0, t->f1, d_y,
+                           t->fu_col, t->fu_val, reinterpret_cast<const double *>((unsigned long long *)t->f1), t->fu_src, t->f0, t->f1, d_y,
                            t->fu_dst, t->d_err);
         SCHWZ_HIP_TRY(hipGetLastError());
         return SCHWZ_OK;
@@ -640,7 +588,7 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
         hipLaunchKernelGGL((trs_flag_kernel<true>), dim3(t->flag_grid), dim3(kBlock), 0, st, t->n, t->fl_rp, t->fl_col,
                            t->fl_val, d_b, t->fl_src, t->f1, t->f0, (double *)nullptr, (const schwz_idx *)nullptr, t->d_err);
         hipLaunchKernelGGL((trs_flag_kernel<false>), dim3(t->flag_grid), dim3(kBlock), 0, st, t->n, t->fu_rp, t->fu_col,
-                           t->fu_val, reinterpret_cast<const double *>(t->f1), t->fu_src, t->f0, t->f1, d_y, t->fu_dst,
+                           t->fu_val, reinterpret_cast<const double *>((unsigned long long *)t->f1), t->fu_src, t->f0, t->f1, d_y, t->fu_dst,
                            t->d_err);
         SCHWZ_HIP_TRY(hipGetLastError());
         return SCHWZ_OK;
@@ -661,7 +609,8 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
                 return SCHWZ_OK;
             }
         if (t->graphs.size() < 4) {
-            if (!t->capture_stream) SCHWZ_HIP_TRY(hipStreamCreateWithFlags(&t->capture_stream, hipStreamNonBlocking));
+            int rc_cs;
+            if (!t->capture_stream && (rc_cs = t->capture_stream.create())) return rc_cs;
             if (hipStreamBeginCapture(t->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
                 capturing = true;
                 st = t->capture_stream;
@@ -694,21 +643,20 @@ int schwz_trs_solve(schwz_trs *t, const double *d_b, double *d_y, schwz_stream s
     }
     hipLaunchKernelGGL(trs_permute_out_kernel, dim3(grid_for(t->n)), dim3(kBlock), 0, st, t->n, t->perm_out, t->w0, d_y);
     if (capturing) {
-        hipGraph_t graph = nullptr;
-        if (hipStreamEndCapture(t->capture_stream, &graph) != hipSuccess || !graph) {
+        Graph graph;
+        if (hipStreamEndCapture(t->capture_stream, &graph.h) != hipSuccess || !graph) {
             (void)hipGetLastError();
             t->graphs_failed = true;
             return schwz_trs_solve(t, d_b, d_y, stream);
         }
         hipGraphExec_t exec = nullptr;
         const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
         if (e != hipSuccess) {  // no graph on this system: launch by launch from now on
             (void)hipGetLastError();
             t->graphs_failed = true;
             return schwz_trs_solve(t, d_b, d_y, stream);
         }
-        t->graphs.push_back({d_b, d_y, exec});
+        t->graphs.push_back({d_b, d_y, GraphExec(exec)});
         SCHWZ_HIP_TRY(hipGraphLaunch(exec, user_stream));
         return SCHWZ_OK;
     }
