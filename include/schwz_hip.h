@@ -933,6 +933,53 @@ int schwz_ras_batch_vector(schwz_subdomain *sd, int which, double **d_ptr, int64
 int schwz_ras_batch_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 int schwz_ras_batch_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 
+/* ---- Outer FGMRES preconditioned by one RAS sweep: the device half (an extension: the reference's only outer
+ * iteration is the stationary one of SchwarzBase::run, source/schwarz_base.cpp:387-452, and it has no outer Krylov
+ * method, so no line of it is replaced).  The host layer (schwz_amd/outer.py) runs right-preconditioned flexible
+ * GMRES(m): z_j = M^-1 v_j is one RAS sweep from a zero start made of the calls above, w = A z_j comes from
+ * schwz_ras_apply_interior, w is orthogonalised against V_0..V_j by classical Gram-Schmidt applied twice, and the
+ * Givens rotations and the small triangular solve run on the host.
+ *
+ * schwz_ras_apply_interior: d_out[i] = (A x~)_i for the local_size interior rows, given up-to-date overlap values in
+ * x~ (after an exchange): the operator, the matrix and its codings are those of the pass of schwz_ras_true_residual_sq,
+ * the vector is kept instead of its norm.  The pass covers all local_size_x rows of the local matrix; on a subdomain
+ * with overlap rows it goes through a vector of local_size_x doubles that the subdomain allocates at the first call.
+ * d_out: device memory, local_size doubles.  Obeys `stream`, does not wait for it.
+ *
+ * One schwz_outer per process, over the n = sum of local_size interior rows of its subdomains, concatenated in
+ * subdomain order: V ((restart + 1) columns), Z (restart columns), w, a copy of b, partial sums and a pinned buffer
+ * for the coefficients, allocated once by schwz_outer_create (1 <= restart <= 128, n >= 0; columns are 256-byte
+ * aligned).  Because the vectors are global within the process, every reduction is one launch over n.
+ * schwz_outer_vector: device pointer of V_j (which = 0, 0 <= j <= restart), Z_j (1, 0 <= j < restart), w (2, j = 0)
+ * or the copy of b (3, j = 0), n doubles each; fixed for the object's life.
+ * schwz_outer_start: V_0 = w * inv_beta.  schwz_outer_normalize: V_(j+1) = w * inv_norm, 0 <= j < restart.
+ * schwz_outer_dots: h_out[i] = V_i . w for i <= j and h_out[j + 1] = w . w (j + 2 values on the host; waits for
+ * `stream`).  One pass that reads w and every V_i once, the accumulators of up to 32 coefficients in registers;
+ * per-workgroup partial sums are folded in a fixed order by a second small launch, no floating-point atomics: the same
+ * bits on every run.
+ * schwz_outer_project_dots: w <- w - sum_(i <= j) h_in[i] V_i and, in the same pass, h_out[i] = V_i . w and
+ * h_out[j + 1] = w . w of the NEW w (a lane keeps its rows' V_i values in registers between the subtraction and the
+ * dots; h_in: j + 1 host values, passed by value).  0 <= j < restart for both; beyond 31 columns (j > 30) the work is
+ * split into launches of 32 columns and the subtraction and the dots become passes of their own.
+ * schwz_outer_combine: d_x[r] += sum_(i < k) h_y[i] Z_i[r] over the n rows, 1 <= k <= restart, one pass per 32
+ * columns; d_x: device memory, n doubles (it may be a vector of the object).
+ * schwz_outer_copy: d_dst[0:n] = d_src[0:n] on the device for pointers of any 8-byte alignment, the copies between
+ * the interior of a subdomain's x~ and its slice of a vector of the object.
+ * Bytes per outer iteration j: dots + two project_dots + normalize = 3 * 8 n (j + 2) + 32 n.
+ * All launches go to `stream`.  A null object, pointer or an index out of range: SCHWZ_ERR_INVALID before any HIP
+ * call. */
+typedef struct schwz_outer schwz_outer;
+int schwz_ras_apply_interior(schwz_subdomain *sd, double *d_out, schwz_stream stream);
+int schwz_outer_create(int64_t n, int restart, schwz_outer **out);
+void schwz_outer_destroy(schwz_outer *o);
+int schwz_outer_vector(schwz_outer *o, int which, int j, double **d_ptr);
+int schwz_outer_start(schwz_outer *o, double inv_beta, schwz_stream stream);
+int schwz_outer_dots(schwz_outer *o, int j, double *h_out, schwz_stream stream);
+int schwz_outer_project_dots(schwz_outer *o, int j, const double *h_in, double *h_out, schwz_stream stream);
+int schwz_outer_normalize(schwz_outer *o, int j, double inv_norm, schwz_stream stream);
+int schwz_outer_combine(schwz_outer *o, int k, const double *h_y, double *d_x, schwz_stream stream);
+int schwz_outer_copy(int64_t n, const double *d_src, double *d_dst, schwz_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

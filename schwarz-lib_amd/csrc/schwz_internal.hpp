@@ -585,6 +585,7 @@ int launch_interface_update(int64_t nrows, int64_t row0, const schwz_idx *rp, co
                             const double *val, const double *x, const double *b, double *bt, hipStream_t s);
 int launch_final_norm(const double *partials, int nparts, double *out, hipStream_t s);
 int launch_copy(int64_t n, const double *src, double *dst, hipStream_t s);
+int launch_copy_any(int64_t n, const double *src, double *dst, hipStream_t s);  // outer.hip: any 8-byte alignment
 int launch_gather_f32(int64_t n, const schwz_idx *idx, const double *from, float *into, hipStream_t s);
 int launch_scatter_f32(int64_t n, const schwz_idx *idx, const float *from, double *into, hipStream_t s);
 
@@ -1037,6 +1038,8 @@ struct schwz_subdomain_device {
     schwz_coarse_part *coarse = nullptr;
     schwz::Dev<int64_t> d_rhs_index;  // device copy of the map of schwz_ras_rhs_gather (schwz_subdomain::rhs_index)
     schwz_ras_batch *batch = nullptr;  // null until asked for
+    // schwz_ras_apply_interior on a subdomain with overlap rows: A x~ on all local_size_x rows (allocated at first need)
+    schwz::Dev<double> d_apply;
 };
 
 namespace schwz {

@@ -582,6 +582,27 @@ int schwz_ras_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream 
     return SCHWZ_OK;
 }
 
+// (A x~) on the interior rows, kept (the outer FGMRES, csrc/outer.hip): the local matrix in the coding the residual
+// launches read, over all its local_size_x rows.  Without overlap rows the pass writes d_out itself; otherwise it goes
+// through d_apply, whose first local_size entries are copied.
+int schwz_ras_apply_interior(schwz_subdomain *sd, double *d_out, schwz_stream stream)
+{
+    REQUIRE_DEVICE(sd, "schwz_ras_apply_interior");
+    SCHWZ_REQUIRE(d_out || sd->local_size == 0, "schwz_ras_apply_interior: null output");
+    if (sd->local_size == 0) return SCHWZ_OK;
+    schwz_subdomain_device *d = sd->dev;
+    hipStream_t st = (hipStream_t)stream;
+    const bool direct = sd->local_size_x == sd->local_size && ((uintptr_t)d_out & 15u) == 0;
+    int rc;
+    if (!direct && !d->d_apply && (rc = d->d_apply.alloc((size_t)sd->local_size_x, true))) return rc;
+    SpmvArgs a;
+    a.x = d->d_x;
+    a.y = direct ? d_out : (double *)d->d_apply;
+    a.stream_part = d->d_stream_part;
+    if ((rc = launch_spmv(d->A->v, kSpmvPlain, a, sd->opt.spmv_variant, st))) return rc;
+    return direct ? SCHWZ_OK : launch_copy_any(sd->local_size, d->d_apply, d_out, st);
+}
+
 int schwz_ras_set_local_max_iters(schwz_subdomain *sd, int max_iters)
 {
     SCHWZ_REQUIRE(sd && sd->dev, "schwz_ras_set_local_max_iters: subdomain is not on the device");

@@ -7,7 +7,7 @@ shared library and fails loudly if it has not been built.
 from . import _capi as capi  # noqa: F401  (loads libschwz_hip.so)
 from ._capi import SchwzError, NotImplementedSchwz  # noqa: F401
 from .comm import InProcessComm, TorchDistComm, WindowComm  # noqa: F401
-from .core import Coarse, dense_inverse  # noqa: F401
+from .core import Coarse, Outer, dense_inverse, outer_copy  # noqa: F401
 from .core import (BatchCg, Bicgstab, Chebyshev, Csr, DeviceWindow, Gmres, Pcg, PcgF32, PeerWindow, Problem, Subdomain, Trs, TrsLU, TrsSweeps, cholesky, gather, ilu0, isai, lu, parilu,  # noqa: F401
                    scatter,
                    partition_regular, partition_regular2d, rhs_random)

@@ -85,7 +85,10 @@ SYMBOLS = [
     "schwz_ras_batch_unpack", "schwz_ras_batch_update_boundary", "schwz_ras_batch_local_residual",
     "schwz_ras_batch_local_solve", "schwz_ras_batch_restrict", "schwz_ras_batch_vector", "schwz_ras_batch_get_interior",
     "schwz_ras_batch_true_residual_sq",
+    "schwz_ras_apply_interior", "schwz_outer_create", "schwz_outer_destroy", "schwz_outer_vector", "schwz_outer_start",
+    "schwz_outer_dots", "schwz_outer_project_dots", "schwz_outer_normalize", "schwz_outer_combine", "schwz_outer_copy",
 ]
+OUTER_MAX_RESTART = 128   # columns of Z a schwz_outer can hold
 BATCH_WIDTHS = (2, 4, 8)  # the block-vector widths the device code is instantiated for
 COARSE_MAX_DOFS = 4096    # aggregates of a coarse space: two bytes per x~ slot, the explicit inverse at most 128 MB
 
@@ -305,6 +308,16 @@ _sig("schwz_ras_batch_restrict", i32, [vp, C.c_uint, vp])
 _sig("schwz_ras_batch_vector", i32, [vp, i32, pvp, C.POINTER(i64)])
 _sig("schwz_ras_batch_get_interior", i32, [vp, vp, vp])
 _sig("schwz_ras_batch_true_residual_sq", i32, [vp, C.POINTER(dbl), vp])
+_sig("schwz_ras_apply_interior", i32, [vp, vp, vp])
+_sig("schwz_outer_create", i32, [i64, i32, pvp])
+_sig("schwz_outer_destroy", None, [vp])
+_sig("schwz_outer_vector", i32, [vp, i32, i32, pvp])
+_sig("schwz_outer_start", i32, [vp, dbl, vp])
+_sig("schwz_outer_dots", i32, [vp, i32, vp, vp])
+_sig("schwz_outer_project_dots", i32, [vp, i32, vp, vp, vp])
+_sig("schwz_outer_normalize", i32, [vp, i32, dbl, vp])
+_sig("schwz_outer_combine", i32, [vp, i32, vp, vp, vp])
+_sig("schwz_outer_copy", i32, [i64, vp, vp, vp])
 
 
 def check(rc):

@@ -888,6 +888,11 @@ class Subdomain:
         check(lib.schwz_ras_true_residual_sq(self.h, C.byref(out), _stream_arg(stream)))
         return out.value
 
+    def apply_interior(self, d_out, stream=0):
+        """(A x~) on the local_size interior rows to the device address d_out (x~ exchanged beforehand); the matrix
+        pass of true_residual_sq with the vector kept (schwz_ras_apply_interior)."""
+        check(lib.schwz_ras_apply_interior(self.h, ptr(d_out), _stream_arg(stream)))
+
     def algorithmic_bytes(self, which=0):
         return int(lib.schwz_ras_algorithmic_bytes(self.h, which))
 
@@ -1063,6 +1068,64 @@ class Coarse:
 
     def __del__(self):
         self.close()
+
+
+class Outer:
+    """The device half of the outer FGMRES (schwz_outer_create): the basis V (restart + 1 columns), the preconditioned
+    directions Z (restart columns), w and a copy of b, each over the n interior rows of the process's subdomains in
+    subdomain order, and the vector passes of one outer iteration."""
+
+    V, Z, W, B = 0, 1, 2, 3
+
+    def __init__(self, n, restart):
+        self.n, self.restart = int(n), int(restart)
+        h = C.c_void_p()
+        check(lib.schwz_outer_create(self.n, self.restart, C.byref(h)))
+        self.h = h
+
+    def vector(self, which, j=0):
+        """Device address of V_j (which = 0), Z_j (1), w (2) or the copy of b (3)."""
+        p = C.c_void_p()
+        check(lib.schwz_outer_vector(self.h, int(which), int(j), C.byref(p)))
+        return p.value
+
+    def start(self, inv_beta, stream=0):
+        check(lib.schwz_outer_start(self.h, float(inv_beta), _stream_arg(stream)))
+
+    def dots(self, j, stream=0):
+        """[V_0 . w, ..., V_j . w, w . w] on the host (waits for the stream)."""
+        out = np.zeros(j + 2)
+        check(lib.schwz_outer_dots(self.h, int(j), ptr(out), _stream_arg(stream)))
+        return out
+
+    def project_dots(self, j, h, stream=0):
+        """w -= sum_i h[i] V_i over i <= j; returns the dots of the new w like dots()."""
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        assert len(h) >= j + 1
+        out = np.zeros(j + 2)
+        check(lib.schwz_outer_project_dots(self.h, int(j), ptr(h), ptr(out), _stream_arg(stream)))
+        return out
+
+    def normalize(self, j, inv_norm, stream=0):
+        check(lib.schwz_outer_normalize(self.h, int(j), float(inv_norm), _stream_arg(stream)))
+
+    def combine(self, y, d_x, stream=0):
+        """x += sum_i y[i] Z_i at the device address d_x (n doubles)."""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        check(lib.schwz_outer_combine(self.h, len(y), ptr(y), ptr(d_x), _stream_arg(stream)))
+
+    def close(self):
+        if getattr(self, "h", None) and lib is not None:
+            lib.schwz_outer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def outer_copy(n, d_src, d_dst, stream=0):
+    """d_dst[0:n] = d_src[0:n] on the device, any 8-byte alignment (schwz_outer_copy)."""
+    check(lib.schwz_outer_copy(int(n), ptr(d_src), ptr(d_dst), _stream_arg(stream)))
 
 
 def lu(rp, col, val, natural=False):

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _capi as capi
 from . import core
+from . import outer
 from .comm import InProcessComm
 
 # Settings::partition_settings / local_solver_settings (include/settings.hpp:96-156)
@@ -164,6 +165,13 @@ class Metadata:
     coarse_space: str = "none"
     coarse_aggregates: int = 0
     coarse_aggregate_vector: object = None
+    # extensions (no field of the reference's Metadata, whose only outer iteration is the stationary one): "richardson"
+    # (run() launch for launch what it was) or "fgmres": run() is right-preconditioned flexible GMRES(outer_restart)
+    # with one RAS sweep as the preconditioner (schwz_amd/outer.py), stopped on ||r_k||_2 <= tolerance * ||b||_2 over
+    # all rows -- not the stationary loop's test.  One level, synchronous two-sided exchange in fp64, one process; any
+    # other name, and an outer_restart outside 1..128, is refused.  solve_many ignores both fields.
+    outer_iteration: str = "richardson"
+    outer_restart: int = 30
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
@@ -642,6 +650,7 @@ class SolverRAS:
         sym_code = _sym_solver_code(s, m)
         basis_code = _gmres_basis_code(s, m)
         coarse_on = _coarse_enabled(s, m)
+        outer.wants_fgmres(s, m, comm)
         self._coarse = None
         if self._distributed_ingest():
             prob = self._ingest_distributed()
@@ -1770,6 +1779,8 @@ class SolverRAS:
         """SchwarzBase::run (schwarz_base.cpp:323-506).  Returns a dict with the
         solution (on the root rank) and the run statistics."""
         m, be, comm = self.metadata, self.backend, self.comm
+        if outer.wants_fgmres(self.settings, m, comm):
+            return outer.run_fgmres(self, gather_solution)
         self.begin_run()
         be.synchronize()
         comm.barrier()
