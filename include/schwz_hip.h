@@ -801,7 +801,10 @@ int schwz_ras_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream 
  * (SURVEY 8d): which: 0 = local SpMV, 1 = one PCG iteration, used by bench.py;
  * 2 = the coarse step of this subdomain (below; 0 without aggregates): 20 B per entry of W and 16 B per own aggregate
  * (residual), the subdomain's m rows of the inverse, 8 m nc, plus 16 nc for s and c (GEMV), and the apply pass,
- * 16 slots + 2 slots, plus 16 local_size_x where y is a buffer of its own */
+ * 16 slots + 2 slots, plus 16 local_size_x where y is a buffer of its own;
+ * 3 = one schwz_ras_aggregate_sums of this subdomain (0 without aggregates): 12 B per interior row (the value and the
+ * row id), 28 B per piece (its record of three ints, its partial sum stored and read), 4 (m + 1) for the offsets of the
+ * fold and 8 m for the sums */
 int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which);
 
 /* ---- Two-level RAS: aggregation coarse correction (an extension: the reference has one level only, so no line of
@@ -846,6 +849,23 @@ int schwz_coarse_vector(schwz_coarse *c, int which, double **d_ptr, int32_t *len
 int schwz_ras_coarse_residual(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream);
 int schwz_coarse_solve(schwz_coarse *c, schwz_stream stream);
 int schwz_ras_coarse_apply(schwz_subdomain *sd, schwz_coarse *c, schwz_stream stream);
+
+/* ---- The aggregate restriction of any vector (an extension, like the coarse correction it belongs to).  A two-level
+ * step whose right-hand side changes with every application -- the preconditioner of the outer FGMRES below, z = z0 +
+ * RAS(v - A z0) with z0 = Z A0^-1 Z^T v -- needs Z^T v once per application, where the stationary iteration needs
+ * beta = Z^T b once per solve.  schwz_ras_aggregate_sums writes
+ *     s[first_agg + a] = sum_{i in a} d_vec[i]     for the subdomain's m aggregates
+ * into s of the coarse object (the vector schwz_ras_coarse_residual writes and schwz_coarse_solve reads) and nothing
+ * else: s outside [first_agg, first_agg + m) and beta of the coarse part keep their values.  d_vec: device memory, at
+ * least local_size doubles in local order -- the address of x~ or of the vector of id 3 both do.
+ * The rows grouped by aggregate are cut on the host into pieces of at most 2048 rows of one aggregate; one workgroup
+ * per piece sums in a fixed tree order and stores one partial sum, a second small launch folds every aggregate's
+ * pieces in table order: no atomics, the same bits from run to run.  A streaming pass -- 12 B per interior row, see
+ * schwz_ras_algorithmic_bytes(sd, 3) -- where schwz_ras_rhs_aggregate, which keeps the host plan's order and bits,
+ * walks an aggregate with one lane.  The tables are shared with schwz_ras_rhs_aggregate and built by the first call of
+ * either (it waits for `stream` once).  Obeys `stream`.  m = 0: SCHWZ_OK, nothing launched.  SCHWZ_ERR_INVALID, before
+ * any HIP call, for a null argument, a subdomain without aggregates and a coarse object with another nc. */
+int schwz_ras_aggregate_sums(schwz_subdomain *sd, schwz_coarse *c, const double *d_vec, schwz_stream stream);
 
 /* ---- One matrix, many right-hand sides (an extension: the reference solves the one system its initialize was handed,
  * SchwarzBase::initialize at source/schwarz_base.cpp:128-271, and has no call that replaces b, so no line of it is
@@ -933,7 +953,8 @@ int schwz_ras_batch_vector(schwz_subdomain *sd, int which, double **d_ptr, int64
 int schwz_ras_batch_get_interior(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 int schwz_ras_batch_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_stream stream);
 
-/* ---- Outer FGMRES preconditioned by one RAS sweep: the device half (an extension: the reference's only outer
+/* ---- Outer FGMRES preconditioned by one RAS sweep, or by one two-level step (schwz_ras_aggregate_sums above, the
+ * coarse solve and apply, then the sweep): the device half (an extension: the reference's only outer
  * iteration is the stationary one of SchwarzBase::run, source/schwarz_base.cpp:387-452, and it has no outer Krylov
  * method, so no line of it is replaced).  The host layer (schwz_amd/outer.py) runs right-preconditioned flexible
  * GMRES(m): z_j = M^-1 v_j is one RAS sweep from a zero start made of the calls above, w = A z_j comes from

@@ -10,6 +10,11 @@
 //   apply     x~[j] += c[id16[j]] over every slot and y[j] += c[id16[j]] over local_size_x in ONE pass, c staged in
 //             LDS (at most 32 KiB); where y is the x~ buffer itself the pass adds once (schwz_ras_coarse_apply,
 //             subdomain.hip, knows where y lives).
+// and, for a preconditioner whose right-hand side changes with every application (the outer FGMRES, outer.py),
+//   restriction  s[first_agg + a] = sum_{i in a} v[i] for any vector v in local order (schwz_ras_aggregate_sums): the
+//             two launches of the residual over the rows grouped by aggregate instead of W -- one workgroup per piece
+//             of at most kCoarsePieceCap rows, 8 B of v and 4 B of row id per interior row, then the fold in table
+//             order.  beta is neither read nor written.
 #include <hip/hip_runtime.h>
 
 #include "coarse_plan.hpp"
@@ -42,6 +47,43 @@ __global__ __launch_bounds__(kBlock) void coarse_fold_kernel(int m, const double
     double t = 0.0;
     for (int p = piece_ptr[a]; p < piece_ptr[a + 1]; ++p) t += partial[p];  // table order
     s_out[a] = beta[a] - t;
+}
+
+// partial[p] = sum of v over the rows of piece p.  A piece holds at most 8 rows per lane: the row ids, then the values,
+// are all asked for before the first addition; a lane adds its rows in ascending order from +0.0 (a row beyond the
+// piece adds +0.0, which changes no bit of a sum that started from +0.0)
+static_assert(kCoarsePieceCap == 8 * kBlock, "agg_partial_kernel: a lane holds 8 rows of a piece");
+__global__ __launch_bounds__(kBlock) void agg_partial_kernel(const int32_t *__restrict__ piece,
+                                                             const int32_t *__restrict__ agg_rows,
+                                                             const double *__restrict__ v, double *__restrict__ partial)
+{
+    __shared__ double red[4];
+    const int p = blockIdx.x;
+    const int begin = piece[3 * p + 1], end = piece[3 * p + 2];
+    int32_t row[8];
+    double val[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int k = begin + u * kBlock + (int)threadIdx.x;
+        row[u] = k < end ? __builtin_nontemporal_load(agg_rows + k) : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) val[u] = row[u] >= 0 ? v[row[u]] : 0.0;
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += val[u];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) partial[p] = s;
+}
+
+__global__ __launch_bounds__(kBlock) void agg_fold_kernel(int m, const int32_t *__restrict__ piece_ptr,
+                                                          const double *__restrict__ partial, double *__restrict__ s_out)
+{
+    const int a = blockIdx.x * kBlock + threadIdx.x;
+    if (a >= m) return;
+    double t = 0.0;
+    for (int p = piece_ptr[a]; p < piece_ptr[a + 1]; ++p) t += partial[p];  // table order
+    s_out[a] = t;
 }
 
 // one wave per row, rows in fixed order; PAIRS: nc is even and the row is read as 16-byte pairs
@@ -123,6 +165,33 @@ int launch_coarse_apply(const schwz_coarse_part *part, const schwz_coarse *c, do
     return SCHWZ_OK;
 }
 
+int ensure_agg_rows(schwz_subdomain *sd, hipStream_t st)
+{
+    schwz_coarse_part *p = sd->dev->coarse;
+    if (p->agg_ready) return SCHWZ_OK;
+    const int64_t n = sd->local_size;
+    std::vector<uint16_t> id((size_t)n);
+    if (n) {
+        SCHWZ_HIP_TRY(hipMemcpyAsync(id.data(), (const uint16_t *)p->id16, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
+    }
+    AggRows g;
+    int rc;
+    if ((rc = group_rows_by_aggregate(n, id.data(), p->first_agg, p->m, &g)) ||
+        (rc = plan_row_pieces(p->m, g.ptr.data(), &g.pieces, &g.piece_ptr)))
+        return rc;
+    std::vector<int32_t> piece;
+    piece.reserve(g.pieces.size() * 3);
+    for (const CoarsePiece &q : g.pieces) piece.insert(piece.end(), {q.agg, q.begin, q.end});
+    // (put returns when its copy has landed: a launch on any stream may follow; every partial is stored before it is read)
+    if ((rc = p->agg_rows.put(g.rows)) || (rc = p->agg_ptr.put(g.ptr)) || (rc = p->row_piece.put(piece)) ||
+        (rc = p->row_piece_ptr.put(g.piece_ptr)) || (rc = p->row_partial.alloc(g.pieces.size() + 1)))
+        return rc;
+    SCHWZ_REQUIRE(p->nrow_pieces == (int32_t)g.pieces.size(), "ensure_agg_rows: the piece table has another length than planned");
+    p->agg_ready = true;
+    return SCHWZ_OK;
+}
+
 }  // namespace schwz
 
 extern "C" {
@@ -198,6 +267,12 @@ int schwz_ras_coarse_set_aggregates(schwz_subdomain *sd, const int32_t *h_slot_a
     part->nslots = nslots;
     part->nw = (int64_t)plan.w_slot.size();
     part->npieces = (int)plan.pieces.size();
+    {
+        // (the count of the row pieces follows from the aggregates' sizes: the byte model knows it before the tables exist)
+        std::vector<int32_t> count((size_t)m, 0);
+        for (int64_t i = 0; i < n; ++i) ++count[(size_t)(h_slot_agg[i] - first_agg)];
+        for (int32_t a = 0; a < m; ++a) part->nrow_pieces += (count[(size_t)a] + kCoarsePieceCap - 1) / kCoarsePieceCap;
+    }
     std::vector<int32_t> piece;
     piece.reserve(plan.pieces.size() * 3);
     for (const CoarsePiece &q : plan.pieces) piece.insert(piece.end(), {q.agg, q.begin, q.end});
@@ -238,6 +313,28 @@ int schwz_ras_coarse_residual(schwz_subdomain *sd, schwz_coarse *c, schwz_stream
     hipLaunchKernelGGL(coarse_fold_kernel, dim3((p->m + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (int)p->m,
                        (const double *)p->beta, (const int32_t *)p->piece_ptr, (const double *)p->partial,
                        (double *)c->s + p->first_agg);
+    SCHWZ_HIP_TRY(hipGetLastError());
+    return SCHWZ_OK;
+}
+
+int schwz_ras_aggregate_sums(schwz_subdomain *sd, schwz_coarse *c, const double *d_vec, schwz_stream stream)
+{
+    SCHWZ_REQUIRE(sd && c && d_vec, "schwz_ras_aggregate_sums: null argument");
+    SCHWZ_REQUIRE(sd->dev && sd->dev->coarse,
+                  "schwz_ras_aggregate_sums: the subdomain has no aggregates (schwz_ras_coarse_set_aggregates)");
+    schwz_coarse_part *p = sd->dev->coarse;
+    SCHWZ_REQUIRE(c->nc == p->nc, "schwz_ras_aggregate_sums: the coarse object has another number of aggregates");
+    if (p->m == 0) return SCHWZ_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = ensure_agg_rows(sd, st);
+    if (rc) return rc;
+    if (p->nrow_pieces > 0) {
+        hipLaunchKernelGGL(agg_partial_kernel, dim3(p->nrow_pieces), dim3(kBlock), 0, st, (const int32_t *)p->row_piece,
+                           (const int32_t *)p->agg_rows, d_vec, (double *)p->row_partial);
+        SCHWZ_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(agg_fold_kernel, dim3((p->m + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (int)p->m,
+                       (const int32_t *)p->row_piece_ptr, (const double *)p->row_partial, (double *)c->s + p->first_agg);
     SCHWZ_HIP_TRY(hipGetLastError());
     return SCHWZ_OK;
 }

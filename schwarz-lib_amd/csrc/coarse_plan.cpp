@@ -92,6 +92,41 @@ int plan_coarse(int64_t local_size, int64_t nslots, const schwz_idx *rp, const s
     return SCHWZ_OK;
 }
 
+int group_rows_by_aggregate(int64_t local_size, const uint16_t *id16, int32_t first_agg, int32_t m, AggRows *out)
+{
+    SCHWZ_REQUIRE(out, "group_rows_by_aggregate: null output");
+    SCHWZ_REQUIRE(local_size >= 0 && m >= 0 && (local_size == 0 || id16), "group_rows_by_aggregate: bad arguments");
+    SCHWZ_REQUIRE(local_size < (int64_t)std::numeric_limits<int32_t>::max(),
+                  "group_rows_by_aggregate: more than 2^31-1 interior rows");
+    const int64_t n = local_size;
+    out->ptr.assign((size_t)m + 1, 0);
+    out->rows.assign((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t a = (int32_t)id16[(size_t)i] - first_agg;
+        SCHWZ_REQUIRE(a >= 0 && a < m, "group_rows_by_aggregate: an interior row's aggregate lies outside the subdomain's range");
+        ++out->ptr[(size_t)a + 1];
+    }
+    for (int32_t a = 0; a < m; ++a) out->ptr[(size_t)a + 1] += out->ptr[(size_t)a];
+    std::vector<int32_t> fill(out->ptr.begin(), out->ptr.end() - 1);
+    for (int64_t i = 0; i < n; ++i) out->rows[(size_t)fill[(size_t)((int32_t)id16[(size_t)i] - first_agg)]++] = (int32_t)i;
+    return SCHWZ_OK;
+}
+
+int plan_row_pieces(int32_t m, const int32_t *agg_ptr, std::vector<CoarsePiece> *pieces, std::vector<int32_t> *piece_ptr)
+{
+    SCHWZ_REQUIRE(pieces && piece_ptr && m >= 0 && agg_ptr, "plan_row_pieces: bad arguments");
+    SCHWZ_REQUIRE(agg_ptr[0] == 0, "plan_row_pieces: the offsets do not start at 0");
+    pieces->clear();
+    piece_ptr->assign((size_t)m + 1, 0);
+    for (int32_t a = 0; a < m; ++a) {
+        SCHWZ_REQUIRE(agg_ptr[a + 1] >= agg_ptr[a], "plan_row_pieces: the offsets do not ascend");
+        for (int32_t b = agg_ptr[a]; b < agg_ptr[a + 1]; b += kCoarsePieceCap)
+            pieces->push_back({a, b, (int32_t)std::min<int64_t>((int64_t)b + kCoarsePieceCap, agg_ptr[a + 1])});
+        (*piece_ptr)[(size_t)a + 1] = (int32_t)pieces->size();
+    }
+    return SCHWZ_OK;
+}
+
 int dense_inverse(int32_t n, const double *a, double *inv)
 {
     SCHWZ_REQUIRE(n >= 0 && (n == 0 || (a && inv)), "schwz_dense_inverse: bad arguments");

@@ -16,7 +16,7 @@
 namespace schwz {
 
 constexpr int kCoarseMaxDofs = 4096;   // nc: aggregate ids fit 16 bits, c fits LDS, the explicit inverse stays <= 128 MB
-constexpr int kCoarsePieceCap = 2048;  // W entries one workgroup reduces
+constexpr int kCoarsePieceCap = 2048;  // W entries, or rows of an aggregate, one workgroup reduces
 
 struct CoarsePiece {
     int32_t agg, begin, end;  // local aggregate and its W entries [begin, end), end - begin <= kCoarsePieceCap
@@ -40,6 +40,25 @@ struct CoarsePlan {
 // an id range outside [0, nc), a slot id outside [0, nc) or an interior slot outside the subdomain's own range.
 int plan_coarse(int64_t local_size, int64_t nslots, const schwz_idx *rp, const schwz_idx *col, const double *val,
                 const double *rhs, const int32_t *slot_agg, int32_t first_agg, int32_t m, int32_t nc, CoarsePlan *out);
+
+// The interior rows grouped by aggregate, and their cut into pieces: what schwz_ras_rhs_aggregate (ptr, rows) and the
+// streaming restriction schwz_ras_aggregate_sums (all four) read.
+struct AggRows {
+    std::vector<int32_t> ptr;           // m + 1: rows of aggregate a are rows[ptr[a], ptr[a + 1]), ascending
+    std::vector<int32_t> rows;          // local_size
+    std::vector<CoarsePiece> pieces;    // aggregate after aggregate: entries [begin, end) of `rows`
+    std::vector<int32_t> piece_ptr;     // m + 1: pieces of aggregate a are [piece_ptr[a], piece_ptr[a + 1])
+};
+
+// id16: the global aggregate of the local_size interior rows (the head of CoarsePlan::id16).  Counting sort: the rows
+// of an aggregate stay ascending, as in plan_coarse.  SCHWZ_ERR_INVALID (message set) for 2^31-1 rows or more and for
+// a row whose aggregate lies outside [first_agg, first_agg + m).  Fills ptr and rows.
+int group_rows_by_aggregate(int64_t local_size, const uint16_t *id16, int32_t first_agg, int32_t m, AggRows *out);
+
+// pieces and piece_ptr from agg_ptr (m + 1 ascending offsets) alone: every aggregate's rows cut front to back into
+// pieces of at most kCoarsePieceCap, an aggregate without rows gets no piece.  SCHWZ_ERR_INVALID (message set) for
+// offsets that do not ascend from 0.
+int plan_row_pieces(int32_t m, const int32_t *agg_ptr, std::vector<CoarsePiece> *pieces, std::vector<int32_t> *piece_ptr);
 
 // inv = a^-1 (n x n, row-major) by LU with partial pivoting and n pairs of triangular solves.  SCHWZ_ERR_INVALID
 // (message set) for a zero, negligible or non-finite pivot.

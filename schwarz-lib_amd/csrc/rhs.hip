@@ -6,7 +6,7 @@
 //   beta of the coarse part     schwz_ras_rhs_aggregate: beta_a = sum_{i in a} b_i, one lane per aggregate, the rows of an
 //                               aggregate in ascending order into one accumulator -- the order of plan_coarse
 //                               (coarse_plan.cpp), so the bits are those of a fresh plan.  The rows grouped by aggregate
-//                               (4 B per interior row) are built from the slot ids at the first call.
+//                               (4 B per interior row) are ensure_agg_rows' (coarse.hip), built at the first call.
 //   ||b||^2 of the owned rows   schwz_ras_rhs_norm_sq, in block_sum's fixed order
 //   d_btilde, x~, y             schwz_ras_restart (subdomain.hip, which knows where y lives) through launch_restart here
 // All of them are plain streaming passes on the caller's stream: they run once per solve, not once per step.
@@ -108,40 +108,6 @@ static int ensure_rhs_index(schwz_subdomain *sd, hipStream_t st)
     if (n) SCHWZ_HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(int64_t), hipMemcpyHostToDevice, st));
     SCHWZ_HIP_TRY(hipStreamSynchronize(st));
     sd->dev->d_rhs_index = std::move(d);
-    return SCHWZ_OK;
-}
-
-// the interior rows grouped by aggregate, from the slot ids the coarse part holds in HBM (counting sort: the rows of an
-// aggregate stay ascending, as in plan_coarse)
-static int ensure_agg_rows(schwz_subdomain *sd, hipStream_t st)
-{
-    schwz_coarse_part *p = sd->dev->coarse;
-    if (p->agg_ready) return SCHWZ_OK;
-    const int64_t n = sd->local_size;
-    const int32_t m = p->m;
-    SCHWZ_REQUIRE(n < (int64_t)INT_MAX, "schwz_ras_rhs_aggregate: more than 2^31-1 interior rows");
-    std::vector<uint16_t> id((size_t)n);
-    if (n) {
-        SCHWZ_HIP_TRY(hipMemcpyAsync(id.data(), (const uint16_t *)p->id16, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-        SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-    }
-    std::vector<int32_t> ptr((size_t)m + 1, 0), rows((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t a = (int32_t)id[(size_t)i] - p->first_agg;
-        SCHWZ_REQUIRE(a >= 0 && a < m, "schwz_ras_rhs_aggregate: an interior row's aggregate lies outside the subdomain's range");
-        ++ptr[(size_t)a + 1];
-    }
-    for (int32_t a = 0; a < m; ++a) ptr[(size_t)a + 1] += ptr[(size_t)a];
-    {
-        std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (int64_t i = 0; i < n; ++i) rows[(size_t)fill[(size_t)((int32_t)id[(size_t)i] - p->first_agg)]++] = (int32_t)i;
-    }
-    int rc;
-    if ((rc = p->agg_rows.alloc((size_t)n)) || (rc = p->agg_ptr.alloc((size_t)m + 1))) return rc;
-    if (n) SCHWZ_HIP_TRY(hipMemcpyAsync(p->agg_rows, rows.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    SCHWZ_HIP_TRY(hipMemcpyAsync(p->agg_ptr, ptr.data(), ((size_t)m + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    SCHWZ_HIP_TRY(hipStreamSynchronize(st));
-    p->agg_ready = true;
     return SCHWZ_OK;
 }
 

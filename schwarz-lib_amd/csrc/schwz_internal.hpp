@@ -923,13 +923,20 @@ struct schwz_coarse_part {
     schwz::Dev<int32_t> w_slot, piece, piece_ptr;  // piece: {aggregate, begin, end} per piece
     schwz::Dev<uint16_t> id16;
     std::vector<double> rows;  // m x nc: the subdomain's rows of A0 (schwz_ras_coarse_rows)
-    // schwz_ras_rhs_aggregate (rhs.hip), built at its first call: the interior rows grouped by aggregate, ascending
-    // inside each (agg_rows, 4 B per interior row), aggregate a's rows at [agg_ptr[a], agg_ptr[a + 1])
-    schwz::Dev<int32_t> agg_rows, agg_ptr;
+    // schwz_ras_rhs_aggregate (rhs.hip) and schwz_ras_aggregate_sums (coarse.hip), built by ensure_agg_rows at the first
+    // call of either: the interior rows grouped by aggregate, ascending inside each (agg_rows, 4 B per interior row),
+    // aggregate a's rows at [agg_ptr[a], agg_ptr[a + 1]); for aggregate_sums their cut into pieces of at most
+    // kCoarsePieceCap rows (row_piece: {aggregate, begin, end} per piece, row_piece_ptr: m + 1) and a partial sum per piece
+    schwz::Dev<int32_t> agg_rows, agg_ptr, row_piece, row_piece_ptr;
+    schwz::Dev<double> row_partial;
+    int32_t nrow_pieces = 0;
     bool agg_ready = false;
 };
 
 namespace schwz {
+// the tables above from the slot ids the coarse part holds in HBM: planned on the host (coarse_plan.cpp), uploaded on
+// `st`, which is waited for; nothing to do after the first call
+int ensure_agg_rows(schwz_subdomain *sd, hipStream_t st);
 // x[j] += c[id16[j]] over nx slots and, where y is a buffer of its own (not null), y[j] += c[id16[j]] over ny <= nx
 int launch_coarse_apply(const schwz_coarse_part *part, const schwz_coarse *c, double *x, int64_t nx, double *y, int64_t ny,
                         hipStream_t st);

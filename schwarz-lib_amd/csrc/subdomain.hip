@@ -974,6 +974,13 @@ int64_t schwz_ras_algorithmic_bytes(const schwz_subdomain *sd, int which)
         return 20 * p->nw + 16 * (int64_t)p->m + 8 * (int64_t)p->m * p->nc + 16 * (int64_t)p->nc + 16 * slots + 2 * slots +
                (own_y ? 16 * n : 0);
     }
+    if (which == 3) {
+        // schwz_ras_aggregate_sums (coarse.hip): a value and a row id per interior row; per piece its record, and its
+        // partial sum stored and read; the offsets of the fold and the m sums stored
+        const schwz_coarse_part *p = sd->dev ? sd->dev->coarse : nullptr;
+        if (!p) return 0;
+        return 12 * sd->local_size + 28 * (int64_t)p->nrow_pieces + 4 * ((int64_t)p->m + 1) + 8 * (int64_t)p->m;
+    }
     switch (local_kind(sd)) {
     case LocalKind::CgF32:
         // cg_f32.hip: 8 B per nonzero, p gathered and q stored in fp32, then e, r read and written, p, q, 1/diag read

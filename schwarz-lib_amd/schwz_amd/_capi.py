@@ -75,7 +75,7 @@ SYMBOLS = [
     "schwz_ras_true_residual_sq", "schwz_ras_algorithmic_bytes",
     "schwz_ras_coarse_set_aggregates", "schwz_ras_coarse_rows", "schwz_dense_inverse", "schwz_coarse_create",
     "schwz_coarse_destroy", "schwz_coarse_vector", "schwz_ras_coarse_residual", "schwz_coarse_solve",
-    "schwz_ras_coarse_apply",
+    "schwz_ras_coarse_apply", "schwz_ras_aggregate_sums",
     "schwz_ras_rhs_set", "schwz_ras_rhs_index", "schwz_ras_rhs_gather", "schwz_ras_rhs_aggregate", "schwz_ras_rhs_norm_sq",
     "schwz_ras_rhs_norm_sq_local",
     "schwz_ras_restart",
@@ -283,6 +283,7 @@ _sig("schwz_coarse_vector", i32, [vp, i32, pvp, C.POINTER(C.c_int32)])
 _sig("schwz_ras_coarse_residual", i32, [vp, vp, vp])
 _sig("schwz_coarse_solve", i32, [vp, vp])
 _sig("schwz_ras_coarse_apply", i32, [vp, vp, vp])
+_sig("schwz_ras_aggregate_sums", i32, [vp, vp, vp, vp])
 _sig("schwz_ras_rhs_set", i32, [vp, vp, i32, vp])
 _sig("schwz_ras_rhs_index", i32, [vp, vp])
 _sig("schwz_ras_rhs_gather", i32, [vp, vp, i64, vp])

@@ -919,6 +919,12 @@ class Subdomain:
     def coarse_apply(self, coarse, stream=0):
         check(lib.schwz_ras_coarse_apply(self.h, coarse.h, _stream_arg(stream)))
 
+    def aggregate_sums(self, coarse, d_vec, stream=0):
+        """s[first_agg + a] = sum of d_vec over the rows of the subdomain's aggregate a, into s of `coarse`; d_vec: the
+        integer address of at least local_size doubles in HBM, in local order (schwz_ras_aggregate_sums)."""
+        check(lib.schwz_ras_aggregate_sums(self.h, coarse.h if coarse is not None else None, ptr(d_vec),
+                                           _stream_arg(stream)))
+
     # ---- a new right-hand side on a set-up subdomain (schwz_ras_rhs_*, schwz_ras_restart) ----
 
     def rhs_set(self, rhs, stream=0):

@@ -1,5 +1,5 @@
-"""Outer FGMRES preconditioned by one RAS sweep (an extension: the reference's only outer iteration is the stationary
-one of SchwarzBase::run, and it has no outer Krylov method).
+"""Outer FGMRES preconditioned by one RAS sweep or by one two-level step (an extension: the reference's only outer
+iteration is the stationary one of SchwarzBase::run, and it has no outer Krylov method).
 
 metadata.outer_iteration = "fgmres" makes SolverRAS.run() -- and with it solve() and a run() after set_rhs() -- a loop
 of its own, as solve_many is: right-preconditioned flexible GMRES(outer_restart) on the global system, flexible
@@ -12,6 +12,17 @@ because an iterative local solve is no fixed linear operator.  Per outer iterati
   orthogonalise    classical Gram-Schmidt applied twice on the device (core.Outer: dots, project_dots twice), the norm
                    of the result by a reduction
   Givens + solve   on the host in float64 (GivensLeastSquares below)
+
+With metadata.outer_preconditioner = "two-level" (and coarse_space = "aggregates") z_j is the stationary two-level step
+from a zero start with the right-hand side v_j, the coarse correction first and the sweep on the corrected residual:
+
+  z0 = Z A0^-1 Z^T v_j,   z_j = z0 + RAS(v_j - A z0)
+
+as: v_j into x~, exchange, rhs_set, aggregate_sums from the vector of id 3 (s = Z^T v_j: the streaming restriction -- beta
+of the coarse plan belongs to the caller's b and is neither used nor touched), the coarse solve once, then per subdomain
+restart(keep_x=False), coarse_apply (x~ = y = c[agg] on every slot, halo included: no second exchange),
+update_boundary (b~ = v_j - A_Gamma z0 on the overlap rows), local_solve from the warm start y = z0, restrict.  The
+additive form RAS(v) + z0 is not offered: with unsmoothed aggregates it needed as many applications as one level.
 
 and at the end of a cycle x += sum y_i Z_i, the true residual recomputed for the next cycle's v_0.  Two exchanges per
 outer iteration where the stationary step has one.  The loop borrows x~, b, b~, y and the solver objects of the
@@ -30,10 +41,11 @@ from . import _capi as capi
 from . import core
 
 OUTER_ITERATIONS = ("richardson", "fgmres")
+OUTER_PRECONDITIONERS = ("ras", "two-level")
 
 
 def wants_fgmres(settings, metadata, comm):
-    """The two Metadata fields checked (ERR_INVALID) and, for "fgmres", the configurations the loop does not exist for
+    """The three Metadata fields checked (ERR_INVALID) and, for "fgmres", the configurations the loop does not exist for
     refused (NotImplementedSchwz).  Touches neither the backend nor a subdomain.  True: run() is the loop below."""
     name = getattr(metadata, "outer_iteration", "richardson")
     if not isinstance(name, str) or name not in OUTER_ITERATIONS:
@@ -43,14 +55,21 @@ def wants_fgmres(settings, metadata, comm):
             or restart > capi.OUTER_MAX_RESTART:
         raise capi.SchwzError(capi.ERR_INVALID, "outer_restart must be an integer in 1..%d, not %r"
                               % (capi.OUTER_MAX_RESTART, restart))
+    pre = getattr(metadata, "outer_preconditioner", "ras")
+    if not isinstance(pre, str) or pre not in OUTER_PRECONDITIONERS:
+        raise capi.SchwzError(capi.ERR_INVALID, "outer_preconditioner must be 'ras' or 'two-level', not %r" % (pre,))
     if name == "richardson":
         return False
 
     def unavailable(what):
         raise capi.NotImplementedSchwz(capi.ERR_NOT_IMPLEMENTED,
                                        "outer_iteration 'fgmres' does not exist for " + what)
-    if getattr(metadata, "coarse_space", "none") != "none":
-        unavailable("coarse_space '%s' (beta of the coarse plan depends on the right-hand side)" % metadata.coarse_space)
+    coarse = getattr(metadata, "coarse_space", "none")
+    if pre == "two-level" and coarse == "none":
+        raise capi.SchwzError(capi.ERR_INVALID, "outer_preconditioner 'two-level' needs coarse_space 'aggregates'")
+    if pre == "ras" and coarse != "none":
+        unavailable("coarse_space '%s' with outer_preconditioner 'ras' (beta of the coarse plan depends on the "
+                    "right-hand side): set outer_preconditioner = 'two-level'" % coarse)
     if settings.comm_settings.enable_onesided:
         unavailable("enable_onesided")
     if settings.comm_settings.enable_overlap:
@@ -163,7 +182,11 @@ def run_fgmres(solver, gather_solution=True):
         n += sd.local_size
     st = _state(solver, locals_, n, restart)
     o, x = st["obj"], st["x"].data_ptr()
+    two_level = getattr(m, "outer_preconditioner", "ras") == "two-level"
+    coarse = solver._coarse["obj"] if two_level else None
     profile = dict(sweep=0.0, apply=0.0, ortho=0.0) if getattr(solver, "outer_profile", False) else None
+    if profile is not None and two_level:
+        profile["coarse"] = 0.0
 
     def clock(key, t0):
         if profile is not None:
@@ -226,9 +249,27 @@ def run_fgmres(solver, gather_solution=True):
                 # z_j = M^-1 v_j: one RAS sweep from a zero start with the right-hand side v_j
                 interiors_from(o.vector(o.V, j))
                 _exchange(solver, stream)
-                for _, sd in locals_:
-                    sd.rhs_set(sd.vector(0)[0], stream)  # (asked for again every time: a restriction swaps the buffers)
-                    sd.restart(False, stream)
+                if not two_level:
+                    for _, sd in locals_:
+                        sd.rhs_set(sd.vector(0)[0], stream)  # (asked for again every time: a restriction swaps the buffers)
+                        sd.restart(False, stream)
+                else:
+                    # z0 = Z A0^-1 Z^T v_j in x~ and y, then the sweep on v_j - A z0 from the warm start z0
+                    for _, sd in locals_:
+                        sd.rhs_set(sd.vector(0)[0], stream)
+                    t0 = clock("sweep", t0)
+                    for _, sd in locals_:
+                        sd.aggregate_sums(coarse, sd.vector(3)[0], stream)
+                    coarse.solve(stream)
+                    t0 = clock("coarse", t0)
+                    for _, sd in locals_:
+                        sd.restart(False, stream)
+                    t0 = clock("sweep", t0)
+                    for _, sd in locals_:
+                        sd.coarse_apply(coarse, stream)
+                    t0 = clock("coarse", t0)
+                    for _, sd in locals_:
+                        sd.update_boundary(stream)
                 for _, sd in locals_:
                     sd.local_solve(stream)
                 for _, sd in locals_:

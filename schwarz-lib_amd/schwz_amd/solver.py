@@ -172,6 +172,10 @@ class Metadata:
     # other name, and an outer_restart outside 1..128, is refused.  solve_many ignores both fields.
     outer_iteration: str = "richardson"
     outer_restart: int = 30
+    # the preconditioner of the outer FGMRES: "ras" (one sweep; with a coarse space the loop is refused) or "two-level"
+    # (needs coarse_space "aggregates": one stationary two-level step from a zero start, the coarse correction first).
+    # With outer_iteration "richardson" the field has no effect, like restart_iter; any other name is refused.
+    outer_preconditioner: str = "ras"
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)
